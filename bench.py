@@ -3,6 +3,8 @@
 on the BASELINE.json C2 tile (1M transcripts, 10k nuclei, k=15), bf16 storage.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full    (+ every secondary record listed below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
     python bench.py --gpus N ...           (no launcher environment: this process starts its own N ranks -- self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,7 +13,23 @@ on the BASELINE.json C2 tile (1M transcripts, 10k nuclei, k=15), bf16 storage.
 One step = one pass of the hot path over one synthetic tile per rank (weak
 scaling: every rank owns a tile of the same size, different seed): encoder
 forward, the three losses, backward, one flat-bucket gradient all-reduce (N>1),
-Adam.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE
+Adam.  Every step starts from the same weights (restored by one multi-tensor copy at the top of the step; Adam's
+moments and step count carry on): the loss-head backward sums with fp32 atomics in an order that varies between runs,
+and weights carried from step to step would turn that rounding into a different trajectory in every run.  `loss` is
+therefore the loss of one step from the seed-0 weights.  Inputs are resident in HBM before the timed region.  A plain
+run sets up, takes --warmup steps, times --steps steps and prints the line: the contract keys, mp_edges_per_s, loss and
+step_algorithmic_frac.  Everything else below (untimed_setup, roofline, roofline_other, predict, f32, strong, c5,
+c5_100m, default_dropin, cpu_baseline, auroc) is measured only with --full; there the --no-* options leave single
+records out.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step hands its caller as float32 .npy
+files: loss.npy and param.<name>.npy (the weights after its Adam update), every character of a parameter name outside
+[A-Za-z0-9_.-] replaced by '_' (1.7 MB at the default sizes, at most 64 MB).  The inputs are seeded (tile: seed = rank;
+weights: torch seed 0; dropout and loss draws: per-step counters and the seeded device generator), so two builds run
+with the same arguments can be compared output for output.  Two runs of one build (C2, bf16, 25 steps): the loss is
+bit-identical, every weight file agrees to 3e-4 of its largest entry (the backward's atomics, through Adam).
+
+Rank 0 prints ONE
 JSON line on stdout -- the COMPACT contract line (`contract_line()`: the contract keys, `roofline` with
 `roofline.dominant` (the destination pass of the backward: the kernel with the largest share of the step) and
 `roofline.source_pass`, `cpu_baseline`, and scalar summaries of everything else; asserted <= 8 KB, round 5's 21 KB line was
@@ -288,6 +306,27 @@ def emit_result(res: dict) -> None:
         log(f"[bench] could not write {DETAILS_FILE}: {e}")
     log("[bench] full record: " + json.dumps(res))
     print(contract_line(res), file=RESULT_OUT, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir: str, model, loss) -> None:
+    """--dump-outputs: the loss of the last timed step and the weights after its Adam update, as float32 .npy files
+    under ``out_dir``."""
+    import re
+    import numpy as np
+    arrays = {"loss": loss.detach()}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p.detach()
+    files = {re.sub(r"[^A-Za-z0-9_.-]", "_", k) + ".npy": v.float().cpu().numpy() for k, v in arrays.items()}
+    assert len(files) == len(arrays), "two outputs map to one file name"
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_MAX_BYTES, f"outputs are {total} bytes (> {DUMP_MAX_BYTES})"
+    os.makedirs(out_dir, exist_ok=True)
+    for fn, a in files.items():
+        np.save(os.path.join(out_dir, fn), a)
+    log(f"[bench] {len(files)} outputs ({total} bytes) written to {out_dir}")
 
 
 def gat_fwd_algorithmic_bytes(n_edges, n_dst, hc, elem):
@@ -1016,6 +1055,12 @@ def main():
     ap.add_argument("--n-bd", type=int, default=10_000)
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure every secondary record (untimed setup, roofline, predict, "
+                         "f32, strong scaling, c5, default_dropin, CPU baseline, AUROC vs the oracle); the --no-* options "
+                         "below leave single ones out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss of the last timed step and the weights after it to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f32", action="store_true", help="skip the fp32 secondary line")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling (fixed FOV) record")
@@ -1097,8 +1142,14 @@ def main():
     broadcast_parameters(model)
     opt = model.configure_optimizers()
     bucket = FlatGradBucket(model.parameters())
+    # every step starts from the same weights (one multi-tensor copy): the loss-head backward sums with fp32 atomics, and
+    # weights carried from step to step would turn their run-to-run rounding into different training trajectories
+    params = list(model.parameters())
+    weights0 = [p.detach().clone() for p in params]
 
     def step():
+        with torch.no_grad():
+            torch._foreach_copy_(params, weights0)
         opt.zero_grad(set_to_none=True)
         loss = model.training_step(batch, 0)
         loss.backward()
@@ -1132,13 +1183,15 @@ def main():
         dt, (etb_all, ett_all, ep_all) = float(tmax[0]), [float(v) for v in sums]
     else:
         etb_all, ett_all, ep_all = float(etb), float(ett), float(ep)
+    if args.dump_outputs and rank == 0:        # before anything below steps the model again
+        dump_outputs(args.dump_outputs, model, loss)
     loss_val = float(loss.detach())
     del loss
 
     # ---- what the timed region leaves out: it replays ONE resident batch, whose sorted edge views, sampler indices,
     # rows-by-gene grouping and loss masks were built by the first warm-up step and are cached on the batch ------------
     untimed = None
-    if True:     # EVERY rank: the uncached step below contains the gradient all-reduce (rank 0 alone would deadlock the job)
+    if args.full:     # EVERY rank: the uncached step below contains the gradient all-reduce (rank 0 alone would deadlock the job)
         from segger_amd.graph import build_edge_graph
         n_tx_, n_bd_ = spec.n_tx, spec.n_bd
 
@@ -1166,7 +1219,7 @@ def main():
 
     # ---- roofline of the dominant kernel: tx-neighbors-tx aggregation, forward -------------------
     roof, extra = None, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         H, C = 2, 64
         hc, elem = H * C, (2 if dtype == torch.bfloat16 else 4)
         n_tx, n_bd = spec.n_tx, spec.n_bd
@@ -1276,7 +1329,7 @@ def main():
 
     # ---- secondary figure: inference-only edge scoring (predict_step) on the same tile ----------------
     predict = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             model.eval()
             with torch.no_grad():
@@ -1290,7 +1343,7 @@ def main():
 
     # ---- secondary figure: the same training step with fp32 storage (the reference's arithmetic width) ---------
     f32 = None
-    if rank == 0 and world == 1 and not args.no_f32 and dtype != torch.float32:
+    if rank == 0 and world == 1 and args.full and not args.no_f32 and dtype != torch.float32:
         try:
             model.model.compute_dtype = torch.float32
             model.train(not args.no_dropout)
@@ -1320,7 +1373,7 @@ def main():
     # ---- strong scaling: ONE fixed FOV streamed as packed tile batches over all ranks (BASELINE config 4) ----
     strong = None
     auroc_fov = c5 = c5_100m = default_dropin = None
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         from segger_amd.dp import seed_rank, strong_scaling_epoch
         from segger_amd.fov import batch_weights, build_fov_batches
         del batch, batch_cpu
@@ -1537,7 +1590,7 @@ def main():
 
     cpu = None
     auroc = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         torch.cuda.empty_cache()
         try:
             ctx = {}

@@ -416,6 +416,24 @@ def test_bench_contract_line_survives_oversized_and_failed_records():
     assert len(c["f32"]["error"]) <= 120
 
 
+def test_bench_dump_outputs_writes_loss_and_weights(tmp_path):
+    """`bench.py --dump-outputs DIR`: the loss and every parameter as float32 .npy under file names that keep the
+    parameter name (characters outside [A-Za-z0-9_.-] -> '_')."""
+    bench = _load_bench()
+    torch.manual_seed(0)
+    m = torch.nn.ModuleDict({"<tx___neighbors___tx>": torch.nn.Linear(3, 2)})
+    loss = m["<tx___neighbors___tx>"](torch.randn(4, 3)).square().sum()
+    loss.backward()
+    bench.dump_outputs(str(tmp_path / "out"), m, loss)
+    got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(got) == {"loss.npy", "param._tx___neighbors___tx_.weight.npy", "param._tx___neighbors___tx_.bias.npy"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    lin = m["<tx___neighbors___tx>"]
+    assert got["loss.npy"].shape == () and got["loss.npy"] == np.float32(loss.item())
+    assert np.array_equal(got["param._tx___neighbors___tx_.weight.npy"], lin.weight.detach().numpy())
+    assert np.array_equal(got["param._tx___neighbors___tx_.bias.npy"], lin.bias.detach().numpy())
+
+
 def test_cli_default_widths_never_leave_the_hand_written_gemms():
     """Every projection of the encoder at segger's CLI defaults (in 128, hidden 64 x 2 heads, out 64; ist_encoder.py:219-287)
     -- forward, data gradient (K and M swapped) and weight gradient, in fp32 / bf16 / f16 -- is covered by the MFMA kernels,

@@ -7,7 +7,7 @@
 #   rNN_small_batch_step_graphed.txt, _sequence.txt          the replayed 1M-edge step (tools/fov_stream.py --graphed-train)
 set -x
 tag=$1; R=$PWD; OUT=$R/gpurun_out/prof_$tag; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2 -- python3 $R/bench.py --no-strong --no-f32 --no-cpu-baseline > $OUT/c2.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2 -- python3 $R/bench.py --full --no-strong --no-f32 --no-cpu-baseline > $OUT/c2.log 2>&1 || exit 1
 cp $(ls $OUT/c2/*/*_kernel_stats.csv | head -1) $OUT/${tag}_bench_c2_kernel_stats.csv
 python3 $R/tools/prof_steps.py $OUT/c2 13 75 > $OUT/${tag}_step_breakdown.txt
 rocprofv3 --kernel-trace --output-format csv -d $OUT/step -- python3 $R/tools/bench_step.py > $OUT/step.log 2>&1 || exit 1
