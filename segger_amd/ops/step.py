@@ -1,0 +1,165 @@
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from .. import _lib
+
+
+_FILLS = {"const": _lib.FILL_CONST, "tile": _lib.FILL_TILE, "div": _lib.FILL_DIV, "mod": _lib.FILL_MOD,
+          "ramp": _lib.FILL_RAMP}
+
+
+def _adam_jobs(opt):
+    """[(param group, [(param, grad, exp_avg, exp_avg_sq, step)])] when ``segger_adam_step`` covers ``opt``, else None."""
+    from ..optim import Adam as _Adam
+    if type(opt) not in (torch.optim.Adam, _Adam):   # (not subclasses in general: torch's AdamW is one)
+        return None
+    # torch's AMP contract for fused optimizers (``_step_supports_amp_scaling``): ``GradScaler.step`` skips its own unscale /
+    # inf check and hands both to the optimizer as ``grad_scale`` / ``found_inf``.  The kernel reads neither: torch's fused
+    # step does the scaled, skippable update.
+    if getattr(opt, "grad_scale", None) is not None or getattr(opt, "found_inf", None) is not None:
+        return None
+    jobs = []
+    for g in opt.param_groups:
+        if (g.get("amsgrad") or g.get("weight_decay") or g.get("maximize") or g.get("differentiable")
+                or not g.get("capturable") or isinstance(g["lr"], Tensor)):
+            return None
+        rows = []
+        for p in g["params"]:
+            if p.grad is None:
+                continue
+            st = opt.state.get(p)
+            if not st or "exp_avg" not in st:
+                return None
+            ts = (p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"])
+            if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts) or p.grad.is_sparse:
+                return None
+            rows.append(ts)
+        jobs.append((g, rows))
+    return jobs
+
+
+def adam_step_counters(opt, params=None) -> Optional[list]:
+    """The step counters ``segger_adam_step`` would advance (one fp32 scalar per parameter ``params`` -- default: those with
+    a gradient -- of a covered optimizer whose state exists), at most 64 in ONE parameter group; None otherwise.  A captured
+    step hands them to :func:`step_draws` and then calls ``adam_step(opt, steps_advanced=True)``."""
+    from ..optim import Adam as _Adam
+    if type(opt) not in (torch.optim.Adam, _Adam) or len(opt.param_groups) != 1:
+        return None
+    g = opt.param_groups[0]
+    if (g.get("amsgrad") or g.get("weight_decay") or g.get("maximize") or g.get("differentiable")
+            or not g.get("capturable") or isinstance(g["lr"], Tensor)):
+        return None
+    out = []
+    for p in (g["params"] if params is None else params):
+        st = opt.state.get(p)
+        if not st or "step" not in st or not st["step"].is_cuda or st["step"].dtype != torch.float32:
+            return None
+        out.append(st["step"])
+    return out if 0 < len(out) <= 64 else None
+
+
+def double_bits(x: float) -> int:
+    """The int64 whose bits are the fp64 pattern of ``x`` (a ``const`` fill of a float64 buffer by :func:`stage`)."""
+    import struct
+    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+
+
+def adam_hyper(opt) -> Optional[tuple]:
+    """(lr, beta1, beta2, eps) of a one-group optimizer of the kind :func:`adam_step` covers (plain capturable Adam, Python
+    float learning rate; the state need not exist yet), else None."""
+    from ..optim import Adam as _Adam
+    if type(opt) not in (torch.optim.Adam, _Adam) or len(opt.param_groups) != 1:
+        return None
+    g = opt.param_groups[0]
+    if (g.get("amsgrad") or g.get("weight_decay") or g.get("maximize") or g.get("differentiable")
+            or not g.get("capturable") or isinstance(g["lr"], Tensor)):
+        return None
+    return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
+
+
+def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = None, counter_inc: int = 0,
+              hyper_dev: Optional[Tensor] = None) -> bool:
+    """``optimizer.step()`` of a plain capturable ``torch.optim.Adam`` through ``segger_adam_step``: every parameter tensor
+    in two launches, on the optimizer's own state tensors (checkpoints and eager ``optimizer.step()`` calls stay
+    interchangeable).  -> False, nothing done, when the optimizer is anything else (amsgrad, weight decay, maximize, a
+    tensor learning rate, non-fp32 or non-contiguous parameters, state not created yet): the caller then runs
+    ``optimizer.step()`` itself.  ``steps_advanced``: the step counters were advanced already (:func:`adam_step_counters`);
+    ``counter`` (int64[1] on the device): ``counter += counter_inc`` rides in the update launch.  ``hyper_dev`` (float64[4]
+    on the device = lr, beta1, beta2, eps; one parameter group): the kernel reads them from there when it RUNS
+    (``segger_adam_step_dev``) -- a captured step follows a learning-rate schedule without a new capture.
+    (Host cost ~135 us per call for 60 tensors, nearly all of it the per-tensor attribute reads; a cached launch table
+    that re-checked pointers and state identity per step measured the same -- tools/host_phases.py.)"""
+    # torch's AMP contract for fused optimizers (``_step_supports_amp_scaling``): ``GradScaler.step`` skips its own unscale /
+    # inf check and hands both to the optimizer as ``grad_scale`` / ``found_inf``.  The kernel reads neither: torch's fused
+    # step does the scaled, skippable update.
+    jobs = _adam_jobs(opt)
+    if jobs is None:
+        return False
+    jobs = [(g, rows) for g, rows in jobs if rows]
+    if (steps_advanced or counter is not None or hyper_dev is not None) and len(jobs) != 1:
+        raise RuntimeError("adam_step: advanced counters / device hyper-parameters need exactly one parameter group with gradients")
+    if hyper_dev is not None and (hyper_dev.dtype != torch.float64 or hyper_dev.numel() != 4 or not hyper_dev.is_contiguous()
+                                  or not hyper_dev.is_cuda):
+        raise ValueError("adam_step: hyper_dev must be a contiguous float64[4] tensor on the device")
+    lib = _lib.load()
+    for g, rows in jobs:
+        arr = (_lib.AdamTensor * len(rows))()
+        for a, (p, gr, m, v, st) in zip(arr, rows):
+            a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.step, a.numel = (p.data_ptr(), gr.data_ptr(), m.data_ptr(),
+                                                                         v.data_ptr(), st.data_ptr(), p.numel())
+        dev = rows[0][0].device
+        b1, b2 = g["betas"]
+        with _lib.on_device(dev):
+            if hyper_dev is not None:
+                rc = lib.segger_adam_step_dev(arr, len(rows), hyper_dev.data_ptr(), 1 if steps_advanced else 0,
+                                              _lib.ptr(counter), int(counter_inc), _lib.stream_ptr(dev))
+            else:
+                rc = lib.segger_adam_step_ex(arr, len(rows), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                                             1 if steps_advanced else 0, _lib.ptr(counter), int(counter_inc), _lib.stream_ptr(dev))
+        _lib.check(rc, "segger_adam_step")
+    return True
+
+
+def float_bits(x: float) -> int:
+    """The int whose low 32 bits are the fp32 pattern of ``x`` (a ``const`` fill of a float buffer)."""
+    import struct
+    return struct.unpack("<i", struct.pack("<f", float(x)))[0]
+
+
+@torch.no_grad()
+def stage(segments, device) -> None:
+    """``segger_stage``: all of ``segments`` in one launch.  A segment is ``(dst, src, fill, a, b, c[, add])``: ``dst`` a
+    contiguous tensor written in full; ``src`` a contiguous tensor (or None) copied to its front; the rest filled by
+    ``fill`` in ("const", "tile", "div", "mod", "ramp") with integer parameters a, b, c (see include/segger_amd.h);
+    ``add`` (integer segments only) is added to every copied / tile-replicated element."""
+    lib = _lib.load()
+    n = len(segments)
+    arr = (_lib.StageSeg * n)()
+    for i, seg in enumerate(segments):
+        dst, src, fill, a, b, c = seg[:6]
+        add = int(seg[6]) if len(seg) > 6 else 0
+        if add and dst.is_floating_point():
+            raise TypeError(f"stage: segment {i}: `add` is for integer segments")
+        if not dst.is_contiguous() or (src is not None and not src.is_contiguous()):
+            raise ValueError("stage: tensors must be contiguous")
+        n_copy = 0 if src is None else int(src.numel())
+        g = arr[i]
+        g.dst, g.src = dst.data_ptr(), (src.data_ptr() if src is not None and src.numel() else None)
+        g.n_copy, g.n_total = n_copy, int(dst.numel())
+        g.a, g.b, g.c = int(a), int(b), int(c)
+        g.dst_bytes, g.src_bytes = dst.element_size(), (src.element_size() if src is not None else dst.element_size())
+        g.fill = _FILLS[fill]
+        g.copy_add = add
+        if n_copy > g.n_total:
+            raise ValueError(f"stage: segment {i}: source longer than destination")
+        if src is not None and src.is_floating_point() != dst.is_floating_point():
+            raise TypeError(f"stage: segment {i}: no conversion between float and integer")
+        if dst.is_floating_point() and src is not None and src.dtype != dst.dtype:
+            raise TypeError(f"stage: segment {i}: float segments copy bit patterns, dtypes must agree")
+    with _lib.on_device(device):
+        rc = lib.segger_stage(arr, n, _lib.stream_ptr(device))
+    _lib.check(rc, "segger_stage")

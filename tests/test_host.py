@@ -461,3 +461,32 @@ def test_cli_default_widths_never_leave_the_hand_written_gemms():
     assert ops.vendor_gemm_calls == {("projection y = x W^T", 96, 192, "bfloat16"): 2}
     assert not ops.linear_supported(96, 192, torch.bfloat16)
     ops.vendor_gemm_calls.clear()
+
+
+OPS_SWITCHES = ("_FWD_PAIR", "_BWD_PAIR", "_CONTRIB_MIN_EDGES", "ONE_LAUNCH_LOSS_HEAD", "LOSS_HEAD_ONE_LAUNCH_MAX_ROWS",
+                "USE_ANCHOR_ROWS", "POS_POLY_F32", "FUSED_WGRAD_DX", "FUSED_GELU_GATE", "F32_SPLIT", "F32_GATE_EPILOGUE",
+                "F32_SPLIT_WGRAD", "LINEAR_PAIR", "WGRAD_PAIR", "FUSED_POSMLP_BWD", "EMBED_LINEAR_ONE_NODE",
+                "EMBED_LINEAR_MAX_GENES")
+
+
+def test_ops_route_switches_live_in_the_package_only():
+    """The route switches are attributes of the package segger_amd.ops and no submodule binds one of them: the submodules
+    read ``ops.NAME`` when called, so ``ops.NAME = value`` (a test's monkeypatch, a tool's A/B flag) reaches every route
+    instead of silently leaving a copy in force.  Every ``ops.NAME`` that bench.py and __graft_entry__.py use resolves, to
+    an operator and not to a submodule of the same name, and the shared mutable state is one object."""
+    import importlib
+    import pkgutil
+    from segger_amd import ops
+    subs = [importlib.import_module(f"segger_amd.ops.{m.name}") for m in pkgutil.iter_modules(ops.__path__)]
+    assert len(subs) >= 2
+    for name in OPS_SWITCHES:
+        assert hasattr(ops, name), name
+        for mod in subs:
+            assert name not in vars(mod), f"{mod.__name__} binds its own {name}"
+    for fn in ("bench.py", "__graft_entry__.py"):
+        src = open(os.path.join(ROOT, fn)).read()
+        for name in sorted(set(re.findall(r"(?<![\w.])ops\.([A-Za-z_]\w*)", src))):      # (not torch.ops.*)
+            assert hasattr(ops, name), f"{fn} uses ops.{name}"
+            assert getattr(ops, name) not in subs, f"{fn}: ops.{name} is a submodule, not the operator"
+    assert ops.vendor_gemm_calls is vars(ops._common)["vendor_gemm_calls"]
+    assert ops._PACKS is vars(ops.packs)["_PACKS"] and ops._TICKETS is vars(ops.heads)["_TICKETS"]

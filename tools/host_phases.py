@@ -38,20 +38,30 @@ def timed(name, fn):
     return w
 
 
-for k, v in list(vars(ops).items()):
-    if isinstance(v, type) and issubclass(v, torch.autograd.Function) and v is not torch.autograd.Function:
-        v.forward = staticmethod(timed(f"{k}.forward", v.forward))
-        v.backward = staticmethod(timed(f"{k}.backward", v.backward))
+# the autograd Functions and functions live in the submodules of segger_amd.ops; a function is wrapped in every namespace that
+# holds it (its own submodule, siblings that import it, the package), so calls from inside the package are timed as well
+submodules = [m for n, m in sorted(sys.modules.items()) if n.startswith("segger_amd.ops.")]
+nodes = {}
+for mod in submodules:
+    for k, v in vars(mod).items():
+        if isinstance(v, type) and issubclass(v, torch.autograd.Function) and v is not torch.autograd.Function:
+            nodes[k] = v
+for k, v in nodes.items():
+    v.forward = staticmethod(timed(f"{k}.forward", v.forward))
+    v.backward = staticmethod(timed(f"{k}.backward", v.backward))
 for name in ("adam_step", "_refresh_stale_packs", "stage", "triplet_sample", "sample_negatives", "dropout_bits_many", "step_advance",
              "rows_by_id", "segment_minmax"):
-    setattr(ops, name, timed(name, getattr(ops, name)))
+    fn = timed(name, next(vars(m)[name] for m in submodules if name in vars(m)))
+    for mod in submodules + [ops]:
+        if name in vars(mod):
+            setattr(mod, name, fn)
 
 # PROFILE_FN=_HeteroGatLayer.backward : cProfile INSIDE that function (on whichever thread runs it), printed at the end
 prof = None
 if os.environ.get("PROFILE_FN"):
     import cProfile, pstats, io
     cname, mname = os.environ["PROFILE_FN"].split(".")
-    cls = getattr(ops, cname)
+    cls = nodes[cname]
     inner = getattr(cls, mname)
     prof = cProfile.Profile()
 
