@@ -19,7 +19,7 @@ segmented reduction.
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -27,7 +27,7 @@ from torch.nn import Embedding, Linear, Module, ModuleDict, ModuleList, Paramete
 from torch.nn import functional as F
 
 from . import ops
-from .graph import EdgeGraph, edge_graph
+from .graph import EdgeCSR, EdgeGraph, edge_graph
 from .hetero import TX_BD, TX_TX, EdgeType
 
 GAT_DROPOUT = 0.2          # ist_encoder.py:116,123
@@ -58,7 +58,12 @@ def sinusoidal_embedding(x: Tensor, dim: int, max_period: float = 1000) -> Tenso
     return emb
 
 
-FUSED_POSMLP = True      # default of Positional2dEmbedder.fused (tools flip it for A/B runs)
+class PosEmbedding(NamedTuple):
+    """The embedder's result.  ``pre``: the value before the GELU where ``out`` = gelu(pre) is a constant for autograd and the
+    gradient arrives for ``pre`` (as ``ops.posmlp(return_pre=True)``: the consumer, ``ops.embed_linear``, applies gelu')."""
+    out: Tensor
+    pre: Optional[Tensor]
+    gelu_applied: bool
 
 
 class Positional2dEmbedder(Module):
@@ -73,7 +78,6 @@ class Positional2dEmbedder(Module):
             Linear(self.dim, self.dim, bias=True),
         )
         self.frequency_embedding_size = frequency_embedding_size
-        self.fused = FUSED_POSMLP    # one-kernel route (ops.posmlp) where it applies; False: posfreq + linear + SiLU + linear
 
     @staticmethod
     def normalize(pos: Tensor, batch: Optional[Tensor], num_graphs: Optional[int] = None) -> Tensor:
@@ -88,12 +92,19 @@ class Positional2dEmbedder(Module):
         return (pos - lo) / (hi - lo + 1e-8)                # ist_encoder.py:74
 
     def forward(self, pos: Tensor, batch: Optional[Tensor] = None, *, num_graphs: Optional[int] = None,
-                dtype: torch.dtype = torch.float32, gelu: bool = False, return_pre: bool = False, minmax=None):
+                dtype: torch.dtype = torch.float32) -> Tensor:
+        return self._embed(pos, batch, num_graphs, dtype).out
+
+    def _embed(self, pos: Tensor, batch: Optional[Tensor], num_graphs: Optional[int], dtype: torch.dtype, *,
+               gelu: bool = False, want_pre: bool = False, minmax=None) -> PosEmbedding:
         """``gelu`` (not in the reference): also apply the GELU that ISTEncoder puts on its concatenated input;
-        ``return_pre`` (with ``gelu``): ``(gelu(h), h)`` as ``ops.posmlp`` documents it, or ``(gelu(h), None)`` on the
-        routes that keep the GELU in autograd."""
-        n = pos.shape[0]
-        fd = self.frequency_embedding_size
+        ``want_pre`` (with ``gelu``): hand the GELU's derivative to the consumer (``PosEmbedding.pre``) on the routes that
+        can; the others keep the GELU in autograd and return ``pre = None``."""
+        n, fd, l0, l2 = pos.shape[0], self.frequency_embedding_size, self.mlp[0], self.mlp[2]
+        biased = l0.bias is not None and l2.bias is not None
+        f32_node = dtype == torch.float32 and ops.F32_GATE_EPILOGUE and biased
+        want_pre = want_pre and gelu
+        node = None          # fp32 storage: the MLP (+ the GELU that follows) behind one autograd node
         if (batch is not None or pos.is_cuda) and fd % 16 == 0:
             # fused: per-graph min/max (one pass) -> normalise + sinusoid written straight in `dtype`
             # (no batch vector = one graph, and the reference normalises it WITHOUT the epsilon, ist_encoder.py:62-64)
@@ -102,61 +113,56 @@ class Positional2dEmbedder(Module):
                 num_graphs = 1
             elif num_graphs is None:
                 num_graphs = int(batch.max()) + 1 if batch.numel() else 0
-            l0, l2 = self.mlp[0], self.mlp[2]
-            use_fused = (self.fused and pos.is_cuda and l0.bias is not None and l2.bias is not None
-                         and ops.posmlp_supported(fd, self.dim, dtype))
             # (the fused kernel and posfreq only look up the graphs of existing nodes: no (0, 0) fix-up for empty ones)
             mins, maxs = ops.segment_minmax(pos, batch, num_graphs, keep_empty=True, out=minmax)
-            if use_fused:
+            if ops.FUSED_POSMLP and pos.is_cuda and biased and ops.posmlp_supported(fd, self.dim, dtype):
                 # sinusoid + Linear + SiLU + Linear in one kernel: the [2n, 256] feature matrix is generated in
                 # registers (and stored once for the weight gradient when training) instead of written and re-read
-                return ops.posmlp(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias, dtype,
-                                  eps=eps_n, max_period=10000.0, gelu=gelu, return_pre=return_pre and gelu)
-            if (dtype == torch.float32 and ops.F32_GATE_EPILOGUE and l0.bias is not None and l2.bias is not None
-                    and ops.pos_poly_mlp_f32_supported(pos, l0.weight, l2.weight)):
-                # fp32 storage: the first Linear as a polynomial of the normalised coordinate (no feature matrix, no K = 256
-                # GEMM: csrc/posenc_poly.hip), SiLU and the 64-wide second Linear (+ the GELU that follows) behind one node
-                if gelu and return_pre:
-                    h, gh = ops.pos_poly_mlp_f32(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias, eps=eps_n,
-                                                 max_period=10000.0, gelu_out=True)
-                    return gh.reshape(n, -1), h.reshape(n, -1)
-                h = ops.pos_poly_mlp_f32(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias, eps=eps_n,
-                                         max_period=10000.0).reshape(n, -1)
-                return F.gelu(h) if gelu else h
-            freq = ops.posfreq(pos, batch, mins, maxs, fd, dtype, eps=eps_n, max_period=10000.0)
+                r = ops.posmlp(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias, dtype,
+                               eps=eps_n, max_period=10000.0, gelu=gelu, return_pre=want_pre)
+                return PosEmbedding(r[0], r[1], True) if want_pre else PosEmbedding(r, None, gelu)
+            if f32_node and ops.pos_poly_mlp_f32_supported(pos, l0.weight, l2.weight):
+                # the first Linear as a polynomial of the normalised coordinate (no feature matrix, no K = 256 GEMM:
+                # csrc/posenc_poly.hip), SiLU and the 64-wide second Linear
+                node = lambda **kw: ops.pos_poly_mlp_f32(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias,
+                                                         eps=eps_n, max_period=10000.0, **kw)
+            else:
+                freq = ops.posfreq(pos, batch, mins, maxs, fd, dtype, eps=eps_n, max_period=10000.0)
         else:
             pos = self.normalize(pos, batch, num_graphs)
             freq = sinusoidal_embedding(pos.flatten(), fd, max_period=10000).reshape(n, 2, fd).to(dtype)
-        l0, l2 = self.mlp[0], self.mlp[2]
-        flat = freq.reshape(-1, fd)
-        if (dtype == torch.float32 and ops.F32_GATE_EPILOGUE and l0.bias is not None and l2.bias is not None
-                and ops.mlp_silu_f32_supported(flat, l0.weight, l2.weight)):
-            # fp32 storage: the MLP as one autograd node (SiLU, and the GELU that follows, in the GEMMs' epilogues; SiLU's
-            # derivative in the data-gradient GEMM's epilogue)
-            if gelu and return_pre:
-                h, gh = ops.mlp_silu_f32(flat, l0.weight, l0.bias, l2.weight, l2.bias, gelu_out=True)
-                return gh.reshape(n, -1), h.reshape(n, -1)
-            h = ops.mlp_silu_f32(flat, l0.weight, l0.bias, l2.weight, l2.bias).reshape(n, -1)
+        if node is None:
+            flat = freq.reshape(-1, fd)
+            if f32_node and ops.mlp_silu_f32_supported(flat, l0.weight, l2.weight):
+                # SiLU in the GEMMs' epilogues, its derivative in the data-gradient GEMM's epilogue
+                node = lambda **kw: ops.mlp_silu_f32(flat, l0.weight, l0.bias, l2.weight, l2.bias, **kw)
+        if node is not None and want_pre:
+            h, gh = node(gelu_out=True)
+            return PosEmbedding(gh.reshape(n, -1), h.reshape(n, -1), True)
+        if node is not None:
+            h = node().reshape(n, -1)
         else:
-            h = F.silu(ops.linear(freq, l0.weight, l0.bias))
-            h = ops.linear(h, l2.weight, l2.bias).flatten(-2)
-        if gelu and return_pre:
-            if dtype == torch.float32 and h.is_cuda and ops.F32_GATE_EPILOGUE:
-                # as ops.posmlp documents it: gelu(h) is a constant for autograd and the gradient arrives for h -- the consumer
-                # (ops.embed_linear) applies gelu'(h) in the epilogue of its data-gradient GEMM instead of a gelu_backward pass
-                return F.gelu(h).detach(), h
-            return F.gelu(h), None
-        return F.gelu(h) if gelu else h
+            h = ops.linear(F.silu(ops.linear(freq, l0.weight, l0.bias)), l2.weight, l2.bias).flatten(-2)
+        if want_pre and dtype == torch.float32 and h.is_cuda and ops.F32_GATE_EPILOGUE:
+            # gelu'(h) in the epilogue of the consumer's data-gradient GEMM instead of a gelu_backward pass
+            return PosEmbedding(F.gelu(h).detach(), h, True)
+        return PosEmbedding(F.gelu(h) if gelu else h, None, gelu)
+
+
+def _pair_node_applies(emb: "Positional2dEmbedder", on_gpu: bool, batched: bool, dtype: torch.dtype) -> bool:
+    """``ops.posmlp_pair`` covers: the fused 16-bit embedder on the GPU, batch vectors + a graph count, training."""
+    l0, l2 = emb.mlp[0], emb.mlp[2]
+    return bool(ops.POS_PAIR_NODE and ops.FUSED_POSMLP and on_gpu and emb.frequency_embedding_size % 16 == 0 and batched
+                and ops.posmlp_pair_supported(l0.weight, l0.bias, l2.weight, l2.bias, dtype))
 
 
 def _pair_node(emb: "Positional2dEmbedder", pos_a, batch_a, pos_b, batch_b, num_graphs, dtype):
     """``((gelu(pe_a), pe_a), pe_b)`` from ONE autograd node (``ops.posmlp_pair``), or None where that route does not
     apply -- then the caller embeds each node type by its own call."""
-    fd = emb.frequency_embedding_size
-    l0, l2 = emb.mlp[0], emb.mlp[2]
-    if not (POS_PAIR_NODE and emb.fused and pos_a.is_cuda and fd % 16 == 0 and batch_a is not None and batch_b is not None
-            and num_graphs is not None and ops.posmlp_pair_supported(l0.weight, l0.bias, l2.weight, l2.bias, dtype)):
+    batched = batch_a is not None and batch_b is not None and num_graphs is not None
+    if not _pair_node_applies(emb, pos_a.is_cuda, batched, dtype):
         return None
+    l0, l2 = emb.mlp[0], emb.mlp[2]
     mm_a = ops.segment_minmax(pos_a, batch_a, num_graphs, keep_empty=True)
     mm_b = ops.segment_minmax(pos_b, batch_b, num_graphs, keep_empty=True)
     return ops.posmlp_pair(pos_a, batch_a, mm_a[0], mm_a[1], pos_b, batch_b, mm_b[0], mm_b[1], l0.weight, l0.bias, l2.weight,
@@ -184,9 +190,50 @@ class _SplitRows(torch.autograd.Function):
         return torch.cat((ga, gb), 0), None
 
 
-MERGED_POS_EMBED = True     # one embedder call for both node types (tools flip it for A/B runs)
-FRONT_JOIN = True           # ... and one gather / concat / GELU launch for both (ops.front_join); False: per type, torch on 'bd'
-POS_PAIR_NODE = True        # large batches (one embedder call per type): both calls behind one autograd node (ops.posmlp_pair)
+class FrontPlan(NamedTuple):
+    """The route of a step's input stage, decided by :meth:`ISTEncoder.front_plan` before anything is launched."""
+    positional: bool = False   # positions are embedded at all
+    table: bool = False        # transcripts through the gene-table kernels (embed_gelu / front_join / embed_linear), not torch
+    split: bool = False        # first layer as per-gene table + positional GEMM: x_tx stays an ops.EmbedInput
+    join: bool = False         # ops.front_join assembles the inputs: both node types when `merged`, else the boundaries
+    merged: bool = False       # one embedder call for both node types
+    pair_node: bool = False    # one embedder call per type, both behind one autograd node (ops.posmlp_pair)
+
+
+class PosPair(NamedTuple):
+    """Both node types' positional embeddings: ``joint`` (un-split [n_tx + n_bd, D], for ``ops.front_join``) or ``tx`` / ``bd``.
+    ``tx_pre`` as ``PosEmbedding.pre``; ``bd_gelu_applied``: else whoever concatenates ``bd`` owes the GELU of ist_encoder.py:320."""
+    tx: Optional[Tensor] = None
+    tx_pre: Optional[Tensor] = None
+    bd: Optional[Tensor] = None
+    joint: Optional[Tensor] = None
+    bd_gelu_applied: bool = False
+
+
+class StagedInputs(NamedTuple):
+    """What a captured step (train_step_graph.py) prepared in its static buffers instead of the forward."""
+    by_gene: Optional[EdgeCSR] = None        # rows grouped by gene id (:func:`rows_by_gene`)
+    pos_all: Optional[Tensor] = None         # positions of both node types, concatenated
+    batch_all: Optional[Tensor] = None       # ... and their graph ids (the boundaries' offset by num_graphs)
+    minmax: Optional[tuple] = None           # where the per-graph minima / maxima go
+    draws: Optional[tuple] = None            # (dropout bit planes | None, constant added to every seed): ops.step_draws
+
+
+def rows_by_gene(ids: Tensor, n_genes: int, cache: Optional[dict], staged: Optional[EdgeCSR] = None) -> EdgeCSR:
+    """``ops.rows_by_id`` of a batch's gene ids (one sort): the view a captured step staged; else the one kept by the store
+    that batches of a resident partition share across epochs (tiles.TilePartition: ``cache["persistent"]``) or, without
+    such a store, by the batch's own cache -- built when missing or when it belongs to other rows."""
+    if staged is not None:
+        return staged
+    keep, key = cache, ("by_gene", ids.data_ptr(), int(ids.shape[0]))
+    if cache is not None and cache.get("persistent") is not None:
+        keep, key = cache["persistent"], "tx_by_gene"
+    hit = keep.get(key) if keep is not None else None
+    if hit is None or hit.n_rows != n_genes or hit.n_edges != ids.shape[0]:
+        hit = ops.rows_by_id(ids, n_genes)
+        if keep is not None:
+            keep[key] = hit
+    return hit
 
 
 class GATv2Conv(Module):
@@ -217,7 +264,6 @@ class GATv2Conv(Module):
     def forward(self, x: Tuple[Tensor, Tensor], graph: EdgeGraph, *, apply_gelu: bool = False, seed: int = 0,
                 return_attention_weights: bool = False):
         x_src, x_dst = x
-        dt = x_src.dtype
         xl = ops.linear(x_src, self.lin_l.weight, self.lin_l.bias)
         xr = ops.linear(x_dst, self.lin_r.weight, self.lin_r.bias)
         p = self.dropout if self.training else 0.0
@@ -269,7 +315,6 @@ class SkipGAT(Module):
                                      validate="deferred")
                       for et in (TX_TX, TX_BD)}
         tt, tb = self.conv[TX_TX], self.conv[TX_BD]
-        dt = x_tx.dtype
         # one fused projection for the three linear maps that read x_tx (stacked and cast once per optimizer step)
         w_tx, b_tx = (tt.lin_l.weight, tt.lin_r.weight, tb.lin_l.weight), (tt.lin_l.bias, tt.lin_r.bias, tb.lin_l.bias)
         if isinstance(x_tx, ops.EmbedInput):
@@ -337,14 +382,6 @@ class ISTEncoder(Module):
                             normalize_embeddings=normalize_embeddings,
                             use_positional_embeddings=use_positional_embeddings)
         self.in_channels, self.n_heads = in_channels, n_heads
-        # 16-bit compute: first-layer projections as per-gene table + positional GEMM (ops.embed_linear); its ~15 extra
-        # tiny launches (table GEMM, weight slices) only pay for themselves on large batches
-        self.split_first_layer = True
-        self.split_first_layer_min_rows = 200_000
-        # fp32 storage: the un-split first layer is a K = 256 GEMM on the exact-fp32 MFMA pipe (157 TFLOP/s) forward, backward
-        # and for its weight gradient -- 0.6 ms of the captured 1M-edge step's 2.4 (profiles/r06_small_batch_step_f32_*.txt) --
-        # while the split form's K = 128 shapes run on the bf16x3 kernels: worth it from far fewer rows
-        self.split_first_layer_min_rows_f32 = 4_096
         self.lin_first = ModuleDict({"tx": Embedding(n_genes, in_channels)})
         if bd_in_channels is not None:
             self.lin_first["bd"] = Linear(bd_in_channels, in_channels)
@@ -408,118 +445,98 @@ class ISTEncoder(Module):
         p = self.conv_layers[0].conv[TX_TX].dropout
         return self.planes_of(views, ops.dropout_bits_many([(c, sd) for _, _, c, sd in views], self.n_heads, p, step))
 
-    def _pos_embed_pair(self, pos_dict, batch_dict, num_graphs, dt, gelu: bool, graphs, joint: bool = False,
-                        bd_plain: bool = False):
-        """(pe_tx, pe_bd, None, plain): ``pos_emb`` of both node types (``plain``: pe_bd comes without the GELU), in one call where the batch vectors allow it.  With ``gelu``
-        pe_tx is the pair ``(gelu(h), h or None)`` of ``Positional2dEmbedder.forward(return_pre=True)``.  ``joint``: when
-        the two types were embedded by one call (and ``gelu`` is off), return ``(None, None, pe)`` instead, ``pe`` the
-        un-split [n_tx + n_bd, D] matrix (for :func:`ops.front_join`).  ``bd_plain``: with one call per type, the
-        boundaries' embedding comes WITHOUT the GELU whatever ``gelu`` says (``ops.front_join`` applies it)."""
-        b_tx, b_bd = batch_dict.get("tx"), batch_dict.get("bd")
-        staged = graphs.get("pos_all") if graphs is not None else None
-        # (large batches -- the `split` route -- keep one call per type: there the launches do not matter, and joining
-        # the two gradients of the embedder's output would copy a [n_tx, D] matrix)
-        if staged is None and (not MERGED_POS_EMBED or gelu or b_tx is None or b_bd is None or num_graphs is None):
-            if gelu and bd_plain:
-                # one call per type, ONE autograd node: the embedder's parameters receive one gradient (16-bit fused route)
-                both = _pair_node(self.pos_emb, pos_dict["tx"], b_tx, pos_dict["bd"], b_bd, num_graphs, dt)
-                if both is not None:
-                    return both[0], both[1], None, True
-            one = lambda k, g=gelu, **kw: self.pos_emb(pos_dict[k], batch_dict.get(k), num_graphs=num_graphs, dtype=dt,
-                                                       gelu=g, **kw)
-            return (one("tx", return_pre=True) if gelu else one("tx")), one("bd", gelu and not bd_plain), None, bd_plain or not gelu
-        if staged is not None:                               # a captured step stages the concatenation itself
-            pos_all, batch_all = staged
+    def front_plan(self, n_tx: int, *, on_gpu: bool, batched: bool, staged_pos: bool = False) -> FrontPlan:
+        """The input stage's route for ``n_tx`` transcripts, from shapes, dtypes, grad mode and the switches of ``ops``: nothing
+        is launched.  ``batched``: both node types have a batch vector and the graph count is known; ``staged_pos``: the
+        caller (a captured step) concatenated the two types' positions itself."""
+        if not self.use_positional_embeddings:
+            return FrontPlan()
+        dt = self.compute_dtype
+        table = self.in_channels % 32 == 0 and self.lin_first["tx"].weight.dtype == torch.float32
+        split = False
+        if table and ops.SPLIT_FIRST_LAYER and on_gpu:
+            first = self.conv_layers[0].conv
+            m_first = sum(int(w.shape[0]) for w in (first[TX_TX].lin_l.weight, first[TX_TX].lin_r.weight,
+                                                    first[TX_BD].lin_l.weight))
+            min_rows = ops.SPLIT_FIRST_LAYER_MIN_ROWS_F32 if dt == torch.float32 else ops.SPLIT_FIRST_LAYER_MIN_ROWS
+            split = n_tx >= min_rows and ops.embed_linear_supported(self.in_channels, m_first, dt)
+        join = table and ops.FRONT_JOIN
+        # ONE embedder call for both node types (the reference calls it per type, ist_encoder.py:314-318): graph ids
+        # of the boundaries are offset by num_graphs, so the per-graph min / max stay per type.  Half the launches
+        # of the front end, and the embedder's parameters receive ONE gradient each (what lets a captured step
+        # postpone its partial sums, ops.deferred_reductions).  `split` (large batches) keeps one call per type: the
+        # launches do not matter there, and joining the two gradients of the embedder's output would copy [n_tx, D].
+        merged = staged_pos or (ops.MERGED_POS_EMBED and not split and batched)
+        pair_node = split and join and not merged and _pair_node_applies(self.pos_emb, on_gpu, batched, dt)
+        return FrontPlan(True, table, split, join, merged, pair_node)
+
+    def _pos_embed_pair(self, plan: FrontPlan, pos_dict, batch_dict, num_graphs, staged: StagedInputs) -> PosPair:
+        """``pos_emb`` of both node types as ``plan`` says.  `split`: the GELU of ist_encoder.py:320 comes applied to the
+        transcripts' half (gelu(cat(a, b)) = cat(gelu(a), gelu(b))), and to the boundaries' unless ``ops.front_join``
+        applies it (``plan.join`` with one call per type)."""
+        dt, emb = self.compute_dtype, self.pos_emb
+        if plan.pair_node:
+            (act, pre), pe_bd = _pair_node(emb, pos_dict["tx"], batch_dict["tx"], pos_dict["bd"], batch_dict["bd"], num_graphs, dt)
+            return PosPair(act, pre, pe_bd)
+        if not plan.merged:
+            tx = emb._embed(pos_dict["tx"], batch_dict.get("tx"), num_graphs, dt, gelu=plan.split, want_pre=True)
+            bd = emb._embed(pos_dict["bd"], batch_dict.get("bd"), num_graphs, dt, gelu=plan.split and not plan.join)
+            return PosPair(tx.out, tx.pre, bd.out, None, bd.gelu_applied)
+        if staged.pos_all is not None:
+            pos_all, batch_all = staged.pos_all, staged.batch_all
         else:
             pos_all = torch.cat((pos_dict["tx"].float(), pos_dict["bd"].float()), 0)
-            batch_all = torch.cat((b_tx.long(), b_bd.long() + int(num_graphs)), 0)
-        pe = self.pos_emb(pos_all, batch_all, num_graphs=2 * int(num_graphs), dtype=dt, gelu=gelu,
-                          minmax=graphs.get("minmax") if graphs is not None else None)
-        if joint and not gelu:
-            return None, None, pe, True
-        pe_tx, pe_bd = _SplitRows.apply(pe, int(pos_dict["tx"].shape[0]))
-        return ((pe_tx, None) if gelu else pe_tx), pe_bd, None, not gelu
+            batch_all = torch.cat((batch_dict["tx"].long(), batch_dict["bd"].long() + int(num_graphs)), 0)
+        pe = emb._embed(pos_all, batch_all, 2 * int(num_graphs), dt, gelu=plan.split, minmax=staged.minmax)
+        if plan.join and not plan.split:
+            return PosPair(joint=pe.out)
+        pe_tx, pe_bd = _SplitRows.apply(pe.out, int(pos_dict["tx"].shape[0]))
+        return PosPair(pe_tx, None, pe_bd, None, pe.gelu_applied)
 
     def _materialize_bd(self, d_in: int, device) -> None:
         if "bd" not in self.lin_first:
             self.lin_first["bd"] = Linear(d_in, self.in_channels).to(device)
 
+    def _front_end(self, x_dict, pos_dict, batch_dict, num_graphs, cache, staged: StagedInputs) -> Dict[str, Tensor]:
+        """The layers' input (ist_encoder.py:312-320): ``gelu(cat(lin_first(x), pos_emb(pos)))`` per node type."""
+        dt = self.compute_dtype
+        self._materialize_bd(x_dict["bd"].shape[-1], x_dict["bd"].device)
+        bd_lin, emb, ids = self.lin_first["bd"], self.lin_first["tx"], x_dict["tx"]
+        x_bd = ops.linear(x_dict["bd"].to(dt), bd_lin.weight, bd_lin.bias)
+        batched = batch_dict.get("tx") is not None and batch_dict.get("bd") is not None and num_graphs is not None
+        plan = self.front_plan(int(ids.shape[0]), on_gpu=x_bd.is_cuda, batched=batched, staged_pos=staged.pos_all is not None)
+        if not plan.positional:
+            return {"bd": F.gelu(x_bd), "tx": F.gelu(emb(ids.long()).to(dt))}
+        pe = self._pos_embed_pair(plan, pos_dict, batch_dict, num_graphs, staged)
+        if pe.joint is None:
+            if pe.bd_gelu_applied:
+                x_bd = torch.cat((F.gelu(x_bd), pe.bd), -1)
+            elif plan.join:      # the boundary side alone through the join (no transcript rows, no table gradient)
+                _, x_bd = ops.front_join(emb.weight.detach(), ids[:0], x_bd, pe.bd, None)
+            else:
+                x_bd = F.gelu(torch.cat((x_bd, pe.bd), -1))
+        if not plan.table:
+            return {"tx": F.gelu(torch.cat((emb(ids.long()).to(dt), pe.tx), -1)), "bd": x_bd}
+        # gather + concat + GELU in one kernel; its table gradient sums over rows grouped by gene id: one sort per
+        # batch (not needed without grad), cached with the batch or staged
+        need = staged.by_gene is not None or (torch.is_grad_enabled() and emb.weight.requires_grad)
+        by_gene = rows_by_gene(ids, emb.weight.shape[0], cache, staged.by_gene) if need else None
+        if pe.joint is not None:
+            # both node types in one launch, and back in one (no torch cat + GELU on 'bd', no cat of the two slices' gradients)
+            x_tx, x_bd = ops.front_join(emb.weight, ids, x_bd, pe.joint, by_gene)
+        elif plan.split:
+            # keep gelu(cat(E[g], pe)) as its parts: the first layer projects it as T[g] + W_pe gelu(pe)
+            x_tx = ops.EmbedInput(emb.weight, ids.to(torch.int32).contiguous(), pe.tx, by_gene, pe.tx_pre)
+        else:
+            x_tx = ops.embed_gelu(emb.weight, ids, pe.tx, by_gene)
+        return {"tx": x_tx, "bd": x_bd}
+
     def forward(self, x_dict: Dict[str, Tensor], edge_index_dict: Dict[EdgeType, Tensor],
                 pos_dict: Dict[str, Tensor], batch_dict: Dict[str, Tensor], *,
                 num_graphs: Optional[int] = None, cache: Optional[dict] = None,
-                graphs: Optional[Dict[EdgeType, EdgeGraph]] = None) -> Dict[str, Tensor]:
-        dt = self.compute_dtype
-        self._materialize_bd(x_dict["bd"].shape[-1], x_dict["bd"].device)
-        bd_lin = self.lin_first["bd"]
-        emb = self.lin_first["tx"]
-        x_bd = ops.linear(x_dict["bd"].to(dt), bd_lin.weight, bd_lin.bias)
-        if self.use_positional_embeddings:
-            fused_tx = self.in_channels % 32 == 0 and emb.weight.dtype == torch.float32
-            split = False
-            if fused_tx:
-                first = self.conv_layers[0].conv
-                m_first = sum(int(w.shape[0]) for w in (first[TX_TX].lin_l.weight, first[TX_TX].lin_r.weight,
-                                                        first[TX_BD].lin_l.weight))
-                probe = ops.EmbedInput(emb.weight, x_dict["tx"], x_bd[:0, : self.in_channels], None)
-                split = (self.split_first_layer
-                         and x_dict["tx"].shape[0] >= (self.split_first_layer_min_rows_f32 if dt == torch.float32
-                                                       else self.split_first_layer_min_rows)
-                         and ops.embed_linear_supported(probe, m_first))
-            # ONE embedder call for both node types (the reference calls it per type, ist_encoder.py:314-318): graph ids
-            # of the boundaries are offset by num_graphs, so the per-graph min / max stay per type.  Half the launches
-            # of the front end, and the embedder's parameters receive ONE gradient each (what lets a captured step
-            # postpone its partial sums, ops.deferred_reductions).  `split`: the GELU of ist_encoder.py:320 comes
-            # applied (gelu(cat(a, b)) = cat(gelu(a), gelu(b))).
-            join = fused_tx and FRONT_JOIN
-            pe_tx, pe_bd, pe_all, bd_plain = self._pos_embed_pair(pos_dict, batch_dict, num_graphs, dt, split, graphs,
-                                                                  joint=join, bd_plain=join)
-            pre_tx = None
-            if split:
-                pe_tx, pre_tx = pe_tx
-            if pe_all is None and join and bd_plain and pe_bd.dtype == x_bd.dtype:
-                # one embedder call per type: the boundary side alone through the join (no transcript rows, no table gradient)
-                _, x_bd = ops.front_join(emb.weight.detach(), x_dict["tx"][:0], x_bd, pe_bd, None)
-            elif pe_all is None:
-                # `bd_plain`: pe_bd came back WITHOUT its GELU (the join applies it), whatever `split` says for the
-                # transcripts -- keyed on the flag the embedder returned, not on `split` (ist_encoder.py:320)
-                gelu_on_pe = bd_plain or not split
-                x_bd = F.gelu(torch.cat((x_bd, pe_bd), -1)) if gelu_on_pe else torch.cat((F.gelu(x_bd), pe_bd), -1)
-            if fused_tx:
-                # gather + concat + GELU in one kernel; its table gradient sums over rows grouped by gene id: one
-                # sort per batch (not needed without grad), cached with the batch or supplied with `graphs`
-                ids = x_dict["tx"]
-                by_gene = graphs.get("tx_by_gene") if graphs is not None else None
-                if by_gene is None and torch.is_grad_enabled() and emb.weight.requires_grad:
-                    # batches of a resident partition keep what depends on the tile set only across epochs
-                    # (tiles.TilePartition: cache["persistent"], shared with the captured step's staging)
-                    store = cache.get("persistent") if cache is not None else None
-                    if store is not None:
-                        by_gene = store.get("tx_by_gene")
-                        if by_gene is None or by_gene.n_rows != emb.weight.shape[0] or by_gene.n_edges != ids.shape[0]:
-                            by_gene = store["tx_by_gene"] = ops.rows_by_id(ids, emb.weight.shape[0])
-                    else:
-                        key = ("by_gene", ids.data_ptr(), int(ids.shape[0]))
-                        by_gene = cache.get(key) if cache is not None else None
-                        if by_gene is None:
-                            by_gene = ops.rows_by_id(ids, emb.weight.shape[0])
-                            if cache is not None:
-                                cache[key] = by_gene
-                if pe_all is not None:
-                    # both node types: gather / concat / GELU in one launch, and back in one (the boundary side's torch cat +
-                    # GELU + their backward, and the full-size cat joining the two slices' gradients of the embedder's output)
-                    x_tx, x_bd = ops.front_join(emb.weight, ids, x_bd, pe_all, by_gene)
-                elif split:
-                    # keep gelu(cat(E[g], pe)) as its parts: the first layer projects it as T[g] + W_pe gelu(pe)
-                    x_tx = ops.EmbedInput(emb.weight, ids.to(torch.int32).contiguous(), pe_tx, by_gene, pre_tx)
-                else:
-                    x_tx = ops.embed_gelu(emb.weight, ids, pe_tx, by_gene)
-            else:
-                x_tx = F.gelu(torch.cat((emb(x_dict["tx"].long()).to(dt), pe_tx), -1))
-        else:
-            x_bd = F.gelu(x_bd)
-            x_tx = F.gelu(emb(x_dict["tx"].long()).to(dt))
-        x = {"tx": x_tx, "bd": x_bd}
-
+                graphs: Optional[Dict[EdgeType, EdgeGraph]] = None,
+                staged: StagedInputs = StagedInputs()) -> Dict[str, Tensor]:
+        x = self._front_end(x_dict, pos_dict, batch_dict, num_graphs, cache, staged)
         if graphs is None:       # sorted views of the edge stores: built once per batch, shared by all layers
             # the by-source view only serves the backward: inference sorts each edge store once, not twice
             # tx-belongs-bd: a transcript lies in at most one boundary (heterodata.py:147), so its backward needs no
@@ -529,13 +546,11 @@ class ISTEncoder(Module):
                                      need_by_src=by_src[et],
                                      validate="deferred")     # checked without a host sync (graph.py)
                       for et in (TX_TX, TX_BD) if et in edge_index_dict}
-        step = self._step_dev
-        seed_off = 0
-        drawn = graphs.get("draws") if self.training else None
-        if drawn is not None:
+        planes, step, seed_off = None, self._step_dev, 0
+        if self.training and staged.draws is not None:
             # a captured step made all of its draws up front in one launch (ops.step_draws) from the counter as it stands
             # and advances it at its end: (planes | None, constant added to every seed)
-            planes, seed_off = drawn
+            planes, seed_off = staged.draws
         elif self.training:
             # every training forward gets its own snapshot of the advanced counter: its backward re-reads THAT word,
             # so a second forward before the first backward (two views, checkpointing, a logging pass) cannot change
@@ -545,8 +560,7 @@ class ISTEncoder(Module):
             else:
                 self._step_dev.add_(256)
                 step = self._step_dev.clone()
-        if drawn is None:
-            planes = self._dropout_planes(graphs, step) if self.training else None
+            planes = self._dropout_planes(graphs, step)
         for li, layer in enumerate(self.conv_layers):
             kb = None if planes is None else {et: (d[li], None if s_ is None else s_[li]) for et, (d, s_) in planes.items()}
             x = layer(x, edge_index_dict, graphs=graphs, apply_gelu=True, seed=(li, step, seed_off), keep_bits=kb)   # conv + GELU (:324-325)

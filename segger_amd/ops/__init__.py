@@ -67,8 +67,25 @@ WGRAD_PAIR = True
 POS_POLY_F32 = True
 # False = the embedder's backward as three kernels, round 2 (tests/test_gpu_heads.py, tools/bench_posmlp_bwd.py)
 FUSED_POSMLP_BWD = True
+# the one-kernel embedder (ops.posmlp) where it applies; False: posfreq + linear + SiLU + linear (tests/test_gpu_model.py)
+FUSED_POSMLP = True
 
-# Encoder front end (frontend.py)
+# Encoder front end (frontend.py; ist_encoder.py reads them when it plans a step's input stage, ISTEncoder.front_plan)
+# one embedder call for both node types (tests/test_host.py)
+MERGED_POS_EMBED = True
+# ... and one gather / concat / GELU launch for both (ops.front_join); False: per type, torch on 'bd' (tests/test_gpu_heads.py)
+FRONT_JOIN = True
+# large batches (one embedder call per type): both calls behind one autograd node (ops.posmlp_pair; tests/test_host.py)
+POS_PAIR_NODE = True
+# first-layer projections as per-gene table + positional GEMM (ops.embed_linear); its ~15 extra tiny launches (table GEMM,
+# weight slices) only pay for themselves on large batches: from this many transcript rows on at 16-bit compute
+# (tests/test_gpu_model.py)
+SPLIT_FIRST_LAYER = True
+SPLIT_FIRST_LAYER_MIN_ROWS = 200_000
+# fp32 storage: the un-split first layer is a K = 256 GEMM on the exact-fp32 MFMA pipe (157 TFLOP/s) forward, backward
+# and for its weight gradient -- 0.6 ms of the captured 1M-edge step's 2.4 (profiles/r06_small_batch_step_f32_*.txt) --
+# while the split form's K = 128 shapes run on the bf16x3 kernels: worth it from far fewer rows
+SPLIT_FIRST_LAYER_MIN_ROWS_F32 = 4_096
 # False = the table and its gradients through torch ops around _RowBiasLinear (tests/test_gpu_model.py)
 EMBED_LINEAR_ONE_NODE = True
 # the one-node first layer for panels of up to this many genes; larger ones take the torch-composed route

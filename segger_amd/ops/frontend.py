@@ -91,11 +91,10 @@ class _RowBiasLinear(torch.autograd.Function):
         return gc, gw, gt, None, None, None
 
 
-def embed_linear_supported(x: "EmbedInput", m_out: int) -> bool:
-    k = int(x.act_pe.shape[1])
-    return (x.act_pe.is_cuda and x.table.dtype == torch.float32 and m_out % 4 == 0 and k in (64, 128)
-            and linear_supported(k, m_out, x.dtype)
-            and linear_supported(m_out, k, x.dtype) and linear_wgrad_supported(m_out, k, x.dtype))
+def embed_linear_supported(k: int, m_out: int, dtype: torch.dtype) -> bool:
+    """The widths :func:`embed_linear` covers on the GPU: positional half ``k`` -> ``m_out`` (asked before any tensor exists)."""
+    return (m_out % 4 == 0 and k in (64, 128) and linear_supported(k, m_out, dtype)
+            and linear_supported(m_out, k, dtype) and linear_wgrad_supported(m_out, k, dtype))
 
 
 def _gene_table_args(table, weights, biases, dt):

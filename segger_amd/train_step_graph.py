@@ -44,6 +44,7 @@ from torch import Tensor
 from . import ops
 from .graph import EdgeCSR, EdgeGraph, batch_cache, edge_graph, padded_view_segments
 from .hetero import TX_BD, TX_TX
+from .ist_encoder import StagedInputs, rows_by_gene
 
 
 def step_bucket(batch, granularity: float = 1.06, floor: int = 256) -> Dict[str, int]:
@@ -218,9 +219,7 @@ class GraphedTrainStep:
                                   bd["mask"] & (bd["cluster"] >= 0), cache)
         if "weight" not in ix_bd:
             ix_bd["weight"] = ix_bd["mask"].float() / _masked_count(ix_bd["mask"])
-        by_gene = keep.get("tx_by_gene")
-        if by_gene is None:
-            by_gene = keep["tx_by_gene"] = ops.rows_by_id(tx["x"], self.n_genes)
+        by_gene = rows_by_gene(tx["x"], self.n_genes, cache)
         ei = batch[TX_BD].edge_index
         of_tx = keep.get("sg_of_tx")
         if of_tx is None:
@@ -302,8 +301,8 @@ class GraphedTrainStep:
         lit, enc, s = self.lit, self.lit.model, self.sizes
         nt = s["tx"]
         tx, bd = self.nodes["tx"], self.nodes["bd"]
-        graphs = {TX_TX: self.g_tt, TX_BD: self.g_tb, "tx_by_gene": self.by_gene,
-                  "pos_all": (self.pos_all, self.batch_all), "minmax": self.minmax}
+        graphs = {TX_TX: self.g_tt, TX_BD: self.g_tb}
+        staged = StagedInputs(self.by_gene, self.pos_all, self.batch_all, self.minmax)
         fixed = self.draws
         drawn = None
         self._late = (0, False)
@@ -323,14 +322,14 @@ class GraphedTrainStep:
                 [(c, sd) for _, _, c, sd in views] if views else [], enc.n_heads, p_drop,
                 [(self.ix_tx, 0x7478 + inc), (self.ix_bd, 0x6264 + inc)], (self.sg_pos, 0, self.n_bd, 0x7367 + inc),
                 enc._step_dev, advance=adv)
-            graphs["draws"] = (enc.planes_of(views, planes) if views else None, inc)
+            staged = staged._replace(draws=(enc.planes_of(views, planes) if views else None, inc))
             drawn = (samples, dst_neg)
             self._late = (inc, adv is not None)
         z = torch.func.functional_call(
             enc, self._alias,
             ({"tx": tx["x"], "bd": bd["x"]}, {TX_TX: None, TX_BD: None}, {"tx": tx["pos"], "bd": bd["pos"]},
              {"tx": tx["batch"], "bd": bd["batch"]}),
-            dict(num_graphs=s["graphs"], graphs=graphs))
+            dict(num_graphs=s["graphs"], graphs=graphs, staged=staged))
         step = enc._step_dev                                  # advanced by the forward: a fresh stream per replay
         # the three losses on the staged sampler indices and their weighted sum as one autograd node (ops.loss_head):
         # means are taken over the padded rows by the kernels and rescaled to the masked real ones by `head_a`

@@ -866,13 +866,13 @@ def test_front_join_autograd(cuda, dtype, n_bd):
 def test_encoder_front_join_equals_the_per_type_route(cuda, dtype, monkeypatch):
     """ISTEncoder with ops.front_join (default) against the per-type route (embed_gelu on 'tx', torch cat + GELU on 'bd'):
     same embeddings and parameter gradients up to the rounding of one GELU implementation against the other."""
-    from segger_amd import ist_encoder as IE
+    from segger_amd import ops
     from segger_amd.synthetic import SyntheticSpec
     from tests.test_gpu_model import build
     spec = SyntheticSpec(n_tx=9000, n_bd=260, k_tx=6, seed=5)
     out = {}
     for on in (True, False):
-        monkeypatch.setattr(IE, "FRONT_JOIN", on)
+        monkeypatch.setattr(ops, "FRONT_JOIN", on)
         m, _, bcpu, _ = build(spec, cuda, dtype=dtype)
         m.eval()
         bg = bcpu.to(cuda)

@@ -59,7 +59,7 @@ def test_encoder_without_positional_embeddings_and_normalisation(oracle, cuda):
 
 
 @pytest.mark.parametrize("front_end", ["fused", "fused+split", "unfused"])
-def test_encoder_bf16_close_to_oracle_and_auroc(oracle, cuda, front_end):
+def test_encoder_bf16_close_to_oracle_and_auroc(oracle, cuda, front_end, monkeypatch):
     """bf16 compute against the float32 oracle through each front-end route: the one-kernel positional embedder
     (default), plus the first layer as per-gene table + positional GEMM (default from 200k rows up), and the
     reference's op sequence (posfreq + linear + SiLU + linear, concatenated input)."""
@@ -67,9 +67,10 @@ def test_encoder_bf16_close_to_oracle_and_auroc(oracle, cuda, front_end):
     spec = SyntheticSpec(n_tx=20000, n_bd=400, k_tx=15, seed=7)
     m, sd, b, aux = build(spec, cuda, dtype=torch.bfloat16)
     m.eval()
-    m.model.pos_emb.fused = front_end != "unfused"
-    m.model.split_first_layer = front_end == "fused+split"
-    m.model.split_first_layer_min_rows = 0
+    from segger_amd import ops
+    monkeypatch.setattr(ops, "FUSED_POSMLP", front_end != "unfused")
+    monkeypatch.setattr(ops, "SPLIT_FIRST_LAYER", front_end == "fused+split")
+    monkeypatch.setattr(ops, "SPLIT_FIRST_LAYER_MIN_ROWS", 0)
     z = m(b.to(cuda))
     z_ref = oracle.ist_encoder_forward({k: v.float() for k, v in sd.items()}, b.x_dict, b.edge_index_dict,
                                        b.pos_dict, b.batch_dict, n_heads=2)
@@ -421,7 +422,7 @@ def test_c2_scale_backward_properties(cuda):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
-def test_split_first_layer_projection_matches_concatenated_input(cuda, dtype):
+def test_split_first_layer_projection_matches_concatenated_input(cuda, dtype, monkeypatch):
     """16-bit compute keeps gelu(cat(E[g], pe)) as its parts and projects it as  T[g] + W_pe gelu(pe)  (per-gene table
     + a GEMM over the positional half, ops.embed_linear): same embeddings and same parameter gradients as the route
     that materialises the concatenated input, up to the rounding of a 16-bit activation."""
@@ -429,11 +430,12 @@ def test_split_first_layer_projection_matches_concatenated_input(cuda, dtype):
     spec = SyntheticSpec(n_tx=6000, n_bd=200, k_tx=7, seed=47)
     m, _, b, _ = build(spec, cuda, dtype=dtype)
     m.eval()                                                   # no dropout: the two routes must agree deterministically
-    m.model.split_first_layer_min_rows = 0                    # (the default reserves the split for large batches)
+    from segger_amd import ops
+    monkeypatch.setattr(ops, "SPLIT_FIRST_LAYER_MIN_ROWS", 0)  # (the default reserves the split for large batches)
     bg = b.to(cuda)
     out = {}
     for split in (True, False):
-        m.model.split_first_layer = split
+        monkeypatch.setattr(ops, "SPLIT_FIRST_LAYER", split)
         m.zero_grad(set_to_none=True)
         z = m(bg)
         (z["tx"].float().square().sum() * 0.3 + z["bd"].float().sum()).backward()
@@ -448,8 +450,7 @@ def test_split_first_layer_projection_matches_concatenated_input(cuda, dtype):
         assert (out[True][2][k] - g).abs().max().item() <= rel * g.abs().max().item() + 2e-3 * rel * gmax, k
     # the split route hands the GELU derivative of the positional half to the projection's backward kernel
     # (ops.FUSED_GELU_GATE): same gradients as with the derivative as an elementwise pass of its own
-    from segger_amd import ops
-    m.model.split_first_layer = True
+    monkeypatch.setattr(ops, "SPLIT_FIRST_LAYER", True)
     ops.FUSED_GELU_GATE = False
     try:
         m.zero_grad(set_to_none=True)
@@ -527,7 +528,7 @@ def test_first_layer_table_route_one_node_equals_the_torch_composed_route(cuda, 
         real = ops._EmbedLinear.apply
         monkeypatch.setattr(ops._EmbedLinear, "apply", staticmethod(lambda *a, **k: (calls.append(1), real(*a, **k))[1]))
         m, _, bcpu, _ = build(spec, cuda, dtype=dtype)
-        m.model.split_first_layer_min_rows = 0            # take the large-batch route on this small tile
+        monkeypatch.setattr(ops, "SPLIT_FIRST_LAYER_MIN_ROWS", 0)   # take the large-batch route on this small tile
         m.eval()
         bg = bcpu.to(cuda)
         z = m(bg)

@@ -348,12 +348,70 @@ def test_embedder_pair_route_declines_what_it_does_not_cover():
     pos_a, pos_b = torch.rand(10, 2), torch.rand(4, 2)
     ba, bb = torch.zeros(10, dtype=torch.int64), torch.zeros(4, dtype=torch.int64)
     assert ie._pair_node(emb, pos_a, ba, pos_b, bb, 1, torch.bfloat16) is None          # CPU tensors
-    assert ie.POS_PAIR_NODE is True
     from segger_amd import ops
+    assert ops.POS_PAIR_NODE is True
     l0, l2 = emb.mlp[0], emb.mlp[2]
     assert not ops.posmlp_pair_supported(l0.weight, l0.bias, l2.weight, l2.bias, torch.float32)
     with torch.no_grad():
         assert not ops.posmlp_pair_supported(l0.weight, l0.bias, l2.weight, l2.bias, torch.bfloat16)
+
+
+def test_front_plan_truth_table(monkeypatch):
+    """``ISTEncoder.front_plan``: the input stage's route from shapes, dtypes, grad mode and the ``ops`` switches alone (no
+    launch, no GPU).  Expected values: the conditions of the encoder as it stood before the plan existed -- table: width a
+    multiple of 32 and an fp32 embedding; split: table, on the GPU, rows >= 200 000 (fp32: 4 096), widths covered; join:
+    table and FRONT_JOIN; merged: staged positions, or MERGED_POS_EMBED and not split and batch vectors + graph count;
+    pair_node: split and join and not merged and the fused 16-bit embedder with something to differentiate."""
+    import torch
+    from segger_amd import ops
+    from segger_amd.ist_encoder import FrontPlan, ISTEncoder
+
+    def enc(dtype, **kw):
+        kw.setdefault("in_channels", 128)
+        return ISTEncoder(256, hidden_channels=64, out_channels=64, n_heads=2, bd_in_channels=128, compute_dtype=dtype, **kw)
+
+    def plan(e, n_tx, on_gpu=True, batched=True, **kw):
+        return e.front_plan(n_tx, on_gpu=on_gpu, batched=batched, **kw)
+
+    P = lambda **kw: FrontPlan(positional=True, **kw)
+    bf, f32 = enc(torch.bfloat16), enc(torch.float32)
+    big = P(table=True, split=True, join=True, pair_node=True)
+    small = P(table=True, join=True, merged=True)
+    assert plan(bf, 1_000_000) == big
+    assert plan(bf, 200_000) == big and plan(bf, 199_999) == small
+    assert plan(bf, 9_000) == small
+    assert plan(f32, 9_000) == P(table=True, split=True, join=True)                # fp32 threshold: 4 096 rows
+    assert plan(f32, 4_096).split and not plan(f32, 4_095).split
+    assert plan(f32, 1_000) == small
+    assert plan(f32, 1_000_000) == P(table=True, split=True, join=True)            # (the one-node pair is 16-bit)
+    for n in (9_000, 1_000_000):
+        assert plan(enc(torch.bfloat16, in_channels=48), n) == P(merged=True)      # no table, no join, nothing to split
+        assert plan(enc(torch.bfloat16, use_positional_embeddings=False), n) == FrontPlan()
+        # no batch vector for a node type, or no graph count: one call per type, each its own node
+        assert plan(bf, n, batched=False) == (big if n > 9_000 else small)._replace(merged=False, pair_node=False)
+        # a captured step concatenated the positions itself: one call, split or not
+        assert plan(bf, n, staged_pos=True) == (big if n > 9_000 else small)._replace(merged=True, pair_node=False)
+    assert plan(bf, 1_000_000, on_gpu=False) == P(table=True, join=True, merged=True)    # the table GEMMs are GPU kernels
+    with torch.no_grad():
+        assert plan(bf, 1_000_000) == big._replace(pair_node=False)                # nothing to differentiate
+        assert plan(bf, 9_000) == small
+    # each switch off in turn: its field off, and what hangs on that field with it
+    off = {"FUSED_POSMLP": (big._replace(pair_node=False), small),
+           "MERGED_POS_EMBED": (big, small._replace(merged=False)),
+           "FRONT_JOIN": (big._replace(join=False, pair_node=False), small._replace(join=False)),
+           "POS_PAIR_NODE": (big._replace(pair_node=False), small),
+           "SPLIT_FIRST_LAYER": (small, small)}
+    for name, (at_big, at_small) in off.items():
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, name, False)
+            assert plan(bf, 1_000_000) == at_big, name
+            assert plan(bf, 9_000) == at_small, name
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "SPLIT_FIRST_LAYER_MIN_ROWS", 0)
+        assert plan(bf, 9_000) == big and plan(f32, 1_000) == small
+        mp.setattr(ops, "SPLIT_FIRST_LAYER_MIN_ROWS_F32", 0)
+        assert plan(f32, 1_000) == P(table=True, split=True, join=True)
+    assert plan(bf, 1_000_000) == big
 
 
 def _load_bench():
@@ -466,7 +524,8 @@ def test_cli_default_widths_never_leave_the_hand_written_gemms():
 OPS_SWITCHES = ("_FWD_PAIR", "_BWD_PAIR", "_CONTRIB_MIN_EDGES", "ONE_LAUNCH_LOSS_HEAD", "LOSS_HEAD_ONE_LAUNCH_MAX_ROWS",
                 "USE_ANCHOR_ROWS", "POS_POLY_F32", "FUSED_WGRAD_DX", "FUSED_GELU_GATE", "F32_SPLIT", "F32_GATE_EPILOGUE",
                 "F32_SPLIT_WGRAD", "LINEAR_PAIR", "WGRAD_PAIR", "FUSED_POSMLP_BWD", "EMBED_LINEAR_ONE_NODE",
-                "EMBED_LINEAR_MAX_GENES")
+                "EMBED_LINEAR_MAX_GENES", "FUSED_POSMLP", "MERGED_POS_EMBED", "FRONT_JOIN", "POS_PAIR_NODE",
+                "SPLIT_FIRST_LAYER", "SPLIT_FIRST_LAYER_MIN_ROWS", "SPLIT_FIRST_LAYER_MIN_ROWS_F32")
 
 
 def test_ops_route_switches_live_in_the_package_only():
@@ -479,9 +538,10 @@ def test_ops_route_switches_live_in_the_package_only():
     from segger_amd import ops
     subs = [importlib.import_module(f"segger_amd.ops.{m.name}") for m in pkgutil.iter_modules(ops.__path__)]
     assert len(subs) >= 2
+    readers = subs + [importlib.import_module("segger_amd.ist_encoder")]
     for name in OPS_SWITCHES:
         assert hasattr(ops, name), name
-        for mod in subs:
+        for mod in readers:
             assert name not in vars(mod), f"{mod.__name__} binds its own {name}"
     for fn in ("bench.py", "__graft_entry__.py"):
         src = open(os.path.join(ROOT, fn)).read()
