@@ -181,6 +181,9 @@ class FrontJoinArgs(C.Structure):
     ]
 
 
+LOSS_HEAD_DEFER_FINISH = 1     # SEGGER_LOSS_HEAD_DEFER_FINISH, a bit of LossHeadArgs.reserved_
+
+
 class LossHeadArgs(C.Structure):
     _fields_ = [
         ("z_tx", vp), ("ld_ztx", C.c_int64), ("n_tx", C.c_int64),

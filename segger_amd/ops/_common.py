@@ -25,6 +25,18 @@ def _rows(t: Tensor, width: int, name: str) -> Tuple[int, int]:
     return t.data_ptr(), max(width, st[0])
 
 
+def _tag_prenorm(z: Tensor, y: Tensor, eps: float) -> Tensor:
+    """Leaves on ``z = l2_normalize(y, eps)`` what it was normalised from (ops.loss_head may differentiate through y directly)."""
+    if torch.is_grad_enabled() and y.requires_grad:
+        z._segger_prenorm = (y, float(eps))
+    return z
+
+
+def _prenorm_of(z: Tensor):
+    """``(y, eps)`` as :func:`_tag_prenorm` left it on ``z``, or None."""
+    return getattr(z, "_segger_prenorm", None)
+
+
 @functools.lru_cache(maxsize=None)
 def _has_specialised(heads: int, channels: int) -> bool:
     return bool(_lib.load().segger_gatv2_has_specialised(heads, channels))

@@ -10,7 +10,7 @@ from .. import _lib
 from .._lib import DTYPE_CODE
 from ..graph import EdgeCSR
 from .. import ops                # route switches: read as ops.NAME when called, never bound here
-from ._common import _rows, _vendor_gemm
+from ._common import _rows, _tag_prenorm, _vendor_gemm
 from .packs import f32_split_planes
 from .linear import (linear_f32_gate_launch, linear_f32_gate_supported, linear_f32_split_launch,
                      linear_f32_split_supported, linear_fwd_launch, linear_supported, linear_wgrad_dx_gate_supported,
@@ -471,21 +471,13 @@ def l2_normalize_many(ys: dict, eps: float = 1e-12) -> dict:
             and vals[0].dtype in DTYPE_CODE and all(v.shape[1] == vals[0].shape[1] and v.dtype == vals[0].dtype for v in vals)
             and all(v.shape[0] > 0 for v in vals)):
         zs = _L2NormMany.apply(float(eps), *vals)
-        out = {}
-        for k, y, z in zip(ys, vals, zs):
-            if torch.is_grad_enabled() and y.requires_grad:
-                z._segger_prenorm = (y, float(eps))
-            out[k] = z
-        return out
+        return {k: _tag_prenorm(z, y, eps) for k, y, z in zip(ys, vals, zs)}
     return {k: l2_normalize(v, eps) for k, v in ys.items()}
 
 
 def l2_normalize(y: Tensor, eps: float = 1e-12) -> Tensor:
     """F.normalize(y, dim=-1) for [n, C] with C in {8,16,32,64,128}; other widths use torch."""
     if y.dim() == 2 and y.shape[1] in (8, 16, 32, 64, 128) and y.dtype in DTYPE_CODE:
-        z = _L2Norm.apply(y, float(eps))
-        if torch.is_grad_enabled() and y.requires_grad:
-            z._segger_prenorm = (y, float(eps))      # (read by ops.loss_head, which may differentiate through y directly)
-        return z
+        return _tag_prenorm(_L2Norm.apply(y, float(eps)), y, eps)
     _lib.require_cuda(y)
     return torch.nn.functional.normalize(y.float(), dim=-1, eps=eps).to(y.dtype)

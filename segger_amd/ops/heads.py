@@ -1,5 +1,6 @@
 from __future__ import annotations
 
+from collections import namedtuple
 import ctypes as C
 from typing import Optional
 
@@ -10,7 +11,7 @@ from .. import _lib
 from .._lib import DTYPE_CODE
 from ..graph import EdgeCSR
 from .. import ops                # route switches: read as ops.NAME when called, never bound here
-from ._common import _rows
+from ._common import _prenorm_of, _rows
 
 
 # --------------------------------------------------------------------------
@@ -58,7 +59,7 @@ def edge_cos_argmax(by_src: EdgeCSR, z_src: Tensor, z_dst: Tensor, *, dst_index:
 # --------------------------------------------------------------------------
 def _triplet_args(src, pos, neg, za, zb, margin, eps, kind: str = "triplet"):
     a = _lib.TripletArgs()
-    a.loss_kind = {"triplet": 0, "bce": 1}[kind]
+    a.loss_kind = _LOSS_KIND[kind]
     a.src, a.pos, a.neg, a.n_edges = src.data_ptr(), pos.data_ptr(), neg.data_ptr(), int(src.numel())
     c = int(za.shape[1])
     a.z_a, a.ld_za = _rows(za, c, "z_a")
@@ -66,6 +67,21 @@ def _triplet_args(src, pos, neg, za, zb, margin, eps, kind: str = "triplet"):
     a.n_a, a.n_b = int(za.shape[0]), int(zb.shape[0])
     a.channels, a.dtype, a.margin, a.eps = c, DTYPE_CODE[za.dtype], margin, eps
     return a
+
+
+def _triplet_grads(a, ga, gb, scale, a_packed=False, b_packed=False, pos_groups=None, anchor_unique=False) -> None:
+    """The gradient side of a ``TripletArgs`` (``*_packed``: 16-bit atomics into a matrix of the embeddings' dtype)."""
+    a.grad_a, a.grad_a_packed, a.grad_b, a.grad_b_packed = ga.data_ptr(), int(a_packed), gb.data_ptr(), int(b_packed)
+    if pos_groups is not None:
+        a.pos_indptr, a.pos_eid = pos_groups.indptr.data_ptr(), (pos_groups.eid.data_ptr() if pos_groups.n_edges else None)
+        a.anchor_unique = int(anchor_unique)      # one walk over the groups: anchor rows stored, not added
+    a.grad_scale, a.grad_scale_dev = 1.0, scale.data_ptr()
+
+
+# ``anchors_unique`` is a bool, or a callable (``EdgeGraph.src_unique``) that may synchronise: asked in a backward only
+_anchors_unique = lambda flag: bool(flag() if callable(flag) else flag)
+# ... and the widths at which ``segger_triplet_bwd`` then takes the anchors in one walk over the groups
+_one_walk_width = lambda c: c % 32 == 0 and c <= 128
 
 
 class _TripletEdgeLoss(torch.autograd.Function):
@@ -108,27 +124,21 @@ class _TripletEdgeLoss(torch.autograd.Function):
         packed = (za.dtype in (torch.bfloat16, torch.float16) and za.shape[1] % 2 == 0
                   and src.numel() >= ops._CONTRIB_MIN_EDGES)
         ga = torch.zeros(za.shape, dtype=za.dtype if packed else torch.float32, device=dev)
-        a.grad_a, a.grad_a_packed, a.grad_b_packed = ga.data_ptr(), int(packed), int(packed and same)
-        pg = ctx.pos_groups
+        pg = None if same else ctx.pos_groups
+        uniq = False
         if same:
             gb = ga
-            a.grad_b = ga.data_ptr()
         elif pg is not None:
             # boundary side: the positives -- a boundary's ~40 edges sit next to each other and would hammer one row
             # (0.58 ms of contended fp32 atomics at C2) -- are a segmented sum over the triplets grouped by positive
             # row (for tx-belongs-bd edges: the by-destination view the encoder already built), which also WRITES
             # every row of grad_b; the uniformly sampled negatives add themselves with (uncontended) fp32 atomics
-            uniq = ctx.anchors_unique
-            uniq = bool(uniq() if callable(uniq) else uniq) and za.shape[1] % 32 == 0 and za.shape[1] <= 128
+            uniq = _anchors_unique(ctx.anchors_unique) and _one_walk_width(za.shape[1])
             gb = (torch.zeros if (uniq or ctx.kind == "bce") else torch.empty)(zb.shape, dtype=torch.float32, device=dev)
-            a.grad_b = gb.data_ptr()
-            a.pos_indptr, a.pos_eid = pg.indptr.data_ptr(), (pg.eid.data_ptr() if pg.n_edges else None)
-            a.anchor_unique = int(uniq)
         else:
             gb = torch.zeros(zb.shape, dtype=torch.float32, device=dev)
-            a.grad_b = gb.data_ptr()
         gs = g.detach().to(torch.float32).reshape(1).contiguous()   # upstream scalar stays on the device
-        a.grad_scale, a.grad_scale_dev = 1.0, gs.data_ptr()
+        _triplet_grads(a, ga, gb, gs, packed, packed and same, pg, uniq)
         with _lib.on_device(dev):
             rc = lib.segger_triplet_bwd(C.byref(a), _lib.stream_ptr(dev))
         _lib.check(rc, "segger_triplet_bwd")
@@ -164,6 +174,25 @@ def bce_edge_loss(za: Tensor, zb: Tensor, src: Tensor, pos: Tensor, neg: Tensor,
     return _TripletEdgeLoss.apply(za, zb, src, pos, neg, 0.0, 0.0, pos_groups, anchors_unique, "bce")
 
 
+# The parts of a LossHeadSpec, as its docstring describes them (``pos_groups``: the segmentation triplets grouped by positive row)
+TxTriplets = namedtuple("TxTriplets", "anchors pos neg margin eps")
+BdMetric = namedtuple("BdMetric", "pos neg d_pos d_neg weight eps")
+SgTriplets = namedtuple("SgTriplets", "src pos neg margin eps pos_groups anchors_unique", defaults=(None, False))
+# their index tensors as the kernels read them (int64 / float32, contiguous; None: not there), saved last by every node
+_Indices = namedtuple("_Indices", "bd_pos bd_neg bd_dpos bd_dneg bd_w tx_anchors tx_pos tx_neg sg_src sg_pos sg_neg",
+                      defaults=(None,) * 6)
+_LOSS_KIND = {"triplet": 0, "bce": 1}
+_i64 = lambda t: t.to(torch.int64).contiguous()
+_f32 = lambda t: t.to(torch.float32).contiguous()
+
+
+def _metric_args(z: Tensor, idx: _Indices, eps: float, name: str = "z_bd") -> tuple:
+    """The eleven leading arguments of ``segger_metric_fwd`` / ``_bwd``."""
+    n, c = z.shape
+    return (*_rows(z, c, name), n, c, DTYPE_CODE[z.dtype], idx.bd_pos.data_ptr(), idx.bd_neg.data_ptr(), idx.bd_dpos.data_ptr(),
+            idx.bd_dneg.data_ptr(), idx.bd_w.data_ptr(), float(eps))
+
+
 class _MetricLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, pos, neg, d_pos, d_neg, w, eps):
@@ -172,34 +201,26 @@ class _MetricLoss(torch.autograd.Function):
         dev = z.device
         if z.dtype not in DTYPE_CODE:
             raise TypeError("metric_loss: unsupported embedding dtype")
-        n, c = z.shape
-        zp, ld = _rows(z, c, "z")
-        pos, neg = pos.to(torch.int64).contiguous(), neg.to(torch.int64).contiguous()
-        d_pos, d_neg, w = (t.to(torch.float32).contiguous() for t in (d_pos, d_neg, w))
+        idx = _Indices(_i64(pos), _i64(neg), _f32(d_pos), _f32(d_neg), _f32(w))
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ws_bytes = lib.segger_triplet_workspace_bytes(n)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = torch.empty(lib.segger_triplet_workspace_bytes(z.shape[0]), dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            rc = lib.segger_metric_fwd(zp, ld, n, c, DTYPE_CODE[z.dtype], pos.data_ptr(), neg.data_ptr(), d_pos.data_ptr(),
-                                       d_neg.data_ptr(), w.data_ptr(), eps, loss.data_ptr(), ws.data_ptr(), ws_bytes,
+            rc = lib.segger_metric_fwd(*_metric_args(z, idx, eps, "z"), loss.data_ptr(), ws.data_ptr(), ws.numel(),
                                        _lib.stream_ptr(dev))
         _lib.check(rc, "segger_metric_fwd")
-        ctx.save_for_backward(z, pos, neg, d_pos, d_neg, w)
+        ctx.save_for_backward(z, *idx)
         ctx.eps = eps
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        z, pos, neg, d_pos, d_neg, w = ctx.saved_tensors
+        z, *idx = ctx.saved_tensors
         lib = _lib.load()
         dev = z.device
-        n, c = z.shape
-        zp, ld = _rows(z, c, "z")
-        gz = torch.zeros((n, c), dtype=torch.float32, device=dev)
+        gz = torch.zeros(z.shape, dtype=torch.float32, device=dev)
         gs = g.detach().to(torch.float32).reshape(1).contiguous()
         with _lib.on_device(dev):
-            rc = lib.segger_metric_bwd(zp, ld, n, c, DTYPE_CODE[z.dtype], pos.data_ptr(), neg.data_ptr(), d_pos.data_ptr(),
-                                       d_neg.data_ptr(), w.data_ptr(), ctx.eps, gs.data_ptr(), gz.data_ptr(),
+            rc = lib.segger_metric_bwd(*_metric_args(z, _Indices(*idx), ctx.eps, "z"), gs.data_ptr(), gz.data_ptr(),
                                        _lib.stream_ptr(dev))
         _lib.check(rc, "segger_metric_bwd")
         return gz.to(z.dtype), None, None, None, None, None, None
@@ -217,11 +238,13 @@ class LossHeadSpec:
     of z_bd); ``sg`` = (src, pos, neg, margin, eps, pos_groups | None[, anchors_unique]) of the segmentation triplets, or
     None when the batch has at most one boundary (lightning_model.py:173-175: that loss is then 0).  ``anchors_unique``
     (bool, or a callable asked in the backward, e.g. ``EdgeGraph.src_unique``): no transcript is the anchor of two
-    triplets -- the backward then walks the groups once and stores the anchors' gradient rows."""
+    triplets -- the backward then walks the groups once and stores the anchors' gradient rows.  Plain tuples, or the
+    named forms they are read as from here on (``TxTriplets``, ``BdMetric``, ``SgTriplets``)."""
 
     def __init__(self, tx, bd, sg, sg_kind: str = "triplet", tx_anchors_are_rows: bool = False, sg_of_tx=None,
-                 tx_state: Optional[Tensor] = None, grad_out_hint: Optional[Tensor] = None):
-        self.tx, self.bd, self.sg, self.sg_kind = tx, bd, sg, sg_kind      # sg_kind "bce": margin / eps unused
+                 tx_state: Optional[Tensor] = None, grad_out_hint: Optional[Tensor] = None, defer_finish: bool = False):
+        self.tx, self.bd, self.sg = TxTriplets(*tx), BdMetric(*bd), (None if sg is None else SgTriplets(*sg))
+        self.sg_kind = sg_kind                                             # "bce": margin / eps unused
         # loss_tx's anchors are arange(n_tx) (possibly with -1 positives = skipped): lets the backward STORE the anchors'
         # gradient rows (loss_head, when z_tx comes straight out of ops.l2_normalize)
         self.tx_anchors_are_rows = bool(tx_anchors_are_rows)
@@ -234,7 +257,14 @@ class LossHeadSpec:
         # one-launch head, with grad_out_hint: leave the finishing launch (the three means, the total) to the BACKWARD launch --
         # the returned loss tensor is then only valid once the backward has run (a captured training step reads it after the
         # replay); the caller promises that a backward with exactly the hinted gradient follows
-        self.defer_finish = False
+        self.defer_finish = bool(defer_finish)
+
+
+def _indices(spec: LossHeadSpec, anchors: bool = True) -> _Indices:
+    t, m, s = spec.tx, spec.bd, spec.sg
+    return _Indices(_i64(m.pos), _i64(m.neg), _f32(m.d_pos), _f32(m.d_neg), _f32(m.weight),
+                    _i64(t.anchors) if anchors else None, _i64(t.pos), _i64(t.neg),
+                    *((None,) * 3 if s is None else (_i64(s.src), _i64(s.pos), _i64(s.neg))))
 
 
 class _LossHead(torch.autograd.Function):
@@ -256,81 +286,62 @@ class _LossHead(torch.autograd.Function):
         c = int(z_tx.shape[1])
         if z_bd.shape[1] != c:
             raise ValueError("loss_head: z_tx / z_bd must have the same width")
-        a = a.detach().to(torch.float32).contiguous()
-        b = b.detach().to(torch.float32).contiguous()
-        i64 = lambda t: t.to(torch.int64).contiguous()
+        a, b = _f32(a.detach()), _f32(b.detach())
+        idx, sg = _indices(spec), spec.sg
+        nb = int(z_bd.shape[0])
         keep = []
         stream = _lib.stream_ptr(dev)
         parts = (C.c_void_p * 3)()
         counts = (C.c_int64 * 3)(0, 0, 0)
         scales = (C.c_float * 3)(0.0, 0.0, 0.0)
-        with _lib.on_device(dev):
-            anchors, pos, neg, margin, eps = spec.tx
-            tx = tuple(i64(t) for t in (anchors, pos, neg))
-            ta = _triplet_args(*tx, z_tx, z_tx, float(margin), float(eps))
+
+        def triplet_partials(k, src, pos, neg, t, zb, kind):       # loss k: per-block partial sums only, and their scale
+            ta = _triplet_args(src, pos, neg, z_tx, zb, float(t.margin), float(t.eps), kind)
             ws = torch.empty(lib.segger_triplet_workspace_bytes(ta.n_edges), dtype=torch.uint8, device=dev)
-            ta.loss, ta.workspace, ta.workspace_bytes = None, ws.data_ptr(), ws.numel()     # partial sums only
+            ta.loss, ta.workspace, ta.workspace_bytes = None, ws.data_ptr(), ws.numel()
             _lib.check(lib.segger_triplet_fwd(C.byref(ta), stream), "segger_triplet_fwd")
             keep.append(ws)
             if ta.n_edges:
-                parts[0], counts[0], scales[0] = ws.data_ptr(), lib.segger_triplet_partial_count(ta.n_edges), 1.0 / ta.n_edges
-            bpos, bneg, dp, dn, w, beps = spec.bd
-            bd = (i64(bpos), i64(bneg)) + tuple(t.to(torch.float32).contiguous() for t in (dp, dn, w))
-            nb = int(z_bd.shape[0])
-            zp, ld = _rows(z_bd, c, "z_bd")
+                parts[k], counts[k] = ws.data_ptr(), lib.segger_triplet_partial_count(ta.n_edges)
+                scales[k] = (0.5 if kind == "bce" else 1.0) / ta.n_edges
+
+        with _lib.on_device(dev):
+            triplet_partials(0, idx.tx_anchors, idx.tx_pos, idx.tx_neg, spec.tx, z_tx, "triplet")
             ws = torch.empty(lib.segger_triplet_workspace_bytes(nb), dtype=torch.uint8, device=dev)
-            _lib.check(lib.segger_metric_fwd(zp, ld, nb, c, DTYPE_CODE[dt], bd[0].data_ptr(), bd[1].data_ptr(),
-                                             bd[2].data_ptr(), bd[3].data_ptr(), bd[4].data_ptr(), float(beps),
-                                             None, ws.data_ptr(), ws.numel(), stream), "segger_metric_fwd")
+            _lib.check(lib.segger_metric_fwd(*_metric_args(z_bd, idx, spec.bd.eps), None, ws.data_ptr(), ws.numel(), stream),
+                       "segger_metric_fwd")
             keep.append(ws)
             if nb:
                 parts[1], counts[1], scales[1] = ws.data_ptr(), lib.segger_triplet_partial_count(nb), 1.0
-            sg = None
-            if spec.sg is not None:
-                src, spos, sneg, smargin, seps, pg = spec.sg[:6]
-                sg = tuple(i64(t) for t in (src, spos, sneg))
-                if pg is not None and (pg.n_rows != nb or pg.n_edges != sg[0].numel()):
+            if sg is not None:
+                if sg.pos_groups is not None and (sg.pos_groups.n_rows != nb or sg.pos_groups.n_edges != idx.sg_src.numel()):
                     raise ValueError("loss_head: pos_groups does not describe the segmentation triplets")
-                sa = _triplet_args(*sg, z_tx, z_bd, float(smargin), float(seps), spec.sg_kind)
-                ws = torch.empty(lib.segger_triplet_workspace_bytes(sa.n_edges), dtype=torch.uint8, device=dev)
-                sa.loss, sa.workspace, sa.workspace_bytes = None, ws.data_ptr(), ws.numel()
-                _lib.check(lib.segger_triplet_fwd(C.byref(sa), stream), "segger_triplet_fwd")
-                keep.append(ws)
-                if sa.n_edges:
-                    parts[2], counts[2] = ws.data_ptr(), lib.segger_triplet_partial_count(sa.n_edges)
-                    scales[2] = (0.5 if spec.sg_kind == "bce" else 1.0) / sa.n_edges
+                triplet_partials(2, idx.sg_src, idx.sg_pos, idx.sg_neg, sg, z_bd, spec.sg_kind)
             out = torch.empty(4, dtype=torch.float32, device=dev)
             # the three means from their per-block partial sums and the weighted total: one launch
             _lib.check(lib.segger_loss_combine_partials_fwd(parts, counts, scales, a.data_ptr(), b.data_ptr(), 3,
                                                             out.data_ptr(), stream), "segger_loss_combine_partials_fwd")
         ctx.keep = keep                                      # (the partial sums are read by the launch above)
-        ctx.save_for_backward(z_tx, z_bd, a, b, *tx, *bd, *(sg or ()))
+        ctx.save_for_backward(z_tx, z_bd, a, b, *idx)
         ctx.spec, ctx.y_tx, ctx.eps_tx = spec, y_tx, float(eps_tx)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        z_tx, z_bd, a, b = ctx.saved_tensors[:4]
-        tx = ctx.saved_tensors[4:7]
-        bd = ctx.saved_tensors[7:12]
-        sg = ctx.saved_tensors[12:15] if ctx.spec.sg is not None else None
-        spec = ctx.spec
+        z_tx, z_bd, a, b, *idx = ctx.saved_tensors
+        idx, spec, tx, sg = _Indices(*idx), ctx.spec, ctx.spec.tx, ctx.spec.sg
         lib = _lib.load()
         dev, dt = z_tx.device, z_tx.dtype
         c = int(z_tx.shape[1])
-        nb = int(z_bd.shape[0])
         g_out = g_out.detach().to(torch.float32).contiguous()
         graw = torch.empty(3, dtype=torch.float32, device=dev)
         # transcript rows collect a handful of terms (once as anchor of either loss, ~2 as positive / negative): packed
         # 16-bit atomics straight into a gradient of the embeddings' dtype on large batches; boundary rows sum dozens
         # of terms and stay fp32 (+ one cast)
-        packed = dt in (torch.bfloat16, torch.float16) and c % 2 == 0 and tx[0].numel() >= ops._CONTRIB_MIN_EDGES
+        packed = dt in (torch.bfloat16, torch.float16) and c % 2 == 0 and idx.tx_anchors.numel() >= ops._CONTRIB_MIN_EDGES
         y_tx = ctx.y_tx
-        pg = spec.sg[5] if spec.sg is not None else None
-        uniq = False
-        if pg is not None and len(spec.sg) > 6 and c % 32 == 0 and c <= 128:
-            uniq = spec.sg[6]
-            uniq = bool(uniq() if callable(uniq) else uniq)
+        pg = sg.pos_groups if sg is not None else None
+        uniq = pg is not None and _one_walk_width(c) and _anchors_unique(sg.anchors_unique)
         gb_written = pg is not None and not uniq and spec.sg_kind != "bce"       # (the two-kernel route writes every row)
         # both gradient matrices out of ONE zero-filled buffer (one fill launch instead of two)
         ga_dt = dt if packed else torch.float32
@@ -347,21 +358,13 @@ class _LossHead(torch.autograd.Function):
             _lib.check(lib.segger_loss_combine_bwd(g_out.data_ptr(), a.data_ptr(), b.data_ptr(), 3, graw.data_ptr(), stream),
                        "segger_loss_combine_bwd")
             if sg is not None:          # first: with pos_groups its positive side WRITES every row of gb
-                sa = _triplet_args(*sg, z_tx, z_bd, float(spec.sg[3]), float(spec.sg[4]), spec.sg_kind)
-                sa.grad_a, sa.grad_a_packed, sa.grad_b, sa.grad_b_packed = ga.data_ptr(), int(packed), gb.data_ptr(), 0
-                if pg is not None:
-                    sa.pos_indptr, sa.pos_eid = pg.indptr.data_ptr(), (pg.eid.data_ptr() if pg.n_edges else None)
-                    sa.anchor_unique = int(uniq)      # one walk over the groups: anchor rows stored, not added
-                sa.grad_scale, sa.grad_scale_dev = 1.0, graw[2:3].data_ptr()
+                sa = _triplet_args(idx.sg_src, idx.sg_pos, idx.sg_neg, z_tx, z_bd, float(sg.margin), float(sg.eps), spec.sg_kind)
+                _triplet_grads(sa, ga, gb, graw[2:3], packed, False, pg, uniq)
                 _lib.check(lib.segger_triplet_bwd(C.byref(sa), stream), "segger_triplet_bwd")
-            zp, ld = _rows(z_bd, c, "z_bd")
-            _lib.check(lib.segger_metric_bwd(zp, ld, nb, c, DTYPE_CODE[dt], bd[0].data_ptr(), bd[1].data_ptr(),
-                                             bd[2].data_ptr(), bd[3].data_ptr(), bd[4].data_ptr(), float(spec.bd[5]),
-                                             graw[1:2].data_ptr(), gb.data_ptr(), stream), "segger_metric_bwd")
-            ta = _triplet_args(*tx, z_tx, z_tx, float(spec.tx[3]), float(spec.tx[4]))
-            ta.grad_a = ta.grad_b = ga.data_ptr()
-            ta.grad_a_packed = ta.grad_b_packed = int(packed)
-            ta.grad_scale, ta.grad_scale_dev = 1.0, graw[0:1].data_ptr()
+            _lib.check(lib.segger_metric_bwd(*_metric_args(z_bd, idx, spec.bd.eps), graw[1:2].data_ptr(), gb.data_ptr(), stream),
+                       "segger_metric_bwd")
+            ta = _triplet_args(idx.tx_anchors, idx.tx_pos, idx.tx_neg, z_tx, z_tx, float(tx.margin), float(tx.eps))
+            _triplet_grads(ta, ga, ga, graw[0:1], packed, packed)
             if ga_rows is not None:
                 ta.grad_a_rows = ga_rows.data_ptr()
             _lib.check(lib.segger_triplet_bwd(C.byref(ta), stream), "segger_triplet_bwd")
@@ -399,12 +402,40 @@ def anchor_index(src: Tensor, n_rows: int) -> Tensor:
 
 
 def loss_head_fused_supported(z_tx: Tensor, z_bd: Tensor, spec: "LossHeadSpec") -> bool:
-    c = int(z_tx.shape[1])
-    n = int(z_tx.shape[0])
+    n, c = int(z_tx.shape[0]), int(z_tx.shape[1])
     return (ops.ONE_LAUNCH_LOSS_HEAD and spec.tx_anchors_are_rows and z_tx.dtype in DTYPE_CODE and z_tx.dtype == z_bd.dtype
             and bool(_lib.load().segger_loss_head_supported(c, DTYPE_CODE[z_tx.dtype])) and int(z_bd.shape[1]) == c
-            and 0 < n <= ops.LOSS_HEAD_ONE_LAUNCH_MAX_ROWS and spec.tx[0].numel() == n and z_bd.shape[0] > 0
-            and (spec.sg is None or (len(spec.sg) > 5 and spec.sg[5] is not None)))
+            and 0 < n <= ops.LOSS_HEAD_ONE_LAUNCH_MAX_ROWS and spec.tx.anchors.numel() == n and z_bd.shape[0] > 0
+            and (spec.sg is None or spec.sg.pos_groups is not None))
+
+
+# what the one-launch forward hands its backward besides the saved tensors (``out`` / ``ws``: a deferred finish completes them)
+_FusedState = namedtuple("_FusedState", "tx_w head nxt gbd graw hot_acc out ws hint deferred")
+
+
+def _loss_head_args(z_tx, z_bd, a, b, idx: _Indices, spec: LossHeadSpec, graw, ws, st: Optional[_FusedState]):
+    """The fields of ``segger_loss_head_args`` that the forward and the backward launch share (``st`` None: a forward that
+    nobody differentiates, without the backward's buffers); each direction adds its own."""
+    tx, sg = spec.tx, spec.sg
+    n_tx, c = int(z_tx.shape[0]), int(z_tx.shape[1])
+    g = _lib.LossHeadArgs()
+    g.z_tx, g.ld_ztx = _rows(z_tx, c, "z_tx")
+    g.z_bd, g.ld_zbd = _rows(z_bd, c, "z_bd")
+    g.n_tx, g.n_bd, g.channels, g.dtype = n_tx, int(z_bd.shape[0]), c, DTYPE_CODE[z_tx.dtype]
+    g.tx_pos, g.tx_neg, g.tx_margin, g.tx_eps = idx.tx_pos.data_ptr(), idx.tx_neg.data_ptr(), float(tx.margin), float(tx.eps)
+    g.bd_pos, g.bd_neg, g.bd_dpos, g.bd_dneg = (t.data_ptr() for t in (idx.bd_pos, idx.bd_neg, idx.bd_dpos, idx.bd_dneg))
+    g.bd_w, g.bd_eps = idx.bd_w.data_ptr(), float(spec.bd.eps)
+    g.sg_kind = _LOSS_KIND[spec.sg_kind]
+    if sg is not None and idx.sg_src.numel():
+        g.sg_src, g.sg_pos, g.sg_neg = idx.sg_src.data_ptr(), idx.sg_pos.data_ptr(), idx.sg_neg.data_ptr()
+        g.n_sg = int(idx.sg_src.numel())
+        g.sg_margin, g.sg_eps = float(sg.margin), float(sg.eps)
+    g.a, g.b, g.grad_raw = a.data_ptr(), b.data_ptr(), graw.data_ptr()
+    g.workspace, g.workspace_bytes, g.ticket = ws.data_ptr(), ws.numel(), _ticket(z_tx.device).data_ptr()
+    if st is not None:
+        g.tx_w, g.tx_state, g.tx_next, g.grad_bd = st.tx_w.data_ptr(), st.head.data_ptr(), st.nxt.data_ptr(), st.gbd.data_ptr()
+        g.tx_hot_id, g.tx_hot_acc = st.nxt[2 * n_tx:].data_ptr(), st.hot_acc.data_ptr()
+    return g
 
 
 class _LossHeadFused(torch.autograd.Function):
@@ -422,40 +453,17 @@ class _LossHeadFused(torch.autograd.Function):
             z_tx, z_bd = t_tx, t_bd
         _lib.require_cuda(z_tx, z_bd, a, b)
         lib = _lib.load()
-        dev, dt = z_tx.device, z_tx.dtype
+        dev = z_tx.device
         n_tx, c = int(z_tx.shape[0]), int(z_tx.shape[1])
         n_bd = int(z_bd.shape[0])
         need = any(ctx.needs_input_grad[:2])
-        a = a.detach().to(torch.float32).contiguous()
-        b = b.detach().to(torch.float32).contiguous()
-        i64 = lambda t: t.to(torch.int64).contiguous()
-        f32 = lambda t: t.to(torch.float32).contiguous()
-        _, pos, neg, margin, eps = spec.tx
-        tx = (i64(pos), i64(neg))
-        bpos, bneg, dp, dn, w, beps = spec.bd
-        bd = (i64(bpos), i64(bneg), f32(dp), f32(dn), f32(w))
-        sg = None
-        if spec.sg is not None:
-            sg = tuple(i64(t) for t in spec.sg[:3])
-        g = _lib.LossHeadArgs()
-        g.z_tx, g.ld_ztx = _rows(z_tx, c, "z_tx")
-        g.z_bd, g.ld_zbd = _rows(z_bd, c, "z_bd")
-        g.n_tx, g.n_bd, g.channels, g.dtype = n_tx, n_bd, c, DTYPE_CODE[dt]
-        g.tx_pos, g.tx_neg, g.tx_margin, g.tx_eps = tx[0].data_ptr(), tx[1].data_ptr(), float(margin), float(eps)
-        g.bd_pos, g.bd_neg, g.bd_dpos, g.bd_dneg, g.bd_w = (t.data_ptr() for t in bd)
-        g.bd_eps = float(beps)
-        g.sg_kind = {"triplet": 0, "bce": 1}[spec.sg_kind]
-        if sg is not None and sg[0].numel():
-            g.sg_src, g.sg_pos, g.sg_neg, g.n_sg = sg[0].data_ptr(), sg[1].data_ptr(), sg[2].data_ptr(), int(sg[0].numel())
-            g.sg_margin, g.sg_eps = float(spec.sg[3]), float(spec.sg[4])
-        g.a, g.b = a.data_ptr(), b.data_ptr()
+        a, b = _f32(a.detach()), _f32(b.detach())
+        idx = _indices(spec, anchors=False)          # (the anchors are the rows themselves)
+        n_sg = int(idx.sg_src.numel()) if idx.sg_src is not None else 0
         out = torch.empty(4, dtype=torch.float32, device=dev)
         graw = torch.empty(3, dtype=torch.float32, device=dev)
-        ws = torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, int(g.n_sg)), dtype=torch.uint8, device=dev)
-        g.out, g.grad_raw, g.workspace, g.workspace_bytes = out.data_ptr(), graw.data_ptr(), ws.data_ptr(), ws.numel()
-        g.ticket = _ticket(dev).data_ptr()
-        hint = spec.grad_out_hint
-        state = None
+        ws = torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, n_sg), dtype=torch.uint8, device=dev)
+        st = None
         if need:
             tx_w = torch.empty((n_tx, 2), dtype=torch.float32, device=dev)
             head = spec.tx_state
@@ -467,33 +475,28 @@ class _LossHeadFused(torch.autograd.Function):
             nxt = torch.empty(2 * n_tx + n_tx + n_hot, dtype=torch.int32, device=dev)        # chain links | hot ids + arrivals
             hot_acc = torch.empty((n_hot, c), dtype=torch.float32, device=dev)
             gbd = torch.empty((n_bd, c), dtype=torch.float32, device=dev)
-            g.tx_w, g.tx_state, g.tx_next, g.grad_bd = tx_w.data_ptr(), head.data_ptr(), nxt.data_ptr(), gbd.data_ptr()
-            g.tx_hot_id, g.tx_hot_acc = nxt[2 * n_tx:].data_ptr(), hot_acc.data_ptr()
+            hint = spec.grad_out_hint
             if hint is not None:
                 hint = hint.detach()
                 if hint.dtype != torch.float32 or hint.numel() != 4 or not hint.is_contiguous() or hint.device != dev:
                     raise ValueError("loss_head: grad_out_hint must be a contiguous float32 [4] tensor on the embeddings' device")
-                g.grad_out = hint.data_ptr()
-                if getattr(spec, "defer_finish", False):
-                    g.reserved_ = 1                      # SEGGER_LOSS_HEAD_DEFER_FINISH
-            state = (tx_w, head, nxt, gbd, graw, hot_acc, out, ws, int(g.reserved_))
+            st = _FusedState(tx_w, head, nxt, gbd, graw, hot_acc, out, ws, hint, bool(hint is not None and spec.defer_finish))
+        g = _loss_head_args(z_tx, z_bd, a, b, idx, spec, graw, ws, st)
+        g.out = out.data_ptr()
+        if st is not None and st.hint is not None:
+            g.grad_out, g.reserved_ = st.hint.data_ptr(), (_lib.LOSS_HEAD_DEFER_FINISH if st.deferred else 0)
         with _lib.on_device(dev):
             rc = lib.segger_loss_head_fwd(C.byref(g), _lib.stream_ptr(dev))
         _lib.check(rc, "segger_loss_head_fwd")
         if need:
-            ctx.save_for_backward(t_tx, t_bd, z_tx, z_bd, a, b, *tx, *bd, *(sg or ()))
-            ctx.spec, ctx.state, ctx.prenorm, ctx.eps = spec, state, prenorm, (float(eps_tx), float(eps_bd))
-            ctx.hint = hint if need else None
+            ctx.save_for_backward(t_tx, t_bd, z_tx, z_bd, a, b, *idx)
+            ctx.spec, ctx.state, ctx.prenorm, ctx.eps = spec, st, prenorm, (float(eps_tx), float(eps_bd))
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        t_tx, t_bd, z_tx, z_bd, a, b = ctx.saved_tensors[:6]
-        tx = ctx.saved_tensors[6:8]
-        bd = ctx.saved_tensors[8:13]
-        spec = ctx.spec
-        sg = ctx.saved_tensors[13:16] if spec.sg is not None else None
-        tx_w, head, nxt, gbd, graw, hot_acc, out_fwd, ws_fwd, deferred = ctx.state
+        t_tx, t_bd, z_tx, z_bd, a, b, *idx = ctx.saved_tensors
+        idx, spec, st, sg = _Indices(*idx), ctx.spec, ctx.state, ctx.spec.sg
         lib = _lib.load()
         dev, dt = z_tx.device, z_tx.dtype
         n_tx, c = int(z_tx.shape[0]), int(z_tx.shape[1])
@@ -502,115 +505,108 @@ class _LossHeadFused(torch.autograd.Function):
             # a second backward over the same graph (retain_graph=True): the forward launch zero-filled the boundary
             # gradient and armed the hot rows' accumulators / arrival counters ONCE -- re-arm them, or this pass would add
             # on top of the first one's sums and never finish a hot row
-            gbd.zero_()
-            hot_acc.zero_()
-            nxt[3 * n_tx:].zero_()
+            st.gbd.zero_()
+            st.hot_acc.zero_()
+            st.nxt[3 * n_tx:].zero_()
         ctx._ran = True
         stream = _lib.stream_ptr(dev)
         g_out = g_out.detach().to(torch.float32).contiguous()
+        hinted = st.hint is not None and g_out.data_ptr() == st.hint.data_ptr()
         # the segmentation triplets' anchor terms ride in the row walk when no transcript anchors two of them
-        pg = spec.sg[5] if spec.sg is not None else None
+        n_sg = int(idx.sg_src.numel()) if sg is not None else 0
         uniq, of_tx = False, None
-        if sg is not None and sg[0].numel():
-            uniq = spec.sg[6] if len(spec.sg) > 6 else False
-            uniq = bool(uniq() if callable(uniq) else uniq)
+        if n_sg:
+            uniq = _anchors_unique(sg.anchors_unique)
             if uniq:
                 of_tx = spec.sg_of_tx() if callable(spec.sg_of_tx) else spec.sg_of_tx
                 if of_tx is None:
-                    of_tx = anchor_index(sg[0], n_tx)
+                    of_tx = anchor_index(idx.sg_src, n_tx)
                 if of_tx.dtype != torch.int32 or of_tx.numel() < n_tx or not of_tx.is_contiguous():
                     raise ValueError("loss_head: sg_of_tx must be a contiguous int32 [n_tx] tensor")
-        fuse_norm = ctx.prenorm and (sg is None or not sg[0].numel() or uniq)
-        g = _lib.LossHeadArgs()
-        g.z_tx, g.ld_ztx = _rows(z_tx, c, "z_tx")
-        g.z_bd, g.ld_zbd = _rows(z_bd, c, "z_bd")
-        g.n_tx, g.n_bd, g.channels, g.dtype = n_tx, n_bd, c, DTYPE_CODE[dt]
-        g.tx_pos, g.tx_neg, g.tx_margin, g.tx_eps = tx[0].data_ptr(), tx[1].data_ptr(), float(spec.tx[3]), float(spec.tx[4])
-        g.bd_pos, g.bd_neg, g.bd_dpos, g.bd_dneg, g.bd_w = (t.data_ptr() for t in bd)
-        g.bd_eps = float(spec.bd[5])
-        g.sg_kind = {"triplet": 0, "bce": 1}[spec.sg_kind]
-        if sg is not None and sg[0].numel():
-            if pg.n_rows != n_bd or pg.n_edges != sg[0].numel():
+            pg = sg.pos_groups
+            if pg.n_rows != n_bd or pg.n_edges != n_sg:
                 raise ValueError("loss_head: pos_groups does not describe the segmentation triplets")
-            g.sg_src, g.sg_pos, g.sg_neg, g.n_sg = sg[0].data_ptr(), sg[1].data_ptr(), sg[2].data_ptr(), int(sg[0].numel())
-            g.sg_margin, g.sg_eps = float(spec.sg[3]), float(spec.sg[4])
+        fuse_norm = ctx.prenorm and (not n_sg or uniq)
+        out_dummy = torch.empty(4, dtype=torch.float32, device=dev)
+        if st.deferred and not hinted:
+            raise RuntimeError("loss_head: defer_finish promised a backward with the hinted gradient")
+        ws = st.ws if st.deferred else torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, n_sg), dtype=torch.uint8,
+                                                   device=dev)
+        g = _loss_head_args(z_tx, z_bd, a, b, idx, spec, st.graw, ws, st)
+        g.out = out_dummy.data_ptr()
+        if st.deferred:
+            # the forward left only its per-block partial sums: this launch finishes the losses (into the forward's output)
+            g.out, g.grad_out, g.reserved_ = st.out.data_ptr(), st.hint.data_ptr(), _lib.LOSS_HEAD_DEFER_FINISH
+        if n_sg:
             g.sg_pos_indptr, g.sg_pos_eid = pg.indptr.data_ptr(), (pg.eid.data_ptr() if pg.n_edges else None)
             g.sg_of_tx = _lib.ptr(of_tx)
-        g.a, g.b, g.grad_raw = a.data_ptr(), b.data_ptr(), graw.data_ptr()
-        out_dummy = torch.empty(4, dtype=torch.float32, device=dev)
-        g.out = out_dummy.data_ptr()
-        if deferred:
-            if ctx.hint is None or g_out.data_ptr() != ctx.hint.data_ptr():
-                raise RuntimeError("loss_head: defer_finish promised a backward with the hinted gradient")
-            # the forward left only its per-block partial sums: this launch finishes the losses (into the forward's output)
-            g.out, g.grad_out, g.reserved_ = out_fwd.data_ptr(), ctx.hint.data_ptr(), 1
-        g.tx_w, g.tx_state, g.tx_next, g.grad_bd = tx_w.data_ptr(), head.data_ptr(), nxt.data_ptr(), gbd.data_ptr()
-        g.tx_hot_id, g.tx_hot_acc = nxt[2 * n_tx:].data_ptr(), hot_acc.data_ptr()
-        ws = ws_fwd if deferred else torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, int(g.n_sg)), dtype=torch.uint8,
-                                                 device=dev)
-        g.workspace, g.workspace_bytes, g.ticket = ws.data_ptr(), ws.numel(), _ticket(dev).data_ptr()
         gtx = torch.empty((n_tx, c), dtype=dt, device=dev)
         g.grad_tx, g.ld_gtx = gtx.data_ptr(), c
         if fuse_norm:
             g.y_tx, g.ld_ytx = _rows(t_tx, c, "y_tx")
             g.norm_eps = ctx.eps[0]
         with _lib.on_device(dev):
-            if ctx.hint is None or g_out.data_ptr() != ctx.hint.data_ptr():      # (else the forward left the factors behind)
-                _lib.check(lib.segger_loss_combine_bwd(g_out.data_ptr(), a.data_ptr(), b.data_ptr(), 3, graw.data_ptr(), stream),
-                           "segger_loss_combine_bwd")
+            if not hinted:                                                       # (else the forward left the factors behind)
+                _lib.check(lib.segger_loss_combine_bwd(g_out.data_ptr(), a.data_ptr(), b.data_ptr(), 3, st.graw.data_ptr(),
+                                                       stream), "segger_loss_combine_bwd")
             _lib.check(lib.segger_loss_head_bwd(C.byref(g), stream), "segger_loss_head_bwd")
-            if sg is not None and sg[0].numel() and not uniq:
+            if n_sg and not uniq:
                 # a transcript anchors two segmentation triplets (never in segger's data): their anchor terms by atomics
                 # on top of the rows just written, the boundary side having been done by the launch above
-                sa = _triplet_args(*sg, z_tx, z_bd, float(spec.sg[3]), float(spec.sg[4]), spec.sg_kind)
+                sa = _triplet_args(idx.sg_src, idx.sg_pos, idx.sg_neg, z_tx, z_bd, float(sg.margin), float(sg.eps), spec.sg_kind)
                 scratch = torch.zeros((n_bd, c), dtype=torch.float32, device=dev)      # (its boundary side is discarded)
-                sa.grad_a, sa.grad_a_packed = gtx.data_ptr(), int(dt != torch.float32)
-                sa.grad_b, sa.grad_b_packed = scratch.data_ptr(), 0
-                sa.grad_scale, sa.grad_scale_dev = 1.0, graw[2:3].data_ptr()
+                _triplet_grads(sa, gtx, scratch, st.graw[2:3], dt != torch.float32)
                 _lib.check(lib.segger_triplet_bwd(C.byref(sa), stream), "segger_triplet_bwd")
             if ctx.prenorm:
                 # boundary side (and, in the rare case above, the transcript side) through the normalisation's backward
                 gy_bd = torch.empty((n_bd, c), dtype=dt, device=dev)
-                segs = (_lib.L2NormSeg * 2)()
-                n_seg = 0
-                yb, ldb = _rows(t_bd, c, "y_bd")
-                segs[0].y, segs[0].ld_y, segs[0].n, segs[0].out, segs[0].ld_out = yb, ldb, n_bd, gy_bd.data_ptr(), c
-                segs[0].gz, segs[0].ld_gz, segs[0].gz_f32 = gbd.data_ptr(), c, 1
-                n_seg = 1
+                todo = [(t_bd, "y_bd", gy_bd, st.gbd, 1)]
                 if not fuse_norm:
-                    gy_tx = torch.empty((n_tx, c), dtype=dt, device=dev)
-                    yt, ldt = _rows(t_tx, c, "y_tx")
-                    segs[1].y, segs[1].ld_y, segs[1].n, segs[1].out, segs[1].ld_out = yt, ldt, n_tx, gy_tx.data_ptr(), c
-                    segs[1].gz, segs[1].ld_gz, segs[1].gz_f32 = gtx.data_ptr(), c, 0
-                    n_seg = 2
-                    gtx = gy_tx
+                    gz_tx, gtx = gtx, torch.empty((n_tx, c), dtype=dt, device=dev)
+                    todo.append((t_tx, "y_tx", gtx, gz_tx, 0))
+                segs = (_lib.L2NormSeg * 2)()
+                for seg, (y, name, gy, gz, gz_f32) in zip(segs, todo):
+                    seg.y, seg.ld_y = _rows(y, c, name)
+                    seg.n, seg.out, seg.ld_out = int(y.shape[0]), gy.data_ptr(), c
+                    seg.gz, seg.ld_gz, seg.gz_f32 = gz.data_ptr(), c, gz_f32
                 # (the two eps are the same number in the encoder; the launch takes one)
-                _lib.check(lib.segger_l2norm_many(segs, n_seg, c, ctx.eps[1], DTYPE_CODE[dt], stream), "segger_l2norm_many")
+                _lib.check(lib.segger_l2norm_many(segs, len(todo), c, ctx.eps[1], DTYPE_CODE[dt], stream), "segger_l2norm_many")
                 return gtx, gy_bd, None, None, None, None, None, None, None
-        return gtx, gbd.to(dt), None, None, None, None, None, None, None
+        return gtx, st.gbd.to(dt), None, None, None, None, None, None, None
+
+
+def loss_head_route(z_tx: Tensor, z_bd: Tensor, spec: LossHeadSpec) -> str:
+    """-> "one_launch_prenorm" | "one_launch" | "anchor_rows" | "kernel_by_kernel": the route :func:`loss_head` takes."""
+    pt = _prenorm_of(z_tx)
+    if loss_head_fused_supported(z_tx, z_bd, spec):
+        pb = _prenorm_of(z_bd)
+        ok = lambda z, p: (p is not None and p[0].requires_grad and p[0].shape == z.shape and p[0].dtype == z.dtype)
+        if torch.is_grad_enabled() and ok(z_tx, pt) and ok(z_bd, pb) and pt[1] == pb[1]:
+            # both embeddings come straight out of the row normalisation: they are constants here and the gradient goes
+            # to its inputs (the transcript side's normalisation backward inside the launch)
+            return "one_launch_prenorm"
+        return "one_launch"
+    # (fp32 storage only: there loss_tx's backward is bound by 12 fp32 atomic instructions per triplet, a third of them the
+    # anchor's -- 1.19 -> 0.8 ms at C2; with 16-bit embeddings the packed atomics are cheap enough that the second matrix
+    # the normalisation backward then reads costs what the stores save: 13.40 vs 13.42 ms per step)
+    if (ops.USE_ANCHOR_ROWS and z_tx.dtype == torch.float32
+            and spec.tx_anchors_are_rows and pt is not None and pt[0].requires_grad and torch.is_grad_enabled()
+            and z_tx.shape[1] % 8 == 0 and pt[0].shape == z_tx.shape and pt[0].dtype == z_tx.dtype
+            and spec.tx.anchors.numel() == z_tx.shape[0]):
+        # z_tx is the output of ops.l2_normalize: treat it as a constant and send the gradient to its input -- the anchors'
+        # rows are then stored, not added atomically, and the normalisation backward reads the two matrices
+        return "anchor_rows"
+    return "kernel_by_kernel"
 
 
 def loss_head(z_tx: Tensor, z_bd: Tensor, a: Tensor, b: Tensor, spec: LossHeadSpec) -> Tensor:
     """-> float32[4] = (a0 * loss_tx, a1 * loss_bd, a2 * loss_sg, sum_i b_i * (the three)): the three losses of
     ``LitISTEncoder.get_losses`` and their weighted sum as one autograd node (see :class:`_LossHead`).  ``a`` / ``b``:
     float32[3] on the device."""
-    if loss_head_fused_supported(z_tx, z_bd, spec):
-        pt, pb = getattr(z_tx, "_segger_prenorm", None), getattr(z_bd, "_segger_prenorm", None)
-        ok = lambda z, p: (p is not None and p[0].requires_grad and p[0].shape == z.shape and p[0].dtype == z.dtype)
-        if torch.is_grad_enabled() and ok(z_tx, pt) and ok(z_bd, pb) and pt[1] == pb[1]:
-            # both embeddings come straight out of the row normalisation: they are constants here and the gradient goes
-            # to its inputs (the transcript side's normalisation backward inside the launch)
-            return _LossHeadFused.apply(pt[0], pb[0], a, b, spec, z_tx.detach(), z_bd.detach(), pt[1], pb[1])
-        return _LossHeadFused.apply(z_tx, z_bd, a, b, spec)
-    pre = getattr(z_tx, "_segger_prenorm", None)
-    # (fp32 storage only: there loss_tx's backward is bound by 12 fp32 atomic instructions per triplet, a third of them the
-    # anchor's -- 1.19 -> 0.8 ms at C2; with 16-bit embeddings the packed atomics are cheap enough that the second matrix
-    # the normalisation backward then reads costs what the stores save: 13.40 vs 13.42 ms per step)
-    if (ops.USE_ANCHOR_ROWS and z_tx.dtype == torch.float32
-            and spec.tx_anchors_are_rows and pre is not None and pre[0].requires_grad and torch.is_grad_enabled()
-            and z_tx.shape[1] % 8 == 0 and pre[0].shape == z_tx.shape and pre[0].dtype == z_tx.dtype
-            and spec.tx[0].numel() == z_tx.shape[0]):
-        # z_tx is the output of ops.l2_normalize: treat it as a constant and send the gradient to its input -- the anchors'
-        # rows are then stored, not added atomically, and the normalisation backward reads the two matrices
-        return _LossHead.apply(z_tx.detach(), z_bd, a, b, spec, pre[0], pre[1])
-    return _LossHead.apply(z_tx, z_bd, a, b, spec)
+    route = loss_head_route(z_tx, z_bd, spec)
+    if route == "one_launch_prenorm":
+        (y_tx, eps_tx), (y_bd, eps_bd) = _prenorm_of(z_tx), _prenorm_of(z_bd)
+        return _LossHeadFused.apply(y_tx, y_bd, a, b, spec, z_tx.detach(), z_bd.detach(), eps_tx, eps_bd)
+    if route == "anchor_rows":
+        return _LossHead.apply(z_tx.detach(), z_bd, a, b, spec, *_prenorm_of(z_tx))
+    return (_LossHeadFused if route == "one_launch" else _LossHead).apply(z_tx, z_bd, a, b, spec)

@@ -347,8 +347,8 @@ class GraphedTrainStep:
                                 (bpos, bneg, dp, dn, self.bd_weight, 1e-8),
                                 (self.sg_src, self.sg_pos, dst_neg, lit._sg_margin, 1e-6, self.g_tb.by_dst, True),
                                 sg_kind=lit._sg_loss_type, tx_anchors_are_rows=True, sg_of_tx=self.sg_of_tx,
-                                tx_state=self.tx_state, grad_out_hint=self._e_loss)
-        spec.defer_finish = DEFER_LOSS_FINISH      # the losses are read after the backward (self.out after the replay)
+                                tx_state=self.tx_state, grad_out_hint=self._e_loss,
+                                defer_finish=DEFER_LOSS_FINISH)      # the losses are read after the backward (self.out after the replay)
         out = ops.loss_head(z["tx"], z["bd"], self.head_a, self.scal[3:6], spec)
         if self.defer_sums:                                   # ~30 partial sums of the backward as one launch
             with ops.deferred_reductions(self.dev):

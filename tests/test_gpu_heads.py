@@ -193,6 +193,7 @@ def test_loss_head_anchor_rows_equal_atomic_anchors(cuda, dtype, monkeypatch):
         spec = ops.LossHeadSpec((torch.arange(n, device=cuda), pos.to(cuda), neg.to(cuda), 0.3, 1e-6),
                                 (bpos.to(cuda), bneg.to(cuda), dp.to(cuda), dn.to(cuda), w.to(cuda), 1e-8),
                                 (src.to(cuda), dst.to(cuda), dneg.to(cuda), 0.4, 1e-6, groups, True), tx_anchors_are_rows=True)
+        assert ops.loss_head_route(z, zb, spec) == ("anchor_rows" if rows and dtype == torch.float32 else "kernel_by_kernel")
         res = ops.loss_head(z, zb, a, b, spec)
         (res[3] * 1.7 + res[0]).backward()
         out[rows] = (res.detach().clone(), y.grad.clone(), zb.grad.clone())
@@ -259,6 +260,8 @@ def test_one_launch_loss_head_equals_the_kernel_by_kernel_head(cuda, dtype, C, k
                                 (src.to(cuda), dst.to(cuda), dneg.to(cuda), 0.4, 1e-6, groups, unique), sg_kind=kind,
                                 tx_anchors_are_rows=True)
         assert ops.loss_head_fused_supported(z, zb, spec) == fused
+        assert ops.loss_head_route(z, zb, spec) == {(True, True): "one_launch_prenorm", (True, False): "one_launch",
+                                                    (False, True): "anchor_rows", (False, False): "kernel_by_kernel"}[fused, prenorm]
         res = ops.loss_head(z, zb, a, b, spec)
         res.backward(gvec)
         out[fused] = (res.detach().clone(), y.grad.float().clone(), yb.grad.float().clone())
@@ -736,6 +739,7 @@ def test_one_launch_loss_head_deferred_finish(cuda, kind):
                                 (src.to(cuda), dst.to(cuda), dneg.to(cuda), 0.4, 1e-6, groups, True), sg_kind=kind,
                                 tx_anchors_are_rows=True, grad_out_hint=hint)
         spec.defer_finish = defer
+        assert ops.loss_head_route(zs["tx"], zs["bd"], spec) == "one_launch_prenorm"
         res = ops.loss_head(zs["tx"], zs["bd"], a, b, spec)
         res.backward(hint)
         out[defer] = (res.detach().clone(), y.grad.float().clone(), yb.grad.float().clone())
@@ -793,6 +797,8 @@ def test_one_launch_loss_head_hot_rows_with_zero_tx_weight(cuda, how, prenorm, m
             z, zb = y, yb
         spec = mk()
         assert ops.loss_head_fused_supported(z, zb, spec) == fused
+        assert ops.loss_head_route(z, zb, spec) == {(True, True): "one_launch_prenorm", (True, False): "one_launch",
+                                                    (False, True): "anchor_rows", (False, False): "kernel_by_kernel"}[fused, prenorm]
         res = ops.loss_head(z, zb, a, b, spec)
         poison = torch.full((y0.shape[0], y0.shape[1]), float("nan"), device=cuda)      # what torch.empty hands out next
         del poison
@@ -818,6 +824,7 @@ def test_one_launch_loss_head_backward_twice(cuda):
     zs = ops.l2_normalize_many({"tx": y, "bd": yb})
     spec = mk()
     assert ops.loss_head_fused_supported(zs["tx"], zs["bd"], spec)
+    assert ops.loss_head_route(zs["tx"], zs["bd"], spec) == "one_launch_prenorm"
     res = ops.loss_head(zs["tx"], zs["bd"], a, b, spec)
     g1 = torch.autograd.grad(res[3], (y, yb), retain_graph=True)
     poison = torch.full_like(y0.to(cuda), float("nan")); del poison

@@ -550,3 +550,52 @@ def test_ops_route_switches_live_in_the_package_only():
             assert getattr(ops, name) not in subs, f"{fn}: ops.{name} is a submodule, not the operator"
     assert ops.vendor_gemm_calls is vars(ops._common)["vendor_gemm_calls"]
     assert ops._PACKS is vars(ops.packs)["_PACKS"] and ops._TICKETS is vars(ops.heads)["_TICKETS"]
+
+
+def test_loss_head_spec_reads_plain_tuples_as_named_fields():
+    """``LossHeadSpec`` takes plain tuples (``sg`` of 6 or 7 items, or None) or the named forms, and is read by name from
+    then on; ``anchors_unique`` defaults to False and stays as given (a callable is not asked at construction);
+    ``defer_finish`` is a constructor keyword, default False, and an ordinary attribute."""
+    from segger_amd import ops
+    from segger_amd.ops.heads import BdMetric, SgTriplets, TxTriplets
+    anchors, pos, neg = torch.arange(5), torch.tensor([1, 2, -1, 0, 3]), torch.tensor([4, 3, 2, 1, 0])
+    bpos, bneg = torch.tensor([1, 0, 2]), torch.tensor([2, 2, 0])
+    dp, dn, w = torch.rand(3), torch.rand(3), torch.full((3,), 1.0 / 3)
+    src, spos, sneg, groups = torch.tensor([0, 2, 4]), torch.tensor([0, 1, 1]), torch.tensor([1, 0, 2]), object()
+    tx, bd = (anchors, pos, neg, 0.3, 1e-6), (bpos, bneg, dp, dn, w, 1e-8)
+    asked = []
+    uniq = lambda: asked.append(1) or True
+
+    def check_common(spec):
+        assert isinstance(spec.tx, TxTriplets) and isinstance(spec.bd, BdMetric)
+        assert spec.tx.anchors is anchors and spec.tx.pos is pos and spec.tx.neg is neg
+        assert (spec.tx.margin, spec.tx.eps) == (0.3, 1e-6)
+        assert spec.bd.pos is bpos and spec.bd.neg is bneg and spec.bd.d_pos is dp and spec.bd.d_neg is dn
+        assert spec.bd.weight is w and spec.bd.eps == 1e-8
+        assert spec.tx_anchors_are_rows is False and spec.sg_of_tx is None and spec.tx_state is None
+        assert spec.grad_out_hint is None
+
+    s6 = ops.LossHeadSpec(tx, bd, (src, spos, sneg, 0.4, 1e-6, groups))
+    check_common(s6)
+    assert isinstance(s6.sg, SgTriplets) and s6.sg.src is src and s6.sg.pos is spos and s6.sg.neg is sneg
+    assert (s6.sg.margin, s6.sg.eps) == (0.4, 1e-6) and s6.sg.pos_groups is groups and s6.sg.anchors_unique is False
+    assert s6.sg_kind == "triplet" and s6.defer_finish is False
+    s6n = ops.LossHeadSpec(tx, bd, (src, spos, sneg, 0.4, 1e-6, None))
+    assert s6n.sg.pos_groups is None and s6n.sg.anchors_unique is False
+    s7 = ops.LossHeadSpec(tx, bd, (src, spos, sneg, 0.4, 1e-6, groups, uniq), defer_finish=True)
+    check_common(s7)
+    assert s7.sg.pos_groups is groups and s7.sg.anchors_unique is uniq and not asked
+    assert s7.defer_finish is True
+    s7.defer_finish = False
+    assert s7.defer_finish is False
+    s7t = ops.LossHeadSpec(tx, bd, (src, spos, sneg, 0.4, 1e-6, groups, True), tx_anchors_are_rows=True)
+    assert s7t.sg.anchors_unique is True and s7t.tx_anchors_are_rows is True
+    s0 = ops.LossHeadSpec(tx, bd, None)
+    check_common(s0)
+    assert s0.sg is None and s0.defer_finish is False
+    sb = ops.LossHeadSpec(tx, bd, (src, spos, sneg, 0.0, 0.0, groups, True), sg_kind="bce", defer_finish=True)
+    check_common(sb)
+    assert sb.sg_kind == "bce" and sb.sg.pos_groups is groups and sb.defer_finish is True
+    named = ops.LossHeadSpec(TxTriplets(*tx), BdMetric(*bd), SgTriplets(src, spos, sneg, 0.4, 1e-6, pos_groups=groups))
+    check_common(named)
+    assert named.sg == s6.sg
