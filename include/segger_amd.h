@@ -43,7 +43,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SEGGER_ABI_VERSION 30
+#define SEGGER_ABI_VERSION 31
 
 enum segger_status {
   SEGGER_OK = 0,
@@ -991,6 +991,47 @@ size_t segger_knn_workspace_bytes(int64_t n_points, int32_t nx, int32_t ny);
 int segger_knn_grid(const float* points, int64_t n_points, const float* queries, int64_t n_queries, int32_t k,
                     float max_dist, float x0, float y0, float cell, int32_t nx, int32_t ny,
                     int32_t* nbr, float* dist, void* workspace, size_t workspace_bytes, segger_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Adaptive quadtree tiling of a slide: the step that decides what a tile is (the reference's default,
+ * tiling_mode="adaptive").  Replaces cuspatial.quadtree_on_points + the retry loop around its invalid trees in
+ * src/segger/geometry/quadtree.py:142-216 (get_quadtree_index), the key decoding at :56-94, and -- for point
+ * geometries -- the `intersects` join + drop_duplicates of QuadTreeTiling / Tiling.label in
+ * src/segger/data/tiling.py:152-196,198-233.
+ *
+ * Frame (the host computes it in float64, quadtree.py:33-42): origin (x0, y0), square cells of side `cell` (a power
+ * of two >= 1), 2^depth x 2^depth of them, 1 <= depth <= 15.  Cell of a point: ix = clamp(floor((double(x) - x0) / cell),
+ * 0, 2^depth - 1), iy alike; Morton key = two bits per level, x in the even bit, y in the odd bit (< 2^30).
+ * The node at depth d in 1..depth is the prefix key >> 2 (depth - d); the root is never a leaf.  A node with c > 0
+ * points is a leaf iff every proper ancestor holds more than max_size points and (c <= max_size or d == depth); empty
+ * quadrants are no leaves.  Leaves are numbered in ascending (d, prefix) order.
+ *
+ * segger_quadtree_build: points [n,2] fp32 (8-byte aligned), 1 <= n < 2^31.  Outputs, all caller-allocated:
+ *   leaf_key / leaf_depth / leaf_count [leaf_cap] int32: prefix, depth d and population of leaf i (entries from *n_leaf
+ *     on are padding: -1 / 0 / 0);
+ *   morton_lo / morton_id [leaf_cap] int32: the same leaves sorted by the first key of their range,
+ *     prefix << 2 (depth - d), with the leaf id (padding: -1 / -1) -- the table segger_quadtree_label searches;
+ *   n_leaf [1] int32: the number of leaves (read it back once per slide);
+ *   labels [n] int32: the leaf of every build point (always >= 0).
+ * Leaf capacity: the nodes split at one depth are disjoint and hold more than max_size points each, and a split turns
+ * one node into at most four, so there are at most min(n, 4 + 3 (depth - 1) floor(n / (max_size + 1))) leaves.  Allocate
+ * that; the kernels never write past leaf_cap, and *n_leaf > leaf_cap tells that the table is incomplete.
+ *
+ * segger_quadtree_label: label of arbitrary points against a built tree; -1 outside the closed root box
+ * [x0, x1] x [y0, y1] and inside empty quadrants.  Half-open by construction: a point on a shared border belongs to the
+ * upper cell (the reference's join gives it to whichever tile comes first in an unspecified order).
+ *
+ * segger_quadtree_workspace_bytes: bytes of workspace for a build (two key arrays, the radix sort's storage, the work
+ * lists), or a negative SEGGER_E* code for arguments a build would reject.
+ * ---------------------------------------------------------------------- */
+int64_t segger_quadtree_workspace_bytes(int64_t n_points, int32_t depth, int64_t max_size, int64_t leaf_cap);
+int segger_quadtree_build(const float* points, int64_t n_points, double x0, double y0, double cell, int32_t depth,
+                          int64_t max_size, int64_t leaf_cap, int32_t* leaf_key, int32_t* leaf_depth, int32_t* leaf_count,
+                          int32_t* morton_lo, int32_t* morton_id, int32_t* n_leaf, int32_t* labels, void* workspace,
+                          size_t workspace_bytes, segger_stream_t stream);
+int segger_quadtree_label(const float* points, int64_t n_points, double x0, double y0, double x1, double y1, double cell,
+                          int32_t depth, const int32_t* leaf_key, const int32_t* leaf_depth, const int32_t* morton_lo,
+                          const int32_t* morton_id, int64_t n_leaf, int32_t* labels, segger_stream_t stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

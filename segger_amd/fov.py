@@ -12,17 +12,25 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .synthetic import SyntheticSpec, fov_edges, fov_graph, fov_nodes, make_fov
-from .tiles import SquareTiling, TileBatchSampler, TilePartition, partition_by_tiling
+from .tiles import QuadTreeTiling, SquareTiling, TileBatchSampler, TilePartition, partition_by_tiling
 
 
 def build_fov_batches(spec: SyntheticSpec, device, *, tile_nodes: int = 50_000, margin: float = 10.0,
-                      edges_per_batch: int = 1_000_000, slide_csr: bool = True, keep_data: bool = False):
+                      edges_per_batch: int = 1_000_000, slide_csr: bool = True, keep_data: bool = False,
+                      tiling: str = "square"):
     """-> (partition, batches, aux, tiling[, data]).  Every rank of a data-parallel run calls this with the same seed
-    and gets the same partition and the same batch list (no data-path collective)."""
+    and gets the same partition and the same batch list (no data-path collective).  ``tiling``: "square" (one side from
+    the mean density) or "adaptive" (the reference's default: quadtree leaves of at most ``tile_nodes`` nodes, built on
+    the transcript and boundary positions stacked, data_module.py:244-252)."""
+    if tiling not in ("square", "adaptive"):
+        raise ValueError(f"tiling must be 'square' or 'adaptive', but got {tiling!r}")
     data, aux = make_fov(spec, device, return_aux=True)
-    L = 10.0 * math.sqrt(spec.n_bd)
-    side = math.sqrt(tile_nodes / (spec.n_tx / (L * L)))
-    tiling = SquareTiling(data["tx"]["pos"], side)
+    if tiling == "adaptive":
+        tiling = QuadTreeTiling(torch.cat([data["tx"]["pos"], data["bd"]["pos"]]), tile_nodes)
+    else:
+        L = 10.0 * math.sqrt(spec.n_bd)
+        side = math.sqrt(tile_nodes / (spec.n_tx / (L * L)))
+        tiling = SquareTiling(data["tx"]["pos"], side)
     part = partition_by_tiling(data, tiling, margin=margin)
     part.add_node_attr("tx", "predict_mask", torch.ones(spec.n_tx, dtype=torch.bool, device=device), permuted=True)
     if slide_csr:

@@ -61,6 +61,9 @@ def main():
     ap.add_argument("--n-bd", type=int, default=500_000)
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--tile-nodes", type=int, default=50_000, help="target transcripts per tile (data_module.py:155)")
+    ap.add_argument("--tiling", default="square", choices=["square", "adaptive"],
+                    help="square: one tile side from the mean density; adaptive: quadtree leaves of at most --tile-nodes "
+                         "nodes (the reference's default, data_module.py:152-155)")
     ap.add_argument("--edges-per-batch", type=int, default=1_000_000)
     ap.add_argument("--margin", type=float, default=10.0, help="tile margin excluded from the losses (um)")
     ap.add_argument("--train-batches", type=int, default=0, help="0 = one full epoch")
@@ -106,7 +109,8 @@ def main():
     from segger_amd.inference import GraphedPredictor, bucket_sizes
     from segger_amd.metrics import assignment_accuracy, auroc
     from segger_amd.synthetic import SyntheticSpec, make_fov
-    from segger_amd.tiles import PredictTileIndex, SquareTiling, TileBatchSampler, partition_by_tiling
+    from segger_amd.tiles import (PredictQuadTreeIndex, PredictTileIndex, QuadTreeTiling, SquareTiling, TileBatchSampler,
+                                  partition_by_tiling)
 
     DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
     times: dict = {}
@@ -119,17 +123,23 @@ def main():
     with Phase("partition_s", times):
         L = 10.0 * math.sqrt(args.n_bd)
         side = math.sqrt(args.tile_nodes / (args.n_tx / (L * L)))
-        tiling = SquareTiling(data["tx"]["pos"], side)
+        if args.tiling == "adaptive":
+            tiling = QuadTreeTiling(torch.cat([data["tx"]["pos"], data["bd"]["pos"]]), args.tile_nodes)
+            index_cls = PredictQuadTreeIndex
+        else:
+            tiling = SquareTiling(data["tx"]["pos"], side)
+            index_cls = PredictTileIndex
         part = partition_by_tiling(data, tiling, margin=args.margin)
         part.add_node_attr("tx", "predict_mask", torch.ones(args.n_tx, dtype=torch.bool, device=dev), permuted=True)
-        pti = PredictTileIndex(data, tiling, margin=args.margin) if args.overlap_predict else None
+        pti = index_cls(data, tiling, margin=args.margin) if args.overlap_predict else None
         del data
         if not args.no_slide_csr:
             part.build_csr()
         sampler = TileBatchSampler(part, args.edges_per_batch, mode="edge", skip_too_big=True)
         batches = list(sampler)
     kept = {"__".join(et): int(v.sum()) for et, v in part.edge_sizes.items()}
-    log(f"[fov] {len(tiling)} tiles of side {side:.1f} um -> {len(batches)} batches; intra-tile edges {kept}")
+    shape = f"of side {side:.1f} um" if args.tiling == "square" else f"(quadtree leaves of <= {args.tile_nodes} nodes)"
+    log(f"[fov] {len(tiling)} tiles {shape} -> {len(batches)} batches; intra-tile edges {kept}")
     torch.cuda.empty_cache()
 
     torch.manual_seed(0)
