@@ -43,7 +43,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SEGGER_ABI_VERSION 31
+#define SEGGER_ABI_VERSION 32
 
 enum segger_status {
   SEGGER_OK = 0,
@@ -1032,6 +1032,49 @@ int segger_quadtree_build(const float* points, int64_t n_points, double x0, doub
 int segger_quadtree_label(const float* points, int64_t n_points, double x0, double y0, double x1, double y1, double cell,
                           int32_t depth, const int32_t* leaf_key, const int32_t* leaf_depth, const int32_t* morton_lo,
                           const int32_t* morton_id, int64_t n_leaf, int32_t* labels, segger_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Streaming transcript -> cell assignment: the best row per transcript over the prediction batches of a slide, kept
+ * on the device batch by batch.  Replaces the concat + sort + unique of ISTSegmentationWriter.assign_transcripts_to_cells
+ * (src/segger/data/writer.py:186-190), which needs every prediction row of the slide at once.
+ *
+ * State, caller-allocated and sized by n_tx, the number of transcripts of the slide (the row_index domain,
+ * 1 <= n_tx < 2^31); the caller zeroes best_key and counters before the first update:
+ *   best_key [n_tx] uint64, 0 = "not seen";  cell [n_tx] int32;  gene_out [n_tx] int32;
+ *   counters [2] uint64: rows seen so far (the base sequence number), rows dropped.
+ *
+ * Key of a candidate row with similarity s and sequence number q (its position in the concatenation of everything fed
+ * so far, q < 2^32):
+ *   b   = bits(s + 0.0f)                      -0.0 becomes +0.0 (denormals are kept)
+ *   b   = isnan(s) ? 0x7FC00000 : b           one canonical NaN, above +inf like torch.sort
+ *   ord = b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000)
+ *   key = ((uint64)ord << 32) | (0xFFFFFFFF - q)
+ * A larger key is a higher similarity and, at equal similarity, the earlier row: the rule of the stable sorts it
+ * replaces.  key == 0 cannot occur for a real row.
+ *
+ * segger_assign_update: tx_index [n] int64, seg [n] int64, sim [n] fp32, gene [n] int32, mask [n] uint8 or NULL
+ * (0 = skip the row).  Enqueues three steps in stream order and never waits for the device:
+ *   1. per row: skipped if masked out; if tx_index is outside [0, n_tx) or q = counters[0] + i does not fit 32 bits the
+ *      row is counted in counters[1] and skipped -- nothing is ever written out of range; otherwise
+ *      atomicMax(best_key[tx], key);
+ *   2. per row whose key equals best_key[tx]: cell[tx] = (int32)seg, gene_out[tx] = gene.  Sequence numbers are
+ *      unique, so exactly one row per transcript wins and nothing races;
+ *   3. counters[0] += n, in a launch of its own, so no block of steps 1-2 sees it early.
+ * The result does not depend on the order or the batching of the rows, bit for bit.  The base sequence number lives in
+ * device memory: a call captured in a hipGraph stays correct on replay.  n == 0 launches nothing.  Cell encodings
+ * must fit int32.
+ *
+ * segger_assign_finalize: similarity_out [n_tx] fp32 = the winning similarity (ord inverted; 0 where not seen),
+ * seen_out [n_tx] uint8 = best_key != 0.
+ *
+ * Both reject on the host with SEGGER_EINVAL, launching nothing: a NULL pointer (mask excepted), a misaligned pointer,
+ * a negative n, n_tx < 1, n_tx >= 2^31.
+ * ---------------------------------------------------------------------- */
+int segger_assign_update(const int64_t* tx_index, const int64_t* seg, const float* sim, const int32_t* gene,
+                         const uint8_t* mask, int64_t n, uint64_t* best_key, int32_t* cell, int32_t* gene_out,
+                         uint64_t* counters, int64_t n_tx, segger_stream_t stream);
+int segger_assign_finalize(const uint64_t* best_key, int64_t n_tx, float* similarity_out, uint8_t* seen_out,
+                           segger_stream_t stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

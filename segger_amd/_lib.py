@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must be imported first: the library binds to torch'
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEGGER_AMD_LIB selects another build of the same library (kernel A/B experiments)
 LIB_PATH = os.environ.get("SEGGER_AMD_LIB") or os.path.join(_HERE, "libsegger_amd.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -329,6 +329,8 @@ EXPORTS = {
                                         vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "segger_quadtree_label": (C.c_int, [vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
                                         vp, vp, vp, vp, C.c_int64, vp, vp]),
+    "segger_assign_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp]),
+    "segger_assign_finalize": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

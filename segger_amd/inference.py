@@ -10,7 +10,8 @@ kernel into one HIP graph per *shape bucket* and replays it for every batch padd
 * one ``segger_stage`` launch per batch writes node attributes and the three CSR views (copied from the batch's own
   views, padding by index arithmetic) into the captured buffers -- no per-batch sort or concatenation;
 * masks (``predict_mask``) and the device->host copy stay outside the graph, as in the reference; ``predict_device``
-  defers both to the caller so that a loop over batches never waits for the GPU.
+  defers both to the caller so that a loop over batches never waits for the GPU; ``predict_into`` hands the rows to a
+  ``postprocess.SegmentationAccumulator`` instead, which keeps only the best row per transcript.
 
 hipGraph capture works because every C-ABI entry point only enqueues on the caller's stream and never
 allocates or synchronises (include/segger_amd.h conventions).
@@ -132,6 +133,12 @@ class GraphedPredictor:
         """-> (tx_index, seg_idx, max_sim, gene_id, predict_mask) on the DEVICE, all [n_tx] and NOT yet filtered by the
         mask: nothing here waits for the GPU, so a loop over batches queues ahead of it; apply the mask (one
         compaction, one sync) after the loop."""
+        self._stage_and_replay(batch)
+        n = batch["tx"].num_nodes
+        return (batch["tx"]["index"], self.out["seg_idx"][:n].clone(), self.out["max_sim"][:n].clone(),
+                batch["tx"]["x"], batch["tx"]["predict_mask"])
+
+    def _stage_and_replay(self, batch) -> None:
         if self.model.training:
             raise RuntimeError("GraphedPredictor needs model.eval()")
         self._stage(batch)
@@ -145,9 +152,16 @@ class GraphedPredictor:
             with torch.cuda.graph(self.graph):
                 self._run()
         self.graph.replay()
+
+    @torch.no_grad()
+    def predict_into(self, batch, acc) -> None:
+        """Score ``batch`` and feed its rows to ``acc`` (a ``postprocess.SegmentationAccumulator``): stage, replay, then
+        one ``acc.update`` straight from the static output buffers on the same stream -- no clone, no compaction, no
+        sync.  The next batch's replay is ordered behind that update, so the buffers are free to be overwritten."""
+        self._stage_and_replay(batch)
         n = batch["tx"].num_nodes
-        return (batch["tx"]["index"], self.out["seg_idx"][:n].clone(), self.out["max_sim"][:n].clone(),
-                batch["tx"]["x"], batch["tx"]["predict_mask"])
+        acc.update(batch["tx"]["index"], self.out["seg_idx"][:n], self.out["max_sim"][:n], batch["tx"]["x"],
+                   mask=batch["tx"]["predict_mask"])
 
     @torch.no_grad()
     def predict(self, batch):
@@ -187,3 +201,6 @@ class GraphedPredictorPool:
 
     def predict_device(self, batch):
         return self._pick(batch).predict_device(batch)
+
+    def predict_into(self, batch, acc) -> None:
+        self._pick(batch).predict_into(batch, acc)

@@ -14,6 +14,10 @@ two stable sorts, one 2-D histogram, one vectorised fixed-point iteration -- no 
 
 Differences from the reference, both documented in oracle/postprocess_oracle.py: no 10 M-value subsampling of
 large genes (every value is used), and similarity ties in the dedup go to the first row of the concatenation.
+
+:class:`SegmentationAccumulator` is the streaming form of the first step: it keeps the best row per transcript on
+the device while the batches arrive (``csrc/assign.hip``: one 64-bit atomic max per row, no sort), so a slide's
+prediction rows never have to exist at once.
 """
 from __future__ import annotations
 
@@ -133,7 +137,11 @@ def assign_transcripts_to_cells(predictions: Sequence[Sequence[Tensor]], device=
     ``similarity_threshold`` (nan for genes without an assigned transcript), plus ``global_threshold`` and
     ``failed_genes``.  A transcript counts as segmented when ``similarity >= similarity_threshold``
     (``writer.py:96-99``)."""
-    out = best_assignment(predictions, device)
+    return _thresholds_and_join(best_assignment(predictions, device), max_iter)
+
+
+def _thresholds_and_join(out: Dict[str, Tensor], max_iter: int) -> Dict[str, Tensor]:
+    """The tail both entry points share: per-gene thresholds over the deduplicated rows, joined back by gene."""
     genes, thr, converged, glob = per_gene_thresholds(out["similarity"], out["gene"], out["cell_encoding"] >= 0, max_iter)
     t = torch.full(out["gene"].shape, float("nan"), dtype=torch.float64, device=out["gene"].device)
     if genes.numel():
@@ -144,6 +152,101 @@ def assign_transcripts_to_cells(predictions: Sequence[Sequence[Tensor]], device=
     out["global_threshold"] = glob
     out["failed_genes"] = genes[~converged]
     return out
+
+
+SEQ_LIMIT = 1 << 32          # sequence numbers (positions in the concatenation of everything fed) are 32 bits
+
+
+class SegmentationAccumulator:
+    """``best_assignment`` as a stream: ``update`` one batch of ``(tx_index, seg_idx, max_sim, gene_id)`` rows at a time,
+    ``result()`` at the end.  The state is 16 bytes per transcript of the slide (a packed ``(similarity, arrival order)``
+    key, the winning cell, its gene) whatever the number of rows or the tile overlap; ``update`` is two passes over the
+    batch (``segger_assign_update``) that never wait for the device, on torch's current stream.
+
+    The result equals ``best_assignment`` over the concatenation of the same batches in the same order -- and does not
+    depend on the order or the chunking, bit for bit -- with three differences:
+
+    * a winning similarity of -0.0 comes back as +0.0;
+    * any winning NaN comes back as the canonical NaN (``0x7FC00000``; NaN wins, as in ``torch.sort``);
+    * cell encodings must be < 2^31 (they are kept as int32).
+
+    ``n_transcripts`` is the ``row_index`` domain: every ``tx_index`` must lie in ``[0, n_transcripts)``.  Rows outside
+    it are never written anywhere; they are counted on the device and ``result()`` raises."""
+
+    def __init__(self, n_transcripts: int, device="cuda"):
+        from . import _lib
+        n = int(n_transcripts)
+        if not 1 <= n < (1 << 31):
+            raise ValueError(f"n_transcripts must be in [1, 2^31), got {n}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.SeggerAmdError("SegmentationAccumulator runs on the MI355X only: there is no CPU fallback "
+                                      "(best_assignment is the CPU form)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _lib
+        self.n_transcripts = n
+        self.best_key = torch.zeros(n, dtype=torch.int64, device=self.device)       # uint64 bit patterns
+        self.cell = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.gene = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=self.device)       # rows seen, rows dropped
+        self.rows_fed = 0
+
+    def reset(self) -> None:
+        """Forget every row (enqueued like an update: no sync)."""
+        self.best_key.zero_()
+        self.counters.zero_()
+        self.rows_fed = 0
+
+    def _col(self, t: Tensor, dtype) -> Tensor:
+        return t.detach().to(device=self.device, dtype=dtype).contiguous().view(-1)
+
+    def update(self, tx_index: Tensor, seg_idx: Tensor, max_sim: Tensor, gene_id: Tensor, mask: Optional[Tensor] = None) -> None:
+        """Feed one batch: CPU tensors (what ``predict_step`` returns) or device tensors of any integer / float dtype.
+        ``mask`` (bool, optional) keeps the rows where it is true, as ``tensor[mask]`` would before the call -- but a
+        masked-out row still takes a sequence number, which changes nothing in the result.  Enqueue only: device tensors
+        of the right dtype (int64, int64, float32, int32, bool) are read in place, anything else is converted or copied
+        to the device first.  (An update captured in a hipGraph is counted in ``rows_fed`` once, at capture; the 2^32 bound
+        on replays is kept by the device, which drops and counts rows past it.)"""
+        n = int(tx_index.numel())
+        if not (int(seg_idx.numel()) == int(max_sim.numel()) == int(gene_id.numel()) == n) or (
+                mask is not None and int(mask.numel()) != n):
+            raise ValueError("SegmentationAccumulator.update: columns of different lengths")
+        if self.rows_fed + n >= SEQ_LIMIT:
+            raise OverflowError(f"SegmentationAccumulator: {self.rows_fed} + {n} rows reach 2^32 (32-bit sequence numbers)")
+        if n == 0:
+            return
+        idx, seg = self._col(tx_index, torch.int64), self._col(seg_idx, torch.int64)
+        sim, gene = self._col(max_sim, torch.float32), self._col(gene_id, torch.int32)
+        m = None if mask is None else self._col(mask, torch.bool)
+        L = self._lib
+        with L.on_device(self.device):
+            rc = L.load().segger_assign_update(idx.data_ptr(), seg.data_ptr(), sim.data_ptr(), gene.data_ptr(), L.ptr(m), n,
+                                               self.best_key.data_ptr(), self.cell.data_ptr(), self.gene.data_ptr(),
+                                               self.counters.data_ptr(), self.n_transcripts, L.stream_ptr(self.device))
+        L.check(rc, "segger_assign_update")
+        self.rows_fed += n
+
+    def result(self) -> Dict[str, Tensor]:
+        """The dict ``best_assignment`` returns (``row_index`` ascending, ``cell_encoding``, ``similarity``, ``gene``), on
+        the device.  The one place that waits for the device; raises if any row was dropped."""
+        L = self._lib
+        sim = torch.empty(self.n_transcripts, dtype=torch.float32, device=self.device)
+        seen = torch.empty(self.n_transcripts, dtype=torch.bool, device=self.device)
+        with L.on_device(self.device):
+            rc = L.load().segger_assign_finalize(self.best_key.data_ptr(), self.n_transcripts, sim.data_ptr(), seen.data_ptr(),
+                                                 L.stream_ptr(self.device))
+        L.check(rc, "segger_assign_finalize")
+        rows, dropped = self.counters.tolist()
+        if dropped:
+            raise L.SeggerAmdError(f"SegmentationAccumulator: {dropped} of {rows} rows were dropped (tx_index outside "
+                                   f"[0, {self.n_transcripts}), or more than 2^32 rows fed); nothing was written for them")
+        row = seen.nonzero().squeeze(1)                      # the compaction to ascending row_index is plumbing
+        return {"row_index": row, "cell_encoding": self.cell[row].long(), "similarity": sim[row], "gene": self.gene[row].long()}
+
+    def segmentation(self, max_iter: int = 250) -> Dict[str, Tensor]:
+        """The dict ``assign_transcripts_to_cells`` returns, through the same thresholds-and-join tail."""
+        return _thresholds_and_join(self.result(), max_iter)
 
 
 def to_frame(result: Dict[str, Tensor], obs=None, cell_id: str = "cell_id", cell_encoding: str = "cell_encoding"):

@@ -79,6 +79,10 @@ def main():
     ap.add_argument("--overlap-predict", action="store_true",
                     help="also run segger's real predict pipeline: overlapping tiles (bbox + margin, predict_mask), "
                          "predict_step per tile, dedup + per-gene thresholds")
+    ap.add_argument("--stream-postprocess", action="store_true",
+                    help="with --graphed / --overlap-predict: repeat the sweep feeding a SegmentationAccumulator batch by "
+                         "batch (predict_into) instead of collecting every batch's rows, and record seconds and peak bytes "
+                         "of both post-processing paths and whether their results are equal")
     ap.add_argument("--no-slide-csr", action="store_true",
                     help="sort the edges of every batch (5 radix sorts) instead of slicing the once-per-slide CSR views")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for dry runs)")
@@ -114,6 +118,41 @@ def main():
 
     DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
     times: dict = {}
+
+    peak_seen = [0]
+
+    def mark_memory():
+        """--stream-postprocess only: start a new peak-memory window (the run's overall peak is kept in peak_seen);
+        -> bytes allocated now."""
+        if not args.stream_postprocess:
+            return 0
+        torch.cuda.synchronize()
+        peak_seen[0] = max(peak_seen[0], torch.cuda.max_memory_allocated())
+        torch.cuda.reset_peak_memory_stats()
+        return torch.cuda.memory_allocated()
+
+    def stream_postprocess(pool, get_batch, n_batches, collected_peak, collected_s, collected_name, ref):
+        """The same sweep again, fed to a SegmentationAccumulator batch by batch; `ref` is the collected path's result."""
+        from segger_amd.postprocess import SegmentationAccumulator
+        base = mark_memory()
+        acc = SegmentationAccumulator(args.n_tx, dev)
+        with Phase(f"{collected_name}_stream_sweep_s", times):
+            for i in range(n_batches):
+                pool.predict_into(get_batch(i), acc)             # no sync inside the loop
+        with Phase(f"{collected_name}_stream_postprocess_s", times):
+            seg = acc.segmentation()
+        peak = torch.cuda.max_memory_allocated() - base
+        equal = all(torch.equal(seg[k], ref[k]) for k in ("row_index", "cell_encoding", "gene"))
+        equal = equal and bool(((seg["similarity"] == ref["similarity"]) | (seg["similarity"].isnan() & ref["similarity"].isnan())).all())
+        thr_equal = bool(((seg["similarity_threshold"] == ref["similarity_threshold"])
+                          | (seg["similarity_threshold"].isnan() & ref["similarity_threshold"].isnan())).all())
+        return {"collected": {"postprocess_seconds": collected_s, "sweep_and_postprocess_peak_bytes": collected_peak},
+                "streamed": {"sweep_seconds": times[f"{collected_name}_stream_sweep_s"],
+                             "postprocess_seconds": times[f"{collected_name}_stream_postprocess_s"],
+                             "sweep_and_postprocess_peak_bytes": peak, "state_bytes": 16 * args.n_tx + 16},
+                "equal_rows": bool(equal), "equal_thresholds": thr_equal,
+                "note": "peak bytes: torch.cuda.max_memory_allocated over sweep + post-processing minus the bytes allocated "
+                        "when the sweep began; the streamed sweep's update() calls run inside sweep_seconds"}
     spec = SyntheticSpec(n_tx=args.n_tx, n_bd=args.n_bd, k_tx=args.k, seed=args.seed)
     with Phase("build_fov_s", times):
         data, aux = make_fov(spec, dev, return_aux=True)
@@ -270,6 +309,7 @@ def main():
         n_out = 0
         outs = []
         for warm in (True, False):                           # first sweep captures one graph per bucket
+            mem_base = mark_memory()
             with Phase("graphed_capture_s" if warm else "graphed_predict_s", times):
                 dev_out = [pool.predict_device(part.batch(ids)) for ids in batches]    # no sync inside the loop
                 mask = torch.cat([o[4] for o in dev_out])
@@ -291,6 +331,10 @@ def main():
             "assigned": int((seg["cell_encoding"] >= 0).sum()),
             "above_threshold": int(((seg["cell_encoding"] >= 0) & (seg["similarity"].double() >= thr)).sum()),
             "global_threshold": seg["global_threshold"], "failed_genes": int(seg["failed_genes"].numel())}
+        if args.stream_postprocess:
+            collected_peak = torch.cuda.max_memory_allocated() - mem_base
+            graphed["stream_postprocess"] = stream_postprocess(pool, lambda i: part.batch(batches[i]), len(batches),
+                                                               collected_peak, times["postprocess_s"], "graphed", seg)
         del outs, seg
         log(f"[fov] graphed: {graphed}")
 
@@ -308,6 +352,7 @@ def main():
         from segger_amd.inference import GraphedPredictorPool
         opool = GraphedPredictorPool(model, spec.bd_dim)
         for phase in ("overlap_graphed_capture_s", "overlap_graphed_predict_s"):
+            mem_base = mark_memory()
             with Phase(phase, times):
                 dev_out = [opool.predict_device(pti[i]) for i in range(len(pti))]
                 mask = torch.cat([o[4] for o in dev_out])
@@ -316,6 +361,14 @@ def main():
                 del dev_out, mask
         same = rows_g == rows and all(
             torch.equal(torch.cat([o[i] for o in outs]).to(dev), outs_g[0][i]) for i in (0, 3))
+        stream = None
+        if args.stream_postprocess:                          # the graphed sweep's own rows through both paths
+            with Phase("overlap_graphed_postprocess_s", times):
+                seg_g = assign_transcripts_to_cells(outs_g, device=dev)
+            collected_peak = torch.cuda.max_memory_allocated() - mem_base
+            stream = stream_postprocess(opool, lambda i: pti[i], len(pti), collected_peak,
+                                        times["overlap_graphed_postprocess_s"], "overlap", seg_g)
+            del seg_g
         del outs_g
         with Phase("overlap_postprocess_s", times):
             seg = assign_transcripts_to_cells(outs, device=dev)
@@ -328,6 +381,8 @@ def main():
                                "capture_sweep_seconds": times["overlap_graphed_capture_s"], "buckets": len(opool.buckets),
                                "same_rows_as_eager": bool(same),
                                "transcripts_per_s": int(seg["row_index"].numel()) / times["overlap_graphed_predict_s"]}}
+        if stream is not None:
+            overlap["graphed"]["stream_postprocess"] = stream
         if args.segmentation_parquet:
             from segger_amd.postprocess import to_frame
             with Phase("write_parquet_s", times):
@@ -349,7 +404,7 @@ def main():
                     f"(~{args.tile_nodes} tx), {len(batches)} batches of <= {args.edges_per_batch} edges",
         "edges_total": n_edges, "edges_intra_tile": kept, "phases_s": times,
         "train": train, "scoring": scoring, "graphed_predict": graphed, "overlap_predict": overlap,
-        "peak_hbm_gib": torch.cuda.max_memory_allocated() / 2 ** 30,
+        "peak_hbm_gib": max(peak_seen[0], torch.cuda.max_memory_allocated()) / 2 ** 30,
     }
     if world > 1:
         dist.destroy_process_group()
