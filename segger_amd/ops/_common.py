@@ -25,6 +25,20 @@ def _rows(t: Tensor, width: int, name: str) -> Tuple[int, int]:
     return t.data_ptr(), max(width, st[0])
 
 
+def _grad_rows(g: Tensor, dt) -> Tensor:
+    """An incoming gradient in the compute dtype with dense rows (what :func:`_rows` takes); the common case costs no torch call."""
+    if g.dtype != dt:
+        g = g.to(dt)
+    if g.dim() != 2 or (g.shape[0] > 1 and g.stride(1) != 1):
+        g = g.contiguous()
+    return g
+
+
+def _seq(v) -> tuple:
+    """A parameter argument that may be one tensor (or None) or a sequence of them, as a tuple."""
+    return tuple(v) if isinstance(v, (list, tuple)) else (v,)
+
+
 def _tag_prenorm(z: Tensor, y: Tensor, eps: float) -> Tensor:
     """Leaves on ``z = l2_normalize(y, eps)`` what it was normalised from (ops.loss_head may differentiate through y directly)."""
     if torch.is_grad_enabled() and y.requires_grad:

@@ -10,11 +10,9 @@ from .. import _lib
 from .._lib import DTYPE_CODE
 from ..graph import EdgeCSR
 from .. import ops                # route switches: read as ops.NAME when called, never bound here
-from ._common import _rows, _tag_prenorm, _vendor_gemm
+from ._common import _grad_rows, _rows, _seq, _tag_prenorm, _vendor_gemm
 from .packs import f32_split_planes
-from .linear import (linear_f32_gate_launch, linear_f32_gate_supported, linear_f32_split_launch,
-                     linear_f32_split_supported, linear_fwd_launch, linear_supported, linear_wgrad_dx_gate_supported,
-                     linear_wgrad_dx_launch, linear_wgrad_dx_supported, linear_wgrad_launch, linear_wgrad_supported,
+from .linear import (_run_backward, backward_plan, linear_f32_split_supported, linear_supported, linear_wgrad_supported,
                      segment_rowsum)
 
 
@@ -63,29 +61,18 @@ class _RowBiasLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         c, w16, pre = ctx.saved_tensors
-        dt = c.dtype
-        gy = gy.to(dt)
-        if gy.shape[0] > 1 and gy.stride(1) != 1:
-            gy = gy.contiguous()
-        gc = gw = gt = None
+        need = ctx.needs_input_grad
+        gy = _grad_rows(gy, c.dtype)
         m, k = w16.shape
-        want_c = ctx.needs_input_grad[0] or (pre is not None and ctx.needs_input_grad[5])
-        gated = False
-        if (ops.FUSED_WGRAD_DX and want_c and ctx.needs_input_grad[1] and c.shape[0] > 0
-                and linear_wgrad_dx_supported(m, k, dt)):
-            gated = pre is not None and ops.FUSED_GELU_GATE and linear_wgrad_dx_gate_supported(m, k, dt)
-            gc, gw, _ = linear_wgrad_dx_launch(gy, c, w16.t().contiguous(), want_bias=False,     # dY read once for both
-                                               gate=pre if gated else None)
-        else:
-            if want_c:
-                gc = linear_fwd_launch(gy, w16.t().contiguous(), None)          # [n, M] @ Wc -> [n, K]
-            if ctx.needs_input_grad[1]:
-                gw, _ = linear_wgrad_launch(gy, c, want_bias=False)
-        if ctx.needs_input_grad[2]:
+        plan = backward_plan(m, k, c.shape[0], c.dtype, need[0] or (pre is not None and need[5]), need[1], False,
+                             pre is not None, site="row_bias")
+        gc, gw, _ = _run_backward(plan, gy, c, lambda form: w16.t().contiguous(), pre)      # (W^T: [n, M] @ Wc -> [n, K])
+        gt = None
+        if need[2]:
             by_gene = ctx.by_gene if ctx.by_gene is not None else rows_by_id(ctx.ids, ctx.n_ids)
             gt = segment_rowsum(gy, by_gene)
         if pre is not None:
-            if gc is not None and not gated:
+            if gc is not None and not plan.gate:
                 gc = torch.ops.aten.gelu_backward(gc, pre)
             return None, gw, gt, None, None, gc
         return gc, gw, gt, None, None, None
@@ -159,29 +146,12 @@ class _EmbedLinear(torch.autograd.Function):
         dev, dt = c.device, c.dtype
         d = int(c.shape[1])
         m = int(wc.shape[0])
-        gy = gy.to(dt)
-        if gy.shape[0] > 1 and gy.stride(1) != 1:
-            gy = gy.contiguous()
+        gy = _grad_rows(gy, dt)
         need = ctx.needs_input_grad
-        want_c = need[0] or (pre is not None and need[1])
-        want_w = any(need[6:6 + n_w])
-        gc = gw = None
-        gated = False
-        if ops.FUSED_WGRAD_DX and want_c and want_w and c.shape[0] > 0 and linear_wgrad_dx_supported(m, d, dt):
-            gated = pre is not None and ops.FUSED_GELU_GATE and linear_wgrad_dx_gate_supported(m, d, dt)
-            gc, gw, _ = linear_wgrad_dx_launch(gy, c, wc_t, want_bias=False, gate=pre if gated else None)
-        else:
-            if want_c:
-                if (dt == torch.float32 and pre is not None and need[1] and gy.stride(0) % 4 == 0 and ops.F32_GATE_EPILOGUE
-                        and linear_f32_gate_supported(m, d)):
-                    gc = linear_f32_gate_launch(gy, wc_t, pre, "gelu")      # dX * gelu'(pre) in one kernel
-                    gated = True
-                elif ops.F32_SPLIT and dt == torch.float32 and gy.stride(0) % 4 == 0 and linear_f32_split_supported(m, d):
-                    gc = linear_f32_split_launch(gy, f32_split_planes(wc, transposed=True), None)
-                else:
-                    gc = linear_fwd_launch(gy, wc_t, None)
-            if want_w:
-                gw, _ = linear_wgrad_launch(gy, c, want_bias=False)
+        plan = backward_plan(m, d, c.shape[0], dt, need[0] or (pre is not None and need[1]), any(need[6:6 + n_w]), False,
+                             pre is not None, need[1], gy.stride(0) % 4 == 0, site="first")
+        gc, gw, _ = _run_backward(plan, gy, c, lambda form: wc_t if form == "wt" else f32_split_planes(wc, transposed=True),
+                                  pre)
         by_gene = ctx.by_gene if ctx.by_gene is not None else rows_by_id(ids, int(table.shape[0]))
         gt = segment_rowsum(gy, by_gene)
         if gw is not None and lib.segger_reductions_pending() >= 0:
@@ -205,7 +175,7 @@ class _EmbedLinear(torch.autograd.Function):
         with _lib.on_device(dev):
             _lib.check(lib.segger_gene_table_bwd(C.byref(a), _lib.stream_ptr(dev)), "segger_gene_table_bwd")
         if pre is not None:
-            if gc is not None and not gated:
+            if gc is not None and not plan.gate:
                 gc = torch.ops.aten.gelu_backward(gc, pre)
             return (None, gc, g_table, None, None, None, *g_w, *g_b)
         return (gc, None, g_table, None, None, None, *g_w, *g_b)
@@ -216,8 +186,7 @@ def embed_linear(x: "EmbedInput", weight, bias) -> Tensor:
     [n, 2D] input: the embedding half depends on a row only through its gene, so it is a per-gene table
     ``T = gelu(table) Wa^T + b`` ([G, M], a tiny GEMM) added in the epilogue of the GEMM over the positional half
     (K: 2D -> D).  Autograd: T's gradient is the by-gene row sum of dY; table, Wa and b receive theirs through T."""
-    weights = tuple(weight) if isinstance(weight, (list, tuple)) else (weight,)
-    biases = tuple(bias) if isinstance(bias, (list, tuple)) else (bias,)
+    weights, biases = _seq(weight), _seq(bias)
     d = int(x.table.shape[1])
     # (the table kernels are latency-sized: a few hundred genes.  A 5k-gene panel's dW reduction would take 0.6 ms on their
     #  24 workgroups -- the torch-composed route with its vendor GEMMs below serves those)

@@ -11,7 +11,7 @@ from .._lib import DTYPE_CODE
 from .. import graph as _graph
 from ..graph import EdgeCSR, EdgeGraph
 from .. import ops                # route switches: read as ops.NAME when called, never bound here
-from ._common import _bits_ptr, _defer_keep, _f32_vec, _gat_bwd_ws_bytes, _has_specialised, _rows, _seed_parts
+from ._common import _bits_ptr, _defer_keep, _f32_vec, _gat_bwd_ws_bytes, _grad_rows, _has_specialised, _rows, _seed_parts
 
 
 # --------------------------------------------------------------------------
@@ -145,10 +145,7 @@ def _gat_bwd_args(g: EdgeGraph, xl: Tensor, xr: Tensor, att: Tensor, bias: Optio
             a.keep_bits_dst = _bits_ptr(keep_bits[0], g.n_edges)
         if keep_bits[1] is not None:
             a.keep_bits_src = _bits_ptr(keep_bits[1], g.n_edges)
-    if grad_out.dtype != dt:
-        grad_out = grad_out.to(dt)
-    if grad_out.dim() == 2 and grad_out.shape[0] > 1 and grad_out.stride(1) != 1:
-        grad_out = grad_out.contiguous()
+    grad_out = _grad_rows(grad_out, dt)
     a.grad_out, a.ld_go = _rows(grad_out, hc, "grad_out")
     a.pre, a.ld_pre = _rows(pre, hc, "pre")
     a.lse = lse.data_ptr()

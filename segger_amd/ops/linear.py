@@ -1,7 +1,7 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -10,13 +10,16 @@ from .. import _lib
 from .._lib import DTYPE_CODE
 from ..graph import EdgeCSR
 from .. import ops                # route switches: read as ops.NAME when called, never bound here
-from ._common import _defer_keep, _f32_vec, _rows, _vendor_gemm, _wgrad_ws_bytes
+from ._common import _defer_keep, _f32_vec, _grad_rows, _rows, _seq, _vendor_gemm, _wgrad_ws_bytes
 from .packs import _pack_for, f32_split_planes
 
 
 # --------------------------------------------------------------------------
 # Tall-skinny projection GEMM (MFMA) with autograd
 # --------------------------------------------------------------------------
+_ACT_KIND = {"gelu": 1, "silu": 2}        # the activation codes of the fp32 gate / act kernels
+
+
 def linear_supported(k_in: int, m_out: int, dtype: torch.dtype) -> bool:
     return dtype in DTYPE_CODE and bool(_lib.load().segger_linear_supported(int(k_in), int(m_out), DTYPE_CODE[dtype]))
 
@@ -54,7 +57,7 @@ def linear_f32_gate_launch(x: Tensor, w: Tensor, gate: Tensor, kind: str) -> Ten
     split = ops.F32_SPLIT and ldx % 4 == 0 and linear_f32_split_supported(k, m)
     wq = f32_split_planes(w) if split else w.detach().float().contiguous()
     with _lib.on_device(x.device):
-        rc = _lib.load().segger_linear_fwd_f32_gate(xp, ldx, wq.data_ptr(), int(split), gp, ldg, {"gelu": 1, "silu": 2}[kind],
+        rc = _lib.load().segger_linear_fwd_f32_gate(xp, ldx, wq.data_ptr(), int(split), gp, ldg, _ACT_KIND[kind],
                                                     y.data_ptr(), m, n, k, m, _lib.stream_ptr(x.device))
     _lib.check(rc, "segger_linear_fwd_f32_gate")
     return y
@@ -74,7 +77,7 @@ def linear_f32_act_launch(x: Tensor, w: Tensor, bias: Optional[Tensor], kind: st
     b = None if bias is None else bias.detach().float().contiguous()
     with _lib.on_device(x.device):
         rc = _lib.load().segger_linear_fwd_f32_act(xp, ldx, w.data_ptr(), _lib.ptr(b), y.data_ptr(), m, ya.data_ptr(), m,
-                                                   {"gelu": 1, "silu": 2}[kind], n, k, m, _lib.stream_ptr(x.device))
+                                                   _ACT_KIND[kind], n, k, m, _lib.stream_ptr(x.device))
     _lib.check(rc, "segger_linear_fwd_f32_act")
     return y, ya
 
@@ -145,6 +148,17 @@ def linear_wgrad_supported(m_out: int, k_in: int, dtype: torch.dtype) -> bool:
     return dtype in DTYPE_CODE and bool(_lib.load().segger_linear_wgrad_supported(int(m_out), int(k_in), DTYPE_CODE[dtype]))
 
 
+def _wgrad_outputs(n: int, m: int, k: int, want_bias: bool, device):
+    """-> (dW [M, K], db [M] | None, workspace, its bytes): what a weight-gradient launch writes, fp32; kept alive for a
+    deferred final sum (``ops.deferred_reductions``)."""
+    gw = torch.empty((m, k), dtype=torch.float32, device=device)
+    gb = torch.empty(m, dtype=torch.float32, device=device) if want_bias else None
+    ws_bytes = _wgrad_ws_bytes(n, m, k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    _defer_keep(ws, gw, gb)
+    return gw, gb, ws, ws_bytes
+
+
 def linear_wgrad_launch(gy: Tensor, x: Tensor, want_bias: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
     """(dW[M, K], db[M]) fp32 of ``y = x @ W.T + b`` from ``gy`` [n, M] and ``x`` [n, K] (row strides allowed):
     one pass over both matrices on the MFMA weight-gradient kernel (``segger_linear_wgrad``)."""
@@ -156,10 +170,7 @@ def linear_wgrad_launch(gy: Tensor, x: Tensor, want_bias: bool = True) -> Tuple[
         raise ValueError("linear_wgrad: gy / x must share the row count and the dtype")
     gp, ldg = _rows(gy, m, "gy")
     xp, ldx = _rows(x, k, "x")
-    gw = torch.empty((m, k), dtype=torch.float32, device=x.device)
-    gb = torch.empty(m, dtype=torch.float32, device=x.device) if want_bias else None
-    ws_bytes = _wgrad_ws_bytes(n, m, k)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    gw, gb, ws, ws_bytes = _wgrad_outputs(n, m, k, want_bias, x.device)
     split = (ops.F32_SPLIT and ops.F32_SPLIT_WGRAD and x.dtype == torch.float32 and ldg % 4 == 0 and ldx % 4 == 0
              and bool(lib.segger_linear_wgrad_f32_split_supported(m, k)))
     with _lib.on_device(x.device):
@@ -170,7 +181,6 @@ def linear_wgrad_launch(gy: Tensor, x: Tensor, want_bias: bool = True) -> Tuple[
             rc = lib.segger_linear_wgrad(gp, ldg, xp, ldx, n, m, k, DTYPE_CODE[x.dtype], gw.data_ptr(), _lib.ptr(gb),
                                          ws.data_ptr(), ws_bytes, _lib.stream_ptr(x.device))
     _lib.check(rc, "segger_linear_wgrad")
-    _defer_keep(ws, gw, gb)
     return gw, gb
 
 
@@ -204,40 +214,39 @@ def linear_wgrad_dx_launch(gy: Tensor, x: Tensor, wt: Tensor, want_bias: bool = 
         _lib.require_cuda(gate)
         qp, ldq = _rows(gate, k, "gate")
     gx = torch.empty((n, k), dtype=x.dtype, device=x.device)
-    gw = torch.empty((m, k), dtype=torch.float32, device=x.device)
-    gb = torch.empty(m, dtype=torch.float32, device=x.device) if want_bias else None
-    ws_bytes = _wgrad_ws_bytes(n, m, k)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    gw, gb, ws, ws_bytes = _wgrad_outputs(n, m, k, want_bias, x.device)
     with _lib.on_device(x.device):
         rc = lib.segger_linear_wgrad_dx(gp, ldg, xp, ldx, wt.data_ptr(), n, m, k, DTYPE_CODE[x.dtype], gw.data_ptr(),
                                         _lib.ptr(gb), gx.data_ptr(), k, qp, ldq, ws.data_ptr(), ws_bytes,
                                         _lib.stream_ptr(x.device))
     _lib.check(rc, "segger_linear_wgrad_dx")
-    _defer_keep(ws, gw, gb)
     return gx, gw, gb
+
+
+def _linear_args(x: Tensor, w: Tensor, bias: Optional[Tensor]):
+    """-> (``segger_linear_args`` of ``y = x @ w.T + bias``, the new y): one side of a paired forward launch."""
+    n, k = x.shape
+    m = int(w.shape[0])
+    if w.dtype != x.dtype or not w.is_contiguous() or w.shape[1] != k:
+        raise ValueError("linear pair: weights must be contiguous [M, K] in the activation dtype")
+    y = torch.empty((n, m), dtype=x.dtype, device=x.device)
+    a = _lib.LinearArgs()
+    a.x, a.ldx = _rows(x, k, "x")
+    a.w, a.bias = w.data_ptr(), _lib.ptr(_f32_vec(bias, m, "bias"))
+    a.y, a.ldy, a.n_rows, a.m_out = y.data_ptr(), m, n, m
+    return a, y
 
 
 def linear_fwd_pair_launch(xa: Tensor, wa: Tensor, xb: Tensor, wb: Tensor) -> Tuple[Tensor, Tensor]:
     """``(xa @ wa.T, xb @ wb.T)`` for 16-bit activations whose widths may differ (``segger_linear_fwd_pair_k``: one launch
     for widths (384, 128) or equal widths -- a first layer's two data gradients -- two otherwise)."""
     _lib.require_cuda(xa, wa, xb, wb)
-    args, outs = [], []
-    for x, w in ((xa, wa), (xb, wb)):
-        n, k = x.shape
-        m = int(w.shape[0])
-        if w.dtype != x.dtype or not w.is_contiguous() or w.shape[1] != k:
-            raise ValueError("linear_fwd_pair: weights must be contiguous [M, K] in the activation dtype")
-        y = torch.empty((n, m), dtype=x.dtype, device=x.device)
-        a = _lib.LinearArgs()
-        a.x, a.ldx = _rows(x, k, "x")
-        a.w, a.y, a.ldy, a.n_rows, a.m_out = w.data_ptr(), y.data_ptr(), m, n, m
-        args.append(a)
-        outs.append(y)
+    (aa, ya), (ab, yb) = _linear_args(xa, wa, None), _linear_args(xb, wb, None)
     with _lib.on_device(xa.device):
-        rc = _lib.load().segger_linear_fwd_pair_k(C.byref(args[0]), int(xa.shape[1]), C.byref(args[1]), int(xb.shape[1]),
+        rc = _lib.load().segger_linear_fwd_pair_k(C.byref(aa), int(xa.shape[1]), C.byref(ab), int(xb.shape[1]),
                                                   DTYPE_CODE[xa.dtype], _lib.stream_ptr(xa.device))
     _lib.check(rc, "segger_linear_fwd_pair_k")
-    return outs[0], outs[1]
+    return ya, yb
 
 
 def linear_wgrad_pair_launch(sides, dx: bool):
@@ -245,7 +254,7 @@ def linear_wgrad_pair_launch(sides, dx: bool):
     ONE launch (``segger_linear_wgrad_pair``; ``dx``: the one-pass form with the data gradients, else dW / db only)."""
     lib = _lib.load()
     dev, dt = sides[0][0].device, sides[0][1].dtype
-    args, outs, keep = [], [], []
+    args, outs = [], []
     for gy, x, wt, want_bias in sides:
         _lib.require_cuda(gy, x)
         n, m = gy.shape
@@ -262,21 +271,15 @@ def linear_wgrad_pair_launch(sides, dx: bool):
                 raise ValueError("linear_wgrad_pair: W^T must be contiguous [K, M] in the activation dtype")
             gx = torch.empty((n, k), dtype=dt, device=dev)
             a.w_t, a.dx, a.ld_dx = wt.data_ptr(), gx.data_ptr(), k
-        gw = torch.empty((m, k), dtype=torch.float32, device=dev)
-        gb = torch.empty(m, dtype=torch.float32, device=dev) if want_bias else None
-        ws_bytes = _wgrad_ws_bytes(n, m, k)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        gw, gb, ws, ws_bytes = _wgrad_outputs(n, m, k, want_bias, dev)
         a.grad_w, a.grad_b, a.workspace, a.workspace_bytes = gw.data_ptr(), _lib.ptr(gb), ws.data_ptr(), ws_bytes
         args.append(a)
-        outs.append((gx, gw, gb))
-        keep.append((ws, gw, gb))
+        outs.append((gx, gw, gb, ws))
     with _lib.on_device(dev):
         rc = lib.segger_linear_wgrad_pair(C.byref(args[0]), C.byref(args[1]), int(sides[0][1].shape[1]), DTYPE_CODE[dt],
                                           _lib.stream_ptr(dev))
     _lib.check(rc, "segger_linear_wgrad_pair")
-    for kk in keep:
-        _defer_keep(*kk)
-    return outs
+    return [o[:3] for o in outs]
 
 
 def _weight_grad_gemm(gy: Tensor, x: Tensor) -> Tensor:
@@ -286,6 +289,130 @@ def _weight_grad_gemm(gy: Tensor, x: Tensor) -> Tensor:
     return (gy.t() @ x).float()
 
 
+class BackwardPlan(NamedTuple):
+    """The route of each output of one projection backward (:func:`backward_plan`)."""
+    dx: Optional[str] = None    # None | "one_pass" (segger_linear_wgrad_dx) | "f32_gate" | "f32_split" | "mfma" | "vendor"
+    dw: Optional[str] = None    # dW / db: None | "one_pass" (they come with dX) | "mfma" | "vendor" (GEMM + colsum)
+    gate: bool = False          # gelu'(pre) is applied inside the data-gradient kernel; else aten.gelu_backward, by the caller
+    want_w: bool = False
+    want_b: bool = False
+
+
+def backward_plan(m: int, k: int, n: int, dt, need_x: bool, want_w: bool, want_b: bool, pre: bool = False,
+                  pre_grad: bool = False, aligned: bool = True, site: str = "generic", have_dw: bool = False) -> BackwardPlan:
+    """The kernels that serve dX [n, K], dW [M, K] and db of ``y = x W^T + b`` at dtype ``dt``, from shapes, needs and the
+    ``ops`` switches alone (no tensor, no launch).  ``pre``: x = gelu(pre) and the data gradient goes to ``pre``
+    (``pre_grad``: it requires one); ``aligned``: dY's rows start on 16 bytes (the fp32 split reads them as such).
+    ``site``: "generic" (:class:`_Linear`, a side of :class:`_LinearPair`) has a vendor route for uncovered shapes; the
+    first layer's nodes are entered with covered ones only -- "first" (``_EmbedLinear``) has the fp32 routes, "row_bias"
+    (``_RowBiasLinear``) does not.  ``have_dw``: a paired launch already left dW / db (a one-pass dX still returns them)."""
+    generic = site == "generic"
+    f32 = dt == torch.float32 and site != "row_bias"
+    dx = dw = None
+    gate = False
+    if ops.FUSED_WGRAD_DX and need_x and (want_w or want_b) and n > 0 and linear_wgrad_dx_supported(m, k, dt):
+        dx = dw = "one_pass"                                 # dY read ONCE for dX, dW and db
+        gate = bool(pre and ops.FUSED_GELU_GATE and linear_wgrad_dx_gate_supported(m, k, dt))
+    else:
+        if not need_x:
+            pass
+        elif f32 and pre and pre_grad and aligned and ops.F32_GATE_EPILOGUE and linear_f32_gate_supported(m, k):
+            dx, gate = "f32_gate", True                      # dX * gelu'(pre) in one kernel
+        elif ops.F32_SPLIT and f32 and aligned and linear_f32_split_supported(m, k):
+            dx = "f32_split"
+        else:
+            dx = "mfma" if not generic or linear_supported(m, k, dt) else "vendor"
+        if have_dw:
+            pass
+        elif not generic:
+            dw = "mfma" if want_w else None
+        elif want_w or want_b:
+            dw = "mfma" if n > 0 and linear_wgrad_supported(m, k, dt) else "vendor"
+    return BackwardPlan(dx, dw, gate, want_w, want_b)
+
+
+def backward_pair_plan(k: int, ms, ns, dt, need_xs, wants, have_grads: bool = True) -> Optional[str]:
+    """Two projection backwards of one K in shared launches: None (each side by its own :func:`backward_plan`) |
+    "one_pass" (one ``segger_linear_wgrad_pair`` launch with both data gradients) | "wgrad" (one without them) |
+    "wgrad+dx" (one without, and one ``segger_linear_fwd_pair_k`` launch for the two data gradients the one-pass kernel
+    does not cover: a first layer reads K = 256).  ``ms`` / ``ns`` / ``need_xs`` / ``wants``: per side M, row count, "the
+    input needs a gradient", "a parameter does"."""
+    if not (ops.WGRAD_PAIR and all(wants) and have_grads and dt in (torch.bfloat16, torch.float16) and all(n > 0 for n in ns)):
+        return None
+    if ops.FUSED_WGRAD_DX and all(need_xs) and all(linear_wgrad_dx_supported(m, k, dt) for m in ms):
+        return "one_pass"
+    if not all(linear_wgrad_supported(m, k, dt) for m in ms):
+        return None
+    return "wgrad+dx" if all(need_xs) and all(linear_supported(m, k, dt) for m in ms) else "wgrad"
+
+
+def _run_backward(plan: BackwardPlan, gy: Tensor, x: Tensor, weights, pre: Optional[Tensor] = None) -> tuple:
+    """-> (gx, gw, gb) of ``plan``.  ``weights(form)``: "wt" = W^T [K, M] (dX = dY @ W), "planes_t" = its bf16x3 planes,
+    "w" = W -- each asked for only on the route that reads it: at fp32 storage the split kernels take the transposed PLANES,
+    and building W^T as well was one stray transposing launch per projection and step."""
+    gx = gw = gb = None
+    if plan.dx == "one_pass":
+        gx, gw, gb = linear_wgrad_dx_launch(gy, x, weights("wt"), want_bias=plan.want_b, gate=pre if plan.gate else None)
+    elif plan.dx == "f32_gate":
+        gx = linear_f32_gate_launch(gy, weights("wt"), pre, "gelu")
+    elif plan.dx == "f32_split":
+        gx = linear_f32_split_launch(gy, weights("planes_t"), None)
+    elif plan.dx == "mfma":
+        gx = linear_fwd_launch(gy, weights("wt"), None)
+    elif plan.dx == "vendor":
+        _vendor_gemm("data gradient dX = dY W", gy.shape[1], x.shape[1], x.dtype)
+        gx = gy @ weights("w")
+    if plan.dw == "mfma":
+        gw, gb = linear_wgrad_launch(gy, x, want_bias=plan.want_b)       # dY and X read once for both
+    elif plan.dw == "vendor":
+        gw = _weight_grad_gemm(gy, x) if plan.want_w else None
+        gb = colsum(gy) if plan.want_b else None
+    return gx, gw, gb
+
+
+class _Saved:
+    """What a projection's forward leaves for its backward beside the input: the pack, the generation of the weights it
+    read (the pack is refreshed IN PLACE after an optimizer step; a backward that runs later than that -- not the case in
+    forward -> backward -> step training -- would see the new weights), the stacked row counts and the bias flags."""
+    __slots__ = ("pack", "key", "rows", "has_bias")
+
+    def __init__(self, pk):
+        self.pack, self.key, self.rows, self.has_bias = pk, pk.key, pk.rows, pk.has_bias
+
+    def weights(self, form: str) -> Tensor:
+        pk = self.pack
+        if pk.key != self.key:
+            raise RuntimeError("the projection weights changed between this forward and its backward "
+                               "(optimizer step in between?): run backward before stepping")
+        return pk.wt if form == "wt" else pk.planes(transposed=True) if form == "planes_t" else pk.w
+
+    def wants(self, need_params) -> Tuple[bool, bool]:
+        """(a weight, a bias) wants a gradient; ``need_params`` = needs_input_grad of the weights, then of the biases."""
+        n_w = len(self.rows)
+        return any(need_params[:n_w]), any(h and g for h, g in zip(self.has_bias, need_params[n_w:]))
+
+
+def _projection_backward(st: _Saved, x, gy, need_x: bool, need_params, done=(None, None, None)) -> tuple:
+    """-> (gx, (*grads_w, *grads_b)) of one projection: plans and runs what ``done`` = (gx, gw, gb) of a paired launch left
+    open; each parameter's gradient is a row window of the stacked result."""
+    gx, gw, gb = done
+    gy = _grad_rows(gy, x.dtype)
+    m, k = st.pack.w.shape
+    plan = backward_plan(m, k, x.shape[0], x.dtype, need_x and gx is None, *st.wants(need_params),
+                         aligned=gy.stride(0) % 4 == 0, have_dw=gw is not None)
+    out = _run_backward(plan, gy, x, st.weights)
+    if plan.dx:
+        gx = out[0]
+    if plan.dw:
+        gw, gb = out[1:]
+    n_w, grads_w, grads_b, r0 = len(st.rows), [], [], 0
+    for i, r in enumerate(st.rows):
+        grads_w.append(gw[r0:r0 + r] if (gw is not None and need_params[i]) else None)
+        grads_b.append(gb[r0:r0 + r] if (gb is not None and st.has_bias[i] and need_params[n_w + i]) else None)
+        r0 += r
+    return gx, tuple(grads_w) + tuple(grads_b)
+
+
 class _Linear(torch.autograd.Function):
     """x [n, K] (bf16/f16); ``n_w`` fp32 master weights [M_i, K] stacked by rows, ``n_w`` fp32 biases (or None)
     -> [n, sum M_i].  Forward, the data gradient and the weight / bias gradients run on the hand-written MFMA kernels
@@ -293,168 +420,70 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n_w, *params):
-        weights, biases = params[:n_w], params[n_w:]
-        pk = _pack_for(weights, biases).get(x.dtype, x.device)
+        pk = _pack_for(params[:n_w], params[n_w:]).get(x.dtype, x.device)
         if ops.F32_SPLIT and x.dtype == torch.float32 and linear_f32_split_supported(x.shape[1], pk.w.shape[0]):
             y = linear_f32_split_launch(x, pk.planes(), pk.b)
         else:
             y = linear_fwd_launch(x, pk.w, pk.b)
         ctx.save_for_backward(x)
-        ctx.n_w = n_w
-        _linear_save(ctx, pk, weights, biases)
+        ctx.st = _Saved(pk)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        return _linear_backward(ctx, x, gy, ctx.needs_input_grad[0], ctx.needs_input_grad[2:])
-
-
-def _linear_save(ctx, pk, weights, biases) -> None:
-    ctx.pack = pk
-    ctx.rows = [int(w.shape[0]) for w in weights]
-    ctx.has_bias = [b is not None for b in biases]
-    # the pack is refreshed IN PLACE after an optimizer step; a backward that runs later than that (not the case in
-    # forward -> backward -> step training) would see the new weights: remember which generation this forward used
-    ctx.w, ctx.wt_of, ctx.w_key = pk.w, pk, pk.key
-
-
-def _grad_rows(gy: Tensor, dt) -> Tensor:
-    if gy.dtype != dt:
-        gy = gy.to(dt)
-    if gy.dim() != 2 or (gy.shape[0] > 1 and gy.stride(1) != 1):
-        gy = gy.contiguous()
-    return gy
-
-
-def _linear_backward(st, x, gy, need_x: bool, need_params, pre=None) -> tuple:
-    """-> (gx, None, *grads_w, *grads_b) of one projection; ``st`` holds what :func:`_linear_save` left, ``need_params`` =
-    needs_input_grad of its weights then biases; ``pre`` = (gx | None, gw, gb) already computed by a paired launch."""
-    dt = x.dtype
-    n_w = len(st.rows)
-    gy = _grad_rows(gy, dt)
-    w = st.w
-    m, k = w.shape
-    gx = None
-    want_w = any(need_params[:n_w])
-    want_b = any(h and g for h, g in zip(st.has_bias, need_params[n_w:]))
-    gw = gb = None
-    if pre is not None:
-        gx, gw, gb = pre
-    if need_x and gx is None:
-        if st.wt_of.key != st.w_key:
-            raise RuntimeError("the projection weights changed between this forward and its backward "
-                               "(optimizer step in between?): run backward before stepping")
-        # (st.wt_of.wt = W^T [K, M], dX = dY @ W -- asked for only where it is read: at fp32 storage the split kernels take
-        #  the transposed PLANES instead, and the property's transposing copy was one stray launch per projection and step)
-        if (ops.FUSED_WGRAD_DX and (want_w or want_b) and x.shape[0] > 0 and linear_wgrad_dx_supported(m, k, dt)):
-            gx, gw, gb = linear_wgrad_dx_launch(gy, x, st.wt_of.wt, want_bias=want_b)    # dY read ONCE for dX, dW and db
-        elif ops.F32_SPLIT and dt == torch.float32 and linear_f32_split_supported(m, k):
-            gx = linear_f32_split_launch(gy, st.wt_of.planes(transposed=True), None)
-        elif linear_supported(m, k, dt):
-            gx = linear_fwd_launch(gy, st.wt_of.wt, None)
-        else:
-            _vendor_gemm("data gradient dX = dY W", m, k, dt)
-            gx = gy @ w
-    if gw is not None:
-        pass
-    elif (want_w or want_b) and x.shape[0] > 0 and linear_wgrad_supported(m, k, dt):
-        gw, gb = linear_wgrad_launch(gy, x, want_bias=want_b)       # dY and X read once for both
-    else:
-        if want_w:
-            gw = _weight_grad_gemm(gy, x)
-        if want_b:
-            gb = colsum(gy)
-    grads_w, grads_b, r0 = [], [], 0
-    for i, r in enumerate(st.rows):
-        grads_w.append(gw[r0:r0 + r] if (gw is not None and need_params[i]) else None)
-        grads_b.append(gb[r0:r0 + r] if (gb is not None and st.has_bias[i] and need_params[n_w + i]) else None)
-        r0 += r
-    return (gx, None) + tuple(grads_w) + tuple(grads_b)
-
-
-class _State:
-    pass
+        gx, grads = _projection_backward(ctx.st, x, gy, ctx.needs_input_grad[0], ctx.needs_input_grad[2:])
+        return (gx, None) + grads
 
 
 class _LinearPair(torch.autograd.Function):
     """Two projections with the same K as one launch (``segger_linear_fwd_pair``): (xa, xb, n_wa, n_wb, *weights_a,
-    *biases_a, *weights_b, *biases_b) -> (ya, yb).  Backward: each side's own :func:`_linear_backward`."""
+    *biases_a, *weights_b, *biases_b) -> (ya, yb).  Backward: what :func:`backward_pair_plan` shares, then each side's own."""
 
     @staticmethod
     def forward(ctx, xa, xb, n_wa, n_wb, *params):
-        pa, pb = params[:2 * n_wa], params[2 * n_wa:]
-        lib = _lib.load()
         sides, args, outs = [], [], []
-        for x, n_w, pp in ((xa, n_wa, pa), (xb, n_wb, pb)):
-            weights, biases = pp[:n_w], pp[n_w:]
-            pk = _pack_for(weights, biases).get(x.dtype, x.device)
-            st = _State()
-            _linear_save(st, pk, weights, biases)
-            sides.append(st)
-            n, k = x.shape
-            m = int(pk.w.shape[0])
-            y = torch.empty((n, m), dtype=x.dtype, device=x.device)
-            a = _lib.LinearArgs()
-            a.x, a.ldx = _rows(x, k, "x")
-            a.w, a.bias = pk.w.data_ptr(), _lib.ptr(_f32_vec(pk.b, m, "bias"))
-            a.y, a.ldy = _rows(y, m, "y")
-            a.n_rows, a.m_out = n, m
+        for x, n_w, pp in ((xa, n_wa, params[:2 * n_wa]), (xb, n_wb, params[2 * n_wa:])):
+            pk = _pack_for(pp[:n_w], pp[n_w:]).get(x.dtype, x.device)
+            sides.append(_Saved(pk))
+            a, y = _linear_args(x, pk.w, pk.b)
             args.append(a)
             outs.append(y)
         with _lib.on_device(xa.device):
-            rc = lib.segger_linear_fwd_pair(C.byref(args[0]), C.byref(args[1]), int(xa.shape[1]), DTYPE_CODE[xa.dtype],
-                                            _lib.stream_ptr(xa.device))
+            rc = _lib.load().segger_linear_fwd_pair(C.byref(args[0]), C.byref(args[1]), int(xa.shape[1]), DTYPE_CODE[xa.dtype],
+                                                    _lib.stream_ptr(xa.device))
         _lib.check(rc, "segger_linear_fwd_pair")
         ctx.save_for_backward(xa, xb)
-        ctx.sides, ctx.n_w = sides, (n_wa, n_wb)
+        ctx.sides = sides
         return outs[0], outs[1]
 
     @staticmethod
-    def backward(ctx, gya, gyb):
-        xa, xb = ctx.saved_tensors
-        n_wa, n_wb = ctx.n_w
-        need = ctx.needs_input_grad
-        na, nb = need[4:4 + 2 * n_wa], need[4 + 2 * n_wa:]
-        pre = (None, None)
-        sts = ctx.sides
-        dt = xa.dtype
-        wants = [any(nn[:len(st.rows)]) or any(h and g for h, g in zip(st.has_bias, nn[len(st.rows):]))
-                 for st, nn in zip(sts, (na, nb))]
-        if (ops.WGRAD_PAIR and all(wants) and gya is not None and gyb is not None and dt in (torch.bfloat16, torch.float16)
-                and xa.shape[0] > 0 and xb.shape[0] > 0):
-            # both sides' backward passes in one launch: with the data gradients when both want them and the one-pass
-            # kernel covers both shapes, else the weight / bias gradients only
-            k = int(xa.shape[1])
-            ms = [int(st.w.shape[0]) for st in sts]
-            dx = (ops.FUSED_WGRAD_DX and need[0] and need[1] and all(linear_wgrad_dx_supported(m, k, dt) for m in ms))
-            if dx or all(linear_wgrad_supported(m, k, dt) for m in ms):
-                for st in sts:
-                    if dx and st.wt_of.key != st.w_key:
-                        raise RuntimeError("the projection weights changed between this forward and its backward "
-                                           "(optimizer step in between?): run backward before stepping")
-                gya, gyb = _grad_rows(gya, dt), _grad_rows(gyb, dt)
-                bias = [any(h and g for h, g in zip(st.has_bias, nn[len(st.rows):])) for st, nn in zip(sts, (na, nb))]
-                pre = linear_wgrad_pair_launch([(gya, xa, sts[0].wt_of.wt if dx else None, bias[0]),
-                                                (gyb, xb, sts[1].wt_of.wt if dx else None, bias[1])], dx)
-                if not dx and need[0] and need[1] and all(linear_supported(m, k, dt) for m in ms):
-                    # the two data gradients the one-pass kernel does not cover (a first layer reads K = 256): one launch
-                    for st in sts:
-                        if st.wt_of.key != st.w_key:
-                            raise RuntimeError("the projection weights changed between this forward and its backward "
-                                               "(optimizer step in between?): run backward before stepping")
-                    gxa, gxb = linear_fwd_pair_launch(gya, sts[0].wt_of.wt, gyb, sts[1].wt_of.wt)
-                    pre = [(gxa,) + tuple(pre[0][1:]), (gxb,) + tuple(pre[1][1:])]
-        ra = _linear_backward(sts[0], xa, gya, need[0], na, pre[0])
-        rb = _linear_backward(sts[1], xb, gyb, need[1], nb, pre[1])
-        return (ra[0], rb[0], None, None) + ra[2:] + rb[2:]
+    def backward(ctx, *gys):
+        xs, sts, need = ctx.saved_tensors, ctx.sides, ctx.needs_input_grad
+        split = 4 + 2 * len(sts[0].rows)
+        needs = (need[4:split], need[split:])
+        wants = [st.wants(nn) for st, nn in zip(sts, needs)]
+        dt = xs[0].dtype
+        pair = backward_pair_plan(int(xs[0].shape[1]), [int(st.pack.w.shape[0]) for st in sts], [x.shape[0] for x in xs], dt,
+                                  need[:2], [w or b for w, b in wants], all(g is not None for g in gys))
+        done = [(None, None, None)] * 2
+        if pair:
+            gys = [_grad_rows(g, dt) for g in gys]
+            dx = pair == "one_pass"
+            done = linear_wgrad_pair_launch([(g, x, st.weights("wt") if dx else None, wb[1])
+                                             for g, x, st, wb in zip(gys, xs, sts, wants)], dx)
+            if pair == "wgrad+dx":
+                gxs = linear_fwd_pair_launch(gys[0], sts[0].weights("wt"), gys[1], sts[1].weights("wt"))
+                done = [(gx,) + d[1:] for gx, d in zip(gxs, done)]
+        (gxa, ga), (gxb, gb) = [_projection_backward(st, x, g, nx, nn, d)
+                                for st, x, g, nx, nn, d in zip(sts, xs, gys, need, needs, done)]
+        return (gxa, gxb, None, None) + ga + gb
 
 
 def linear_pair(xa: Tensor, wa, ba, xb: Tensor, wb, bb) -> Tuple[Tensor, Tensor]:
     """``(linear(xa, wa, ba), linear(xb, wb, bb))`` -- as ONE launch when both are 2-D activations of the same dtype and
     width on the MFMA kernels (a hetero layer's transcript and boundary projections, ``lin_last`` of both node types)."""
-    tup = lambda v: tuple(v) if isinstance(v, (list, tuple)) else (v,)
-    wa, ba, wb, bb = tup(wa), tup(ba), tup(wb), tup(bb)
+    wa, ba, wb, bb = _seq(wa), _seq(ba), _seq(wb), _seq(bb)
     ma, mb = sum(int(w.shape[0]) for w in wa), sum(int(w.shape[0]) for w in wb)
     ok = (ops.LINEAR_PAIR and xa.dim() == 2 and xb.dim() == 2 and xa.is_cuda and xb.is_cuda and xa.dtype == xb.dtype
           and xa.dtype in (torch.bfloat16, torch.float16)
@@ -475,8 +504,7 @@ def linear(x: Tensor, weight, bias) -> Tensor:
     stacked by rows into one GEMM (``[lin_l | lin_r | ...](x)``).  Activations with a covered (K, M) use the MFMA
     kernels -- bf16 / f16 on v_mfma_f32_32x32x16, fp32 (the reference's arithmetic width) on the exact-fp32
     v_mfma_f32_32x32x2_f32 -- and only uncovered shapes fall to the vendor GEMM."""
-    weights = tuple(weight) if isinstance(weight, (list, tuple)) else (weight,)
-    biases = tuple(bias) if isinstance(bias, (list, tuple)) else (bias,)
+    weights, biases = _seq(weight), _seq(bias)
     if len(biases) != len(weights):
         raise ValueError("linear: one bias (or None) per weight")
     lead = x.shape[:-1]

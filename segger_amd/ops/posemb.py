@@ -8,7 +8,7 @@ from torch import Tensor
 from .. import _lib
 from .._lib import DTYPE_CODE
 from .. import ops                # route switches: read as ops.NAME when called, never bound here
-from ._common import _defer_keep, _rows
+from ._common import _defer_keep, _grad_rows, _rows
 from .packs import _pack_for
 from .linear import (linear_f32_act_launch, linear_f32_gate_launch, linear_f32_gate_supported, linear_fwd_launch,
                      linear_supported, linear_wgrad_launch, linear_wgrad_supported)
@@ -242,9 +242,7 @@ class _PosMlp(torch.autograd.Function):
             return (None,) * 13
         if pre is not None and not ctx.by_pre:               # the output was gelu(embedder output)
             gpe = torch.ops.aten.gelu_backward(gpe.to(dt), pre)
-        g = gpe.to(dt).reshape(-1, d)
-        if g.shape[0] > 1 and g.stride(1) != 1:
-            g = g.contiguous()
+        g = _grad_rows(gpe.reshape(-1, d), dt)
         if ctx.pk2.key != ctx.key2:
             raise RuntimeError("the positional MLP's weights changed between this forward and its backward")
         need = ctx.needs_input_grad
@@ -349,9 +347,7 @@ class _PosMlpPair(torch.autograd.Function):
         def rows(g):
             if g is None:
                 return None, d, 0
-            g = g.to(dt).reshape(-1, d)
-            if g.shape[0] > 1 and g.stride(1) != 1:
-                g = g.contiguous()
+            g = _grad_rows(g.reshape(-1, d), dt)
             gp, ldg = _rows(g, d, "g")
             return (g, gp), ldg, int(g.shape[0])
         ga, lda, na = rows(gpre_a)

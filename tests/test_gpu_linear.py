@@ -570,3 +570,87 @@ def test_linear_f32_gate_epilogue(cuda, k, m, n, split, kind, monkeypatch):
     #  absolute error into a product whose own size vanishes)
     bound = x.double().abs() @ w.double().abs().t()
     assert ((y.double() - ref).abs() / (bound + 1e-6)).max().item() < 2e-5
+
+
+@pytest.mark.parametrize("k,ma,mb,na,nb", [(128, 384, 128, 257, 7), (256, 384, 128, 130, 1)])
+def test_linear_pair_backward_switches(cuda, monkeypatch, k, ma, mb, na, nb):
+    """``ops.linear_pair`` forward + backward with WGRAD_PAIR off, and with LINEAR_PAIR off, against both on: outputs and
+    every gradient bit for bit (the paired launches run the single launches' arithmetic, test_linear_pair_equals_two_launches).
+    K = 128: one paired backward launch with the data gradients; K = 256 (the one-pass kernel does not cover it): one without
+    them.  A side none of whose parameters wants a gradient: no paired backward launch, gradients equal to two ``ops.linear``."""
+    import importlib
+    from segger_amd import ops
+    lin = importlib.import_module("segger_amd.ops.linear")
+    launches, real = [], lin.linear_wgrad_pair_launch
+    monkeypatch.setattr(lin, "linear_wgrad_pair_launch", lambda sides, dx: (launches.append(dx), real(sides, dx))[1])
+    g = torch.Generator().manual_seed(k + na)
+    xa0, xb0 = torch.randn(na, k, generator=g).bfloat16(), torch.randn(nb, k, generator=g).bfloat16()
+    ws = [torch.randn(m, k, generator=g) * 0.05 for m in [ma // 3] * 3 + [mb]]
+    bs = [torch.randn(w.shape[0], generator=g) for w in ws]
+
+    def run(b_params=True, one_call=True):
+        del launches[:]
+        xa, xb = xa0.to(cuda).requires_grad_(True), xb0.to(cuda).requires_grad_(True)
+        w = [t.to(cuda).requires_grad_(b_params or i < 3) for i, t in enumerate(ws)]
+        b = [t.to(cuda).requires_grad_(b_params or i < 3) for i, t in enumerate(bs)]
+        if one_call:
+            ya, yb = ops.linear_pair(xa, w[:-1], b[:-1], xb, w[-1], b[-1])
+        else:
+            ya, yb = ops.linear(xa, w[:-1], b[:-1]), ops.linear(xb, w[-1], b[-1])
+        (ya.float().square().sum() + yb.float().sum()).backward()
+        return [ya.detach(), yb.detach(), xa.grad, xb.grad] + [t.grad for t in w] + [t.grad for t in b]
+
+    def same(got, want):
+        assert len(got) == len(want)
+        for a, r in zip(got, want):
+            assert (a is None and r is None) or torch.equal(a, r)
+
+    both = run()
+    assert launches == [k == 128] and all(t is not None for t in both)
+    for name in ("WGRAD_PAIR", "LINEAR_PAIR"):
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, name, False)
+            off = run()
+        assert not launches, name
+        same(off, both)
+    one_sided = run(b_params=False)
+    assert not launches and one_sided[-1] is None and one_sided[7] is None and one_sided[3] is not None
+    same(one_sided, run(b_params=False, one_call=False))
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_linear_backward_needs_only_what_is_asked(cuda, dtype):
+    """``ops.linear`` (three stacked weights and biases, K = 128 -> M = 384, 17 rows) when only the input, only the weights,
+    or only one of the three biases wants a gradient: each gradient asked for equals the one of the run where everything
+    does, bit for bit, and nothing else is returned.  The data: small integers, every product and sum exactly representable,
+    so the comparison does not hang on the order of summation -- a lone data gradient comes from another kernel (the forward
+    kernel on W^T) than the one-pass backward's (test_linear_autograd_fused_equals_separate_kernels: within one rounding on
+    50 003 random rows; on 17 random rows the two agreed bit for bit as well)."""
+    from segger_amd import ops
+    k, m, n = 128, 384, 17
+    r = torch.arange(n, device=cuda)
+    x0 = ((r[:, None] * 2 + torch.arange(k, device=cuda)[None] * 11) % 5 - 2).to(dtype)
+    gy = ((r[:, None] * 3 + torch.arange(m, device=cuda)[None] * 5) % 7 - 3).to(dtype)
+    w0 = ((torch.arange(m, device=cuda)[:, None] * 7 + torch.arange(k, device=cuda)[None] * 3) % 5 - 2).float()
+    b0 = (torch.arange(m, device=cuda) % 9 - 4).float()
+
+    def run(need_x, need_w, need_b):
+        x = x0.clone().requires_grad_(need_x)
+        w = [w0[i * 128:(i + 1) * 128].clone().requires_grad_(need_w) for i in range(3)]
+        b = [b0[i * 128:(i + 1) * 128].clone().requires_grad_(i in need_b) for i in range(3)]
+        ops.linear(x, w, b).backward(gy)
+        return [x.grad] + [t.grad for t in w] + [t.grad for t in b]
+
+    full = run(True, True, (0, 1, 2))
+    assert all(t is not None for t in full)
+    assert torch.equal(full[0], (gy.float() @ w0).to(dtype))          # (exact in fp32; one rounding to the storage dtype)
+    assert torch.equal(torch.cat(full[1:4]), gy.float().t() @ x0.float()) and torch.equal(torch.cat(full[4:]), gy.float().sum(0))
+    for asked in ((True, False, ()), (False, True, ()), (False, False, (1,))):
+        got = run(*asked)
+        want = [asked[0]] + [asked[1]] * 3 + [i in asked[2] for i in range(3)]
+        for i, (t, ref, w_) in enumerate(zip(got, full, want)):
+            if w_:
+                print(asked, i, "max |diff| to the all-gradients run:", float((t.float() - ref.float()).abs().max()))
+                assert torch.equal(t, ref), (asked, i)
+            else:
+                assert t is None, (asked, i)

@@ -414,6 +414,140 @@ def test_front_plan_truth_table(monkeypatch):
     assert plan(bf, 1_000_000) == big
 
 
+def test_projection_backward_plan_truth_table(monkeypatch):
+    """``ops.linear.backward_plan`` / ``backward_pair_plan``: the kernels of a projection backward from shapes, needs, dtype
+    and the ``ops`` switches alone (no tensor, no launch, no GPU).  Expected values: the conditions of the four autograd nodes
+    as they stood before the plan existed -- one pass (dX, dW, db from one read of dY): FUSED_WGRAD_DX, the input and a
+    parameter want gradients, rows > 0, 16-bit and a covered (M, K); else dX by the fp32 gate epilogue (first layer, fp32,
+    ``pre`` wants the gradient, aligned rows), the fp32 split (fp32, aligned rows, covered), the MFMA forward kernel on W^T, or
+    -- generic site only -- the vendor GEMM; dW / db by the MFMA weight-gradient kernel (generic site: rows > 0 and covered,
+    else vendor GEMM + colsum).  (M, K) = (192, 96) is covered by nothing, K = 256 not by the one-pass kernel."""
+    import importlib
+    from segger_amd import ops
+    lin = importlib.import_module("segger_amd.ops.linear")
+    P, bf, f32 = lin.BackwardPlan, torch.bfloat16, torch.float32
+    covered = ((384, 128), (128, 128), (64, 128))
+    # what the hand-written expectations below rest on
+    for m, k in covered:
+        assert ops.linear_wgrad_dx_supported(m, k, bf) and not ops.linear_wgrad_dx_supported(m, k, f32)
+        assert ops.linear_f32_gate_supported(m, k) and ops.linear_supported(m, k, f32) and ops.linear_wgrad_supported(m, k, f32)
+    assert [ops.linear_wgrad_dx_gate_supported(m, k, bf) for m, k in covered] == [True, True, False]
+    assert [ops.linear_f32_split_supported(m, k) for m, k in covered] == [True, True, False]
+    for dt in (bf, f32):
+        assert not ops.linear_wgrad_dx_supported(384, 256, dt) and ops.linear_supported(384, 256, dt)
+        assert ops.linear_wgrad_supported(384, 256, dt) and not ops.linear_supported(192, 96, dt)
+        assert not ops.linear_wgrad_supported(192, 96, dt) and not ops.linear_wgrad_dx_supported(192, 96, dt)
+    assert not ops.linear_f32_split_supported(384, 256) and not ops.linear_f32_gate_supported(384, 256)
+
+    def plan(site, mk, dt, need_x=True, want_w=True, want_b=None, n=1000, pre=False, pre_grad=None, aligned=True, **kw):
+        want_b = (site == "generic") if want_b is None else want_b          # (the first layer's nodes have no bias of their own)
+        return lin.backward_plan(mk[0], mk[1], n, dt, need_x, want_w, want_b, pre, pre if pre_grad is None else pre_grad,
+                                 aligned, site=site, **kw)
+
+    def table():
+        """{case: (the plan at the current switches, the plan expected at the default switches)}"""
+        t = {}
+        for mk in covered:
+            split = "f32_split" if mk != (64, 128) else "mfma"
+            gate = mk != (64, 128)
+            # generic site, 16-bit: one pass whenever the input and a parameter want gradients
+            t["g16 all", mk] = plan("generic", mk, bf), P("one_pass", "one_pass", False, True, True)
+            t["g16 x+w", mk] = plan("generic", mk, bf, want_b=False), P("one_pass", "one_pass", False, True, False)
+            t["g16 x+b", mk] = plan("generic", mk, bf, want_w=False), P("one_pass", "one_pass", False, False, True)
+            t["g16 x", mk] = plan("generic", mk, bf, want_w=False, want_b=False), P("mfma", None)
+            t["g16 w", mk] = plan("generic", mk, bf, need_x=False, want_b=False), P(None, "mfma", False, True, False)
+            t["g16 b", mk] = plan("generic", mk, bf, need_x=False, want_w=False), P(None, "mfma", False, False, True)
+            t["g16 none", mk] = plan("generic", mk, bf, need_x=False, want_w=False, want_b=False), P()
+            t["g16 n=0", mk] = plan("generic", mk, bf, n=0), P("mfma", "vendor", False, True, True)
+            t["g16 paired", mk] = plan("generic", mk, bf, need_x=False, have_dw=True), P(None, None, False, True, True)
+            # generic site, fp32: no one-pass kernel; the split where it covers the shape and dY's rows are aligned
+            t["g32 all", mk] = plan("generic", mk, f32), P(split, "mfma", False, True, True)
+            t["g32 unaligned", mk] = plan("generic", mk, f32, aligned=False), P("mfma", "mfma", False, True, True)
+            t["g32 x", mk] = plan("generic", mk, f32, want_w=False, want_b=False), P(split, None)
+            t["g32 n=0", mk] = plan("generic", mk, f32, n=0), P(split, "vendor", False, True, True)
+            for site in ("first", "row_bias"):
+                # 16-bit: one pass, gelu'(pre) inside it where the gated kernel covers the shape
+                t[site, "16 pre", mk] = plan(site, mk, bf, pre=True), P("one_pass", "one_pass", gate, True, False)
+                t[site, "16", mk] = plan(site, mk, bf), P("one_pass", "one_pass", False, True, False)
+                t[site, "16 x", mk] = plan(site, mk, bf, want_w=False, pre=True), P("mfma", None)
+                t[site, "16 w", mk] = plan(site, mk, bf, need_x=False, pre=True), P(None, "mfma", False, True, False)
+                t[site, "16 n=0", mk] = plan(site, mk, bf, n=0, pre=True), P("mfma", "mfma", False, True, False)
+            # fp32: the first-layer node has the gate epilogue and the split, the row-bias node neither
+            t["first 32 pre", mk] = plan("first", mk, f32, pre=True), P("f32_gate", "mfma", True, True, False)
+            t["first 32 pre const", mk] = plan("first", mk, f32, pre=True, pre_grad=False), P(split, "mfma", False, True, False)
+            t["first 32", mk] = plan("first", mk, f32), P(split, "mfma", False, True, False)
+            t["first 32 unaligned", mk] = plan("first", mk, f32, pre=True, aligned=False), P("mfma", "mfma", False, True, False)
+            t["first 32 n=0", mk] = plan("first", mk, f32, pre=True, n=0), P("f32_gate", "mfma", True, True, False)
+            t["row_bias 32 pre", mk] = plan("row_bias", mk, f32, pre=True), P("mfma", "mfma", False, True, False)
+            t["row_bias 32", mk] = plan("row_bias", mk, f32), P("mfma", "mfma", False, True, False)
+        for dt in (bf, f32):
+            for n in (0, 1000):
+                # K = 256: the MFMA kernels, one per output; (192, 96): the generic site's vendor routes
+                t["g K256", dt, n] = plan("generic", (384, 256), dt, n=n), P("mfma", "mfma" if n else "vendor", False, True, True)
+                t["g 192x96", dt, n] = plan("generic", (192, 96), dt, n=n), P("vendor", "vendor", False, True, True)
+                for site in ("first", "row_bias"):        # (no vendor route: entered through embed_linear_supported only)
+                    for mk in ((384, 256), (192, 96)):
+                        t[site, mk, dt, n] = plan(site, mk, dt, n=n, pre=True), P("mfma", "mfma", False, True, False)
+            t["g 192x96 b", dt] = plan("generic", (192, 96), dt, need_x=False, want_w=False), P(None, "vendor", False, False, True)
+            t["g 192x96 x", dt] = plan("generic", (192, 96), dt, want_w=False, want_b=False), P("vendor", None)
+        return t
+
+    def plans():
+        return {case: got for case, (got, _) in table().items()}
+
+    for case, (got, want) in table().items():
+        assert got == want, case
+    base = plans()
+
+    def changed(name, edit):
+        """With switch ``name`` off every plan equals ``edit(case, default plan)`` (None: unchanged) -- and at least one differs."""
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, name, False)
+            now = plans()
+        n_changed = 0
+        for case, was in base.items():
+            want = edit(case, was) or was
+            assert now[case] == want, (name, case)
+            n_changed += want != was
+        assert n_changed, name
+
+    # FUSED_WGRAD_DX: every one-pass plan becomes the MFMA forward kernel on W^T + the MFMA weight-gradient kernel, ungated
+    changed("FUSED_WGRAD_DX", lambda c, p: p._replace(dx="mfma", dw="mfma", gate=False) if p.dx == "one_pass" else None)
+    # FUSED_GELU_GATE: only the gate of a one-pass plan
+    changed("FUSED_GELU_GATE", lambda c, p: p._replace(gate=False) if p.dx == "one_pass" else None)
+    # F32_SPLIT: the split data gradients go to the exact kernel; the gate epilogue keeps only the exact kernel's shapes (its
+    # x operand [n, 384] is not one of them)
+    changed("F32_SPLIT", lambda c, p: p._replace(dx="mfma", gate=False)
+            if p.dx == "f32_split" or (p.dx == "f32_gate" and c[-1] == (384, 128)) else None)
+    # F32_GATE_EPILOGUE: the gated data gradient falls to the split (or, uncovered, to the exact kernel), ungated
+    changed("F32_GATE_EPILOGUE", lambda c, p: p._replace(dx="mfma" if c[-1] == (64, 128) else "f32_split", gate=False)
+            if p.dx == "f32_gate" else None)
+
+    # ---- the pair: (K, (Ma, Mb)) with rows (257, 7)
+    def pair(k, ms=(384, 128), dt=bf, ns=(257, 7), need_xs=(True, True), wants=(True, True), have_grads=True):
+        return lin.backward_pair_plan(k, ms, ns, dt, need_xs, wants, have_grads)
+
+    def pair_table():
+        return [pair(128), pair(256), pair(128, need_xs=(True, False)), pair(256, need_xs=(False, False)),
+                pair(128, dt=f32), pair(256, dt=f32), pair(128, wants=(True, False)), pair(128, wants=(False, True)),
+                pair(128, ns=(257, 0)), pair(128, have_grads=False), pair(96, ms=(192, 192)), pair(128, dt=torch.float16)]
+
+    default = ["one_pass", "wgrad+dx", "wgrad", "wgrad", None, None, None, None, None, None, None, "one_pass"]
+    assert pair_table() == default
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "WGRAD_PAIR", False)
+        assert pair_table() == [None] * len(default)
+        assert plans() == base                                # (the per-side plans do not read it)
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "FUSED_WGRAD_DX", False)
+        assert pair_table() == ["wgrad+dx" if p == "one_pass" else p for p in default]
+    for name in ("FUSED_GELU_GATE", "F32_SPLIT", "F32_GATE_EPILOGUE"):
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, name, False)
+            assert pair_table() == default, name
+    assert pair_table() == default and plans() == base
+
+
 def _load_bench():
     import importlib.util
     spec = importlib.util.spec_from_file_location("segger_bench", os.path.join(ROOT, "bench.py"))
