@@ -1076,6 +1076,56 @@ int segger_assign_update(const int64_t* tx_index, const int64_t* seg, const floa
 int segger_assign_finalize(const uint64_t* best_key, int64_t n_tx, float* similarity_out, uint8_t* seen_out,
                            segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Expression matrix of a segmentation: cell x gene counts of the segmented transcripts, in canonical CSR, with the
+ * per-pair mean similarity and the per-cell row count and mean position.  Replaces the filter + polars group-by +
+ * scipy coo_matrix(...).tocsr() of ISTSegmentationWriter.write_anndata (src/segger/data/writer.py:91-129) and
+ * anndata_from_transcripts (src/segger/data/utils/anndata.py:18-102).
+ * Purely additive: two new symbols, no existing signature or struct changes, so SEGGER_ABI_VERSION stays 32.
+ *
+ * Inputs over the n_rows deduplicated transcripts of a slide (0 <= n_rows < 2^31), in ascending row_index:
+ *   cell [n_rows] int32 (-1 = unassigned), gene [n_rows] int32, similarity [n_rows] fp32,
+ *   threshold [n_rows] fp64 (the similarity_threshold column; NaN = the gene has no threshold),
+ *   xy [n_rows, 2] fp32 or NULL;  1 <= n_cells < 2^31, 1 <= n_genes < 2^31 (ids are int32; n_cells * n_genes < 2^63).
+ * A row is KEPT iff cell >= 0 && (double)similarity >= threshold: a NaN on either side is not kept, equality is.  A kept
+ * row with cell >= n_cells or gene outside [0, n_genes) is never used as an index: it is counted in n_bad and takes no
+ * part in any other output.
+ *
+ * Outputs, caller-allocated at their upper bounds, the real sizes in counters [5] uint64 =
+ * {n_kept, nnz, n_cells_present, n_genes_present, n_bad} (n_kept counts the in-range kept rows):
+ *   cell_ids [min(n_rows, n_cells)] int32        ascending cells that own a kept row       (n_cells_present entries)
+ *   gene_ids [min(n_rows, n_genes)] int32        ascending genes that own a kept row       (n_genes_present entries)
+ *   indptr [min(n_rows, n_cells) + 1] int64      CSR row pointers                          (n_cells_present + 1 entries)
+ *   indices [n_rows] int32                       POSITION IN gene_ids, strictly ascending inside a row  (nnz entries)
+ *   counts [n_rows] int32                        kept rows of the (cell, gene) pair        (nnz entries)
+ *   mean_similarity [n_rows] fp64                mean similarity of the pair               (nnz entries)
+ *   cell_count [min(n_rows, n_cells)] int64      kept rows of the cell                     (n_cells_present entries)
+ *   centroid [min(n_rows, n_cells), 2] fp64      mean xy of the cell; NULL exactly when xy is NULL
+ * Entries past the real sizes are not written.
+ *
+ * Route: key = (cell << bit_length(n_genes - 1)) | gene per kept row, the sentinel n_cells << bit_length(n_genes - 1) for
+ * the others; one stable radix sort over bit_length(sentinel) bits with the row position as value; a compaction of the run
+ * heads; one lane per run (runs of up to 64 rows, summed first row to last) or one wave per run (longer: lane l sums
+ * rows l, l + 64, ... and the 64 partial sums meet in a fixed butterfly); the same reduction over the rows of a cell in
+ * sorted order (gene by gene, ascending row position) for cell_count and centroid.
+ * Arithmetic: counts and indices are exact; sums are float64; every output is a function of the inputs alone -- the same
+ * bits from run to run and for any launch geometry.  No floating-point atomics; integer atomics only count.
+ *
+ * Workspace: segger_expression_workspace_bytes (28 bytes per row + 8 per cell + 8 per gene + the radix sort's storage),
+ * 256-byte aligned; a negative SEGGER_E* code for sizes a build would reject.  n_rows == 0 launches nothing: the
+ * caller's zeroed counters and indptr[0] are the result (both must be given; every other pointer is ignored).  Otherwise
+ * the build zeroes counters itself, every call.
+ * Rejected on the host with SEGGER_EINVAL, nothing launched: a NULL pointer (xy and centroid excepted, as a pair), a
+ * misaligned pointer, n_rows < 0 or >= 2^31, n_cells < 1, n_genes < 1, an overflowing n_cells * n_genes; a workspace
+ * below segger_expression_workspace_bytes gives SEGGER_EWORKSPACE.
+ * ---------------------------------------------------------------------- */
+int64_t segger_expression_workspace_bytes(int64_t n_rows, int64_t n_cells, int64_t n_genes);
+int segger_expression_build(const int32_t* cell, const int32_t* gene, const float* similarity, const double* threshold,
+                            const float* xy, int64_t n_rows, int64_t n_cells, int64_t n_genes, int32_t* cell_ids,
+                            int32_t* gene_ids, int64_t* indptr, int32_t* indices, int32_t* counts, double* mean_similarity,
+                            int64_t* cell_count, double* centroid, uint64_t* counters, void* workspace,
+                            size_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

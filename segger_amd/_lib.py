@@ -331,6 +331,9 @@ EXPORTS = {
                                         vp, vp, vp, vp, C.c_int64, vp, vp]),
     "segger_assign_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp]),
     "segger_assign_finalize": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
+    "segger_expression_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "segger_expression_build": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, C.c_size_t, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

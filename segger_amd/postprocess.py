@@ -18,6 +18,11 @@ large genes (every value is used), and similarity ties in the dedup go to the fi
 :class:`SegmentationAccumulator` is the streaming form of the first step: it keeps the best row per transcript on
 the device while the batches arrive (``csrc/assign.hip``: one 64-bit atomic max per row, no sort), so a slide's
 prediction rows never have to exist at once.
+
+:func:`expression_matrix` is the second artefact of ``segger segment``, ``segger_anndata.h5ad`` (``writer.py:91-129``,
+``data/utils/anndata.py:18-102``): the cell x gene counts of the segmented transcripts in canonical CSR, the per-pair mean
+similarity and the per-cell mean position, built on the device (``csrc/expression.hip``); :func:`expression_to_scipy`
+hands it to scipy / AnnData.
 """
 from __future__ import annotations
 
@@ -247,6 +252,110 @@ class SegmentationAccumulator:
     def segmentation(self, max_iter: int = 250) -> Dict[str, Tensor]:
         """The dict ``assign_transcripts_to_cells`` returns, through the same thresholds-and-join tail."""
         return _thresholds_and_join(self.result(), max_iter)
+
+    def expression(self, xy: Optional[Tensor] = None, max_iter: int = 250) -> Dict[str, Tensor]:
+        """``expression_matrix(self.segmentation(max_iter), xy)``: the count matrix of what has been fed so far."""
+        return expression_matrix(self.segmentation(max_iter), xy)
+
+
+EXPRESSION_COUNTERS = ("n_kept", "nnz", "n_cells_present", "n_genes_present", "n_bad")
+
+
+def expression_matrix(result: Dict[str, Tensor], xy: Optional[Tensor] = None, n_cells: Optional[int] = None,
+                      n_genes: Optional[int] = None) -> Dict[str, Tensor]:
+    """The cell x gene count matrix of the segmented transcripts of ``result`` (what ``assign_transcripts_to_cells`` or
+    ``SegmentationAccumulator.segmentation()`` returns), on the device (``segger_expression_build``).
+
+    A transcript is counted iff ``cell_encoding >= 0`` and ``similarity >= similarity_threshold`` (NaN on either side:
+    not counted; equality: counted).  ``xy`` is ``[n_transcripts_of_the_slide, 2]``, indexed by ``row_index``.
+    ``n_cells`` / ``n_genes`` are the id domains; they default to ``max + 1`` of the columns (one more wait for the
+    device).  Returns device tensors sliced to their real sizes:
+
+    * ``cell_ids`` int32, ``gene_ids`` int32: ascending ids that own at least one counted transcript;
+    * ``indptr`` int64, ``indices`` int32 (positions in ``gene_ids``, strictly ascending inside a row), ``counts`` int32:
+      canonical CSR, what ``coo_matrix(...).tocsr()`` + ``sort_indices()`` gives;
+    * ``mean_similarity`` float64 per stored entry, ``cell_count`` int64 per row;
+    * ``centroid`` float64 ``[n_cells_present, 2]``, only when ``xy`` is given;
+    * ``n_kept``: the number of counted transcripts (a Python int).
+
+    Sums are float64 in an order fixed by the row positions: every output has the same bits from run to run and however
+    the rows were fed.  Waits for the device exactly once, to read the five sizes; raises if a counted transcript has a
+    cell or gene id outside its domain (it is never used as an index)."""
+    from . import _lib as L
+    cols = [result[k] for k in ("cell_encoding", "gene", "similarity", "similarity_threshold")]
+    if not all(t.is_cuda for t in cols):
+        raise L.SeggerAmdError("expression_matrix runs on the MI355X only: there is no CPU fallback "
+                               "(tests/expression_cases.py holds the CPU oracle)")
+    dev = cols[0].device
+    n = int(cols[0].numel())
+    if any(int(t.numel()) != n for t in cols):
+        raise ValueError("expression_matrix: columns of different lengths")
+    if n >= (1 << 31):
+        raise ValueError("expression_matrix: 2^31 rows or more")
+    cell = cols[0].detach().to(torch.int32).contiguous().view(-1)
+    gene = cols[1].detach().to(torch.int32).contiguous().view(-1)
+    sim = cols[2].detach().to(torch.float32).contiguous().view(-1)
+    thr = cols[3].detach().to(torch.float64).contiguous().view(-1)
+    pts = None
+    if xy is not None:                                       # the gather by row_index is plumbing
+        pts = xy.detach().to(device=dev, dtype=torch.float32)[result["row_index"].to(dev)].contiguous()
+    if n_cells is None or n_genes is None:
+        top = torch.stack([cell.max(), gene.max()]).tolist() if n else [-1, -1]          # one sync, like result()
+        n_cells = max(int(top[0]) + 1, 1) if n_cells is None else n_cells
+        n_genes = max(int(top[1]) + 1, 1) if n_genes is None else n_genes
+    n_cells, n_genes = int(n_cells), int(n_genes)
+    lib = L.load()
+    ws_bytes = lib.segger_expression_workspace_bytes(n, n_cells, n_genes)
+    L.check(min(ws_bytes, 0), "segger_expression_workspace_bytes")
+    cap_c, cap_g = min(n, n_cells), min(n, n_genes)
+    i32 = dict(dtype=torch.int32, device=dev)
+    cell_ids, gene_ids = torch.empty(cap_c, **i32), torch.empty(cap_g, **i32)
+    indices, counts = torch.empty(n, **i32), torch.empty(n, **i32)
+    indptr = torch.empty(cap_c + 1, dtype=torch.int64, device=dev) if n else torch.zeros(1, dtype=torch.int64, device=dev)
+    mean = torch.empty(n, dtype=torch.float64, device=dev)
+    cell_count = torch.empty(cap_c, dtype=torch.int64, device=dev)
+    centroid = torch.empty(cap_c, 2, dtype=torch.float64, device=dev) if pts is not None else None
+    counters = torch.zeros(len(EXPRESSION_COUNTERS), dtype=torch.int64, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with L.on_device(dev):
+        rc = lib.segger_expression_build(cell.data_ptr(), gene.data_ptr(), sim.data_ptr(), thr.data_ptr(), L.ptr(pts), n,
+                                         n_cells, n_genes, cell_ids.data_ptr(), gene_ids.data_ptr(), indptr.data_ptr(),
+                                         indices.data_ptr(), counts.data_ptr(), mean.data_ptr(), cell_count.data_ptr(),
+                                         L.ptr(centroid), counters.data_ptr(), ws.data_ptr(), ws_bytes, L.stream_ptr(dev))
+    L.check(rc, "segger_expression_build")
+    n_kept, nnz, n_c, n_g, n_bad = counters.tolist()         # the one wait for the device
+    if n_bad:
+        raise L.SeggerAmdError(f"expression_matrix: {n_bad} segmented transcripts have a cell id outside [0, {n_cells}) or "
+                               f"a gene id outside [0, {n_genes}); they were counted nowhere")
+    out = {"cell_ids": cell_ids[:n_c], "gene_ids": gene_ids[:n_g], "indptr": indptr[:n_c + 1], "indices": indices[:nnz],
+           "counts": counts[:nnz], "mean_similarity": mean[:nnz], "cell_count": cell_count[:n_c], "n_kept": n_kept}
+    if centroid is not None:
+        out["centroid"] = centroid[:n_c]
+    return out
+
+
+def expression_to_scipy(expr: Dict[str, Tensor], obs=None, cell_id: str = "cell_id", cell_encoding: str = "cell_encoding"):
+    """-> ``(X, scores, obs_names, var_ids, X_spatial)``, the pieces ``AnnData(X=X, obs=..., var=..., layers={"scores":
+    scores}, obsm={"X_spatial": X_spatial})`` takes: ``X`` the counts and ``scores`` the mean similarities as
+    ``scipy.sparse.csr_matrix`` of one sparsity pattern (canonical: sorted, no duplicates), ``obs_names`` the cell ids
+    looked up in ``obs[[cell_id, cell_encoding]]`` as :func:`to_frame` does (the encodings themselves when ``obs`` is
+    None), ``var_ids`` the gene ids of the columns, ``X_spatial`` the centroids (None without ``xy``)."""
+    import numpy as np
+    import scipy.sparse as sp
+    enc = expr["cell_ids"].cpu().numpy()
+    var_ids = expr["gene_ids"].cpu().numpy()
+    indptr, indices = expr["indptr"].cpu().numpy(), expr["indices"].cpu().numpy()
+    shape = (enc.size, var_ids.size)
+    X = sp.csr_matrix((expr["counts"].cpu().numpy(), indices, indptr), shape=shape)
+    scores = sp.csr_matrix((expr["mean_similarity"].cpu().numpy(), indices.copy(), indptr.copy()), shape=shape)
+    if obs is not None:
+        import pandas as pd
+        lut = pd.Series(obs[cell_id].to_numpy(), index=obs[cell_encoding].to_numpy().astype(np.int64))
+        obs_names = lut.reindex(enc.astype(np.int64)).to_numpy()
+    else:
+        obs_names = enc
+    X_spatial = expr["centroid"].cpu().numpy() if "centroid" in expr else None
+    return X, scores, obs_names, var_ids, X_spatial
 
 
 def to_frame(result: Dict[str, Tensor], obs=None, cell_id: str = "cell_id", cell_encoding: str = "cell_encoding"):
