@@ -1126,6 +1126,61 @@ int segger_expression_build(const int32_t* cell, const int32_t* gene, const floa
                             int64_t* cell_count, double* centroid, uint64_t* counters, void* workspace,
                             size_t workspace_bytes, segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Per-gene similarity thresholds of a segmentation: min(Yen, Li) over the ASSIGNED rows (cell >= 0) of every gene.
+ * Replaces the per-gene polars loop of ISTSegmentationWriter.assign_transcripts_to_cells (src/segger/data/writer.py:
+ * 196-241) and the sorts / float64 copies of postprocess.per_gene_thresholds.  The reference's 10 M-per-gene
+ * subsampling (polars RNG) is not reproduced: every value is used.
+ * Purely additive: two new symbols, no existing signature or struct changes, so SEGGER_ABI_VERSION stays 32.
+ *
+ * Inputs over n_rows rows (0 <= n_rows < 2^31): similarity [n_rows] fp32, gene [n_rows] int32, cell [n_rows] int32
+ * (-1 = unassigned); 1 <= n_genes < 2^31 is the gene id domain; max_iter >= 1 (the reference gives up after 250).
+ * An assigned row with gene outside [0, n_genes) is counted in n_bad, an assigned in-range row with a NaN similarity in
+ * n_nan; neither is used as an index or takes part in any output.
+ *
+ * Outputs, dense over the gene ids, all [n_genes]: threshold fp64, yen fp64, li fp64, count int64 (assigned rows of
+ * the gene), converged uint8; counters [4] int64 = {n_assigned (the rows used), n_genes_present, n_bad, n_nan}, zeroed
+ * by the call.  A gene without a row: threshold = yen = li = NaN, count = 0, converged = 1.  Otherwise
+ *   yen: 256 bins over [min, max] (a gene of one value: [min - 0.5, max + 0.5]); edges lo + i * (hi - lo) / 256, edge
+ *        256 pinned to hi; a value is in bin i iff edge_i <= v < edge_{i+1}, the last bin closed (numpy.histogram);
+ *        pmf = counts / count; P1 = cumsum(pmf), P1sq = cumsum(pmf^2), P2sq = cumsum(pmf^2 reversed) reversed, each a
+ *        sequential float64 running sum; crit_i = log((1 / (P1sq_i * P2sq_{i+1})) * (P1_i * (1 - P1_i))^2), i < 255;
+ *        k = the first NaN of crit, else its first maximum (numpy.argmax); yen = (edge_k + edge_{k+1}) / 2.
+ *   li:  on a = v - min in float64: tol = half the smallest positive difference of consecutive sorted a (-0.0 and +0.0
+ *        are equal: no gap); t_next = mean(a), t_curr = -2 tol, calls = 1; while |t_next - t_curr| > tol: t_curr = t_next;
+ *        mean_back = mean(a <= t_curr), mean_fore = mean(a > t_curr); stop if mean_back == 0; t_next = (mean_back -
+ *        mean_fore) / (log mean_back - log mean_fore); if ++calls > max_iter the gene has FAILED (converged = 0) and
+ *        stops.  li = t_next + min; a gene of one value: li = min, converged = 1.
+ *   threshold = li < yen ? li : yen, also for a failed gene: the median back-fill of writer.py:238-241 is the caller's.
+ *
+ * Route: key = ((uint64)gene << 32) | ord(similarity) per used row (ord: the order-preserving uint32 image of the
+ * float's bits, b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000)), all ones for the others; ONE keys-only radix sort over
+ * 32 + bit_length(n_genes) bits -- the sorted keys are the data, there is no value array and no permutation; segment
+ * bounds from adjacent high words; float64 sums of a over chunks of SEGGER_THRESHOLDS_CHUNK sorted positions that lie
+ * inside one gene (thread t of 256 adds positions t, t + 256, ..., a fixed butterfly per wave, the four waves first to
+ * last) and a sequential prefix over a gene's chunks; then one workgroup per gene: Yen's counts are differences of
+ * binary-search positions of the 257 edges, a Li iteration is one binary search plus the chunk prefix plus a sum of
+ * fewer than SEGGER_THRESHOLDS_CHUNK rows.  Every output is a function of the multiset of used rows: the same bits
+ * from run to run and for any order of the rows.  No floating-point atomics; integer atomics count and take the minimum
+ * gap (as the bit pattern of a positive double).
+ *
+ * Workspace: segger_thresholds_workspace_bytes = 16 bytes per row (the keys, in and out of the sort) + the radix sort's
+ * own storage (histograms and, on gfx950, one more array of keys: 8 bytes per row) + 16 bytes per gene + 8 bytes per
+ * SEGGER_THRESHOLDS_CHUNK rows, each part rounded up to 256 bytes; 256-byte aligned; a negative SEGGER_E* code for
+ * sizes a build would reject.  With n_rows and n_genes below 2^31 the sum is below 2^37: it cannot overflow.
+ * n_rows == 0 is a no-op that fills the per-gene outputs with the values of a gene without a row and zeroes the counters:
+ * similarity, gene, cell and workspace are not looked at and may be NULL.
+ * Rejected on the host with SEGGER_EINVAL, nothing launched: n_rows < 0 or >= 2^31, n_genes < 1 or >= 2^31,
+ * max_iter < 1, workspace_bytes < 0, a NULL pointer, a misaligned pointer; a workspace below
+ * segger_thresholds_workspace_bytes gives SEGGER_EWORKSPACE.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_THRESHOLDS_CHUNK 1024
+int64_t segger_thresholds_workspace_bytes(int64_t n_rows, int64_t n_genes);
+int segger_thresholds_build(const float* similarity, const int32_t* gene, const int32_t* cell, int64_t n_rows,
+                            int64_t n_genes, int32_t max_iter, double* threshold, double* yen, double* li, int64_t* count,
+                            uint8_t* converged, int64_t* counters, void* workspace, int64_t workspace_bytes,
+                            segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -8,6 +8,6 @@ host-side mirrors of the reference's ``ISTEncoder`` and ``LitISTEncoder``.
 from .hetero import HeteroBatch, collate, TX_TX, TX_BD, TX_NB_BD  # noqa: F401
 from .ist_encoder import ISTEncoder, SkipGAT, Positional2dEmbedder, GATv2Conv  # noqa: F401
 from .lightning_model import LitISTEncoder  # noqa: F401
-from .postprocess import SegmentationAccumulator, expression_matrix, expression_to_scipy  # noqa: F401
+from .postprocess import SegmentationAccumulator, expression_matrix, expression_to_scipy, gene_thresholds  # noqa: F401
 
 __version__ = "0.1.0"

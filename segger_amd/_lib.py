@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEGGER_AMD_LIB selects another build of the same library (kernel A/B experiments)
 LIB_PATH = os.environ.get("SEGGER_AMD_LIB") or os.path.join(_HERE, "libsegger_amd.so")
 ABI_VERSION = 32
+THRESHOLDS_CHUNK = 1024          # SEGGER_THRESHOLDS_CHUNK: sorted positions per partial sum of segger_thresholds_build
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -334,6 +335,9 @@ EXPORTS = {
     "segger_expression_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "segger_expression_build": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp, C.c_size_t, vp]),
+    "segger_thresholds_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "segger_thresholds_build": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int64,
+                                          vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -2,7 +2,8 @@
 
 Restates ``ISTSegmentationWriter.assign_transcripts_to_cells`` (reference ``src/segger/data/writer.py:131-259``)
 as segmented tensor operations that run wherever the tensors live (on the MI355X for a 100 M-transcript slide:
-two stable sorts, one 2-D histogram, one vectorised fixed-point iteration -- no per-gene Python loop, no polars):
+two stable sorts, one 2-D histogram, one vectorised fixed-point iteration -- no per-gene Python loop, no polars;
+:func:`gene_thresholds` is the same threshold step as HIP kernels over one keys-only sort, ``thresholds="kernel"``):
 
 * best row per transcript over overlapping prediction tiles (``:186-190``: sort by row_index, similarity
   descending, keep the first);
@@ -136,17 +137,106 @@ def per_gene_thresholds(similarity: Tensor, gene: Tensor, assigned: Tensor, max_
     return genes, thr, converged, glob
 
 
+THRESHOLD_ROUTES = ("torch", "kernel")
+THRESHOLDS_COUNTERS = ("n_assigned", "n_genes_present", "n_bad", "n_nan")
+
+
+def _check_route(thresholds: str) -> None:
+    if thresholds not in THRESHOLD_ROUTES:
+        raise ValueError(f"thresholds must be one of {THRESHOLD_ROUTES}, got {thresholds!r}")
+
+
+def gene_thresholds(similarity: Tensor, gene: Tensor, cell_encoding: Tensor, n_genes: Optional[int] = None,
+                    max_iter: int = 250) -> Dict[str, Tensor]:
+    """``per_gene_thresholds`` on the device (``segger_thresholds_build``, ``csrc/thresholds.hip``): ``min(Yen, Li)`` per
+    gene over the rows with ``cell_encoding >= 0``, from one keys-only radix sort of ``(gene, similarity)`` -- 16 bytes of
+    workspace per row plus the sort's storage, where the torch route keeps over 60.
+
+    ``n_genes`` is the gene id domain (ids must fit int32); it defaults to ``max(gene) + 1`` (one more wait for the
+    device).  Returns tensors on the device, dense over the gene ids, ``[n_genes]``:
+
+    * ``threshold`` float64: ``min(yen, li)``, the median of the converged genes' thresholds for a gene whose Li iteration
+      failed, NaN for a gene without an assigned row;
+    * ``yen``, ``li`` float64: the two thresholds on their own (``li`` of a failed gene is its last iterate);
+    * ``count`` int64: assigned rows of the gene; ``converged`` bool (true for a gene without a row);
+    * ``global_threshold`` (a Python float, NaN when no gene has a threshold) and ``failed_genes`` int64, ascending.
+
+    Every value is used: the reference's 10 M-per-gene subsampling is not reproduced.  The same bits from run to run and
+    for any order of the rows.  Waits for the device once, to read the counters and the median (and once more when a
+    gene failed, to list it); raises if an assigned row has a gene id outside ``[0, n_genes)`` or a NaN similarity
+    (neither is ever used as an index)."""
+    from . import _lib as L
+    cols = [similarity, gene, cell_encoding]
+    if not all(t.is_cuda for t in cols):
+        raise L.SeggerAmdError("gene_thresholds runs on the MI355X only: there is no CPU fallback "
+                               "(per_gene_thresholds is the CPU form)")
+    dev = cols[0].device
+    n = int(cols[0].numel())
+    if any(int(t.numel()) != n for t in cols):
+        raise ValueError("gene_thresholds: columns of different lengths")
+    if n >= (1 << 31):
+        raise ValueError("gene_thresholds: 2^31 rows or more")
+    sim = similarity.detach().to(torch.float32).contiguous().view(-1)
+    g32 = gene.detach().to(torch.int32).contiguous().view(-1)
+    cell = cell_encoding.detach().view(-1)
+    if cell.dtype != torch.int32:                            # only the sign is read: wider encodings must not wrap
+        cell = (cell >= 0).to(torch.int32) - 1
+    cell = cell.contiguous()
+    if n_genes is None:
+        n_genes = max(int(g32.max()) + 1, 1) if n else 1
+    n_genes = int(n_genes)
+    lib = L.load()
+    ws_bytes = lib.segger_thresholds_workspace_bytes(n, n_genes)
+    L.check(min(ws_bytes, 0), "segger_thresholds_workspace_bytes")
+    f64 = dict(dtype=torch.float64, device=dev)
+    thr, yen, li = torch.empty(n_genes, **f64), torch.empty(n_genes, **f64), torch.empty(n_genes, **f64)
+    count = torch.empty(n_genes, dtype=torch.int64, device=dev)
+    conv = torch.empty(n_genes, dtype=torch.uint8, device=dev)
+    counters = torch.zeros(len(THRESHOLDS_COUNTERS), dtype=torch.int64, device=dev)
+    ws = torch.empty(ws_bytes if n else 0, dtype=torch.uint8, device=dev)
+    with L.on_device(dev):
+        rc = lib.segger_thresholds_build(L.ptr(sim) if n else None, L.ptr(g32) if n else None, L.ptr(cell) if n else None,
+                                         n, n_genes, int(max_iter), thr.data_ptr(), yen.data_ptr(), li.data_ptr(),
+                                         count.data_ptr(), conv.data_ptr(), counters.data_ptr(),
+                                         L.ptr(ws) if n else None, int(ws.numel()), L.stream_ptr(dev))
+    L.check(rc, "segger_thresholds_build")
+    del ws
+    converged = conv.bool()
+    # median of the converged present genes' thresholds and the back-fill: [n_genes] torch ops (plumbing)
+    voted = converged & (count > 0)
+    glob = torch.nanquantile(torch.where(voted, thr, torch.full_like(thr, float("nan"))), 0.5)
+    glob = torch.where((voted & thr.isnan()).any(), torch.full_like(glob, float("nan")), glob)     # quantile: a NaN wins
+    n_failed = (~converged).sum()
+    stats = torch.cat([counters.double(), n_failed.double().view(1), glob.view(1)]).tolist()       # the one wait
+    n_bad, n_nan, n_failed, glob_f = int(stats[2]), int(stats[3]), int(stats[4]), float(stats[5])
+    if n_bad or n_nan:
+        raise L.SeggerAmdError(f"gene_thresholds: {n_bad} assigned rows have a gene id outside [0, {n_genes}) and {n_nan} "
+                               f"a NaN similarity; they took part in nothing")
+    failed = (~converged).nonzero().squeeze(1) if n_failed else torch.empty(0, dtype=torch.int64, device=dev)
+    return {"threshold": torch.where(converged, thr, glob), "yen": yen, "li": li, "count": count, "converged": converged,
+            "global_threshold": glob_f, "failed_genes": failed}
+
+
 def assign_transcripts_to_cells(predictions: Sequence[Sequence[Tensor]], device=None,
-                                max_iter: int = 250) -> Dict[str, Tensor]:
+                                max_iter: int = 250, thresholds: str = "torch") -> Dict[str, Tensor]:
     """-> ``row_index`` (unique, ascending), ``cell_encoding`` (-1 = unassigned), ``similarity``, ``gene``,
     ``similarity_threshold`` (nan for genes without an assigned transcript), plus ``global_threshold`` and
     ``failed_genes``.  A transcript counts as segmented when ``similarity >= similarity_threshold``
-    (``writer.py:96-99``)."""
-    return _thresholds_and_join(best_assignment(predictions, device), max_iter)
+    (``writer.py:96-99``).  ``thresholds="kernel"`` computes the per-gene thresholds with :func:`gene_thresholds`
+    (device tensors only) instead of :func:`per_gene_thresholds`."""
+    _check_route(thresholds)
+    return _thresholds_and_join(best_assignment(predictions, device), max_iter, thresholds)
 
 
-def _thresholds_and_join(out: Dict[str, Tensor], max_iter: int) -> Dict[str, Tensor]:
+def _thresholds_and_join(out: Dict[str, Tensor], max_iter: int, thresholds: str = "torch") -> Dict[str, Tensor]:
     """The tail both entry points share: per-gene thresholds over the deduplicated rows, joined back by gene."""
+    _check_route(thresholds)
+    if thresholds == "kernel":                               # dense over the gene ids: the join is a gather
+        res = gene_thresholds(out["similarity"], out["gene"], out["cell_encoding"], None, max_iter)
+        out["similarity_threshold"] = res["threshold"][out["gene"].long()]
+        out["global_threshold"] = res["global_threshold"]
+        out["failed_genes"] = res["failed_genes"]
+        return out
     genes, thr, converged, glob = per_gene_thresholds(out["similarity"], out["gene"], out["cell_encoding"] >= 0, max_iter)
     t = torch.full(out["gene"].shape, float("nan"), dtype=torch.float64, device=out["gene"].device)
     if genes.numel():
@@ -249,13 +339,15 @@ class SegmentationAccumulator:
         row = seen.nonzero().squeeze(1)                      # the compaction to ascending row_index is plumbing
         return {"row_index": row, "cell_encoding": self.cell[row].long(), "similarity": sim[row], "gene": self.gene[row].long()}
 
-    def segmentation(self, max_iter: int = 250) -> Dict[str, Tensor]:
-        """The dict ``assign_transcripts_to_cells`` returns, through the same thresholds-and-join tail."""
-        return _thresholds_and_join(self.result(), max_iter)
+    def segmentation(self, max_iter: int = 250, thresholds: str = "torch") -> Dict[str, Tensor]:
+        """The dict ``assign_transcripts_to_cells`` returns, through the same thresholds-and-join tail
+        (``thresholds="kernel"``: :func:`gene_thresholds`)."""
+        _check_route(thresholds)
+        return _thresholds_and_join(self.result(), max_iter, thresholds)
 
-    def expression(self, xy: Optional[Tensor] = None, max_iter: int = 250) -> Dict[str, Tensor]:
-        """``expression_matrix(self.segmentation(max_iter), xy)``: the count matrix of what has been fed so far."""
-        return expression_matrix(self.segmentation(max_iter), xy)
+    def expression(self, xy: Optional[Tensor] = None, max_iter: int = 250, thresholds: str = "torch") -> Dict[str, Tensor]:
+        """``expression_matrix(self.segmentation(max_iter, thresholds), xy)``: the count matrix of what has been fed so far."""
+        return expression_matrix(self.segmentation(max_iter, thresholds), xy)
 
 
 EXPRESSION_COUNTERS = ("n_kept", "nnz", "n_cells_present", "n_genes_present", "n_bad")

@@ -83,6 +83,9 @@ def main():
                     help="with --graphed / --overlap-predict: repeat the sweep feeding a SegmentationAccumulator batch by "
                          "batch (predict_into) instead of collecting every batch's rows, and record seconds and peak bytes "
                          "of both post-processing paths and whether their results are equal")
+    ap.add_argument("--kernel-thresholds", action="store_true",
+                    help="with --stream-postprocess: the streamed path takes its per-gene thresholds from the HIP kernels "
+                         "(segmentation(thresholds='kernel')); equal_thresholds then compares them with the torch route's")
     ap.add_argument("--no-slide-csr", action="store_true",
                     help="sort the edges of every batch (5 radix sorts) instead of slicing the once-per-slide CSR views")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for dry runs)")
@@ -140,7 +143,7 @@ def main():
             for i in range(n_batches):
                 pool.predict_into(get_batch(i), acc)             # no sync inside the loop
         with Phase(f"{collected_name}_stream_postprocess_s", times):
-            seg = acc.segmentation()
+            seg = acc.segmentation(thresholds="kernel" if args.kernel_thresholds else "torch")
         peak = torch.cuda.max_memory_allocated() - base
         equal = all(torch.equal(seg[k], ref[k]) for k in ("row_index", "cell_encoding", "gene"))
         equal = equal and bool(((seg["similarity"] == ref["similarity"]) | (seg["similarity"].isnan() & ref["similarity"].isnan())).all())
@@ -151,6 +154,7 @@ def main():
                              "postprocess_seconds": times[f"{collected_name}_stream_postprocess_s"],
                              "sweep_and_postprocess_peak_bytes": peak, "state_bytes": 16 * args.n_tx + 16},
                 "equal_rows": bool(equal), "equal_thresholds": thr_equal,
+                "thresholds_route": "kernel" if args.kernel_thresholds else "torch",
                 "note": "peak bytes: torch.cuda.max_memory_allocated over sweep + post-processing minus the bytes allocated "
                         "when the sweep began; the streamed sweep's update() calls run inside sweep_seconds"}
     spec = SyntheticSpec(n_tx=args.n_tx, n_bd=args.n_bd, k_tx=args.k, seed=args.seed)
