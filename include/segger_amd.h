@@ -1181,6 +1181,58 @@ int segger_thresholds_build(const float* similarity, const int32_t* gene, const 
                             uint8_t* converged, int64_t* counters, void* workspace, int64_t workspace_bytes,
                             segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Boundary and gene features of a count matrix: the two kernels behind segger_amd.features.expression_features, which
+ * restates the reference's setup_anndata (src/segger/data/utils/anndata.py:184-259): normalize_total, np.corrcoef of
+ * the densified matrix, PCA of the correlation matrix (X_corr), PCA of the cells (X_pca).  Both the correlation and the
+ * covariance come from ONE second-moment matrix of the weighted sparse rows; nothing dense of size n_rows x n_cols
+ * exists anywhere.  csrc/features.hip.  Purely additive: four new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * The matrix is CSR as segger_expression_build leaves it: indptr [n_rows + 1] int64, indices [nnz] int32 strictly
+ * ascending inside a row, values [nnz] int32; row_weight [n_rows] fp64 (finite).  0 <= n_rows < 2^31,
+ * 1 <= n_cols <= SEGGER_FEATURES_MAX_COLS, nnz >= 0 (indices and values may be NULL when it is 0).  Row extents are
+ * clamped to [0, nnz] and a column outside [0, n_cols) is never used as an index.
+ *
+ * segger_sparse_gram:  S [n_cols, n_cols] fp64 = sum_r w_r^2 x_r x_r^T,  s [n_cols] fp64 = sum_r w_r x_r.
+ *   A row of weight 0 takes no part (this is how a caller restricts the sums to a subset of the rows).  Both triangles
+ *   of S are written; S[i, j] and S[j, i] have the same bits (the upper triangle is computed, then mirrored).
+ *   Route: one workgroup per pair (ti <= tj) of SEGGER_FEATURES_TILE-column tiles and per slab of rows; 32 rows at a time
+ *   are densified into zero-filled LDS tiles (entry * w_r; the start of a tile's range by binary search in the row) and
+ *   accumulated with v_mfma_f64_16x16x4_f64; each workgroup leaves one tile of partial sums and a second kernel adds the
+ *   slabs first to last.  segger_features_gram_slabs(n_rows, n_cols) = min(ceil(n_rows / SEGGER_FEATURES_SLAB_ROWS),
+ *   ceil(SEGGER_FEATURES_TARGET_GROUPS / n_pairs), SEGGER_FEATURES_MAX_SLABS), at least 1, n_pairs = t (t + 1) / 2,
+ *   t = ceil(n_cols / SEGGER_FEATURES_TILE); a slab is ceil(n_rows / slabs) rows rounded up to a multiple of 32.  The
+ *   slab count and every summation order are functions of (n_rows, n_cols) alone: the same bits from call to call and
+ *   on any stream.  No floating-point atomics, no scratch memory.  n_rows == 0 zeroes S and s without a kernel.
+ *   Workspace: segger_features_workspace_bytes(n_rows, n_cols) = slabs * (n_pairs * TILE^2 + t * TILE) * 8 bytes,
+ *   256-byte aligned: fewer than SEGGER_FEATURES_TARGET_GROUPS + n_pairs tiles of 32 KiB plus the column sums -- it
+ *   follows the number of column tiles, never n_rows * n_cols (33 MiB at 10^6 x 500).  Both size queries return a
+ *   negative SEGGER_E* code for sizes a call would reject.
+ *
+ * segger_sparse_project:  out [n_rows, k] = w_r * sum_j x_rj V[j, :] - offset,  V [n_cols, k] fp64 row-major,
+ *   offset [k] fp64, 1 <= k <= SEGGER_FEATURES_MAX_K, out fp32 (out_f64 = 0) or fp64 (out_f64 = 1).  One wave per row;
+ *   lane l owns columns l, l + 64, l + 128, l + 192 and adds the row's entries in CSR order with float64 FMAs, then
+ *   rounds fma(w_r, sum, -offset) once to the output type: bit-reproducible.  w_r == 0 gives exactly -offset.
+ *
+ * Rejected on the host with SEGGER_EINVAL, nothing launched: a NULL or misaligned pointer, n_rows < 0 or >= 2^31,
+ * n_cols < 1 or > SEGGER_FEATURES_MAX_COLS, nnz < 0, k outside 1 .. SEGGER_FEATURES_MAX_K, out_f64 other than 0 / 1,
+ * workspace_bytes < 0; a workspace below segger_features_workspace_bytes gives SEGGER_EWORKSPACE.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_FEATURES_TILE 64
+#define SEGGER_FEATURES_SLAB_ROWS 512
+#define SEGGER_FEATURES_MAX_SLABS 32
+#define SEGGER_FEATURES_TARGET_GROUPS 1024
+#define SEGGER_FEATURES_MAX_COLS 32768
+#define SEGGER_FEATURES_MAX_K 256
+int64_t segger_features_gram_slabs(int64_t n_rows, int64_t n_cols);
+int64_t segger_features_workspace_bytes(int64_t n_rows, int64_t n_cols);
+int segger_sparse_gram(const int64_t* indptr, const int32_t* indices, const int32_t* values, const double* row_weight,
+                       int64_t n_rows, int64_t n_cols, int64_t nnz, double* S, double* s, void* workspace,
+                       int64_t workspace_bytes, segger_stream_t stream);
+int segger_sparse_project(const int64_t* indptr, const int32_t* indices, const int32_t* values, const double* row_weight,
+                          int64_t n_rows, int64_t n_cols, int64_t nnz, const double* V, const double* offset, int32_t k,
+                          void* out, int32_t out_f64, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGGER_AMD_LIB") or os.path.join(_HERE, "libsegger_amd.so")
 ABI_VERSION = 32
 THRESHOLDS_CHUNK = 1024          # SEGGER_THRESHOLDS_CHUNK: sorted positions per partial sum of segger_thresholds_build
+FEATURES_TILE, FEATURES_SLAB_ROWS, FEATURES_MAX_SLABS = 64, 512, 32        # SEGGER_FEATURES_*: the geometry of segger_sparse_gram
+FEATURES_MAX_COLS, FEATURES_MAX_K = 32768, 256
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -338,6 +340,10 @@ EXPORTS = {
     "segger_thresholds_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "segger_thresholds_build": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int64,
                                           vp]),
+    "segger_features_gram_slabs": (C.c_int64, [C.c_int64, C.c_int64]),
+    "segger_features_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "segger_sparse_gram": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp]),
+    "segger_sparse_project": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None
