@@ -1233,6 +1233,69 @@ int segger_sparse_project(const int64_t* indptr, const int32_t* indices, const i
                           int64_t n_rows, int64_t n_cols, int64_t nnz, const double* V, const double* offset, int32_t k,
                           void* out, int32_t out_f64, segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Phenograph clustering: the kernels behind segger_amd.phenograph (knn_bruteforce, jaccard_graph, louvain), which
+ * restates the reference's phenograph_rapids (src/segger/data/utils/neighbors.py:18-51: cuML kneighbors, cuGraph jaccard,
+ * cuGraph louvain) without RAPIDS.  csrc/phenograph.hip.  Purely additive: six new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * segger_knn_bruteforce:  for every row of X [n, d] fp32 row-major its k nearest rows of X, ITSELF INCLUDED, as
+ *   idx [n, k] int32 and dist2 [n, k] fp32 (squared Euclidean), each row sorted by (dist2, idx).  1 <= n < 2^31,
+ *   1 <= d <= SEGGER_KNN_BF_MAX_D, 1 <= k <= min(SEGGER_KNN_BF_MAX_K, n); n * k may pass 2^31 (64-bit offsets).
+ *   Selection runs on the score (|a|^2 + |b|^2) - 2 a.b: the norms are fp32 FMA chains over ascending dimensions, the
+ *   inner products v_mfma_f32_16x16x4_f32 (an fp32 FMA chain in a fixed permutation of the dimensions, d padded with
+ *   zeros to 32 / 64 / 128 / 256), the score fmaf(-2, a.b, |a|^2 + |b|^2).  A workgroup of 512 threads owns 128 query
+ *   rows, resident in registers, against one slab of candidate rows staged 64 at a time through LDS; every query row
+ *   keeps its k smallest (score bits in float order, index) keys in the lanes of the wave that owns it and merges a tile
+ *   only when one of its 64 candidates beats the k-th (bitonic sort + merge in the wave).  The kept set is the k
+ *   smallest keys of the slab whatever the order of arrival.  segger_knn_bruteforce_slabs(n, d, k) = min(ceil(
+ *   SEGGER_KNN_BF_TARGET_GROUPS / ceil(n / 128)), floor(n / 128), SEGGER_KNN_BF_MAX_SLABS), at least 1; a slab is
+ *   ceil(n / slabs) rows rounded up to a multiple of 64, and the count returned is ceil(n / that).  The finish kernel
+ *   (one wave per row) merges the slabs' lists, recomputes the k distances as acc = fmaf(a_t - b_t, a_t - b_t, acc) over
+ *   t ascending and sorts.  No n x n or n x tile score matrix is written; no floating-point atomics; no scratch; no loop
+ *   bound depends on the data: the same bits from call to call and on any stream.  Rows that hold NaN are not supported.
+ *   Workspace: segger_knn_bruteforce_workspace_bytes(n, d, k) = n * 4 rounded up to 256, plus slabs * n * k * 8 bytes.
+ *
+ * segger_jaccard_weights:  weight [nnz] fp64 of every stored edge of a simple undirected graph in CSR (indptr [n + 1]
+ *   int64, indices [nnz] int32 ascending inside a row, both directions stored, no self-loops): |N[u] & N[v]| /
+ *   |N[u] | N[v]| over the CLOSED neighbourhoods N[x] = adj[x] + {x}.  One thread per edge finds its row by binary search
+ *   in indptr and merges the two adjacency lists (any degree); the weight is ONE fp64 division of the two integers, so
+ *   weight[u -> v] and weight[v -> u] have the same bits.
+ *
+ * segger_louvain_move:  one sub-round of synchronous local moving.  weight [nnz] and kdeg [n] (the weighted degree, self
+ *   weight included) are int64 fixed point (round(w * 2^32)); comm [n] int32, tot [n] int64 and size [n] int32 are the
+ *   community of every vertex and the degree sum and member count of every community.  For every vertex v with
+ *   v mod n_sub == sub, one wave evaluates g(c) = k_vc - (gamma * k_v) * tot_c / two_m in fp64 for the community c of
+ *   every neighbour (k_vc an exact integer sum; for v's own community tot excludes k_v), proposes the largest g, the
+ *   lowest c on a tie, only if it is strictly above staying, and never from a singleton into a singleton of a higher id;
+ *   all reads are of the state at entry.  A second kernel applies the proposals with integer atomics (exact in any
+ *   order).  The neighbour sums are quadratic in the degree inside the wave: correct for any degree, no fixed-size list.
+ *
+ * segger_louvain_modularity:  in_c [n] int64 = self_weight of the members + the stored edges inside the community
+ *   (integer atomics), then q[0] = sum_c in_c / two_m - (gamma * (tot_c / two_m)) * (tot_c / two_m) in fp64 by ONE
+ *   workgroup: thread t adds the terms t, t + 256, ... in turn, the 256 sums fold in halves.  A fixed order.
+ *
+ * Rejected on the host with SEGGER_EINVAL, nothing launched: a NULL or misaligned pointer, n, d or k out of range,
+ * k > n, nnz < 0, sub / n_sub out of range, two_m <= 0, gamma < 0, workspace_bytes < 0; a workspace below
+ * segger_knn_bruteforce_workspace_bytes gives SEGGER_EWORKSPACE.  The two size queries return the negative code.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_KNN_BF_MAX_D 256
+#define SEGGER_KNN_BF_MAX_K 64
+#define SEGGER_KNN_BF_TARGET_GROUPS 512
+#define SEGGER_KNN_BF_MAX_SLABS 32
+#define SEGGER_LOUVAIN_MAX_SUBROUNDS 64
+int64_t segger_knn_bruteforce_slabs(int64_t n, int32_t d, int32_t k);
+int64_t segger_knn_bruteforce_workspace_bytes(int64_t n, int32_t d, int32_t k);
+int segger_knn_bruteforce(const float* X, int64_t n, int32_t d, int32_t k, int32_t* idx, float* dist2, void* workspace,
+                          int64_t workspace_bytes, segger_stream_t stream);
+int segger_jaccard_weights(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, double* weight,
+                           segger_stream_t stream);
+int segger_louvain_move(const int64_t* indptr, const int32_t* indices, const int64_t* weight, const int64_t* kdeg, int64_t n,
+                        int64_t nnz, int32_t sub, int32_t n_sub, double gamma, double two_m, int32_t* comm, int64_t* tot,
+                        int32_t* size, int32_t* proposal, segger_stream_t stream);
+int segger_louvain_modularity(const int64_t* indptr, const int32_t* indices, const int64_t* weight, const int64_t* self_weight,
+                              const int32_t* comm, const int64_t* tot, int64_t n, int64_t nnz, double gamma, double two_m,
+                              int64_t* in_c, double* q, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

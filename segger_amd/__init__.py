@@ -9,6 +9,8 @@ from .hetero import HeteroBatch, collate, TX_TX, TX_BD, TX_NB_BD  # noqa: F401
 from .ist_encoder import ISTEncoder, SkipGAT, Positional2dEmbedder, GATv2Conv  # noqa: F401
 from .lightning_model import LitISTEncoder  # noqa: F401
 from .postprocess import SegmentationAccumulator, expression_matrix, expression_to_scipy, gene_thresholds  # noqa: F401
-from .features import expression_features, sparse_gram, sparse_project, cluster_cosine_similarity  # noqa: F401
+from .features import expression_features, sparse_gram, sparse_project, cluster_cosine_similarity, anndata_features  # noqa: F401
+from . import phenograph  # noqa: F401  (the module: its function of the same name stays segger_amd.phenograph.phenograph)
+from .phenograph import knn_bruteforce, jaccard_graph, louvain  # noqa: F401
 
 __version__ = "0.1.0"

@@ -19,6 +19,7 @@ ABI_VERSION = 32
 THRESHOLDS_CHUNK = 1024          # SEGGER_THRESHOLDS_CHUNK: sorted positions per partial sum of segger_thresholds_build
 FEATURES_TILE, FEATURES_SLAB_ROWS, FEATURES_MAX_SLABS = 64, 512, 32        # SEGGER_FEATURES_*: the geometry of segger_sparse_gram
 FEATURES_MAX_COLS, FEATURES_MAX_K = 32768, 256
+KNN_BF_MAX_D, KNN_BF_MAX_K, KNN_BF_MAX_SLABS = 256, 64, 32                  # SEGGER_KNN_BF_*: the range of segger_knn_bruteforce
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -344,6 +345,13 @@ EXPORTS = {
     "segger_features_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "segger_sparse_gram": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp]),
     "segger_sparse_project": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, vp, C.c_int32, vp]),
+    "segger_knn_bruteforce_slabs": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "segger_knn_bruteforce_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "segger_knn_bruteforce": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, vp]),
+    "segger_jaccard_weights": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp]),
+    "segger_louvain_move": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                      vp, vp, vp, vp, vp]),
+    "segger_louvain_modularity": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double, vp, vp, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -3,7 +3,8 @@
 
 ``expression_features`` gives the cell PCA (``X_pca``, what the reference stores as ``bd.x``), the gene embedding
 (``X_corr``, the PCA of the gene-gene correlation matrix) and the intermediate numbers; ``cluster_cosine_similarity``
-gives the two cluster-similarity tables the triplet loss samples from, once cluster labels exist.
+gives a cluster-similarity table the triplet loss samples from; ``anndata_features`` adds the phenograph clusters of the
+cells and the genes (:mod:`segger_amd.phenograph`) and both tables (``anndata.py:261-291``).
 
 Both the correlation matrix and the covariance the cell PCA needs are ONE ``G x G`` second-moment matrix of the weighted
 sparse rows (``segger_sparse_gram``, float64 MFMA over row blocks densified in LDS); the cells are projected onto the
@@ -11,13 +12,15 @@ components by a CSR x dense product (``segger_sparse_project``).  Nothing dense 
 built.  Everything around the two kernels -- integer sums, the median, ``torch.linalg.eigh`` on ``G x G``, sign flips --
 is torch on the device.  There is no CPU path.
 
-Not built (cluster labels stay an input): the phenograph clustering (kNN -> Jaccard -> Louvain); morphology features;
+The phenograph clustering (kNN -> Jaccard -> Louvain) is :mod:`segger_amd.phenograph`: cluster labels are computed on
+the device, by a deterministic Louvain that is cuGraph's in objective, not in move order.  Not built: morphology features;
 sklearn's randomized solver, which sklearn's ``auto`` policy picks when ``G > 500`` -- the exact PCA is computed for
 every ``G``; cuML's own sign convention for ``X_pca`` -- sklearn's is used for both embeddings.  scanpy's
 ``normalize_total`` casts integer counts to float32 first; here the normalised values are float64 throughout.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Tuple
 
 import torch
@@ -25,7 +28,7 @@ from torch import Tensor
 
 from . import _lib as L
 
-__all__ = ["expression_features", "sparse_gram", "sparse_project", "cluster_cosine_similarity"]
+__all__ = ["expression_features", "sparse_gram", "sparse_project", "cluster_cosine_similarity", "anndata_features"]
 
 
 def _csr(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, int, int]:
@@ -171,3 +174,38 @@ def cluster_cosine_similarity(embedding: Tensor, clusters: Tensor) -> Tensor:
     sums.index_add_(0, inverse, torch.nn.functional.normalize(embedding, p=2, dim=1, eps=1e-8))
     means = sums / torch.bincount(inverse, minlength=n).unsqueeze(1)
     return means @ means.T
+
+
+@contextlib.contextmanager
+def deterministic_sums():
+    """torch's deterministic algorithms for the block: ``cluster_cosine_similarity`` sums rows with ``index_add_``, whose
+    default route on the device is floating-point atomics -- the same table to the last bit needs the ordered route."""
+    enabled, warn_only = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(enabled, warn_only=warn_only)
+
+
+def anndata_features(expr: Dict[str, Tensor], embedding_size: int = 128, cells_min_counts: int = 10, genes_min_counts: int = 100,
+                     cells_clusters_n_neighbors: int = 10, cells_clusters_resolution: float = 2.0,
+                     genes_clusters_n_neighbors: int = 5, genes_clusters_resolution: float = 2.0,
+                     out_dtype: torch.dtype = torch.float32) -> Dict[str, Tensor]:
+    """Everything :func:`expression_features` returns plus the reference's clusters (``anndata.py:261-291``, the defaults
+    of ``data_module.py:138-144``): ``cell_clusters`` int64 over the cells -- the phenograph of ``X_pca`` of the FILTERED
+    cells with ``min_size=100``, -1 for a removed cell; ``gene_clusters`` int64 over the kept genes -- the phenograph of
+    ``X_corr`` with ``min_size=-1``; ``cell_cluster_similarities`` and ``gene_cluster_similarities`` from
+    :func:`cluster_cosine_similarity` (-1 is a cluster like any other there, as in the reference), summed in a fixed order
+    (:func:`deterministic_sums`): the whole result has the same bits from call to call."""
+    from .phenograph import phenograph
+    out = expression_features(expr, embedding_size, cells_min_counts, genes_min_counts, out_dtype)
+    filtered, X_pca, X_corr = out["filtered"], out["X_pca"], out["X_corr"]
+    cell_clusters = torch.full((int(filtered.numel()),), -1, dtype=torch.int64, device=filtered.device)
+    cell_clusters[filtered] = phenograph(X_pca[filtered], cells_clusters_n_neighbors, cells_clusters_resolution, min_size=100)
+    out["cell_clusters"] = cell_clusters
+    out["gene_clusters"] = phenograph(X_corr, genes_clusters_n_neighbors, genes_clusters_resolution, min_size=-1)
+    with deterministic_sums():                                        # the same tables from call to call
+        out["cell_cluster_similarities"] = cluster_cosine_similarity(X_pca, cell_clusters)
+        out["gene_cluster_similarities"] = cluster_cosine_similarity(X_corr, out["gene_clusters"])
+    return out
