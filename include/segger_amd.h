@@ -1296,6 +1296,59 @@ int segger_louvain_modularity(const int64_t* indptr, const int32_t* indices, con
                               const int32_t* comm, const int64_t* tot, int64_t n, int64_t nnz, double gamma, double two_m,
                               int64_t* in_c, double* q, segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Contamination scoring of a segmentation: the kernels behind segger_amd.validation (neighbor_frequencies,
+ * calculate_contamination), which restates the reference's src/segger/validation/contamination.py without cuML, scanpy or
+ * AnnData.  csrc/contamination.hip.  Purely additive: two new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * segger_neighbor_frequencies:  nbr [n, k] int32 and dist [n, k] fp32 are the tables segger_knn_grid returns for a point
+ *   set queried against itself (the point itself included at distance 0, the padding id n), labels [n] int32 the type of
+ *   every point.  A neighbour counts iff its id is in [0, n), (double) dist <= max_distance (+inf: no limit) and its label
+ *   is in [0, n_types) -- -1, or any other value outside the range, is "unlabelled" and is never used as an index.
+ *   counts [n, n_types] int32 = the neighbours of every type; freq [n, n_types] fp32 = (float)(count * (1.0 / sum)) with
+ *   the product in fp64, all zero when sum = 0.  1 <= k <= SEGGER_CONTAM_MAX_K, 1 <= n_types <= SEGGER_CONTAM_MAX_TYPES.
+ *   One wave per point, every output element written once by the lane that owns it: no atomics.
+ *
+ * segger_contamination_posterior:  for every stored entry (row r, column c, count v) of a CSR count matrix (indptr
+ *   [n_rows + 1] int64, indices [nnz] int32, counts [nnz] int32) a three-way posterior against a per-type expression table.
+ *   gene_map [n_cols] int32 gives the table column g of CSR column c (outside [0, n_ref_genes): the table lacks the gene),
+ *   host_type [n_rows] int32 the row's type (outside [0, n_types): none), freq [n_rows, n_types] fp32 the neighbour
+ *   frequencies.  THE TABLE IS GENE-MAJOR: Lt [n_ref_genes, ld_L] fp32 with Lt[g, t] = L[t, g], 16-byte aligned, ld_L a
+ *   multiple of 4 and >= n_types (columns n_types .. ld_L - 1 are never read); back [n_ref_genes] fp64 is the background
+ *   A @ L.  In fp64, the types summed in ascending order:
+ *     P_self  = Lt[g, type_r], or eps when the row has no type;
+ *     P_neigh = sum_{t != type_r} freq[r, t] * Lt[g, t] + eps  (all t when the row has no type);
+ *     P_back  = back[g] + eps;
+ *     q_x     = alpha_x * P_x / ((alpha_self * P_self + alpha_neighbor * P_neigh) + alpha_background * P_back).
+ *   q_self, q_neighbor, q_background [nnz] fp32 are each rounded once from fp64; contamination [nnz] int32 = v where the fp64
+ *   q_self < contam_cutoff, else 0; an entry whose gene the table lacks gets three zeros and is never flagged.  Per row:
+ *   contaminated and total int64 (exact sums of the flagged and of all counts) and percent fp64 = (100.0 * contaminated) /
+ *   max(total, 1).  One wave per row: the row's frequencies are staged in LDS with the host type's slot zeroed, lanes take
+ *   the entries 64 at a time and read four types of Lt per load; the table itself is copied into LDS (row stride padded
+ *   so that stride / 4 is odd) when n_ref_genes * stride * 4 plus the four strips fit SEGGER_CONTAM_LDS_BYTES (as many
+ *   workgroups per CU as its LDS holds copies, at most 8) and is read through L2 otherwise -- the same arithmetic in the same order on both routes.  Nothing of size nnz x n_types exists;
+ *   no atomics; the same bits from call to call.
+ *
+ * Rejected on the host with SEGGER_EINVAL, nothing launched: a NULL or misaligned pointer, a negative size, 2^31 - 1 rows,
+ * points or columns or more, n_types outside 1 .. SEGGER_CONTAM_MAX_TYPES, k outside 1 .. SEGGER_CONTAM_MAX_K, n_ref_genes
+ * outside 1 .. SEGGER_CONTAM_MAX_REF_GENES, a bad ld_L, max_distance < 0 or NaN, a non-finite alpha or eps, a NaN cutoff.
+ * n = 0 (frequencies), n_rows = 0 or nnz = 0 (posterior) return SEGGER_OK and launch and write nothing: with nnz = 0 the
+ * caller zero-fills the three per-row outputs.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_CONTAM_MAX_TYPES 256
+#define SEGGER_CONTAM_MAX_K 64                /* segger_knn_grid's range */
+#define SEGGER_CONTAM_MAX_REF_GENES 32768     /* SEGGER_FEATURES_MAX_COLS: the flow table goes through segger_sparse_project */
+#define SEGGER_CONTAM_LDS_BYTES 65536
+int segger_neighbor_frequencies(const int32_t* nbr, const float* dist, const int32_t* labels, int64_t n, int32_t k,
+                                int32_t n_types, double max_distance, int32_t* counts, float* freq, segger_stream_t stream);
+int segger_contamination_posterior(const int64_t* indptr, const int32_t* indices, const int32_t* counts, int64_t n_rows,
+                                   int64_t n_cols, int64_t nnz, const int32_t* gene_map, const int32_t* host_type,
+                                   const float* freq, const float* Lt, int64_t ld_L, const double* back, int32_t n_types,
+                                   int32_t n_ref_genes, double alpha_self, double alpha_neighbor, double alpha_background,
+                                   double eps, double contam_cutoff, float* q_self, float* q_neighbor, float* q_background,
+                                   int32_t* contamination, int64_t* contaminated, int64_t* total, double* percent,
+                                   segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -12,5 +12,7 @@ from .postprocess import SegmentationAccumulator, expression_matrix, expression_
 from .features import expression_features, sparse_gram, sparse_project, cluster_cosine_similarity, anndata_features  # noqa: F401
 from . import phenograph  # noqa: F401  (the module: its function of the same name stays segger_amd.phenograph.phenograph)
 from .phenograph import knn_bruteforce, jaccard_graph, louvain  # noqa: F401
+from . import validation  # noqa: F401
+from .validation import neighbor_frequencies, reference_table, contamination_posterior, calculate_contamination, contamination_flow  # noqa: F401
 
 __version__ = "0.1.0"
