@@ -433,3 +433,28 @@ def require_cuda(*tensors: torch.Tensor) -> None:
             raise SeggerAmdError(
                 "segger_amd runs on MI355X only: got a CPU tensor and there is no CPU fallback "
                 "(the CPU oracle under oracle/ is test infrastructure, not a code path)")
+
+
+# ------------------------------------------------------------------ the post-processing modules' call scaffolding ---
+# (the training ops under segger_amd/ops/ are latency-sensitive and keep their own launch plans)
+def need_device(who: str, *tensors, hint: str = "") -> None:
+    """Raise unless every given tensor (or ``torch.device``; None passes) is on the GPU.  ``hint`` names what to use
+    instead, if anything."""
+    if not all(t is None or (t.type == "cuda" if isinstance(t, torch.device) else t.is_cuda) for t in tensors):
+        raise SeggerAmdError(f"{who} runs on the MI355X only: there is no CPU fallback" + (f" ({hint})" if hint else ""))
+
+
+def workspace(fn_name: str, device, *sizes):
+    """``lib.<fn_name>(*sizes)`` bytes of scratch on ``device`` -> (uint8 tensor, its size).  A signed size function
+    reports a rejected shape as a negative code: raised with the library's message."""
+    n_bytes = getattr(load(), fn_name)(*sizes)
+    if EXPORTS[fn_name][0] is C.c_int64:
+        check(min(n_bytes, 0), fn_name)
+    return torch.empty(n_bytes, dtype=torch.uint8, device=device), n_bytes
+
+
+def call(fn_name: str, device, *args) -> None:
+    """``lib.<fn_name>(*args, stream)`` on torch's current stream of ``device``; raises when it fails."""
+    with on_device(device):
+        rc = getattr(load(), fn_name)(*args, stream_ptr(device))
+    check(rc, fn_name)

@@ -6,6 +6,7 @@
 // 1M-edge training step).  Here: one tiny launch that advances the step counters, one launch whose workgroups find
 // their (tensor, offset) by a search over a prefix table carried in the kernel arguments.
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -100,7 +101,7 @@ extern "C" int segger_adam_step_ex(const segger_adam_tensor* tensors, int32_t n_
 
 extern "C" int segger_adam_step_dev(const segger_adam_tensor* tensors, int32_t n_tensors, const double* hyper, int32_t flags,
                                     int64_t* counter, int64_t counter_inc, segger_stream_t stream_) {
-  SEGGER_REQUIRE(hyper != nullptr && ((uintptr_t)hyper % 8) == 0, "segger_adam_step_dev: hyper is NULL or misaligned");
+  SEGGER_REQUIRE(hyper != nullptr && is_aligned(hyper, 8), "segger_adam_step_dev: hyper is NULL or misaligned");
   return adam_launch(tensors, n_tensors, 0., 0., 0., 0., hyper, flags, counter, counter_inc, stream_);
 }
 

@@ -4,6 +4,7 @@
 // order-independent and the keys unique -- with the same bits whatever order the rows arrive in.
 // Per row: 25 bytes streamed in, one 8-byte atomic, one 8-byte read back; per winner two 4-byte stores.
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -102,8 +103,6 @@ unsigned assign_grid(int64_t n) {
   return (unsigned)(blocks < kAssignMaxBlocks ? blocks : kAssignMaxBlocks);
 }
 
-bool assign_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 int assign_check_n_tx(const char* who, int64_t n_tx) {
   SEGGER_REQUIRE(n_tx >= 1, "%s: n_tx must be at least 1", who);
   SEGGER_REQUIRE(n_tx <= 0x7fffffffLL, "%s: 2^31 transcripts or more", who);
@@ -126,10 +125,10 @@ extern "C" int segger_assign_update(const int64_t* tx_index, const int64_t* seg,
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(tx_index && seg && sim && gene && best_key && cell && gene_out && counters,
                  "segger_assign_update: NULL pointer");
-  SEGGER_REQUIRE(assign_aligned(tx_index, 8) && assign_aligned(seg, 8) && assign_aligned(best_key, 8) &&
-                     assign_aligned(counters, 8),
+  SEGGER_REQUIRE(is_aligned(tx_index, 8) && is_aligned(seg, 8) && is_aligned(best_key, 8) &&
+                     is_aligned(counters, 8),
                  "segger_assign_update: tx_index, seg, best_key and counters must be 8-byte aligned");
-  SEGGER_REQUIRE(assign_aligned(sim, 4) && assign_aligned(gene, 4) && assign_aligned(cell, 4) && assign_aligned(gene_out, 4),
+  SEGGER_REQUIRE(is_aligned(sim, 4) && is_aligned(gene, 4) && is_aligned(cell, 4) && is_aligned(gene_out, 4),
                  "segger_assign_update: sim, gene, cell and gene_out must be 4-byte aligned");
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(best_key);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
@@ -149,8 +148,8 @@ extern "C" int segger_assign_finalize(const uint64_t* best_key, int64_t n_tx, fl
   const int rc = assign_check_n_tx("segger_assign_finalize", n_tx);
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(best_key && similarity_out && seen_out, "segger_assign_finalize: NULL pointer");
-  SEGGER_REQUIRE(assign_aligned(best_key, 8), "segger_assign_finalize: best_key must be 8-byte aligned");
-  SEGGER_REQUIRE(assign_aligned(similarity_out, 4), "segger_assign_finalize: similarity_out must be 4-byte aligned");
+  SEGGER_REQUIRE(is_aligned(best_key, 8), "segger_assign_finalize: best_key must be 8-byte aligned");
+  SEGGER_REQUIRE(is_aligned(similarity_out, 4), "segger_assign_finalize: similarity_out must be 4-byte aligned");
   hipLaunchKernelGGL(assign_finalize_kernel, dim3(assign_grid(n_tx)), dim3(kAssignThreads), 0, (hipStream_t)stream,
                      reinterpret_cast<const unsigned long long*>(best_key), n_tx, similarity_out, seen_out);
   SEGGER_LAUNCH_CHECK("assign_finalize_kernel");

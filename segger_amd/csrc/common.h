@@ -32,8 +32,6 @@ int hip_fail(hipError_t e, const char* what);
     if (_e != hipSuccess) return ::segger::hip_fail(_e, name);      \
   } while (0)
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // Compute units of the CURRENT device, cached per device id (a process may drive several GPUs: a persistent grid sized
 // from whichever device asked first would be wrong on a heterogeneous node).  0 = unknown.
 inline int device_cu_count() {

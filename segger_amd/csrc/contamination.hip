@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -29,9 +30,6 @@ constexpr int kTypeChunks = SEGGER_CONTAM_MAX_TYPES / kWave;     // types per la
 
 static_assert(SEGGER_CONTAM_MAX_TYPES % kWave == 0, "a lane owns whole 64-type chunks");
 static_assert(SEGGER_CONTAM_MAX_K <= kWave, "one lane per neighbour");
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-bool contam_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 __global__ __launch_bounds__(kContamThreads) void neighbor_frequencies_kernel(
     const int32_t* __restrict__ nbr, const float* __restrict__ dist, const int32_t* __restrict__ labels, int64_t n, int k, int T,
@@ -77,16 +75,6 @@ struct PosteriorArgs {
   float* q_self; float* q_neighbor; float* q_background; int32_t* contamination;
   int64_t* contaminated; int64_t* total; double* percent;
 };
-
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, kWave);
-    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)v >> 32), m, kWave);
-    v += (int64_t)(((uint64_t)hi << 32) | lo);
-  }
-  return v;
-}
 
 // kLds: the table sits in LDS (row stride a.ld_s) in front of the frequency strips; otherwise rows of a.Lt are read
 template <bool kLds>
@@ -202,8 +190,8 @@ extern "C" int segger_neighbor_frequencies(const int32_t* nbr, const float* dist
   SEGGER_REQUIRE(max_distance >= 0.0, "%s: max_distance must be >= 0 (+inf for none)", who);             // NaN fails too
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(nbr && dist && labels && counts && freq, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(contam_aligned(nbr, 4) && contam_aligned(dist, 4) && contam_aligned(labels, 4) && contam_aligned(counts, 4) &&
-                     contam_aligned(freq, 4), "%s: every array must be 4-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(nbr, 4) && is_aligned(dist, 4) && is_aligned(labels, 4) && is_aligned(counts, 4) &&
+                     is_aligned(freq, 4), "%s: every array must be 4-byte aligned", who);
   hipLaunchKernelGGL(neighbor_frequencies_kernel, dim3((unsigned)contam_grid(n, 16)), dim3(kContamThreads), 0, stream, nbr, dist,
                      labels, n, (int)k, (int)n_types, max_distance, counts, freq);
   SEGGER_LAUNCH_CHECK("neighbor_frequencies_kernel");
@@ -235,14 +223,14 @@ extern "C" int segger_contamination_posterior(
   SEGGER_REQUIRE(n_cols >= 1, "%s: stored entries but n_cols = 0", who);
   SEGGER_REQUIRE(q_self && q_neighbor && q_background && contamination && contaminated && total && percent, "%s: NULL pointer",
                  who);
-  SEGGER_REQUIRE(contam_aligned(indptr, 8) && contam_aligned(back, 8) && contam_aligned(contaminated, 8) &&
-                     contam_aligned(total, 8) && contam_aligned(percent, 8),
+  SEGGER_REQUIRE(is_aligned(indptr, 8) && is_aligned(back, 8) && is_aligned(contaminated, 8) &&
+                     is_aligned(total, 8) && is_aligned(percent, 8),
                  "%s: indptr, back, contaminated, total and percent must be 8-byte aligned", who);
-  SEGGER_REQUIRE(contam_aligned(indices, 4) && contam_aligned(counts, 4) && contam_aligned(gene_map, 4) &&
-                     contam_aligned(host_type, 4) && contam_aligned(freq, 4) && contam_aligned(q_self, 4) &&
-                     contam_aligned(q_neighbor, 4) && contam_aligned(q_background, 4) && contam_aligned(contamination, 4),
+  SEGGER_REQUIRE(is_aligned(indices, 4) && is_aligned(counts, 4) && is_aligned(gene_map, 4) &&
+                     is_aligned(host_type, 4) && is_aligned(freq, 4) && is_aligned(q_self, 4) &&
+                     is_aligned(q_neighbor, 4) && is_aligned(q_background, 4) && is_aligned(contamination, 4),
                  "%s: every 32-bit array must be 4-byte aligned", who);
-  SEGGER_REQUIRE(contam_aligned(Lt, 16), "%s: Lt must be 16-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(Lt, 16), "%s: Lt must be 16-byte aligned", who);
   PosteriorArgs a;
   a.indptr = indptr; a.indices = indices; a.counts = counts;
   a.n_rows = n_rows; a.n_cols = n_cols; a.nnz = nnz;

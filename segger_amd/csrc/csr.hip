@@ -1,6 +1,7 @@
 // segger_csr_from_coo: COO edge_index -> CSR (indptr, col, eid) by a stable
 // device radix sort on the row id.  Built once per batch and edge type.
 #include "common.h"
+#include "post_common.h"
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -75,7 +76,6 @@ int key_bits(int64_t n_rows) {
   return b;
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 size_t sort_temp_bytes(int64_t n_edges, int64_t n_rows) {
   size_t bytes = 0;
@@ -92,7 +92,7 @@ using namespace segger;
 
 extern "C" size_t segger_csr_from_coo_workspace_bytes(int64_t n_edges, int64_t n_rows) {
   if (n_edges <= 0) return 256;
-  return 3 * align_up((size_t)n_edges * 4) + align_up(sort_temp_bytes(n_edges, n_rows)) + 256;
+  return 3 * align256((size_t)n_edges * 4) + align256(sort_temp_bytes(n_edges, n_rows)) + 256;
 }
 
 extern "C" int segger_csr_from_coo(const int64_t* row, const int64_t* colv, int64_t n_edges, int64_t n_rows, int64_t n_cols,
@@ -115,7 +115,7 @@ extern "C" int segger_csr_from_coo(const int64_t* row, const int64_t* colv, int6
     set_error("segger_csr_from_coo: workspace %zu < %zu bytes", workspace_bytes, need);
     return SEGGER_EWORKSPACE;
   }
-  const size_t seg = align_up((size_t)n_edges * 4);
+  const size_t seg = align256((size_t)n_edges * 4);
   char* base = static_cast<char*>(workspace);
   uint32_t* keys_in = reinterpret_cast<uint32_t*>(base);
   uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + seg);

@@ -7,8 +7,9 @@
 // Per row: 20 bytes streamed in, 12 bytes of key + position through the sort, one 4-byte (similarity) and one 8-byte
 // (xy) gather through the sort permutation -- the gathers are the cost to watch; positions ascend inside a run.
 #include "common.h"
+#include "post_common.h"
+#include "sort_config.h"
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -20,13 +21,6 @@ constexpr int kExprThreads = 256;
 constexpr int64_t kExprMaxBlocks = 1024;        // grid-stride above 262 144 items: four blocks per CU of the MI355X
 constexpr int kExprWaves = kExprThreads / kWave;
 
-// rocprim's default onesweep pass for (uint64, int32) pairs on gfx950 ranks with the `match` algorithm and keeps 80 bytes
-// of scratch per lane; the `basic` ranking at the same 8 bits per pass and 256 x 12 keys per block compiles without any.
-using ExprSortConfig = rocprim::radix_sort_config<
-    rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<256, 12>, rocprim::kernel_config<256, 12>, 8,
-                                        rocprim::block_radix_rank_algorithm::basic>>;
-
 // counters block of segger_expression_build
 enum { kKept = 0, kNnz = 1, kCellsPresent = 2, kGenesPresent = 3, kBad = 4, kExprCounters = 5 };
 
@@ -37,23 +31,11 @@ struct ExprKeying {
   unsigned long long sentinel;
 };
 
-int expr_bit_length(unsigned long long v) {
-  int b = 0;
-  while (v) { ++b; v >>= 1; }
-  return b;
-}
-
 ExprKeying expr_keying(int64_t n_cells, int64_t n_genes) {
   ExprKeying k;
-  k.gene_bits = expr_bit_length((unsigned long long)(n_genes - 1));
+  k.gene_bits = bit_length((unsigned long long)(n_genes - 1));
   k.sentinel = (unsigned long long)n_cells << k.gene_bits;       // n_cells, n_genes < 2^31: below 2^62
   return k;
-}
-
-__device__ __forceinline__ int expr_wave_sum_i32(int v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-  return v;
 }
 
 // One key per row; the rows that are not kept take the sentinel and sort behind every kept row.  A kept row whose cell
@@ -81,8 +63,8 @@ __global__ __launch_bounds__(kExprThreads) void expression_keys_kernel(
     keys[i] = key;
     pos[i] = (int32_t)i;
   }
-  n_kept = expr_wave_sum_i32(n_kept);                            // at most 2^31 / (1024 * 256) + 1 rows per thread
-  n_bad = expr_wave_sum_i32(n_bad);
+  n_kept = wave_sum_i32(n_kept);                            // at most 2^31 / (1024 * 256) + 1 rows per thread
+  n_bad = wave_sum_i32(n_bad);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     if (n_kept) atomicAdd(counters + kKept, (unsigned long long)n_kept);
     if (n_bad) atomicAdd(counters + kBad, (unsigned long long)n_bad);
@@ -244,14 +226,7 @@ __global__ __launch_bounds__(kExprThreads) void expression_cells_kernel(
       });
 }
 
-size_t expr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-unsigned expr_grid(int64_t n_items) {
-  const int64_t blocks = (n_items + kExprThreads - 1) / kExprThreads;
-  return (unsigned)(blocks < 1 ? 1 : (blocks < kExprMaxBlocks ? blocks : kExprMaxBlocks));
-}
-
-bool expr_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+unsigned expr_grid(int64_t n_items) { return grid_stride_blocks(n_items, kExprThreads, kExprMaxBlocks); }
 
 int expr_check_sizes(const char* who, int64_t n_rows, int64_t n_cells, int64_t n_genes) {
   SEGGER_REQUIRE(n_rows >= 0, "%s: negative n_rows", who);
@@ -273,25 +248,24 @@ struct ExprLayout {
 ExprLayout expr_layout(int64_t n_rows, int64_t n_cells, int64_t n_genes) {
   ExprLayout L;
   const ExprKeying kg = expr_keying(n_cells, n_genes);
-  L.key_bits = expr_bit_length(kg.sentinel);
+  L.key_bits = bit_length(kg.sentinel);
   const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += expr_align(bytes); return at; };
-  L.keys_a = take(n * 8);
-  L.keys_b = take(n * 8);
-  L.pos_a = take(n * 4);
-  L.pos_b = take(n * 4);
-  L.run_start = take(n * 4);
-  L.cell_present = take((size_t)n_cells * 4);
-  L.cell_pos = take((size_t)n_cells * 4);
-  L.gene_present = take((size_t)n_genes * 4);
-  L.gene_pos = take((size_t)n_genes * 4);
+  Carver ws;
+  L.keys_a = ws.take(n * 8);
+  L.keys_b = ws.take(n * 8);
+  L.pos_a = ws.take(n * 4);
+  L.pos_b = ws.take(n * 4);
+  L.run_start = ws.take(n * 4);
+  L.cell_present = ws.take((size_t)n_cells * 4);
+  L.cell_pos = ws.take((size_t)n_cells * 4);
+  L.gene_present = ws.take((size_t)n_genes * 4);
+  L.gene_pos = ws.take((size_t)n_genes * 4);
   size_t a = 0, b = 0, c = 0, d = 0;
   uint64_t* k64 = nullptr;
   int32_t* v32 = nullptr;
   int32_t* i32 = nullptr;
   size_t* cnt = nullptr;
-  (void)rocprim::radix_sort_pairs<ExprSortConfig>(nullptr, a, k64, k64, v32, v32, n, 0, (unsigned)L.key_bits, (hipStream_t)0);
+  (void)rocprim::radix_sort_pairs<NoScratchSortConfig>(nullptr, a, k64, k64, v32, v32, n, 0, (unsigned)L.key_bits, (hipStream_t)0);
   (void)rocprim::select(nullptr, b, rocprim::counting_iterator<int32_t>(0), i32, cnt, n, ExprRunHead{nullptr, 0}, (hipStream_t)0);
   (void)rocprim::exclusive_scan(nullptr, c, i32, i32, (int32_t)0, (size_t)n_cells, rocprim::plus<int32_t>(), (hipStream_t)0);
   (void)rocprim::exclusive_scan(nullptr, d, i32, i32, (int32_t)0, (size_t)n_genes, rocprim::plus<int32_t>(), (hipStream_t)0);
@@ -299,8 +273,8 @@ ExprLayout expr_layout(int64_t n_rows, int64_t n_cells, int64_t n_genes) {
   if (b > L.temp_bytes) L.temp_bytes = b;
   if (c > L.temp_bytes) L.temp_bytes = c;
   if (d > L.temp_bytes) L.temp_bytes = d;
-  L.temp = take(L.temp_bytes > 0 ? L.temp_bytes : 1);
-  L.total = off;
+  L.temp = ws.take(L.temp_bytes > 0 ? L.temp_bytes : 1);
+  L.total = ws.total();
   return L;
 }
 
@@ -332,31 +306,27 @@ extern "C" int segger_expression_build(const int32_t* cell, const int32_t* gene,
   SEGGER_REQUIRE(cell && gene && similarity && threshold && cell_ids && gene_ids && indptr && indices && counts &&
                      mean_similarity && cell_count && counters && workspace, "%s: NULL pointer", who);
   SEGGER_REQUIRE((xy == nullptr) == (centroid == nullptr), "%s: xy and centroid are given together or not at all", who);
-  SEGGER_REQUIRE(expr_aligned(threshold, 8) && expr_aligned(xy, 8) && expr_aligned(indptr, 8) &&
-                     expr_aligned(mean_similarity, 8) && expr_aligned(cell_count, 8) && expr_aligned(centroid, 8) &&
-                     expr_aligned(counters, 8),
+  SEGGER_REQUIRE(is_aligned(threshold, 8) && is_aligned(xy, 8) && is_aligned(indptr, 8) &&
+                     is_aligned(mean_similarity, 8) && is_aligned(cell_count, 8) && is_aligned(centroid, 8) &&
+                     is_aligned(counters, 8),
                  "%s: threshold, xy, indptr, mean_similarity, cell_count, centroid and counters must be 8-byte aligned", who);
-  SEGGER_REQUIRE(expr_aligned(cell, 4) && expr_aligned(gene, 4) && expr_aligned(similarity, 4) && expr_aligned(cell_ids, 4) &&
-                     expr_aligned(gene_ids, 4) && expr_aligned(indices, 4) && expr_aligned(counts, 4),
+  SEGGER_REQUIRE(is_aligned(cell, 4) && is_aligned(gene, 4) && is_aligned(similarity, 4) && is_aligned(cell_ids, 4) &&
+                     is_aligned(gene_ids, 4) && is_aligned(indices, 4) && is_aligned(counts, 4),
                  "%s: cell, gene, similarity, cell_ids, gene_ids, indices and counts must be 4-byte aligned", who);
-  SEGGER_REQUIRE(expr_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
   const ExprLayout L = expr_layout(n_rows, n_cells, n_genes);
-  if (workspace_bytes < L.total) {
-    set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, L.total);
-    return SEGGER_EWORKSPACE;
-  }
+  if (workspace_bytes < L.total) return workspace_too_small(who, workspace_bytes, L.total);
 
-  char* base = static_cast<char*>(workspace);
-  uint64_t* keys_a = reinterpret_cast<uint64_t*>(base + L.keys_a);     // uint64 keys, int32 values: the pair quadtree.hip sorts
-  uint64_t* keys_b = reinterpret_cast<uint64_t*>(base + L.keys_b);
-  int32_t* pos_a = reinterpret_cast<int32_t*>(base + L.pos_a);
-  int32_t* pos_b = reinterpret_cast<int32_t*>(base + L.pos_b);
-  int32_t* run_start = reinterpret_cast<int32_t*>(base + L.run_start);
-  int32_t* cell_present = reinterpret_cast<int32_t*>(base + L.cell_present);
-  int32_t* cell_pos = reinterpret_cast<int32_t*>(base + L.cell_pos);
-  int32_t* gene_present = reinterpret_cast<int32_t*>(base + L.gene_present);
-  int32_t* gene_pos = reinterpret_cast<int32_t*>(base + L.gene_pos);
-  void* temp = base + L.temp;
+  uint64_t* keys_a = at<uint64_t>(workspace, L.keys_a);     // uint64 keys, int32 values: the pair quadtree.hip sorts
+  uint64_t* keys_b = at<uint64_t>(workspace, L.keys_b);
+  int32_t* pos_a = at<int32_t>(workspace, L.pos_a);
+  int32_t* pos_b = at<int32_t>(workspace, L.pos_b);
+  int32_t* run_start = at<int32_t>(workspace, L.run_start);
+  int32_t* cell_present = at<int32_t>(workspace, L.cell_present);
+  int32_t* cell_pos = at<int32_t>(workspace, L.cell_pos);
+  int32_t* gene_present = at<int32_t>(workspace, L.gene_present);
+  int32_t* gene_pos = at<int32_t>(workspace, L.gene_pos);
+  void* temp = at<char>(workspace, L.temp);
   size_t temp_bytes = L.temp_bytes;
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
   const ExprKeying kg = expr_keying(n_cells, n_genes);
@@ -367,7 +337,7 @@ extern "C" int segger_expression_build(const int32_t* cell, const int32_t* gene,
   hipLaunchKernelGGL(expression_keys_kernel, dim3(expr_grid(n_rows)), dim3(kExprThreads), 0, stream, cell, gene, similarity,
                      threshold, n_rows, n_cells, n_genes, kg, keys_a, pos_a, cell_present, gene_present, cnt);
   SEGGER_LAUNCH_CHECK("expression_keys_kernel");
-  SEGGER_HIP(rocprim::radix_sort_pairs<ExprSortConfig>(temp, temp_bytes, keys_a, keys_b, pos_a, pos_b, (size_t)n_rows, 0,
+  SEGGER_HIP(rocprim::radix_sort_pairs<NoScratchSortConfig>(temp, temp_bytes, keys_a, keys_b, pos_a, pos_b, (size_t)n_rows, 0,
                                                        (unsigned)L.key_bits, stream));
   temp_bytes = L.temp_bytes;
   SEGGER_HIP(rocprim::select(temp, temp_bytes, rocprim::counting_iterator<int32_t>(0), run_start,

@@ -12,6 +12,7 @@
 // Project: out[r, :] = w_r * sum_j x_rj V[j, :] - offset, one wave per row, the entries in CSR order, lane l owning the
 // columns l, l + 64, l + 128, l + 192 in float64.
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -37,8 +38,6 @@ struct GramPlan {
   size_t partial, colsum, total;                        // byte offsets into the workspace
 };
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // Slabs: as many as keep ~SEGGER_FEATURES_TARGET_GROUPS workgroups busy, never more than SEGGER_FEATURES_MAX_SLABS, never
 // shorter than SEGGER_FEATURES_SLAB_ROWS rows -- a function of (n_rows, n_cols) only.
 GramPlan gram_plan(int64_t n_rows, int64_t n_cols) {
@@ -52,9 +51,10 @@ GramPlan gram_plan(int64_t n_rows, int64_t n_cols) {
   if (slabs < 1) slabs = 1;
   p.n_slabs = slabs;
   p.slab_rows = ceil_div(ceil_div(n_rows > 0 ? n_rows : 1, slabs), kRowBlock) * kRowBlock;
-  p.partial = 0;
-  p.colsum = (size_t)(p.n_slabs * p.n_pairs * kTileElems) * sizeof(double);
-  p.total = p.colsum + (size_t)(p.n_slabs * p.n_tiles * kTile) * sizeof(double);
+  Carver ws;                                            // both regions are whole multiples of 512 bytes: nothing is padded
+  p.partial = ws.take((size_t)(p.n_slabs * p.n_pairs * kTileElems) * sizeof(double));
+  p.colsum = ws.take((size_t)(p.n_slabs * p.n_tiles * kTile) * sizeof(double));
+  p.total = ws.total();
   return p;
 }
 
@@ -239,8 +239,6 @@ int project_launch(const int64_t* indptr, const int32_t* indices, const int32_t*
   return SEGGER_OK;
 }
 
-bool feat_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 int feat_check_sizes(const char* who, int64_t n_rows, int64_t n_cols) {
   SEGGER_REQUIRE(n_rows >= 0, "%s: negative n_rows", who);
   SEGGER_REQUIRE(n_rows <= 0x7fffffffLL, "%s: 2^31 rows or more", who);
@@ -253,8 +251,8 @@ int feat_check_csr(const char* who, const int64_t* indptr, const int32_t* indice
                    const double* row_weight, int64_t nnz) {
   SEGGER_REQUIRE(nnz >= 0, "%s: negative nnz", who);
   SEGGER_REQUIRE(indptr && row_weight && (nnz == 0 || (indices && values)), "%s: NULL pointer", who);
-  SEGGER_REQUIRE(feat_aligned(indptr, 8) && feat_aligned(row_weight, 8), "%s: indptr and row_weight must be 8-byte aligned", who);
-  SEGGER_REQUIRE(feat_aligned(indices, 4) && feat_aligned(values, 4), "%s: indices and values must be 4-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(indptr, 8) && is_aligned(row_weight, 8), "%s: indptr and row_weight must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(indices, 4) && is_aligned(values, 4), "%s: indices and values must be 4-byte aligned", who);
   return SEGGER_OK;
 }
 
@@ -283,7 +281,7 @@ extern "C" int segger_sparse_gram(const int64_t* indptr, const int32_t* indices,
   int rc = feat_check_sizes(who, n_rows, n_cols);
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(S && s, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(feat_aligned(S, 8) && feat_aligned(s, 8), "%s: S and s must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(S, 8) && is_aligned(s, 8), "%s: S and s must be 8-byte aligned", who);
   SEGGER_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", who);
   if (n_rows == 0) {                                     // an empty matrix: zeros, no kernel
     SEGGER_HIP(hipMemsetAsync(S, 0, (size_t)(n_cols * n_cols) * sizeof(double), stream));
@@ -293,15 +291,11 @@ extern "C" int segger_sparse_gram(const int64_t* indptr, const int32_t* indices,
   rc = feat_check_csr(who, indptr, indices, values, row_weight, nnz);
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(workspace, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(feat_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
   const GramPlan plan = gram_plan(n_rows, n_cols);
-  if ((size_t)workspace_bytes < plan.total) {
-    set_error("%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, plan.total);
-    return SEGGER_EWORKSPACE;
-  }
-  char* base = static_cast<char*>(workspace);
-  double* partial = reinterpret_cast<double*>(base + plan.partial);
-  double* colsum = reinterpret_cast<double*>(base + plan.colsum);
+  if ((size_t)workspace_bytes < plan.total) return workspace_too_small(who, (size_t)workspace_bytes, plan.total);
+  double* partial = at<double>(workspace, plan.partial);
+  double* colsum = at<double>(workspace, plan.colsum);
   hipLaunchKernelGGL(features_gram_kernel, dim3((unsigned)plan.n_pairs, (unsigned)plan.n_slabs), dim3(kFeatThreads), 0, stream,
                      indptr, indices, values, row_weight, n_rows, nnz, plan.n_tiles, plan.n_pairs, plan.slab_rows, partial,
                      colsum);
@@ -326,7 +320,7 @@ extern "C" int segger_sparse_project(const int64_t* indptr, const int32_t* indic
   rc = feat_check_csr(who, indptr, indices, values, row_weight, nnz);
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(V && offset && out, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(feat_aligned(V, 8) && feat_aligned(offset, 8) && feat_aligned(out, out_f64 ? 8 : 4),
+  SEGGER_REQUIRE(is_aligned(V, 8) && is_aligned(offset, 8) && is_aligned(out, out_f64 ? 8 : 4),
                  "%s: V, offset and out must be aligned to their element size", who);
   if (out_f64)
     return project_launch<double>(indptr, indices, values, row_weight, n_rows, n_cols, nnz, V, offset, (int)k,

@@ -7,6 +7,7 @@
 // Reference: src/segger/models/ist_encoder.py:22-31,57-79 (sinusoid / normalisation), :312-320
 // (embedding, concat, GELU), :331-332 (normalize).
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -484,7 +485,7 @@ extern "C" int segger_posfreq(const float* pos, const int64_t* batch, const floa
   SEGGER_REQUIRE(n >= 0 && freq_dim >= 16 && freq_dim % 16 == 0, "segger_posfreq: freq_dim must be a positive multiple of 16");
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(pos && mins && maxs && out, "segger_posfreq: NULL pointer");
-  SEGGER_REQUIRE(aligned16(out), "segger_posfreq: out must be 16-byte aligned");
+  SEGGER_REQUIRE(is_aligned(out, 16), "segger_posfreq: out must be 16-byte aligned");
   const int half = freq_dim / 2;
   const int64_t items = 2 * n * (half / 8);
   const int64_t nb = (items + 255) / 256;
@@ -504,7 +505,7 @@ extern "C" int segger_embed_gelu_fwd(const float* table, const int32_t* ids, con
   SEGGER_REQUIRE(n >= 0 && D > 0 && D % 8 == 0, "segger_embed_gelu_fwd: D must be a positive multiple of 8");
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(table && ids && pe && out, "segger_embed_gelu_fwd: NULL pointer");
-  SEGGER_REQUIRE(aligned16(table) && aligned16(pe) && aligned16(out), "segger_embed_gelu_fwd: 16-byte alignment required");
+  SEGGER_REQUIRE(is_aligned(table, 16) && is_aligned(pe, 16) && is_aligned(out, 16), "segger_embed_gelu_fwd: 16-byte alignment required");
   SEGGER_REQUIRE((ld_pe * esize(dtype)) % 16 == 0 && (ld_out * esize(dtype)) % 16 == 0 && ld_pe >= D && ld_out >= 2 * D,
                  "segger_embed_gelu_fwd: bad leading dimension");
   const int64_t items = n * (2 * D / 8);
@@ -566,7 +567,7 @@ extern "C" int segger_embed_gelu_bwd(const void* gx0, int64_t ld_g, const float*
     return SEGGER_OK;
   }
   SEGGER_REQUIRE(gx0 && pe && gpe, "segger_embed_gelu_bwd: NULL pointer");
-  SEGGER_REQUIRE(aligned16(gx0) && aligned16(pe) && aligned16(gpe), "segger_embed_gelu_bwd: 16-byte alignment required");
+  SEGGER_REQUIRE(is_aligned(gx0, 16) && is_aligned(pe, 16) && is_aligned(gpe, 16), "segger_embed_gelu_bwd: 16-byte alignment required");
   SEGGER_REQUIRE((ld_g * esize(dtype)) % 16 == 0 && ld_g >= 2 * D, "segger_embed_gelu_bwd: bad leading dimension of gx0");
   {
     const int64_t items = n * (D / 8);
@@ -592,10 +593,10 @@ static int front_join_fill(const segger_front_join_args* a, bool bwd, FrontJoin*
   SEGGER_REQUIRE(a->dtype == SEGGER_F32 || a->dtype == SEGGER_BF16 || a->dtype == SEGGER_F16, "segger_front_join: unknown dtype %d", a->dtype);
   const size_t es = esize(a->dtype);
   const int D = a->D;
-  auto ok = [&](const void* p, int64_t ld, int width) { return p && aligned16(p) && ld >= width && ((size_t)ld * es) % 16 == 0; };
+  auto ok = [&](const void* p, int64_t ld, int width) { return p && is_aligned(p, 16) && ld >= width && ((size_t)ld * es) % 16 == 0; };
   const int64_t n_all = a->n_tx + a->n_bd;
   SEGGER_REQUIRE(n_all == 0 || ok(a->pe, a->ld_pe, D), "segger_front_join: pe NULL, misaligned or ld < D");
-  SEGGER_REQUIRE(a->n_tx == 0 || (a->table && a->ids && aligned16(a->table)), "segger_front_join: table / ids");
+  SEGGER_REQUIRE(a->n_tx == 0 || (a->table && a->ids && is_aligned(a->table, 16)), "segger_front_join: table / ids");
   SEGGER_REQUIRE(a->n_bd == 0 || ok(a->xb, a->ld_xb, D), "segger_front_join: xb NULL, misaligned or ld < D");
   if (!bwd) {
     SEGGER_REQUIRE(a->n_tx == 0 || ok(a->out_tx, a->ld_out_tx, 2 * D), "segger_front_join_fwd: out_tx");
@@ -675,7 +676,7 @@ extern "C" int segger_segment_rowsum(const void* x, int64_t ld, int64_t n, int32
     return SEGGER_OK;
   }
   SEGGER_REQUIRE(x && seg_ptr && seg_rows, "segger_segment_rowsum: NULL pointer");
-  SEGGER_REQUIRE(aligned16(x) && ld >= D && (ld * esize(dtype)) % 16 == 0, "segger_segment_rowsum: bad pointer / leading dimension");
+  SEGGER_REQUIRE(is_aligned(x, 16) && ld >= D && (ld * esize(dtype)) % 16 == 0, "segger_segment_rowsum: bad pointer / leading dimension");
   const size_t need = segger_segment_rowsum_workspace_bytes(n, n_segments, D);
   if (!workspace || workspace_bytes < need) {
     set_error("segger_segment_rowsum: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -710,7 +711,7 @@ extern "C" int segger_colsum(const void* x, int64_t ld, int64_t n, int32_t cols,
     SEGGER_HIP(hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), stream));
     return SEGGER_OK;
   }
-  SEGGER_REQUIRE(x && aligned16(x) && ld >= cols && (ld * esize(dtype)) % 16 == 0, "segger_colsum: bad pointer / leading dimension");
+  SEGGER_REQUIRE(x && is_aligned(x, 16) && ld >= cols && (ld * esize(dtype)) % 16 == 0, "segger_colsum: bad pointer / leading dimension");
   const size_t need = segger_colsum_workspace_bytes(n, cols);
   if (!workspace || workspace_bytes < need) {
     set_error("segger_colsum: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -734,7 +735,7 @@ extern "C" int segger_l2norm_fwd(const void* y, int64_t ld_y, int64_t n, int32_t
                                  int32_t dtype, segger_stream_t stream) {
   SEGGER_REQUIRE(n >= 0 && channels > 0, "segger_l2norm_fwd: bad sizes");
   if (n == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(y && z && aligned16(y) && aligned16(z), "segger_l2norm_fwd: NULL or misaligned pointer");
+  SEGGER_REQUIRE(y && z && is_aligned(y, 16) && is_aligned(z, 16), "segger_l2norm_fwd: NULL or misaligned pointer");
   SEGGER_REQUIRE((ld_y * esize(dtype)) % 16 == 0 && (ld_z * esize(dtype)) % 16 == 0, "segger_l2norm_fwd: bad leading dimension");
   DISPATCH_DTYPE(dtype,
                  return (launch_l2norm<float, false>(y, ld_y, nullptr, 0, n, channels, eps, z, ld_z, (hipStream_t)stream)),
@@ -748,7 +749,7 @@ extern "C" int segger_l2norm_bwd2(const void* y, int64_t ld_y, const void* gz, i
                                   segger_stream_t stream) {
   SEGGER_REQUIRE(n >= 0 && channels > 0, "segger_l2norm_bwd: bad sizes");
   if (n == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(y && gz && gy && aligned16(y) && aligned16(gz) && aligned16(gy) && aligned16(gz2),
+  SEGGER_REQUIRE(y && gz && gy && is_aligned(y, 16) && is_aligned(gz, 16) && is_aligned(gy, 16) && is_aligned(gz2, 16),
                  "segger_l2norm_bwd: NULL or misaligned pointer");
   const size_t es = esize(dtype);
   SEGGER_REQUIRE((ld_y * es) % 16 == 0 && (ld_gz * es) % 16 == 0 && (ld_gy * es) % 16 == 0 && (!gz2 || (ld_gz2 * es) % 16 == 0),
@@ -780,7 +781,7 @@ extern "C" int segger_l2norm_many(const segger_l2norm_seg* segs, int32_t n_segs,
     const segger_l2norm_seg& g = segs[i];
     SEGGER_REQUIRE(g.n >= 0, "segger_l2norm_many: segment %d: negative size", i);
     if (g.n == 0) continue;
-    SEGGER_REQUIRE(g.y && g.out && aligned16(g.y) && aligned16(g.out) && aligned16(g.gz), "segger_l2norm_many: segment %d: NULL or misaligned pointer", i);
+    SEGGER_REQUIRE(g.y && g.out && is_aligned(g.y, 16) && is_aligned(g.out, 16) && is_aligned(g.gz, 16), "segger_l2norm_many: segment %d: NULL or misaligned pointer", i);
     SEGGER_REQUIRE((g.ld_y * es) % 16 == 0 && (g.ld_out * es) % 16 == 0 && g.ld_y >= channels && g.ld_out >= channels &&
                        (!g.gz || ((g.ld_gz * (g.gz_f32 ? 4 : es)) % 16 == 0 && g.ld_gz >= channels)),
                    "segger_l2norm_many: segment %d: bad leading dimension", i);

@@ -1,6 +1,7 @@
 // Host launchers for the fused GATv2 kernels (C ABI: include/segger_amd.h).
 #include "gatv2_launch.h"
 #include "draws.h"
+#include "post_common.h"
 
 namespace segger {
 
@@ -75,7 +76,7 @@ int check_rows(const char* name, const void* ptr, int64_t ld, int dtype, int hc)
   SEGGER_REQUIRE(ld >= hc, "gatv2: ld of %s (%lld) < heads*channels (%d)", name, (long long)ld, hc);
   SEGGER_REQUIRE(ld * (int64_t)elem_size(dtype) < 0xffffffffLL, "gatv2: row stride of %s exceeds 4 GiB", name);
   if (g_need_align) {
-    SEGGER_REQUIRE(aligned16(ptr), "gatv2: %s is not 16-byte aligned", name);
+    SEGGER_REQUIRE(is_aligned(ptr, 16), "gatv2: %s is not 16-byte aligned", name);
     SEGGER_REQUIRE((ld * (int64_t)elem_size(dtype)) % 16 == 0, "gatv2: row stride of %s is not a multiple of 16 bytes", name);
   }
   return SEGGER_OK;
@@ -397,7 +398,7 @@ extern "C" int segger_dropout_bits(const int32_t* eid, int64_t n_edges, int32_t 
                  "segger_dropout_bits: plane_stride must be a multiple of 4 >= n_edges and bits 4-byte aligned");
   BitsParams p{};
   p.eid = eid; p.n_edges = n_edges; p.plane_stride = plane_stride; p.heads = heads; p.n_seeds = n_seeds;
-  p.seed_dev = seed_dev; p.bits = bits; p.eid_aligned = aligned16(eid) ? 1 : 0;
+  p.seed_dev = seed_dev; p.bits = bits; p.eid_aligned = is_aligned(eid, 16) ? 1 : 0;
   p.thr = (uint32_t)((double)dropout_p * 16777216.0);
   for (int l = 0; l < n_seeds; ++l) p.seeds[l] = seeds[l];
   hipLaunchKernelGGL(dropout_bits_kernel, dim3((unsigned)((n_edges + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, p);
@@ -414,7 +415,7 @@ int fill_bits_params(const segger_bits_job& jb, int heads, float dropout_p, cons
   BitsParams& p = *out;
   p = BitsParams{};
   p.eid = jb.eid; p.n_edges = jb.n_edges; p.plane_stride = jb.plane_stride; p.heads = heads; p.n_seeds = jb.n_seeds;
-  p.seed_dev = seed_dev; p.bits = jb.bits; p.eid_aligned = aligned16(jb.eid) ? 1 : 0;
+  p.seed_dev = seed_dev; p.bits = jb.bits; p.eid_aligned = is_aligned(jb.eid, 16) ? 1 : 0;
   p.thr = (uint32_t)((double)dropout_p * 16777216.0);
   for (int l = 0; l < jb.n_seeds; ++l) p.seeds[l] = jb.seeds[l];
   return SEGGER_OK;

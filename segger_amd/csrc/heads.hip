@@ -1,6 +1,7 @@
 // Scoring heads: fused cosine-similarity + per-transcript arg-max + assignment
 // (prediction) and the triplet margin loss over tx-belongs-bd edges (training).
 #include "common.h"
+#include "post_common.h"
 #include "draws.h"
 
 namespace segger {
@@ -117,7 +118,7 @@ int launch_argmax(const ArgmaxParams& p, hipStream_t stream) {
     const int64_t nb = (p.n_rows + rows_per_block - 1) / rows_per_block;
     hipLaunchKernelGGL((edge_cos_argmax_kernel<T, LPC>), dim3((unsigned)nb), dim3(256), 0, stream, p);
   };
-  const bool vec_ok = (C % 8 == 0) && aligned16(p.zs) && aligned16(p.zd) &&
+  const bool vec_ok = (C % 8 == 0) && is_aligned(p.zs, 16) && is_aligned(p.zd, 16) &&
                       (p.ld_zs * sizeof(T)) % 16 == 0 && (p.ld_zd * sizeof(T)) % 16 == 0;
   if (vec_ok && C == 8) go(std::integral_constant<int, 1>{});
   else if (vec_ok && C == 16) go(std::integral_constant<int, 2>{});
@@ -808,7 +809,7 @@ static int triplet_common(const segger_triplet_args* a, bool bwd, hipStream_t st
     SEGGER_REQUIRE(!(a->grad_a == a->grad_b) || a->grad_a_packed == a->grad_b_packed,
                    "segger_triplet_bwd: one shared gradient buffer cannot be both packed and fp32");
     SEGGER_REQUIRE(!a->grad_a_rows || (a->channels % 2 == 0 && !a->contrib && a->loss_kind == SEGGER_LOSS_TRIPLET &&
-                                       a->n_edges == a->n_a && ((uintptr_t)a->grad_a_rows % 8) == 0),
+                                       a->n_edges == a->n_a && is_aligned(a->grad_a_rows, 8)),
                    "segger_triplet_bwd: grad_a_rows needs an even channel count, one triplet per row of z_a, no contrib");
     p.scale = a->grad_scale / (float)a->n_edges;
     p.scale_dev = a->grad_scale_dev;

@@ -11,6 +11,7 @@
 // Output rows are sorted by distance; missing neighbours (fewer than k within max_dist) are padded with
 // index n_points and distance +inf, exactly like scipy.
 #include "common.h"
+#include "post_common.h"
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -115,7 +116,6 @@ int key_bits(int64_t n_cells) {
   while (b < 32 && (1LL << b) < n_cells) ++b;
   return b;
 }
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t sort_temp_bytes(int64_t n, int64_t n_cells) {
   size_t bytes = 0;
   uint32_t* k = nullptr;
@@ -133,8 +133,8 @@ extern "C" size_t segger_knn_workspace_bytes(int64_t n_points, int32_t nx, int32
   if (n_points <= 0 || nx <= 0 || ny <= 0) return 256;
   const int64_t n_cells = (int64_t)nx * ny;
   // keys_in, keys_out, vals_in, perm (4 B each) + sorted points (8 B) + cell_start + sort temp
-  return 4 * align_up((size_t)n_points * 4) + align_up((size_t)n_points * 8) + align_up((size_t)(n_cells + 1) * 4) +
-         align_up(sort_temp_bytes(n_points, n_cells)) + 256;
+  return 4 * align256((size_t)n_points * 4) + align256((size_t)n_points * 8) + align256((size_t)(n_cells + 1) * 4) +
+         align256(sort_temp_bytes(n_points, n_cells)) + 256;
 }
 
 extern "C" int segger_knn_grid(const float* points, int64_t n_points, const float* queries, int64_t n_queries, int32_t k,
@@ -157,14 +157,14 @@ extern "C" int segger_knn_grid(const float* points, int64_t n_points, const floa
     return SEGGER_EWORKSPACE;
   }
   char* base = static_cast<char*>(workspace);
-  const size_t seg = align_up((size_t)(n_points > 0 ? n_points : 1) * 4);
+  const size_t seg = align256((size_t)(n_points > 0 ? n_points : 1) * 4);
   uint32_t* keys_in = reinterpret_cast<uint32_t*>(base);
   uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + seg);
   int32_t* vals_in = reinterpret_cast<int32_t*>(base + 2 * seg);
   int32_t* perm = reinterpret_cast<int32_t*>(base + 3 * seg);
   float2* sorted_pts = reinterpret_cast<float2*>(base + 4 * seg);
-  int32_t* cell_start = reinterpret_cast<int32_t*>(base + 4 * seg + align_up((size_t)(n_points > 0 ? n_points : 1) * 8));
-  void* temp = reinterpret_cast<char*>(cell_start) + align_up((size_t)(n_cells + 1) * 4);
+  int32_t* cell_start = reinterpret_cast<int32_t*>(base + 4 * seg + align256((size_t)(n_points > 0 ? n_points : 1) * 8));
+  void* temp = reinterpret_cast<char*>(cell_start) + align256((size_t)(n_cells + 1) * 4);
   Grid g{x0, y0, 1.0f / cell, cell, nx, ny};
   if (n_points > 0) {
     const unsigned nb = (unsigned)((n_points + 255) / 256);

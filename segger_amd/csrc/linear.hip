@@ -15,6 +15,7 @@
 //     4-column groups, so the epilogue packs 4 bf16 -> ds_write_b64 into a wave-private
 //     LDS tile and streams it out as full 128-byte row segments (16 B per lane).
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -461,7 +462,7 @@ extern "C" int segger_linear_fwd_pair_k(const segger_linear_args* a, int32_t k_a
       return SEGGER_EUNSUPPORTED;
     }
     SEGGER_REQUIRE(q->n_rows == 0 || (q->x && q->w && q->y), "segger_linear_fwd_pair: NULL pointer");
-    SEGGER_REQUIRE(aligned16(q->x) && aligned16(q->w) && aligned16(q->y), "segger_linear_fwd_pair: pointers must be 16-byte aligned");
+    SEGGER_REQUIRE(is_aligned(q->x, 16) && is_aligned(q->w, 16) && is_aligned(q->y, 16), "segger_linear_fwd_pair: pointers must be 16-byte aligned");
     SEGGER_REQUIRE(q->ldx >= k_in && q->ldy >= q->m_out && (q->ldx * 2) % 16 == 0 && (q->ldy * 2) % 16 == 0,
                    "segger_linear_fwd_pair: bad leading dimension");
     p[i] = LinearParams{q->x, q->ldx, q->w, q->bias, q->y, q->ldy, q->n_rows, q->m_out, nullptr, nullptr, 0, nullptr, 0};
@@ -488,7 +489,7 @@ extern "C" int segger_linear_fwd_silu_grad(const void* x, int64_t ldx, const voi
   SEGGER_REQUIRE(segger_linear_supported(k_in, m_out, dtype) && k_in == 64 && dtype != SEGGER_F32,
                  "segger_linear_fwd_silu_grad: k_in 64, m_out %% 64 == 0, bf16 / f16");
   SEGGER_REQUIRE(x && w && y && gate, "segger_linear_fwd_silu_grad: NULL pointer");
-  SEGGER_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(gate),
+  SEGGER_REQUIRE(is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16) && is_aligned(gate, 16),
                  "segger_linear_fwd_silu_grad: pointers must be 16-byte aligned");
   SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && ld_gate >= m_out && (ldx * 2) % 16 == 0 && (ldy * 2) % 16 == 0 &&
                      (ld_gate * 2) % 8 == 0, "segger_linear_fwd_silu_grad: bad leading dimension");
@@ -509,12 +510,12 @@ extern "C" int segger_linear_fwd_rowbias(const void* x, int64_t ldx, const void*
     return SEGGER_EUNSUPPORTED;
   }
   SEGGER_REQUIRE(x && w && y, "segger_linear_fwd: NULL pointer");
-  SEGGER_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y), "segger_linear_fwd: pointers must be 16-byte aligned");
+  SEGGER_REQUIRE(is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16), "segger_linear_fwd: pointers must be 16-byte aligned");
   if (dtype == SEGGER_F32) {       // fp32 storage: exact-fp32 MFMA kernel (csrc/linear_f32.hip); plain projection only
     SEGGER_REQUIRE(!rowbias == !rowidx, "segger_linear_fwd_rowbias: rowbias and rowidx go together");
-    SEGGER_REQUIRE(!rowbias || (aligned16(rowbias) && ld_rb >= m_out && ld_rb % 4 == 0),
+    SEGGER_REQUIRE(!rowbias || (is_aligned(rowbias, 16) && ld_rb >= m_out && ld_rb % 4 == 0),
                    "segger_linear_fwd_rowbias: the fp32 table needs 16-byte aligned rows of at least m_out elements");
-    SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && (!bias || aligned16(bias)),
+    SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && (!bias || is_aligned(bias, 16)),
                    "segger_linear_fwd: fp32 rows (and the bias) must be 16-byte aligned");
     return linear_f32_launch(x, ldx, w, bias, y, ldy, n_rows, k_in, m_out, (hipStream_t)stream,
                              static_cast<const float*>(rowbias), rowidx, ld_rb);
@@ -522,7 +523,7 @@ extern "C" int segger_linear_fwd_rowbias(const void* x, int64_t ldx, const void*
   SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && (ldx * 2) % 16 == 0 && (ldy * 2) % 16 == 0,
                  "segger_linear_fwd: bad leading dimension");
   SEGGER_REQUIRE(!rowbias == !rowidx, "segger_linear_fwd_rowbias: rowbias and rowidx go together");
-  SEGGER_REQUIRE(!rowbias || (aligned16(rowbias) && ld_rb >= m_out && ld_rb % 8 == 0),
+  SEGGER_REQUIRE(!rowbias || (is_aligned(rowbias, 16) && ld_rb >= m_out && ld_rb % 8 == 0),
                  "segger_linear_fwd_rowbias: the table needs 16-byte aligned rows of at least m_out elements");
   LinearParams p{x, ldx, w, bias, y, ldy, n_rows, m_out, rowbias, rowidx, ld_rb, nullptr, 0};
   return dtype == SEGGER_BF16 ? launch_linear<bf16_t>(p, k_in, (hipStream_t)stream)

@@ -13,6 +13,7 @@
 //     K = 128 (forward of the 128 -> M projections), or K = 384 with M = 128 (their data gradient dX = dY W: W^T planes)
 #include <cstdlib>
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -1094,7 +1095,7 @@ extern "C" int segger_linear_fwd_f32_split(const float* x, int64_t ldx, const vo
 extern "C" int segger_linear_fwd_f32_split_rowbias(const float* x, int64_t ldx, const void* w3, const float* rowbias, int64_t ld_rb,
                                                    const int32_t* rowidx, float* y, int64_t ldy, int64_t n_rows, int32_t k_in,
                                                    int32_t m_out, segger_stream_t stream) {
-  SEGGER_REQUIRE(n_rows == 0 || (rowbias && rowidx && aligned16(rowbias) && ld_rb >= m_out && ld_rb % 4 == 0),
+  SEGGER_REQUIRE(n_rows == 0 || (rowbias && rowidx && is_aligned(rowbias, 16) && ld_rb >= m_out && ld_rb % 4 == 0),
                  "segger_linear_fwd_f32_split_rowbias: table NULL, misaligned or ld < m_out");
   return split_fwd_launch(x, ldx, w3, nullptr, rowbias, ld_rb, rowidx, y, ldy, n_rows, k_in, m_out, stream);
 }
@@ -1104,7 +1105,7 @@ extern "C" int segger_linear_fwd_f32_act(const float* x, int64_t ldx, const floa
                                          int32_t m_out, segger_stream_t stream) {
   SEGGER_REQUIRE(n_rows >= 0 && (act_kind == 1 || act_kind == 2), "segger_linear_fwd_f32_act: act_kind 1 (GELU) or 2 (SiLU)");
   if (n_rows == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(x && w && y && y_act && aligned16(x) && aligned16(w) && aligned16(y) && aligned16(y_act) && (!bias || aligned16(bias)) &&
+  SEGGER_REQUIRE(x && w && y && y_act && is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16) && is_aligned(y_act, 16) && (!bias || is_aligned(bias, 16)) &&
                      ldx >= k_in && ldy >= m_out && ld_yact >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && ld_yact % 4 == 0,
                  "segger_linear_fwd_f32_act: NULL pointer or rows not 16-byte aligned");
   if (!((k_in == 64 || k_in == 128 || k_in == 256) && m_out > 0 && m_out % 64 == 0)) {
@@ -1120,7 +1121,7 @@ extern "C" int segger_linear_fwd_f32_gate(const float* x, int64_t ldx, const voi
                                           int32_t m_out, segger_stream_t stream) {
   SEGGER_REQUIRE(n_rows >= 0 && (gate_kind == 1 || gate_kind == 2), "segger_linear_fwd_f32_gate: gate_kind 1 (GELU) or 2 (SiLU)");
   if (n_rows == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(x && w && y && gate && aligned16(x) && aligned16(w) && aligned16(y) && aligned16(gate) && ldx >= k_in &&
+  SEGGER_REQUIRE(x && w && y && gate && is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16) && is_aligned(gate, 16) && ldx >= k_in &&
                      ldy >= m_out && ld_gate >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && ld_gate % 4 == 0,
                  "segger_linear_fwd_f32_gate: NULL pointer or rows not 16-byte aligned");
   if (w_is_planes) return split_fwd_launch(x, ldx, w, nullptr, nullptr, 0, nullptr, y, ldy, n_rows, k_in, m_out, stream, gate, ld_gate, gate_kind);
@@ -1142,7 +1143,7 @@ static int split_fwd_launch(const float* x, int64_t ldx, const void* w3, const f
   }
   if (n_rows == 0) return SEGGER_OK;
   SEGGER_REQUIRE(x && w3 && y, "segger_linear_fwd_f32_split: NULL pointer");
-  SEGGER_REQUIRE(aligned16(x) && aligned16(w3) && aligned16(y) && (!bias || aligned16(bias)) && ldx >= k_in && ldy >= m_out &&
+  SEGGER_REQUIRE(is_aligned(x, 16) && is_aligned(w3, 16) && is_aligned(y, 16) && (!bias || is_aligned(bias, 16)) && ldx >= k_in && ldy >= m_out &&
                      ldx % 4 == 0 && ldy % 4 == 0, "segger_linear_fwd_f32_split: rows (and the bias) must be 16-byte aligned");
   const int64_t nb = (n_rows + 127) / 128;
   SEGGER_REQUIRE(nb <= 0x7fffffffLL, "segger_linear_fwd_f32_split: too many rows");

@@ -26,6 +26,7 @@
 // waits below include them.
 #include <cstdlib>
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -836,13 +837,13 @@ extern "C" int segger_linear_wgrad_dx(const void* dy, int64_t ld_dy, const void*
     return SEGGER_OK;
   }
   SEGGER_REQUIRE(dy && x && w_t && dx, "segger_linear_wgrad_dx: NULL pointer");
-  SEGGER_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(w_t) && aligned16(dx),
+  SEGGER_REQUIRE(is_aligned(dy, 16) && is_aligned(x, 16) && is_aligned(w_t, 16) && is_aligned(dx, 16),
                  "segger_linear_wgrad_dx: pointers must be 16-byte aligned");
   SEGGER_REQUIRE(ld_dy >= m_out && ld_x >= k_in && ld_dx >= k_in && (ld_dy * 2) % 16 == 0 && (ld_x * 2) % 16 == 0 &&
                      (ld_dx * 2) % 16 == 0, "segger_linear_wgrad_dx: bad leading dimension");
   if (gelu_gate) {
     SEGGER_REQUIRE(dx_gate_ok(m_out, k_in), "segger_linear_wgrad_dx: the gate form covers m_out in {128, 384} (k_in 128)");
-    SEGGER_REQUIRE(aligned16(gelu_gate) && ld_gate >= k_in && (ld_gate * 2) % 16 == 0,
+    SEGGER_REQUIRE(is_aligned(gelu_gate, 16) && ld_gate >= k_in && (ld_gate * 2) % 16 == 0,
                    "segger_linear_wgrad_dx: gate rows must be 16-byte aligned");
   }
   const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in);     // (the dX form never uses more slabs)
@@ -886,7 +887,7 @@ extern "C" int segger_linear_wgrad(const void* dy, int64_t ld_dy, const void* x,
     return SEGGER_OK;
   }
   SEGGER_REQUIRE(dy && x, "segger_linear_wgrad: NULL input");
-  SEGGER_REQUIRE(aligned16(dy) && aligned16(x), "segger_linear_wgrad: inputs must be 16-byte aligned");
+  SEGGER_REQUIRE(is_aligned(dy, 16) && is_aligned(x, 16), "segger_linear_wgrad: inputs must be 16-byte aligned");
   const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in);
   if (workspace == nullptr || workspace_bytes < need) {
     set_error("segger_linear_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -953,7 +954,7 @@ extern "C" int segger_linear_wgrad_f32_split(const float* dy, int64_t ld_dy, con
     if (grad_b) SEGGER_HIP(hipMemsetAsync(grad_b, 0, (size_t)m_out * sizeof(float), stream));
     return SEGGER_OK;
   }
-  SEGGER_REQUIRE(dy && x && aligned16(dy) && aligned16(x) && ld_dy >= m_out && ld_x >= k_in && ld_dy % 4 == 0 && ld_x % 4 == 0,
+  SEGGER_REQUIRE(dy && x && is_aligned(dy, 16) && is_aligned(x, 16) && ld_dy >= m_out && ld_x >= k_in && ld_dy % 4 == 0 && ld_x % 4 == 0,
                  "segger_linear_wgrad_f32_split: rows must be 16-byte aligned");
   const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in);
   if (workspace == nullptr || workspace_bytes < need) {
@@ -993,7 +994,7 @@ extern "C" int segger_linear_wgrad_pair(const segger_wgrad_args* a, const segger
     if (!ok) return separately();
     SEGGER_REQUIRE(q->grad_w != nullptr, "segger_linear_wgrad_pair: grad_w is NULL");
     SEGGER_REQUIRE(q->dy && q->x && (!dx || q->dx), "segger_linear_wgrad_pair: NULL pointer");
-    SEGGER_REQUIRE(aligned16(q->dy) && aligned16(q->x) && aligned16(q->w_t) && aligned16(q->dx),
+    SEGGER_REQUIRE(is_aligned(q->dy, 16) && is_aligned(q->x, 16) && is_aligned(q->w_t, 16) && is_aligned(q->dx, 16),
                    "segger_linear_wgrad_pair: pointers must be 16-byte aligned");
     SEGGER_REQUIRE(q->ld_dy >= q->m_out && q->ld_x >= k_in && (q->ld_dy * 2) % 16 == 0 && (q->ld_x * 2) % 16 == 0 &&
                        (!dx || (q->ld_dx >= k_in && (q->ld_dx * 2) % 16 == 0)), "segger_linear_wgrad_pair: bad leading dimension");
@@ -1058,7 +1059,7 @@ extern "C" int segger_posmlp_wgrad(const void* dz1, int64_t ld_dz1, const float*
     return SEGGER_OK;
   }
   SEGGER_REQUIRE(dz1 && pn, "segger_posmlp_wgrad: NULL input");
-  SEGGER_REQUIRE(aligned16(dz1) && aligned16(pn) && ld_dz1 >= M && (ld_dz1 * 2) % 16 == 0,
+  SEGGER_REQUIRE(is_aligned(dz1, 16) && is_aligned(pn, 16) && ld_dz1 >= M && (ld_dz1 * 2) % 16 == 0,
                  "segger_posmlp_wgrad: dz1 rows and pn must be 16-byte aligned");
   const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, M, K);
   if (workspace == nullptr || workspace_bytes < need) {
@@ -1112,7 +1113,7 @@ extern "C" int segger_posmlp_bwd_pair(const void* g_a, int64_t ld_ga, const void
     SEGGER_HIP(hipMemsetAsync(grad_b2, 0, (size_t)kPbD * sizeof(float), stream));
     return SEGGER_OK;
   }
-  SEGGER_REQUIRE(w2_t && aligned16(w2_t), "segger_posmlp_bwd: NULL / misaligned W2^T");
+  SEGGER_REQUIRE(w2_t && is_aligned(w2_t, 16), "segger_posmlp_bwd: NULL / misaligned W2^T");
   const size_t need = segger_posmlp_bwd_pair_workspace_bytes(n_rows_a, n_rows_b);
   if (workspace == nullptr || workspace_bytes < need) {
     set_error("segger_posmlp_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -1127,7 +1128,7 @@ extern "C" int segger_posmlp_bwd_pair(const void* g_a, int64_t ld_ga, const void
                   PosBwdParams& out) -> int {
     if (n_rows == 0) { out = PosBwdParams{nullptr, kPbD, nullptr, nullptr, w2_t, 0, 0, 0, part2, part0, lmp}; return SEGGER_OK; }
     SEGGER_REQUIRE(g && z1 && pn, "segger_posmlp_bwd: NULL input");
-    SEGGER_REQUIRE(aligned16(g) && aligned16(z1) && aligned16(pn) && ld_g >= kPbD && (ld_g * 2) % 16 == 0,
+    SEGGER_REQUIRE(is_aligned(g, 16) && is_aligned(z1, 16) && is_aligned(pn, 16) && ld_g >= kPbD && (ld_g * 2) % 16 == 0,
                    "segger_posmlp_bwd: rows must be 16-byte aligned");
     const int64_t stages = (n_rows + kStageRows - 1) / kStageRows;
     SEGGER_REQUIRE(((stages + grid_s - 1) / grid_s + kPbAhead) * kStageRows * ld_g * 2 < (int64_t)kOutOfRange,

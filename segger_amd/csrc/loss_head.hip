@@ -30,6 +30,7 @@
 //
 // Row layout: 16 lanes per row, CPL = C / 16 consecutive channels per lane (C in {32, 64, 128}).
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -615,7 +616,7 @@ int fill_params(const segger_loss_head_args* a, bool bwd, LossHeadParams* out) {
     SEGGER_REQUIRE(!a->tx_w == !a->tx_state && !a->tx_state == !a->tx_next && !a->tx_next == !a->tx_hot_id && !a->tx_hot_id == !a->tx_hot_acc,
                    "segger_loss_head_fwd: tx_w, tx_state, tx_next, tx_hot_id and tx_hot_acc go together");
     SEGGER_REQUIRE(!a->grad_out || a->grad_raw, "segger_loss_head_fwd: grad_out needs grad_raw");
-    SEGGER_REQUIRE(!a->grad_bd || ((uintptr_t)a->grad_bd % 16) == 0, "segger_loss_head_fwd: grad_bd must be 16-byte aligned");
+    SEGGER_REQUIRE(!a->grad_bd || is_aligned(a->grad_bd, 16), "segger_loss_head_fwd: grad_bd must be 16-byte aligned");
   } else {
     SEGGER_REQUIRE(a->grad_raw && a->tx_w && a->tx_state && a->tx_next && a->tx_hot_id && a->tx_hot_acc,
                    "segger_loss_head_bwd: needs grad_raw and the forward's tx_w / tx_state / tx_next / tx_hot_id / tx_hot_acc");

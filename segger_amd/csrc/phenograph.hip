@@ -14,6 +14,7 @@
 //
 // Nothing here is contracted by the compiler: every fused multiply-add is an explicit fma()/fmaf().
 #include "common.h"
+#include "post_common.h"
 #pragma clang fp contract(off)
 
 namespace segger {
@@ -31,8 +32,6 @@ constexpr int kQThreads = 256;                          // the single workgroup 
 
 static_assert(kCTile == kWave, "selection: one candidate of the tile per lane");
 static_assert(SEGGER_KNN_BF_MAX_K <= kWave, "a row's list is one key per lane");
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 struct KnnPlan {
   int64_t q_tiles, n_slabs, slab_len;
@@ -52,23 +51,15 @@ KnnPlan knn_plan(int64_t n, int64_t d, int64_t k) {
   p.n_slabs = slabs;
   p.slab_len = ceil_div(ceil_div(n > 0 ? n : 1, slabs), kCTile) * kCTile;
   p.n_slabs = ceil_div(n > 0 ? n : 1, p.slab_len);       // no empty slab at the end
-  p.norm = 0;
-  p.partial = ((size_t)n * sizeof(float) + 255) / 256 * 256;
-  p.total = p.partial + (size_t)p.n_slabs * (size_t)n * (size_t)k * sizeof(uint64_t);
+  const size_t partial_bytes = (size_t)p.n_slabs * (size_t)n * (size_t)k * sizeof(uint64_t);
+  Carver ws;
+  p.norm = ws.take((size_t)n * sizeof(float));
+  p.partial = ws.take(partial_bytes);
+  p.total = p.partial + partial_bytes;                  // the last region is not rounded up
   return p;
 }
 
 // ---------------------------------------------------------------- wave-wide 64-bit helpers ---
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, kWave);
-  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, kWave);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask, kWave);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask, kWave);
-  return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a < b ? b : a; }
 
@@ -95,17 +86,8 @@ __device__ __forceinline__ uint64_t wave_merge(uint64_t a, uint64_t b, int lane)
   }
   return key;
 }
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) v += (int64_t)shfl_xor64((uint64_t)v, m);
-  return v;
-}
 
-// float bits whose unsigned order is the float order (a cancelled score may be slightly negative)
-__device__ __forceinline__ uint32_t ordered_bits(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// scores in float order (a cancelled score may be slightly negative)
 __device__ __forceinline__ uint64_t score_key(float s, uint32_t index) { return ((uint64_t)ordered_bits(s) << 32) | index; }
 
 // ---------------------------------------------------------------- kNN ---
@@ -390,8 +372,6 @@ __global__ __launch_bounds__(kQThreads) void louvain_modularity_kernel(const int
   if (threadIdx.x == 0) q[0] = part[0];
 }
 
-bool pg_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 int knn_check_sizes(const char* who, int64_t n, int64_t d, int64_t k) {
   SEGGER_REQUIRE(n >= 1, "%s: n must be at least 1", who);
   SEGGER_REQUIRE(n <= 0x7fffffffLL, "%s: 2^31 rows or more", who);
@@ -406,7 +386,7 @@ int graph_check(const char* who, const int64_t* indptr, const int32_t* indices, 
   SEGGER_REQUIRE(n <= 0x7fffffffLL, "%s: 2^31 vertices or more", who);
   SEGGER_REQUIRE(nnz >= 0, "%s: negative nnz", who);
   SEGGER_REQUIRE(indptr && (nnz == 0 || indices), "%s: NULL pointer", who);
-  SEGGER_REQUIRE(pg_aligned(indptr, 8) && pg_aligned(indices, 4), "%s: indptr must be 8-byte and indices 4-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(indptr, 8) && is_aligned(indices, 4), "%s: indptr must be 8-byte and indices 4-byte aligned", who);
   return SEGGER_OK;
 }
 
@@ -434,18 +414,14 @@ extern "C" int segger_knn_bruteforce(const float* X, int64_t n, int32_t d, int32
   int rc = knn_check_sizes(who, n, d, k);
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(X && idx && dist2 && workspace, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(pg_aligned(X, 4) && pg_aligned(idx, 4) && pg_aligned(dist2, 4), "%s: X, idx and dist2 must be 4-byte aligned",
+  SEGGER_REQUIRE(is_aligned(X, 4) && is_aligned(idx, 4) && is_aligned(dist2, 4), "%s: X, idx and dist2 must be 4-byte aligned",
                  who);
-  SEGGER_REQUIRE(pg_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
   SEGGER_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", who);
   const KnnPlan plan = knn_plan(n, d, k);
-  if ((size_t)workspace_bytes < plan.total) {
-    set_error("%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, plan.total);
-    return SEGGER_EWORKSPACE;
-  }
-  char* base = static_cast<char*>(workspace);
-  float* norm = reinterpret_cast<float*>(base + plan.norm);
-  uint64_t* partial = reinterpret_cast<uint64_t*>(base + plan.partial);
+  if ((size_t)workspace_bytes < plan.total) return workspace_too_small(who, (size_t)workspace_bytes, plan.total);
+  float* norm = at<float>(workspace, plan.norm);
+  uint64_t* partial = at<uint64_t>(workspace, plan.partial);
   hipLaunchKernelGGL(knn_norm_kernel, dim3((unsigned)ceil_div(n, kRowThreads)), dim3(kRowThreads), 0, stream, X, n, (int)d, norm);
   SEGGER_LAUNCH_CHECK("knn_norm_kernel");
   if (d <= 32) rc = knn_select_launch<32>(X, norm, n, d, k, plan, partial, stream);
@@ -467,7 +443,7 @@ extern "C" int segger_jaccard_weights(const int64_t* indptr, const int32_t* indi
   if (rc != SEGGER_OK) return rc;
   if (n == 0 || nnz == 0) return SEGGER_OK;
   SEGGER_REQUIRE(weight, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(pg_aligned(weight, 8), "%s: weight must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(weight, 8), "%s: weight must be 8-byte aligned", who);
   hipLaunchKernelGGL(jaccard_kernel, dim3((unsigned)ceil_div(nnz, kRowThreads)), dim3(kRowThreads), 0, stream, indptr, indices, n,
                      nnz, weight);
   SEGGER_LAUNCH_CHECK("jaccard_kernel");
@@ -487,8 +463,8 @@ extern "C" int segger_louvain_move(const int64_t* indptr, const int32_t* indices
   SEGGER_REQUIRE(two_m > 0.0 && gamma >= 0.0, "%s: two_m must be positive and gamma not negative", who);
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(kdeg && comm && tot && size && proposal && (nnz == 0 || weight), "%s: NULL pointer", who);
-  SEGGER_REQUIRE(pg_aligned(weight, 8) && pg_aligned(kdeg, 8) && pg_aligned(tot, 8) && pg_aligned(comm, 4) &&
-                     pg_aligned(size, 4) && pg_aligned(proposal, 4),
+  SEGGER_REQUIRE(is_aligned(weight, 8) && is_aligned(kdeg, 8) && is_aligned(tot, 8) && is_aligned(comm, 4) &&
+                     is_aligned(size, 4) && is_aligned(proposal, 4),
                  "%s: weight, kdeg and tot must be 8-byte, comm, size and proposal 4-byte aligned", who);
   const int64_t active = ceil_div(n - sub > 0 ? n - sub : 0, n_sub);
   if (active == 0) return SEGGER_OK;
@@ -512,8 +488,8 @@ extern "C" int segger_louvain_modularity(const int64_t* indptr, const int32_t* i
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(two_m > 0.0 && gamma >= 0.0, "%s: two_m must be positive and gamma not negative", who);
   SEGGER_REQUIRE(q && (n == 0 || (self_weight && comm && tot && in_c)) && (nnz == 0 || weight), "%s: NULL pointer", who);
-  SEGGER_REQUIRE(pg_aligned(weight, 8) && pg_aligned(self_weight, 8) && pg_aligned(tot, 8) && pg_aligned(in_c, 8) &&
-                     pg_aligned(q, 8) && pg_aligned(comm, 4),
+  SEGGER_REQUIRE(is_aligned(weight, 8) && is_aligned(self_weight, 8) && is_aligned(tot, 8) && is_aligned(in_c, 8) &&
+                     is_aligned(q, 8) && is_aligned(comm, 4),
                  "%s: weight, self_weight, tot, in_c and q must be 8-byte, comm 4-byte aligned", who);
   if (n > 0) {
     SEGGER_HIP(hipMemsetAsync(in_c, 0, (size_t)n * sizeof(int64_t), stream));

@@ -2,6 +2,7 @@
 // Replaces the Python loop over graphs (one boolean mask + two reductions + a
 // host sync per graph) of reference src/segger/models/ist_encoder.py:66-73.
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -124,7 +125,7 @@ extern "C" int segger_segment_minmax_ex(const float* pos, const int64_t* batch, 
   if (n_graphs == 0) return SEGGER_OK;
   SEGGER_REQUIRE(mins && maxs, "segger_segment_minmax: NULL output");
   SEGGER_REQUIRE(n == 0 || pos, "segger_segment_minmax: pos is NULL");
-  SEGGER_REQUIRE((reinterpret_cast<uintptr_t>(pos) & 7u) == 0, "segger_segment_minmax: pos must be 8-byte aligned");
+  SEGGER_REQUIRE(is_aligned(pos, 8), "segger_segment_minmax: pos must be 8-byte aligned");
   const int64_t n2 = 2 * n_graphs;
   const unsigned gb = (unsigned)((n2 + 255) / 256);
   if (!(flags & SEGGER_MINMAX_INITIALISED))

@@ -21,6 +21,7 @@
 // posmlp.hip).  Nothing here is approximate beyond the 1.6e-10 truncation: the arithmetic is fp32 FMA, the reductions fp32
 // per lane and float64 across workgroups.
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -242,7 +243,7 @@ extern "C" int segger_posenc_poly_fwd(const float* pos, const int64_t* batch, co
   SEGGER_REQUIRE(n >= 0 && (dim == 32 || dim == 64 || dim == 128), "segger_posenc_poly_fwd: negative size or dim not in 32 / 64 / 128");
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(pos && mins && maxs && coef && z1, "segger_posenc_poly_fwd: NULL pointer");
-  SEGGER_REQUIRE(aligned16(z1) && aligned16(h1), "segger_posenc_poly_fwd: z1 / h1 must be 16-byte aligned");
+  SEGGER_REQUIRE(is_aligned(z1, 16) && is_aligned(h1, 16), "segger_posenc_poly_fwd: z1 / h1 must be 16-byte aligned");
   PolyFwd p{pos, batch, mins, maxs, n, eps, coef, z1, h1, pn};
   // (no partial tables here: as many workgroups as there are pairs of row batches -- a row's loads are a dependent chain
   //  batch id -> min / max -> position, which only other workgroups can hide)
@@ -272,7 +273,7 @@ extern "C" int segger_posenc_poly_wgrad(const float* dz1, int64_t ld, const floa
     if (grad_b0) SEGGER_HIP(hipMemsetAsync(grad_b0, 0, (size_t)dim * sizeof(float), (hipStream_t)stream));
     return SEGGER_OK;
   }
-  SEGGER_REQUIRE(dz1 && pn && aligned16(dz1) && ld >= dim && ld % 4 == 0, "segger_posenc_poly_wgrad: dz1 NULL, misaligned or ld < dim");
+  SEGGER_REQUIRE(dz1 && pn && is_aligned(dz1, 16) && ld >= dim && ld % 4 == 0, "segger_posenc_poly_wgrad: dz1 NULL, misaligned or ld < dim");
   const size_t need = segger_posenc_poly_wgrad_workspace_bytes(n_rows, dim);
   if (!workspace || workspace_bytes < need) {
     set_error("segger_posenc_poly_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);

@@ -10,6 +10,7 @@
 // dW0 = dz1^T F regenerates F the same way (segger_posmlp_wgrad: linear_wgrad.hip's kernel with a generated operand).  The second GEMM consumes the first one's accumulators without a transpose:
 // the k order of a GEMM is free, so the A operand (W2) is read from LDS in the order the accumulator lanes hold h1.
 #include "common.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -283,12 +284,12 @@ extern "C" int segger_posmlp_fwd(const float* pos, const int64_t* batch, const f
   SEGGER_REQUIRE(pos && mins && maxs && w0 && b0 && w2 && b2 && pe, "segger_posmlp_fwd: NULL pointer");
   SEGGER_REQUIRE(!z1 == !pn && (z1 || !h1),
                  "segger_posmlp_fwd: z1 and pn go together (both for training, none for inference); h1 only with them");
-  SEGGER_REQUIRE(aligned16(h1), "segger_posmlp_fwd: h1 must be 16-byte aligned");
-  SEGGER_REQUIRE(aligned16(w0) && aligned16(w2) && aligned16(pe) && aligned16(z1) && aligned16(pn),
+  SEGGER_REQUIRE(is_aligned(h1, 16), "segger_posmlp_fwd: h1 must be 16-byte aligned");
+  SEGGER_REQUIRE(is_aligned(w0, 16) && is_aligned(w2, 16) && is_aligned(pe, 16) && is_aligned(z1, 16) && is_aligned(pn, 16),
                  "segger_posmlp_fwd: matrices must be 16-byte aligned");
   SEGGER_REQUIRE(!pe_pre || (gelu && z1), "segger_posmlp_fwd: pe_pre is the training output of the gelu variant");
   SEGGER_REQUIRE(!(gelu && z1) || pe_pre, "segger_posmlp_fwd: training with gelu needs pe_pre");
-  SEGGER_REQUIRE(aligned16(pe_pre), "segger_posmlp_fwd: pe_pre must be 16-byte aligned");
+  SEGGER_REQUIRE(is_aligned(pe_pre, 16), "segger_posmlp_fwd: pe_pre must be 16-byte aligned");
   PosMlpParams p{pos, batch, mins, maxs, n, eps, logf(max_period), w0, b0, w2, b2, pe, z1, pn, pe_pre, h1};
   const int64_t n_tiles = (2 * n + 31) / 32;
   int64_t blocks = (n_tiles + kPmWaves - 1) / kPmWaves;

@@ -1,0 +1,80 @@
+// Host-side scaffolding shared by the translation units (included after common.h): the predicates that decide whether a
+// pointer may be dereferenced, the rule that places the scratch arrays inside a caller's workspace, and the whole-wave
+// integer helpers of the post-processing kernels.  One definition each: a fix to the carving rule or to an alignment
+// check is made here and nowhere else.
+#pragma once
+#include "common.h"
+
+namespace segger {
+
+// ---------------------------------------------------------------- host: sizes and pointers ---
+// bytes is a power of two.  NULL counts as aligned: optional pointers pass, and are rejected (or not) by the NULL checks.
+inline bool is_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline int bit_length(unsigned long long v) {
+  int b = 0;
+  while (v) { ++b; v >>= 1; }
+  return b;
+}
+
+// grid of a grid-stride kernel: one thread per item up to max_blocks blocks, never an empty grid
+inline unsigned grid_stride_blocks(int64_t n_items, int threads, int64_t max_blocks) {
+  const int64_t blocks = ceil_div(n_items, threads);
+  return (unsigned)(blocks < 1 ? 1 : (blocks < max_blocks ? blocks : max_blocks));
+}
+
+// The regions of a workspace, first to last: every region starts on a 256-byte boundary of a 256-byte aligned base.
+struct Carver {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t start = off;
+    off += align256(bytes);
+    return start;
+  }
+  size_t total() const { return off; }
+};
+
+template <typename T>
+inline T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
+inline int workspace_too_small(const char* who, size_t have, size_t need) {
+  set_error("%s: workspace %zu < %zu bytes", who, have, need);
+  return SEGGER_EWORKSPACE;
+}
+
+// ---------------------------------------------------------------- device: whole-wave integer sums ---
+// every lane returns the total
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+  return v;
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, kWave);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, kWave);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask, kWave);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask, kWave);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v += (int64_t)shfl_xor64((uint64_t)v, m);
+  return v;
+}
+
+// float bits whose unsigned order is the float order: -0.0 sorts just below +0.0 as a value of its own and NaNs are the
+// caller's business (csrc/assign.hip's mapping canonicalises both and is a different function)
+__device__ __forceinline__ uint32_t ordered_bits(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+}  // namespace segger

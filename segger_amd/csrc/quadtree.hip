@@ -3,6 +3,7 @@
 // The tree itself is tiny: a node's population is the difference of two binary searches on the sorted keys, so the leaves
 // come from one small work-list kernel per depth over the nodes that were split one depth up.
 #include "common.h"
+#include "post_common.h"
 #include <cmath>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -150,8 +151,6 @@ __global__ __launch_bounds__(256) void quadtree_label_kernel(const float2* __res
   labels[i] = lab;
 }
 
-size_t qt_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int qt_key_bits(int depth) { return 2 * depth; }
 
 size_t qt_sort_temp_bytes(int64_t n, int depth, int64_t leaf_cap) {
@@ -192,22 +191,21 @@ struct QtLayout {
 QtLayout qt_layout(int64_t n, int depth, int64_t max_size, int64_t leaf_cap) {
   QtLayout L;
   L.split_cap = qt_split_cap(n, max_size);
-  const size_t split_bytes = qt_align((size_t)(L.split_cap > 0 ? L.split_cap : 1) * 4);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += qt_align(bytes); return at; };
-  L.keys_a = take((size_t)n * 4);
-  L.keys_b = take((size_t)n * 4);
-  L.split_a = take(split_bytes);
-  L.split_b = take(split_bytes);
-  L.counters = take((size_t)(kQtMaxDepth + 1) * 4);
-  L.code_a = take((size_t)leaf_cap * 8);
-  L.code_b = take((size_t)leaf_cap * 8);
-  L.cnt_a = take((size_t)leaf_cap * 4);
-  L.mlo_a = take((size_t)leaf_cap * 4);
-  L.mid_a = take((size_t)leaf_cap * 4);
+  const size_t split_bytes = align256((size_t)(L.split_cap > 0 ? L.split_cap : 1) * 4);
+  Carver ws;
+  L.keys_a = ws.take((size_t)n * 4);
+  L.keys_b = ws.take((size_t)n * 4);
+  L.split_a = ws.take(split_bytes);
+  L.split_b = ws.take(split_bytes);
+  L.counters = ws.take((size_t)(kQtMaxDepth + 1) * 4);
+  L.code_a = ws.take((size_t)leaf_cap * 8);
+  L.code_b = ws.take((size_t)leaf_cap * 8);
+  L.cnt_a = ws.take((size_t)leaf_cap * 4);
+  L.mlo_a = ws.take((size_t)leaf_cap * 4);
+  L.mid_a = ws.take((size_t)leaf_cap * 4);
   L.temp_bytes = qt_sort_temp_bytes(n, depth, leaf_cap);
-  L.temp = take(L.temp_bytes > 0 ? L.temp_bytes : 1);
-  L.total = off;
+  L.temp = ws.take(L.temp_bytes > 0 ? L.temp_bytes : 1);
+  L.total = ws.total();
   return L;
 }
 
@@ -231,25 +229,22 @@ extern "C" int segger_quadtree_build(const float* points, int64_t n_points, doub
   if (rc != SEGGER_OK) return rc;
   SEGGER_REQUIRE(points && leaf_key && leaf_depth && leaf_count && morton_lo && morton_id && n_leaf && labels,
                  "segger_quadtree_build: NULL pointer");
-  SEGGER_REQUIRE((reinterpret_cast<uintptr_t>(points) & 7u) == 0, "segger_quadtree_build: points must be 8-byte aligned");
+  SEGGER_REQUIRE(is_aligned(points, 8), "segger_quadtree_build: points must be 8-byte aligned");
   SEGGER_REQUIRE(std::isfinite(x0) && std::isfinite(y0), "segger_quadtree_build: origin is not finite");
   SEGGER_REQUIRE(qt_power_of_two(cell) && cell >= 1.0, "segger_quadtree_build: cell must be a power of two >= 1");
   const QtLayout L = qt_layout(n_points, depth, max_size, leaf_cap);
-  if (workspace == nullptr || workspace_bytes < L.total) {
-    set_error("segger_quadtree_build: workspace %zu < %zu bytes", workspace_bytes, L.total);
-    return SEGGER_EWORKSPACE;
-  }
-  char* base = static_cast<char*>(workspace);
-  uint32_t* keys_a = reinterpret_cast<uint32_t*>(base + L.keys_a);
-  uint32_t* keys_b = reinterpret_cast<uint32_t*>(base + L.keys_b);
-  uint32_t* split[2] = {reinterpret_cast<uint32_t*>(base + L.split_a), reinterpret_cast<uint32_t*>(base + L.split_b)};
-  int32_t* n_split = reinterpret_cast<int32_t*>(base + L.counters);        // [d]: nodes split at depth d
-  uint64_t* code_a = reinterpret_cast<uint64_t*>(base + L.code_a);
-  uint64_t* code_b = reinterpret_cast<uint64_t*>(base + L.code_b);
-  int32_t* cnt_a = reinterpret_cast<int32_t*>(base + L.cnt_a);
-  uint32_t* mlo_a = reinterpret_cast<uint32_t*>(base + L.mlo_a);
-  int32_t* mid_a = reinterpret_cast<int32_t*>(base + L.mid_a);
-  void* temp = base + L.temp;
+  if (workspace == nullptr || workspace_bytes < L.total)
+    return workspace_too_small("segger_quadtree_build", workspace_bytes, L.total);
+  uint32_t* keys_a = at<uint32_t>(workspace, L.keys_a);
+  uint32_t* keys_b = at<uint32_t>(workspace, L.keys_b);
+  uint32_t* split[2] = {at<uint32_t>(workspace, L.split_a), at<uint32_t>(workspace, L.split_b)};
+  int32_t* n_split = at<int32_t>(workspace, L.counters);        // [d]: nodes split at depth d
+  uint64_t* code_a = at<uint64_t>(workspace, L.code_a);
+  uint64_t* code_b = at<uint64_t>(workspace, L.code_b);
+  int32_t* cnt_a = at<int32_t>(workspace, L.cnt_a);
+  uint32_t* mlo_a = at<uint32_t>(workspace, L.mlo_a);
+  int32_t* mid_a = at<int32_t>(workspace, L.mid_a);
+  void* temp = at<char>(workspace, L.temp);
   size_t temp_bytes = L.temp_bytes;
 
   const QtFrame f{x0, y0, INFINITY, INFINITY, 1.0 / cell, (int)depth};
@@ -304,7 +299,7 @@ extern "C" int segger_quadtree_label(const float* points, int64_t n_points, doub
   SEGGER_REQUIRE(qt_power_of_two(cell) && cell >= 1.0, "segger_quadtree_label: cell must be a power of two >= 1");
   if (n_points == 0) return SEGGER_OK;
   SEGGER_REQUIRE(points && leaf_key && leaf_depth && morton_lo && morton_id && labels, "segger_quadtree_label: NULL pointer");
-  SEGGER_REQUIRE((reinterpret_cast<uintptr_t>(points) & 7u) == 0, "segger_quadtree_label: points must be 8-byte aligned");
+  SEGGER_REQUIRE(is_aligned(points, 8), "segger_quadtree_label: points must be 8-byte aligned");
   const QtFrame f{x0, y0, x1, y1, 1.0 / cell, (int)depth};
   hipLaunchKernelGGL(quadtree_label_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const float2*>(points), n_points, f, leaf_key, leaf_depth,

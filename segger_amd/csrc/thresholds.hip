@@ -8,8 +8,8 @@
 // Per row: 12 bytes streamed in, 8 bytes of key through the sort, two streaming reads of the sorted keys; per gene one
 // workgroup: 255 binary searches for Yen's histogram, and per Li iteration one binary search plus a sum of < kThrChunk rows.
 #include "common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "post_common.h"
+#include "sort_config.h"
 
 // numpy rounds every product before it adds: a fused multiply-add would move a bin edge by an ulp past a value that sits on it
 #pragma clang fp contract(off)
@@ -26,17 +26,13 @@ constexpr uint32_t kThrNoGene = 0xffffffffu;    // high word of the sentinel key
 constexpr unsigned long long kThrSentinel = ~0ull;
 constexpr unsigned long long kThrInfBits = 0x7ff0000000000000ull;
 
-// the `basic` ranking of the onesweep pass keeps no scratch (csrc/expression.hip has the measurement for pairs)
-using ThrSortConfig = rocprim::radix_sort_config<
-    rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<256, 12>, rocprim::kernel_config<256, 12>, 8,
-                                        rocprim::block_radix_rank_algorithm::basic>>;
-
 // counters block of segger_thresholds_build
 enum { kThrAssigned = 0, kThrGenesPresent = 1, kThrBad = 2, kThrNan = 3, kThrCounters = 4 };
 
-// similarity bits -> unsigned order, as csrc/assign.hip's but without its canonicalisation: -0.0 sorts just below
-// +0.0 as a key of its own, and a NaN never gets here
+// similarity bits -> unsigned order: the same mapping as ordered_bits (post_common.h) -- -0.0 sorts just below +0.0 as a
+// key of its own, and a NaN never gets here -- written as one xor.  It stays a function of this file because the
+// compiler turns the two spellings into different code: with ordered_bits the row loop of thresholds_keys_kernel gains
+// a branch and four SGPRs.
 __device__ __forceinline__ uint32_t thr_ord(float s) {
   const uint32_t b = __float_as_uint(s);
   return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
@@ -48,12 +44,6 @@ __device__ __forceinline__ double thr_value(unsigned long long key) {
 }
 
 __device__ __forceinline__ uint32_t thr_gene(unsigned long long key) { return (uint32_t)(key >> 32); }
-
-__device__ __forceinline__ int thr_wave_sum_i32(int v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-  return v;
-}
 
 // One key per row; unassigned and rejected rows take the sentinel and sort behind every real key.  An assigned row with a
 // gene outside [0, n_genes) or a NaN similarity is counted and never used as an index.  The same grid initialises the
@@ -82,9 +72,9 @@ __global__ __launch_bounds__(kThrThreads) void thresholds_keys_kernel(
     n_bad += (assigned && !in_range) ? 1 : 0;
     n_nan += (assigned && in_range && is_nan) ? 1 : 0;
   }
-  n_ok = thr_wave_sum_i32(n_ok);                                 // at most 2^31 / (1024 * 256) + 1 rows per thread
-  n_bad = thr_wave_sum_i32(n_bad);
-  n_nan = thr_wave_sum_i32(n_nan);
+  n_ok = wave_sum_i32(n_ok);                                 // at most 2^31 / (1024 * 256) + 1 rows per thread
+  n_bad = wave_sum_i32(n_bad);
+  n_nan = wave_sum_i32(n_nan);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     if (n_ok) atomicAdd(counters + kThrAssigned, (unsigned long long)n_ok);
     if (n_bad) atomicAdd(counters + kThrBad, (unsigned long long)n_bad);
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(kThrThreads) void thresholds_segments_kernel(
     }
     if (p == n - 1 || thr_gene(keys[p + 1]) != g) end[g] = (int32_t)(p + 1);
   }
-  n_present = thr_wave_sum_i32(n_present);
+  n_present = wave_sum_i32(n_present);
   if ((threadIdx.x & (kWave - 1)) == 0 && n_present) atomicAdd(counters + kThrGenesPresent, (unsigned long long)n_present);
 }
 
@@ -327,20 +317,7 @@ __global__ __launch_bounds__(kThrThreads) void thresholds_absent_kernel(int64_t 
   }
 }
 
-size_t thr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-unsigned thr_grid(int64_t n_items) {
-  const int64_t blocks = (n_items + kThrThreads - 1) / kThrThreads;
-  return (unsigned)(blocks < 1 ? 1 : (blocks < kThrMaxBlocks ? blocks : kThrMaxBlocks));
-}
-
-bool thr_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
-int thr_bit_length(unsigned long long v) {
-  int b = 0;
-  while (v) { ++b; v >>= 1; }
-  return b;
-}
+unsigned thr_grid(int64_t n_items) { return grid_stride_blocks(n_items, kThrThreads, kThrMaxBlocks); }
 
 int thr_check_sizes(const char* who, int64_t n_rows, int64_t n_genes) {
   SEGGER_REQUIRE(n_rows >= 0, "%s: negative n_rows", who);
@@ -359,22 +336,21 @@ struct ThrLayout {
 // with n_rows and n_genes below 2^31 every term is below 2^36 bytes: nothing here can overflow
 ThrLayout thr_layout(int64_t n_rows, int64_t n_genes) {
   ThrLayout L;
-  L.key_bits = 32 + thr_bit_length((unsigned long long)n_genes);   // the sentinel is all ones in these bits, above every gene
+  L.key_bits = 32 + bit_length((unsigned long long)n_genes);   // the sentinel is all ones in these bits, above every gene
   const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += thr_align(bytes); return at; };
-  L.keys_a = take(n * 8);
-  L.keys_b = take(n * 8);
-  L.beg = take((size_t)n_genes * 4);
-  L.end = take((size_t)n_genes * 4);
-  L.gap = take((size_t)n_genes * 8);
-  L.chunk_sum = take((n + (size_t)kThrChunk - 1) / (size_t)kThrChunk * 8);
+  Carver ws;
+  L.keys_a = ws.take(n * 8);
+  L.keys_b = ws.take(n * 8);
+  L.beg = ws.take((size_t)n_genes * 4);
+  L.end = ws.take((size_t)n_genes * 4);
+  L.gap = ws.take((size_t)n_genes * 8);
+  L.chunk_sum = ws.take((n + (size_t)kThrChunk - 1) / (size_t)kThrChunk * 8);
   size_t a = 0;
   unsigned long long* k64 = nullptr;
-  (void)rocprim::radix_sort_keys<ThrSortConfig>(nullptr, a, k64, k64, n, 0, (unsigned)L.key_bits, (hipStream_t)0);
+  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, a, k64, k64, n, 0, (unsigned)L.key_bits, (hipStream_t)0);
   L.temp_bytes = a;
-  L.temp = take(a > 0 ? a : 1);
-  L.total = off;
+  L.temp = ws.take(a > 0 ? a : 1);
+  L.total = ws.total();
   return L;
 }
 
@@ -401,8 +377,8 @@ extern "C" int segger_thresholds_build(const float* similarity, const int32_t* g
   SEGGER_REQUIRE(workspace_bytes >= 0, "%s: negative workspace size", who);
   SEGGER_REQUIRE(threshold && yen && li && count && converged && counters, "%s: NULL pointer", who);
   SEGGER_REQUIRE(n_rows == 0 || (similarity && gene && cell && workspace), "%s: NULL pointer", who);
-  SEGGER_REQUIRE(thr_aligned(threshold, 8) && thr_aligned(yen, 8) && thr_aligned(li, 8) && thr_aligned(count, 8) &&
-                     thr_aligned(counters, 8),
+  SEGGER_REQUIRE(is_aligned(threshold, 8) && is_aligned(yen, 8) && is_aligned(li, 8) && is_aligned(count, 8) &&
+                     is_aligned(counters, 8),
                  "%s: threshold, yen, li, count and counters must be 8-byte aligned", who);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
   if (n_rows == 0) {                               // no row pointer and no workspace is looked at
@@ -412,22 +388,18 @@ extern "C" int segger_thresholds_build(const float* similarity, const int32_t* g
     SEGGER_LAUNCH_CHECK("thresholds_absent_kernel");
     return SEGGER_OK;
   }
-  SEGGER_REQUIRE(thr_aligned(similarity, 4) && thr_aligned(gene, 4) && thr_aligned(cell, 4),
+  SEGGER_REQUIRE(is_aligned(similarity, 4) && is_aligned(gene, 4) && is_aligned(cell, 4),
                  "%s: similarity, gene and cell must be 4-byte aligned", who);
-  SEGGER_REQUIRE(thr_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
   const ThrLayout L = thr_layout(n_rows, n_genes);
-  if ((size_t)workspace_bytes < L.total) {
-    set_error("%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, L.total);
-    return SEGGER_EWORKSPACE;
-  }
+  if ((size_t)workspace_bytes < L.total) return workspace_too_small(who, (size_t)workspace_bytes, L.total);
 
-  char* base = static_cast<char*>(workspace);
-  unsigned long long* keys_a = reinterpret_cast<unsigned long long*>(base + L.keys_a);
-  unsigned long long* keys_b = reinterpret_cast<unsigned long long*>(base + L.keys_b);
-  int32_t* beg = reinterpret_cast<int32_t*>(base + L.beg);
-  int32_t* end = reinterpret_cast<int32_t*>(base + L.end);
-  unsigned long long* gap = reinterpret_cast<unsigned long long*>(base + L.gap);
-  double* chunk_sum = reinterpret_cast<double*>(base + L.chunk_sum);
+  unsigned long long* keys_a = at<unsigned long long>(workspace, L.keys_a);
+  unsigned long long* keys_b = at<unsigned long long>(workspace, L.keys_b);
+  int32_t* beg = at<int32_t>(workspace, L.beg);
+  int32_t* end = at<int32_t>(workspace, L.end);
+  unsigned long long* gap = at<unsigned long long>(workspace, L.gap);
+  double* chunk_sum = at<double>(workspace, L.chunk_sum);
   size_t temp_bytes = L.temp_bytes;
 
   SEGGER_HIP(hipMemsetAsync(cnt, 0, kThrCounters * sizeof(unsigned long long), stream));
@@ -435,7 +407,7 @@ extern "C" int segger_thresholds_build(const float* similarity, const int32_t* g
   hipLaunchKernelGGL(thresholds_keys_kernel, dim3(thr_grid(n_items)), dim3(kThrThreads), 0, stream, similarity, gene, cell,
                      n_rows, n_genes, keys_a, beg, end, gap, cnt);
   SEGGER_LAUNCH_CHECK("thresholds_keys_kernel");
-  SEGGER_HIP(rocprim::radix_sort_keys<ThrSortConfig>(base + L.temp, temp_bytes, keys_a, keys_b, (size_t)n_rows, 0,
+  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, L.temp), temp_bytes, keys_a, keys_b, (size_t)n_rows, 0,
                                                      (unsigned)L.key_bits, stream));
   hipLaunchKernelGGL(thresholds_segments_kernel, dim3(thr_grid(n_rows)), dim3(kThrThreads), 0, stream,
                      (const unsigned long long*)keys_b, n_rows, beg, end, cnt);

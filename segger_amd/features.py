@@ -32,7 +32,7 @@ __all__ = ["expression_features", "sparse_gram", "sparse_project", "cluster_cosi
 
 
 def _csr(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, int, int]:
-    L.require_cuda(indptr, indices, values, row_weight)
+    L.need_device("sparse_gram / sparse_project", indptr, indices, values, row_weight)
     indptr = indptr.detach().to(torch.int64).contiguous().view(-1)
     indices = indices.detach().to(torch.int32).contiguous().view(-1)
     values = values.detach().to(torch.int32).contiguous().view(-1)
@@ -44,6 +44,13 @@ def _csr(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: Tensor) ->
     return indptr, indices, values, row_weight, n_rows, nnz
 
 
+def csr_row_sums(indptr: Tensor, values: Tensor) -> Tensor:
+    """exact int64 row sums of a CSR: differences of one running sum at the row pointers"""
+    running = torch.zeros(int(values.numel()) + 1, dtype=torch.int64, device=values.device)
+    torch.cumsum(values.long(), 0, out=running[1:])
+    return running[indptr[1:]] - running[indptr[:-1]]
+
+
 def sparse_gram(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: Tensor, n_cols: int) -> Tuple[Tensor, Tensor]:
     """``S = sum_r w_r^2 x_r x_r^T`` ``[n_cols, n_cols]`` and ``s = sum_r w_r x_r`` ``[n_cols]``, float64, over the rows of
     a CSR matrix (``indices`` strictly ascending inside a row, integer ``values``); a row of weight 0 takes no part.
@@ -52,16 +59,11 @@ def sparse_gram(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: Ten
     indptr, indices, values, row_weight, n_rows, nnz = _csr(indptr, indices, values, row_weight)
     dev = indptr.device
     n_cols = int(n_cols)
-    lib = L.load()
-    ws_bytes = lib.segger_features_workspace_bytes(n_rows, n_cols)
-    L.check(min(ws_bytes, 0), "segger_features_workspace_bytes")
+    ws, ws_bytes = L.workspace("segger_features_workspace_bytes", dev, n_rows, n_cols)   # never empty: one slab at least
     S = torch.empty(n_cols, n_cols, dtype=torch.float64, device=dev)
     s = torch.empty(n_cols, dtype=torch.float64, device=dev)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    with L.on_device(dev):
-        rc = lib.segger_sparse_gram(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), row_weight.data_ptr(), n_rows,
-                                    n_cols, nnz, S.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes, L.stream_ptr(dev))
-    L.check(rc, "segger_sparse_gram")
+    L.call("segger_sparse_gram", dev, indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), row_weight.data_ptr(), n_rows,
+           n_cols, nnz, S.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes)
     return S, s
 
 
@@ -71,7 +73,7 @@ def sparse_project(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: 
     ``[k]`` float64, ``1 <= k <= 256``, ``out`` float32 or float64.  Accumulated in float64 in CSR order and rounded once;
     a row of weight 0 gives exactly ``-offset`` (``segger_sparse_project``)."""
     indptr, indices, values, row_weight, n_rows, nnz = _csr(indptr, indices, values, row_weight)
-    L.require_cuda(V, offset)
+    L.need_device("sparse_project", V, offset)
     if out_dtype not in (torch.float32, torch.float64):
         raise ValueError("sparse_project: out_dtype is torch.float32 or torch.float64")
     if V.dim() != 2 or offset.numel() != V.shape[1]:
@@ -81,11 +83,8 @@ def sparse_project(indptr: Tensor, indices: Tensor, values: Tensor, row_weight: 
     offset = offset.detach().to(torch.float64).contiguous().view(-1)
     n_cols, k = int(V.shape[0]), int(V.shape[1])
     out = torch.empty(n_rows, k, dtype=out_dtype, device=dev)
-    with L.on_device(dev):
-        rc = L.load().segger_sparse_project(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), row_weight.data_ptr(),
-                                            n_rows, n_cols, nnz, V.data_ptr(), offset.data_ptr(), k, out.data_ptr(),
-                                            int(out_dtype == torch.float64), L.stream_ptr(dev))
-    L.check(rc, "segger_sparse_project")
+    L.call("segger_sparse_project", dev, indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), row_weight.data_ptr(),
+           n_rows, n_cols, nnz, V.data_ptr(), offset.data_ptr(), k, out.data_ptr(), int(out_dtype == torch.float64))
     return out
 
 
@@ -121,19 +120,14 @@ def expression_features(expr: Dict[str, Tensor], embedding_size: int = 128, cell
     ``corr_explained_variance`` ``[k]``.  Raises ``ValueError`` when ``embedding_size > min(n_genes_kept, n_filtered)``,
     where sklearn's exact solver refuses.  Waits for the device once (the two counts)."""
     indptr, indices, counts = expr["indptr"], expr["indices"], expr["counts"]
-    if not (indptr.is_cuda and indices.is_cuda and counts.is_cuda):
-        raise L.SeggerAmdError("expression_features runs on the MI355X only: there is no CPU fallback "
-                               "(tests/features_cases.py holds the CPU oracle)")
+    L.need_device("expression_features", indptr, indices, counts, hint="tests/features_cases.py holds the CPU oracle")
     dev = indptr.device
     k = int(embedding_size)
     n_cells, n_genes = int(indptr.numel()) - 1, int(expr["gene_ids"].numel())
     cols = indices.long()
     gene_total = torch.zeros(n_genes, dtype=torch.int64, device=dev).index_add_(0, cols, counts.long())
     gene_keep = gene_total >= int(genes_min_counts)
-    # row sums over the kept genes: differences of one exact int64 running sum at the row pointers
-    running = torch.zeros(int(cols.numel()) + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts.long() * gene_keep[cols], 0, out=running[1:])
-    n_counts = running[indptr[1:]] - running[indptr[:-1]]
+    n_counts = csr_row_sums(indptr, counts.long() * gene_keep[cols])       # over the kept genes
     filtered = n_counts >= int(cells_min_counts)
     n_kept_genes, n_filtered = torch.stack([gene_keep.sum(), filtered.sum()]).tolist()          # the one wait
     if k < 1 or k > min(n_kept_genes, n_filtered):

@@ -23,7 +23,6 @@ def knn_grid(points: Tensor, k: int, max_dist: float = math.inf, query: Optional
              return_dist: bool = False, points_per_cell: float = 2.0) -> Tuple[Tensor, Optional[Tensor]]:
     """Neighbour table ``[m, k]`` (int32; ids into ``points`` sorted by distance; ``len(points)`` = padding)."""
     _lib.require_cuda(points)
-    lib = _lib.load()
     dev = points.device
     pts = points.to(torch.float32).contiguous()
     q = pts if query is None else query.to(device=dev, dtype=torch.float32).contiguous()
@@ -46,13 +45,9 @@ def knn_grid(points: Tensor, k: int, max_dist: float = math.inf, query: Optional
         cell = min(cell, max_dist)
     cell = max(cell, math.sqrt(w * h / (4.0 * n)), max(w, h) / 30000.0)              # <= 4n cells, < 2^31 cells
     nx, ny = int(w / cell) + 1, int(h / cell) + 1
-    ws_bytes = lib.segger_knn_workspace_bytes(n, nx, ny)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        rc = lib.segger_knn_grid(pts.data_ptr(), n, None if query is None else q.data_ptr(), m, k, float(max_dist),
-                                 x0, y0, cell, nx, ny, nbr.data_ptr(), _lib.ptr(dist), ws.data_ptr(), ws_bytes,
-                                 _lib.stream_ptr(dev))
-    _lib.check(rc, "segger_knn_grid")
+    ws, ws_bytes = _lib.workspace("segger_knn_workspace_bytes", dev, n, nx, ny)
+    _lib.call("segger_knn_grid", dev, pts.data_ptr(), n, None if query is None else q.data_ptr(), m, k, float(max_dist),
+              x0, y0, cell, nx, ny, nbr.data_ptr(), _lib.ptr(dist), ws.data_ptr(), ws_bytes)
     return nbr, dist
 
 

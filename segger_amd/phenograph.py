@@ -49,7 +49,7 @@ def knn_bruteforce(X: Tensor, k: int) -> Tuple[Tensor, Tensor]:
     ``cuml.NearestNeighbors.kneighbors(X)`` on its own training set: ``idx`` ``[N, k]`` int32 and ``dist2`` ``[N, k]``
     float32 (squared Euclidean, recomputed directly), every row sorted by (dist2, idx).  ``X`` is cast to float32.
     ``1 <= d <= 256``, ``1 <= k <= min(64, N)``, else ``ValueError``.  Bit-identical from call to call."""
-    L.require_cuda(X)
+    L.need_device("knn_bruteforce", X)
     if X.dim() != 2:
         raise ValueError("knn_bruteforce: X is [N, d]")
     n, d, k = int(X.shape[0]), int(X.shape[1]), int(k)
@@ -61,16 +61,10 @@ def knn_bruteforce(X: Tensor, k: int) -> Tuple[Tensor, Tensor]:
         raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {k}, n_samples_fit = {n}")
     dev = X.device
     X = X.detach().to(torch.float32).contiguous()
-    lib = L.load()
-    ws_bytes = lib.segger_knn_bruteforce_workspace_bytes(n, d, k)
-    L.check(min(ws_bytes, 0), "segger_knn_bruteforce_workspace_bytes")
+    ws, ws_bytes = L.workspace("segger_knn_bruteforce_workspace_bytes", dev, n, d, k)
     idx = torch.empty(n, k, dtype=torch.int32, device=dev)
     dist2 = torch.empty(n, k, dtype=torch.float32, device=dev)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with L.on_device(dev):
-        rc = lib.segger_knn_bruteforce(X.data_ptr(), n, d, k, idx.data_ptr(), dist2.data_ptr(), ws.data_ptr(), ws_bytes,
-                                       L.stream_ptr(dev))
-    L.check(rc, "segger_knn_bruteforce")
+    L.call("segger_knn_bruteforce", dev, X.data_ptr(), n, d, k, idx.data_ptr(), dist2.data_ptr(), ws.data_ptr(), ws_bytes)
     return idx, dist2
 
 
@@ -79,7 +73,7 @@ def jaccard_graph(idx: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     ``j -> i``, deduplicate -- a simple undirected graph in CSR (``indptr`` int64 ``[N + 1]``, ``indices`` int32 ascending
     inside a row, both directions stored) -- and weigh every edge by ``|N[u] & N[v]| / |N[u] | N[v]|`` over the closed
     neighbourhoods (``weight`` float64, one division of two integers; the two directions of an edge carry the same bits)."""
-    L.require_cuda(idx)
+    L.need_device("jaccard_graph", idx)
     if idx.dim() != 2:
         raise ValueError("jaccard_graph: idx is [N, k]")
     dev = idx.device
@@ -96,17 +90,13 @@ def jaccard_graph(idx: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         torch.cumsum(torch.bincount(rows, minlength=n), 0, out=indptr[1:])
     nnz = int(indices.numel())
     weight = torch.empty(nnz, dtype=torch.float64, device=dev)
-    with L.on_device(dev):
-        rc = L.load().segger_jaccard_weights(indptr.data_ptr(), indices.data_ptr(), n, nnz, weight.data_ptr(), L.stream_ptr(dev))
-    L.check(rc, "segger_jaccard_weights")
+    L.call("segger_jaccard_weights", dev, indptr.data_ptr(), indices.data_ptr(), n, nnz, weight.data_ptr())
     return indptr, indices, weight
 
 
-def _modularity(lib, dev, indptr, indices, w, self_w, comm, tot, n, nnz, gamma, two_m, in_c, q) -> float:
-    with L.on_device(dev):
-        rc = lib.segger_louvain_modularity(indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), self_w.data_ptr(), comm.data_ptr(),
-                                           tot.data_ptr(), n, nnz, gamma, two_m, in_c.data_ptr(), q.data_ptr(), L.stream_ptr(dev))
-    L.check(rc, "segger_louvain_modularity")
+def _modularity(dev, indptr, indices, w, self_w, comm, tot, n, nnz, gamma, two_m, in_c, q) -> float:
+    L.call("segger_louvain_modularity", dev, indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), self_w.data_ptr(),
+           comm.data_ptr(), tot.data_ptr(), n, nnz, gamma, two_m, in_c.data_ptr(), q.data_ptr())
     return float(q.item())                                                         # the one wait of a round
 
 
@@ -116,7 +106,7 @@ def louvain(indptr: Tensor, indices: Tensor, weight: Tensor, resolution: float =
     ``Q = sum_c in_c / 2m - resolution * (tot_c / 2m)**2``.  Returns ``labels`` int32 ``[N]`` (``0..C-1``, in the
     ascending order of the last level's community ids) and ``modularity`` (float).  The same labels on every
     call.  ``return_stats`` adds a dict with the levels and rounds run.  The module docstring has the scheme."""
-    L.require_cuda(indptr, indices, weight)
+    L.need_device("louvain", indptr, indices, weight)
     dev = indptr.device
     lib = L.load()
     gamma = float(resolution)
@@ -150,12 +140,12 @@ def louvain(indptr: Tensor, indices: Tensor, weight: Tensor, resolution: float =
         size = torch.ones(n, dtype=torch.int32, device=dev)
         proposal = torch.empty(n, dtype=torch.int32, device=dev)
         in_c = torch.empty(n, dtype=torch.int64, device=dev)
-        args = (lib, dev, indptr, indices, w, self_w)
+        args = (dev, indptr, indices, w, self_w)
         q_start = q_prev = _modularity(*args, comm, tot, n, nnz, gamma, two_m, in_c, q_buf)
         stats["levels"] += 1
         for _ in range(MAX_ROUNDS):
             comm_prev = comm.clone()
-            with L.on_device(dev):
+            with L.on_device(dev):                                                 # one guard around the four sub-rounds
                 for sub in range(SUBROUNDS):
                     rc = lib.segger_louvain_move(indptr.data_ptr(), indices.data_ptr(), w.data_ptr(), kdeg.data_ptr(), n, nnz, sub,
                                                  SUBROUNDS, gamma, two_m, comm.data_ptr(), tot.data_ptr(), size.data_ptr(),
@@ -245,7 +235,7 @@ def phenograph(X: Tensor, n_neighbors: int, resolution: float = 1.0, min_size: i
     """``phenograph_rapids``: kNN of ``X`` (its float64 column means subtracted before the float32 cast -- distances do not
     change, the expanded form's cancellation shrinks), the Jaccard graph, Louvain at ``resolution``, labels ranked by
     cluster size with ``-1`` for clusters of ``min_size`` members or fewer.  int64 ``[N]``, on ``X``'s device."""
-    L.require_cuda(X)
+    L.need_device("phenograph", X)
     if X.dim() != 2:
         raise ValueError("phenograph: X is [N, d]")
     centred = X.detach().to(torch.float64)

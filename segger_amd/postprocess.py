@@ -167,9 +167,7 @@ def gene_thresholds(similarity: Tensor, gene: Tensor, cell_encoding: Tensor, n_g
     (neither is ever used as an index)."""
     from . import _lib as L
     cols = [similarity, gene, cell_encoding]
-    if not all(t.is_cuda for t in cols):
-        raise L.SeggerAmdError("gene_thresholds runs on the MI355X only: there is no CPU fallback "
-                               "(per_gene_thresholds is the CPU form)")
+    L.need_device("gene_thresholds", *cols, hint="per_gene_thresholds is the CPU form")
     dev = cols[0].device
     n = int(cols[0].numel())
     if any(int(t.numel()) != n for t in cols):
@@ -185,21 +183,17 @@ def gene_thresholds(similarity: Tensor, gene: Tensor, cell_encoding: Tensor, n_g
     if n_genes is None:
         n_genes = max(int(g32.max()) + 1, 1) if n else 1
     n_genes = int(n_genes)
-    lib = L.load()
-    ws_bytes = lib.segger_thresholds_workspace_bytes(n, n_genes)
-    L.check(min(ws_bytes, 0), "segger_thresholds_workspace_bytes")
+    ws, ws_bytes = L.workspace("segger_thresholds_workspace_bytes", dev, n, n_genes)
+    if not n:                                                # no row pointer and no workspace is looked at
+        ws, ws_bytes = None, 0
     f64 = dict(dtype=torch.float64, device=dev)
     thr, yen, li = torch.empty(n_genes, **f64), torch.empty(n_genes, **f64), torch.empty(n_genes, **f64)
     count = torch.empty(n_genes, dtype=torch.int64, device=dev)
     conv = torch.empty(n_genes, dtype=torch.uint8, device=dev)
     counters = torch.zeros(len(THRESHOLDS_COUNTERS), dtype=torch.int64, device=dev)
-    ws = torch.empty(ws_bytes if n else 0, dtype=torch.uint8, device=dev)
-    with L.on_device(dev):
-        rc = lib.segger_thresholds_build(L.ptr(sim) if n else None, L.ptr(g32) if n else None, L.ptr(cell) if n else None,
-                                         n, n_genes, int(max_iter), thr.data_ptr(), yen.data_ptr(), li.data_ptr(),
-                                         count.data_ptr(), conv.data_ptr(), counters.data_ptr(),
-                                         L.ptr(ws) if n else None, int(ws.numel()), L.stream_ptr(dev))
-    L.check(rc, "segger_thresholds_build")
+    L.call("segger_thresholds_build", dev, L.ptr(sim) if n else None, L.ptr(g32) if n else None, L.ptr(cell) if n else None,
+           n, n_genes, int(max_iter), thr.data_ptr(), yen.data_ptr(), li.data_ptr(), count.data_ptr(), conv.data_ptr(),
+           counters.data_ptr(), L.ptr(ws), ws_bytes)
     del ws
     converged = conv.bool()
     # median of the converged present genes' thresholds and the back-fill: [n_genes] torch ops (plumbing)
@@ -274,9 +268,7 @@ class SegmentationAccumulator:
         if not 1 <= n < (1 << 31):
             raise ValueError(f"n_transcripts must be in [1, 2^31), got {n}")
         self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.SeggerAmdError("SegmentationAccumulator runs on the MI355X only: there is no CPU fallback "
-                                      "(best_assignment is the CPU form)")
+        _lib.need_device("SegmentationAccumulator", self.device, hint="best_assignment is the CPU form")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._lib = _lib
@@ -315,11 +307,8 @@ class SegmentationAccumulator:
         sim, gene = self._col(max_sim, torch.float32), self._col(gene_id, torch.int32)
         m = None if mask is None else self._col(mask, torch.bool)
         L = self._lib
-        with L.on_device(self.device):
-            rc = L.load().segger_assign_update(idx.data_ptr(), seg.data_ptr(), sim.data_ptr(), gene.data_ptr(), L.ptr(m), n,
-                                               self.best_key.data_ptr(), self.cell.data_ptr(), self.gene.data_ptr(),
-                                               self.counters.data_ptr(), self.n_transcripts, L.stream_ptr(self.device))
-        L.check(rc, "segger_assign_update")
+        L.call("segger_assign_update", self.device, idx.data_ptr(), seg.data_ptr(), sim.data_ptr(), gene.data_ptr(), L.ptr(m), n,
+               self.best_key.data_ptr(), self.cell.data_ptr(), self.gene.data_ptr(), self.counters.data_ptr(), self.n_transcripts)
         self.rows_fed += n
 
     def result(self) -> Dict[str, Tensor]:
@@ -328,10 +317,8 @@ class SegmentationAccumulator:
         L = self._lib
         sim = torch.empty(self.n_transcripts, dtype=torch.float32, device=self.device)
         seen = torch.empty(self.n_transcripts, dtype=torch.bool, device=self.device)
-        with L.on_device(self.device):
-            rc = L.load().segger_assign_finalize(self.best_key.data_ptr(), self.n_transcripts, sim.data_ptr(), seen.data_ptr(),
-                                                 L.stream_ptr(self.device))
-        L.check(rc, "segger_assign_finalize")
+        L.call("segger_assign_finalize", self.device, self.best_key.data_ptr(), self.n_transcripts, sim.data_ptr(),
+               seen.data_ptr())
         rows, dropped = self.counters.tolist()
         if dropped:
             raise L.SeggerAmdError(f"SegmentationAccumulator: {dropped} of {rows} rows were dropped (tx_index outside "
@@ -375,9 +362,7 @@ def expression_matrix(result: Dict[str, Tensor], xy: Optional[Tensor] = None, n_
     cell or gene id outside its domain (it is never used as an index)."""
     from . import _lib as L
     cols = [result[k] for k in ("cell_encoding", "gene", "similarity", "similarity_threshold")]
-    if not all(t.is_cuda for t in cols):
-        raise L.SeggerAmdError("expression_matrix runs on the MI355X only: there is no CPU fallback "
-                               "(tests/expression_cases.py holds the CPU oracle)")
+    L.need_device("expression_matrix", *cols, hint="tests/expression_cases.py holds the CPU oracle")
     dev = cols[0].device
     n = int(cols[0].numel())
     if any(int(t.numel()) != n for t in cols):
@@ -396,9 +381,7 @@ def expression_matrix(result: Dict[str, Tensor], xy: Optional[Tensor] = None, n_
         n_cells = max(int(top[0]) + 1, 1) if n_cells is None else n_cells
         n_genes = max(int(top[1]) + 1, 1) if n_genes is None else n_genes
     n_cells, n_genes = int(n_cells), int(n_genes)
-    lib = L.load()
-    ws_bytes = lib.segger_expression_workspace_bytes(n, n_cells, n_genes)
-    L.check(min(ws_bytes, 0), "segger_expression_workspace_bytes")
+    ws, ws_bytes = L.workspace("segger_expression_workspace_bytes", dev, n, n_cells, n_genes)
     cap_c, cap_g = min(n, n_cells), min(n, n_genes)
     i32 = dict(dtype=torch.int32, device=dev)
     cell_ids, gene_ids = torch.empty(cap_c, **i32), torch.empty(cap_g, **i32)
@@ -408,13 +391,10 @@ def expression_matrix(result: Dict[str, Tensor], xy: Optional[Tensor] = None, n_
     cell_count = torch.empty(cap_c, dtype=torch.int64, device=dev)
     centroid = torch.empty(cap_c, 2, dtype=torch.float64, device=dev) if pts is not None else None
     counters = torch.zeros(len(EXPRESSION_COUNTERS), dtype=torch.int64, device=dev)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with L.on_device(dev):
-        rc = lib.segger_expression_build(cell.data_ptr(), gene.data_ptr(), sim.data_ptr(), thr.data_ptr(), L.ptr(pts), n,
-                                         n_cells, n_genes, cell_ids.data_ptr(), gene_ids.data_ptr(), indptr.data_ptr(),
-                                         indices.data_ptr(), counts.data_ptr(), mean.data_ptr(), cell_count.data_ptr(),
-                                         L.ptr(centroid), counters.data_ptr(), ws.data_ptr(), ws_bytes, L.stream_ptr(dev))
-    L.check(rc, "segger_expression_build")
+    L.call("segger_expression_build", dev, cell.data_ptr(), gene.data_ptr(), sim.data_ptr(), thr.data_ptr(), L.ptr(pts), n,
+           n_cells, n_genes, cell_ids.data_ptr(), gene_ids.data_ptr(), indptr.data_ptr(), indices.data_ptr(),
+           counts.data_ptr(), mean.data_ptr(), cell_count.data_ptr(), L.ptr(centroid), counters.data_ptr(), ws.data_ptr(),
+           ws_bytes)
     n_kept, nnz, n_c, n_g, n_bad = counters.tolist()         # the one wait for the device
     if n_bad:
         raise L.SeggerAmdError(f"expression_matrix: {n_bad} segmented transcripts have a cell id outside [0, {n_cells}) or "

@@ -226,21 +226,15 @@ class QuadTreeTiling:
 
     def _build_device(self, positions: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         from . import _lib
-        lib = _lib.load()
         dev, n = positions.device, int(positions.shape[0])
         cap = self.leaf_capacity(n)
-        ws_bytes = lib.segger_quadtree_workspace_bytes(n, self.depth, self.max_tile_size, cap)
-        _lib.check(min(ws_bytes, 0), "segger_quadtree_workspace_bytes")
+        ws, ws_bytes = _lib.workspace("segger_quadtree_workspace_bytes", dev, n, self.depth, self.max_tile_size, cap)
         table = torch.empty((5, cap), dtype=torch.int32, device=dev)     # leaf key, depth, count; Morton start, id
         n_leaf = torch.empty(1, dtype=torch.int32, device=dev)
         labels = torch.empty(n, dtype=torch.int32, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            rc = lib.segger_quadtree_build(positions.data_ptr(), n, self.x0, self.y0, self.cell, self.depth,
-                                           self.max_tile_size, cap, table[0].data_ptr(), table[1].data_ptr(),
-                                           table[2].data_ptr(), table[3].data_ptr(), table[4].data_ptr(),
-                                           n_leaf.data_ptr(), labels.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-        _lib.check(rc, "segger_quadtree_build")
+        _lib.call("segger_quadtree_build", dev, positions.data_ptr(), n, self.x0, self.y0, self.cell, self.depth,
+                  self.max_tile_size, cap, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
+                  table[4].data_ptr(), n_leaf.data_ptr(), labels.data_ptr(), ws.data_ptr(), ws_bytes)
         t = int(n_leaf.item())                               # the one sync per slide (cf. knn_grid's extent)
         if not 1 <= t <= cap:
             raise _lib.SeggerAmdError(f"segger_quadtree_build: {t} leaves for a capacity of {cap}")
@@ -279,17 +273,13 @@ class QuadTreeTiling:
 
     def _label_device(self, pos: Tensor) -> Tensor:
         from . import _lib
-        lib = _lib.load()
         dev, n = pos.device, int(pos.shape[0])
         keys, depths, m_lo, m_id = self._table(dev, torch.int32)
         out = torch.empty(n, dtype=torch.int32, device=dev)
         if n == 0:
             return out
-        with _lib.on_device(dev):
-            rc = lib.segger_quadtree_label(pos.data_ptr(), n, self.x0, self.y0, self.x1, self.y1, self.cell, self.depth,
-                                           keys.data_ptr(), depths.data_ptr(), m_lo.data_ptr(), m_id.data_ptr(),
-                                           int(keys.numel()), out.data_ptr(), _lib.stream_ptr(dev))
-        _lib.check(rc, "segger_quadtree_label")
+        _lib.call("segger_quadtree_label", dev, pos.data_ptr(), n, self.x0, self.y0, self.x1, self.y1, self.cell, self.depth,
+                  keys.data_ptr(), depths.data_ptr(), m_lo.data_ptr(), m_id.data_ptr(), int(keys.numel()), out.data_ptr())
         return out
 
     def mask(self, pos: Tensor, margin: float) -> Tensor:

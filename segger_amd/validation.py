@@ -30,16 +30,13 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .features import deterministic_sums, sparse_project
+from .features import csr_row_sums, deterministic_sums, sparse_project
 from .neighbors import knn_grid
 
 __all__ = ["neighbor_frequencies", "reference_table", "contamination_posterior", "calculate_contamination", "contamination_flow"]
 
 
-def _need_device(who: str, *tensors: Tensor) -> None:
-    if not all(t.is_cuda for t in tensors if t is not None):
-        raise L.SeggerAmdError(f"{who} runs on the MI355X only: segger_amd runs on MI355X only and there is no CPU fallback "
-                               "(tests/contamination_cases.py holds the CPU oracle)")
+_CPU_HINT = "tests/contamination_cases.py holds the CPU oracle"
 
 
 def _n_types(n_types: int) -> int:
@@ -47,13 +44,6 @@ def _n_types(n_types: int) -> int:
     if not 1 <= n_types <= L.CONTAM_MAX_TYPES:
         raise ValueError(f"n_types = {n_types} outside 1 .. {L.CONTAM_MAX_TYPES}")
     return n_types
-
-
-def _row_sums(indptr: Tensor, values: Tensor) -> Tensor:
-    """exact int64 row sums of a CSR: differences of one running sum at the row pointers"""
-    running = torch.zeros(int(values.numel()) + 1, dtype=torch.int64, device=values.device)
-    torch.cumsum(values.long(), 0, out=running[1:])
-    return running[indptr[1:]] - running[indptr[:-1]]
 
 
 def _gene_map(expr: Dict[str, Tensor], gene_map: Optional[Tensor], n_ref: int) -> Tensor:
@@ -71,7 +61,7 @@ def neighbor_frequencies(xy: Tensor, labels: Tensor, k: int, n_types: int, max_d
     ``[n, n_types]`` and ``freq`` float32, each row of ``counts`` times ``1.0 / sum`` in float64 and rounded (zeros when the
     sum is 0); with ``normalize=False`` ``freq`` is ``counts`` as float32.  ``knn`` = ``(nbr, dist)`` uses a neighbour table
     computed elsewhere, in ``knn_grid``'s format, instead of searching.  Waits for the device once, inside ``knn_grid``."""
-    _need_device("neighbor_frequencies", xy, labels)
+    L.need_device("neighbor_frequencies", xy, labels, hint=_CPU_HINT)
     n_types = _n_types(n_types)
     dev = xy.device
     n = int(xy.shape[0])
@@ -80,17 +70,15 @@ def neighbor_frequencies(xy: Tensor, labels: Tensor, k: int, n_types: int, max_d
         raise ValueError("neighbor_frequencies: one label per point")
     max_distance = math.inf if max_distance is None else float(max_distance)
     nbr, dist = knn_grid(xy, int(k), return_dist=True) if knn is None else knn
-    _need_device("neighbor_frequencies", nbr, dist)
+    L.need_device("neighbor_frequencies", nbr, dist, hint=_CPU_HINT)
     nbr = nbr.detach().to(torch.int32).contiguous()
     dist = dist.detach().to(torch.float32).contiguous()
     if nbr.dim() != 2 or nbr.shape != dist.shape or int(nbr.shape[0]) != n:
         raise ValueError("neighbor_frequencies: nbr and dist are [n, k]")
     counts = torch.empty(n, n_types, dtype=torch.int32, device=dev)
     freq = torch.empty(n, n_types, dtype=torch.float32, device=dev)
-    with L.on_device(dev):
-        rc = L.load().segger_neighbor_frequencies(nbr.data_ptr(), dist.data_ptr(), labels.data_ptr(), n, int(nbr.shape[1]),
-                                                  n_types, max_distance, counts.data_ptr(), freq.data_ptr(), L.stream_ptr(dev))
-    L.check(rc, "segger_neighbor_frequencies")
+    L.call("segger_neighbor_frequencies", dev, nbr.data_ptr(), dist.data_ptr(), labels.data_ptr(), n, int(nbr.shape[1]),
+           n_types, max_distance, counts.data_ptr(), freq.data_ptr())
     return (freq if normalize else counts.float()), counts
 
 
@@ -105,7 +93,7 @@ def reference_table(indptr: Tensor, indices: Tensor, counts: Tensor, cell_type: 
 
     Device torch under :func:`~segger_amd.features.deterministic_sums`: this runs once over a small annotated atlas -- it is
     plumbing, not a kernel."""
-    _need_device("reference_table", indptr, indices, counts, cell_type)
+    L.need_device("reference_table", indptr, indices, counts, cell_type, hint=_CPU_HINT)
     n_types = _n_types(n_types)
     dev = indptr.device
     if n_genes is None:
@@ -114,7 +102,7 @@ def reference_table(indptr: Tensor, indices: Tensor, counts: Tensor, cell_type: 
     n_cells = int(indptr.numel()) - 1
     cell_type = cell_type.to(device=dev, dtype=torch.int64).view(-1)
     rows = torch.repeat_interleave(torch.arange(n_cells, device=dev), indptr.diff(), output_size=int(indices.numel()))
-    total = _row_sums(indptr, counts).double()
+    total = csr_row_sums(indptr, counts).double()
     value = torch.log1p(counts.double() / (total / 1e4)[rows])
     kind = cell_type[rows]
     keep = (counts >= int(min_counts)) & (kind >= 0) & (kind < n_types) & (value > 0)
@@ -151,7 +139,7 @@ def contamination_posterior(indptr: Tensor, indices: Tensor, counts: Tensor, gen
     :func:`calculate_contamination` ends in): the CSR, ``gene_map`` int32 per CSR column, ``host_type`` int32 per row,
     ``freq`` float32 ``[n, n_types]``, ``lik_t`` float32 ``[G_ref, ld]`` -- the likelihood table GENE-MAJOR, ``ld`` a multiple
     of 4 and ``>= n_types`` -- and ``back`` float64 ``[G_ref]``.  Returns the seven kernel outputs."""
-    _need_device("contamination_posterior", indptr, indices, counts, gene_map, host_type, freq, lik_t, back)
+    L.need_device("contamination_posterior", indptr, indices, counts, gene_map, host_type, freq, lik_t, back, hint=_CPU_HINT)
     dev = indptr.device
     T = _n_types(n_types)
     indptr = indptr.detach().to(torch.int64).contiguous()
@@ -174,14 +162,12 @@ def contamination_posterior(indptr: Tensor, indices: Tensor, counts: Tensor, gen
     out["contaminated"] = per_cell(n, dtype=torch.int64, device=dev)
     out["total"] = per_cell(n, dtype=torch.int64, device=dev)
     out["percent_contamination"] = per_cell(n, dtype=torch.float64, device=dev)
-    with L.on_device(dev):
-        rc = L.load().segger_contamination_posterior(
-            indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), n, int(gene_map.numel()), nnz, gene_map.data_ptr(),
-            host_type.data_ptr(), freq.data_ptr(), lik_t.data_ptr(), ld, back.data_ptr(), T, G_ref, float(alpha_self),
-            float(alpha_neighbor), float(alpha_background), float(eps), float(contam_cutoff), out["q_self"].data_ptr(),
-            out["q_neighbor"].data_ptr(), out["q_background"].data_ptr(), out["contamination"].data_ptr(),
-            out["contaminated"].data_ptr(), out["total"].data_ptr(), out["percent_contamination"].data_ptr(), L.stream_ptr(dev))
-    L.check(rc, "segger_contamination_posterior")
+    L.call("segger_contamination_posterior", dev,
+           indptr.data_ptr(), indices.data_ptr(), counts.data_ptr(), n, int(gene_map.numel()), nnz, gene_map.data_ptr(),
+           host_type.data_ptr(), freq.data_ptr(), lik_t.data_ptr(), ld, back.data_ptr(), T, G_ref, float(alpha_self),
+           float(alpha_neighbor), float(alpha_background), float(eps), float(contam_cutoff), out["q_self"].data_ptr(),
+           out["q_neighbor"].data_ptr(), out["q_background"].data_ptr(), out["contamination"].data_ptr(),
+           out["contaminated"].data_ptr(), out["total"].data_ptr(), out["percent_contamination"].data_ptr())
     return out
 
 
@@ -205,7 +191,7 @@ def calculate_contamination(expr: Dict[str, Tensor], cell_type: Tensor, weight: 
     if "centroid" not in expr:
         raise ValueError("calculate_contamination: expr holds no centroid -- call expression_matrix(..., xy=)")
     indptr, indices, counts, xy = expr["indptr"], expr["indices"], expr["counts"], expr["centroid"]
-    _need_device("calculate_contamination", indptr, indices, counts, xy, cell_type, weight)
+    L.need_device("calculate_contamination", indptr, indices, counts, xy, cell_type, weight, hint=_CPU_HINT)
     if weight.dim() != 2:
         raise ValueError("calculate_contamination: weight is [n_types, n_ref_genes]")
     dev = indptr.device
@@ -233,7 +219,7 @@ def contamination_flow(expr: Dict[str, Tensor], contamination: Tensor, cell_type
     the table lacks are dropped, and ``ValueError`` is raised when none is shared (one wait).  Unlabelled cells belong to
     no host type.  ``n_host_types`` defaults to ``D``.  Float64 (the reference's ``W`` is float32), a fixed order."""
     indptr, indices, counts = expr["indptr"], expr["indices"], expr["counts"]
-    _need_device("contamination_flow", indptr, indices, counts, contamination, cell_type, weight)
+    L.need_device("contamination_flow", indptr, indices, counts, contamination, cell_type, weight, hint=_CPU_HINT)
     dev = indptr.device
     D, G_ref = int(weight.shape[0]), int(weight.shape[1])
     H = D if n_host_types is None else int(n_host_types)
@@ -243,7 +229,7 @@ def contamination_flow(expr: Dict[str, Tensor], contamination: Tensor, cell_type
     W = weight.detach().double().T.contiguous()
     row_sum = W.sum(dim=1, keepdim=True)
     W = W / torch.where(row_sum == 0, torch.ones_like(row_sum), row_sum)
-    libsize = _row_sums(indptr, counts)
+    libsize = csr_row_sums(indptr, counts)
     kept = gmap[indices.long()]                                        # -1 for a dropped gene: sparse_project skips it
     percent = sparse_project(indptr, kept, contamination, 100.0 / libsize.clamp_min(1).double(), W,
                              torch.zeros(D, dtype=torch.float64, device=dev), torch.float64)
