@@ -66,6 +66,12 @@ class PosEmbedding(NamedTuple):
     gelu_applied: bool
 
 
+class EmbedRoute(NamedTuple):
+    """The route of one embedder call, decided by :meth:`Positional2dEmbedder.route` before anything is launched."""
+    features: str    # the sinusoid features: "none" (never materialised) | "posfreq" (segger_posfreq) | "torch"
+    mlp: str         # "fused16" (ops.posmlp) | "poly_f32" (ops.pos_poly_mlp_f32) | "mlp_f32" (ops.mlp_silu_f32) | "composed"
+
+
 class Positional2dEmbedder(Module):
     """Per-graph min-max normalised (x, y) -> 2 x sinusoid(256) -> shared MLP -> concat."""
 
@@ -95,64 +101,74 @@ class Positional2dEmbedder(Module):
                 dtype: torch.dtype = torch.float32) -> Tensor:
         return self._embed(pos, batch, num_graphs, dtype).out
 
+    def route(self, *, on_gpu: bool, batched: bool, dtype: torch.dtype, rows: int, pos_grad: bool = False) -> EmbedRoute:
+        """The route of one :meth:`_embed` call from shapes, dtypes and the switches of ``ops``: nothing is launched.
+        ``batched``: there is a batch vector; ``rows``: the number of positions; ``pos_grad``: they require a gradient."""
+        fd, dim, l0, l2 = self.frequency_embedding_size, self.dim, self.mlp[0], self.mlp[2]
+        biased = l0.bias is not None and l2.bias is not None
+        if not ((batched or on_gpu) and fd % 16 == 0):
+            # (the fp32 nodes below are GPU kernels for widths that are multiples of 16: none of them applies here)
+            return EmbedRoute("torch", "composed")
+        if ops.FUSED_POSMLP and on_gpu and biased and ops.posmlp_supported(fd, dim, dtype):
+            return EmbedRoute("none", "fused16")
+        # fp32 storage: the MLP behind ONE autograd node, over at least one row
+        f32_node = dtype == torch.float32 and ops.F32_GATE_EPILOGUE and biased and on_gpu and rows > 0
+        if (f32_node and not pos_grad and l0.weight.dtype == l2.weight.dtype == torch.float32
+                and ops.pos_poly_f32_covers(fd, dim)):
+            return EmbedRoute("none", "poly_f32")
+        # (segger_posfreq's features are constants for autograd, whatever the positions require)
+        return EmbedRoute("posfreq", "mlp_f32" if f32_node and ops.mlp_silu_f32_covers(fd, dim, dim) else "composed")
+
     def _embed(self, pos: Tensor, batch: Optional[Tensor], num_graphs: Optional[int], dtype: torch.dtype, *,
                gelu: bool = False, want_pre: bool = False, minmax=None) -> PosEmbedding:
         """``gelu`` (not in the reference): also apply the GELU that ISTEncoder puts on its concatenated input;
         ``want_pre`` (with ``gelu``): hand the GELU's derivative to the consumer (``PosEmbedding.pre``) on the routes that
         can; the others keep the GELU in autograd and return ``pre = None``."""
         n, fd, l0, l2 = pos.shape[0], self.frequency_embedding_size, self.mlp[0], self.mlp[2]
-        biased = l0.bias is not None and l2.bias is not None
-        f32_node = dtype == torch.float32 and ops.F32_GATE_EPILOGUE and biased
+        w = (l0.weight, l0.bias, l2.weight, l2.bias)
         want_pre = want_pre and gelu
-        node = None          # fp32 storage: the MLP (+ the GELU that follows) behind one autograd node
-        if (batch is not None or pos.is_cuda) and fd % 16 == 0:
-            # fused: per-graph min/max (one pass) -> normalise + sinusoid written straight in `dtype`
-            # (no batch vector = one graph, and the reference normalises it WITHOUT the epsilon, ist_encoder.py:62-64)
-            eps_n = 1e-8 if batch is not None else 0.0
-            if batch is None:
-                num_graphs = 1
-            elif num_graphs is None:
-                num_graphs = int(batch.max()) + 1 if batch.numel() else 0
-            # (the fused kernel and posfreq only look up the graphs of existing nodes: no (0, 0) fix-up for empty ones)
-            mins, maxs = ops.segment_minmax(pos, batch, num_graphs, keep_empty=True, out=minmax)
-            if ops.FUSED_POSMLP and pos.is_cuda and biased and ops.posmlp_supported(fd, self.dim, dtype):
-                # sinusoid + Linear + SiLU + Linear in one kernel: the [2n, 256] feature matrix is generated in
-                # registers (and stored once for the weight gradient when training) instead of written and re-read
-                r = ops.posmlp(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias, dtype,
-                               eps=eps_n, max_period=10000.0, gelu=gelu, return_pre=want_pre)
-                return PosEmbedding(r[0], r[1], True) if want_pre else PosEmbedding(r, None, gelu)
-            if f32_node and ops.pos_poly_mlp_f32_supported(pos, l0.weight, l2.weight):
-                # the first Linear as a polynomial of the normalised coordinate (no feature matrix, no K = 256 GEMM:
-                # csrc/posenc_poly.hip), SiLU and the 64-wide second Linear
-                node = lambda **kw: ops.pos_poly_mlp_f32(pos, batch, mins, maxs, l0.weight, l0.bias, l2.weight, l2.bias,
-                                                         eps=eps_n, max_period=10000.0, **kw)
-            else:
-                freq = ops.posfreq(pos, batch, mins, maxs, fd, dtype, eps=eps_n, max_period=10000.0)
-        else:
+        route = self.route(on_gpu=pos.is_cuda, batched=batch is not None, dtype=dtype, rows=n, pos_grad=pos.requires_grad)
+        if route.features == "torch":
             pos = self.normalize(pos, batch, num_graphs)
             freq = sinusoidal_embedding(pos.flatten(), fd, max_period=10000).reshape(n, 2, fd).to(dtype)
-        if node is None:
-            flat = freq.reshape(-1, fd)
-            if f32_node and ops.mlp_silu_f32_supported(flat, l0.weight, l2.weight):
-                # SiLU in the GEMMs' epilogues, its derivative in the data-gradient GEMM's epilogue
-                node = lambda **kw: ops.mlp_silu_f32(flat, l0.weight, l0.bias, l2.weight, l2.bias, **kw)
-        if node is not None and want_pre:
-            h, gh = node(gelu_out=True)
-            return PosEmbedding(gh.reshape(n, -1), h.reshape(n, -1), True)
-        if node is not None:
-            h = node().reshape(n, -1)
         else:
+            # per-graph min/max (one pass); the kernels normalise with them and only look up the graphs of existing nodes: no
+            # (0, 0) fix-up for empty ones.  No batch vector = one graph, normalised WITHOUT the epsilon (ist_encoder.py:62-64)
+            if batch is None or num_graphs is None:
+                num_graphs = 1 if batch is None else int(batch.max()) + 1 if batch.numel() else 0
+            mins, maxs = ops.segment_minmax(pos, batch, num_graphs, keep_empty=True, out=minmax)
+            eps_n = 1e-8 if batch is not None else 0.0
+            if route.features == "posfreq":                  # normalise + sinusoid written straight in `dtype`
+                freq = ops.posfreq(pos, batch, mins, maxs, fd, dtype, eps_n, 10000.0, num_graphs)
+        # h: the embedder's output; act: gelu(h) where the route's own kernel made it (with `want_pre` a constant for autograd)
+        act = None
+        if route.mlp == "fused16":
+            # sinusoid + Linear + SiLU + Linear in one kernel: the [2n, 256] feature matrix is generated in registers
+            # (and stored once for the weight gradient when training) instead of written and re-read
+            r = ops.posmlp(pos, batch, mins, maxs, *w, dtype, eps_n, 10000.0, gelu, want_pre, num_graphs)
+            act, h = r if want_pre else (r, None) if gelu else (None, r)
+        elif route.mlp == "composed":
             h = ops.linear(F.silu(ops.linear(freq, l0.weight, l0.bias)), l2.weight, l2.bias).flatten(-2)
-        if want_pre and dtype == torch.float32 and h.is_cuda and ops.F32_GATE_EPILOGUE:
-            # gelu'(h) in the epilogue of the consumer's data-gradient GEMM instead of a gelu_backward pass
-            return PosEmbedding(F.gelu(h).detach(), h, True)
-        return PosEmbedding(F.gelu(h) if gelu else h, None, gelu)
+        else:                    # fp32 storage: the MLP (+ the GELU that follows) behind one autograd node, as [2n, dim] rows
+            if route.mlp == "poly_f32":
+                # the first Linear as a polynomial of the normalised coordinate (no feature matrix, no K = 256 GEMM:
+                # csrc/posenc_poly.hip), SiLU and the 64-wide second Linear
+                r = ops.pos_poly_mlp_f32(pos, batch, mins, maxs, *w, eps=eps_n, max_period=10000.0, gelu_out=want_pre,
+                                         num_graphs=num_graphs)
+            else:                # SiLU in the GEMMs' epilogues, its derivative in the data-gradient GEMM's epilogue
+                r = ops.mlp_silu_f32(freq.reshape(-1, fd), *w, gelu_out=want_pre)
+            h, act = (t.reshape(n, -1) for t in r) if want_pre else (r.reshape(n, -1), None)
+        if gelu and act is None:
+            # fp32 storage: gelu'(h) in the epilogue of the consumer's data-gradient GEMM instead of a gelu_backward pass
+            want_pre = want_pre and dtype == torch.float32 and h.is_cuda and ops.F32_GATE_EPILOGUE
+            act = F.gelu(h).detach() if want_pre else F.gelu(h)
+        return PosEmbedding(act if gelu else h, h if want_pre else None, gelu)
 
 
 def _pair_node_applies(emb: "Positional2dEmbedder", on_gpu: bool, batched: bool, dtype: torch.dtype) -> bool:
-    """``ops.posmlp_pair`` covers: the fused 16-bit embedder on the GPU, batch vectors + a graph count, training."""
+    """``ops.posmlp_pair`` covers: the fused 16-bit embedder (``emb.route``), batch vectors + a graph count, training."""
     l0, l2 = emb.mlp[0], emb.mlp[2]
-    return bool(ops.POS_PAIR_NODE and ops.FUSED_POSMLP and on_gpu and emb.frequency_embedding_size % 16 == 0 and batched
+    return bool(ops.POS_PAIR_NODE and batched and emb.route(on_gpu=on_gpu, batched=batched, dtype=dtype, rows=1).mlp == "fused16"
                 and ops.posmlp_pair_supported(l0.weight, l0.bias, l2.weight, l2.bias, dtype))
 
 
@@ -166,7 +182,7 @@ def _pair_node(emb: "Positional2dEmbedder", pos_a, batch_a, pos_b, batch_b, num_
     mm_a = ops.segment_minmax(pos_a, batch_a, num_graphs, keep_empty=True)
     mm_b = ops.segment_minmax(pos_b, batch_b, num_graphs, keep_empty=True)
     return ops.posmlp_pair(pos_a, batch_a, mm_a[0], mm_a[1], pos_b, batch_b, mm_b[0], mm_b[1], l0.weight, l0.bias, l2.weight,
-                           l2.bias, dtype, eps=1e-8, max_period=10000.0)
+                           l2.bias, dtype, eps=1e-8, max_period=10000.0, num_graphs=num_graphs)
 
 
 class _SplitRows(torch.autograd.Function):

@@ -59,16 +59,20 @@ LINEAR_PAIR = True
 # ... and per projection backward
 WGRAD_PAIR = True
 
-# Positional embedder (posemb.py)
-# fp32 storage: the positional embedder's first Linear as a degree-12 polynomial of the normalised coordinate
+# Positional embedder (posemb.py; ist_encoder.py reads them when it names an embedder call's route, Positional2dEmbedder.route:
+# where the sinusoid features come from -- "none" | "posfreq" | "torch" -- and the form of the MLP -- "fused16" | "poly_f32" |
+# "mlp_f32" | "composed")
+# "fused16", the whole 16-bit embedder in one kernel (ops.posmlp), where it applies; False: "posfreq" + "composed", i.e.
+# linear + SiLU + linear (tests/test_gpu_model.py)
+FUSED_POSMLP = True
+# False = the backward of "fused16" as three kernels, round 2 (tests/test_gpu_heads.py, tools/bench_posmlp_bwd.py)
+FUSED_POSMLP_BWD = True
+# fp32 storage, "poly_f32": the positional embedder's first Linear as a degree-12 polynomial of the normalised coordinate
 # (csrc/posenc_poly.hip) -- no [2n, 256] feature matrix (2 GB at C2: segger_posfreq wrote it, two exact-fp32 GEMMs read it)
-# and no K = 256 GEMM, forward or weight gradient.  False: posfreq + _MlpSiluF32 (round 5's route).
+# and no K = 256 GEMM, forward or weight gradient.  False: "posfreq" + "mlp_f32" (_MlpSiluF32, round 5's route); with
+# F32_GATE_EPILOGUE off as well, or a Linear without bias: "posfreq" + "composed".
 # (tests/test_gpu_model.py)
 POS_POLY_F32 = True
-# False = the embedder's backward as three kernels, round 2 (tests/test_gpu_heads.py, tools/bench_posmlp_bwd.py)
-FUSED_POSMLP_BWD = True
-# the one-kernel embedder (ops.posmlp) where it applies; False: posfreq + linear + SiLU + linear (tests/test_gpu_model.py)
-FUSED_POSMLP = True
 
 # Encoder front end (frontend.py; ist_encoder.py reads them when it plans a step's input stage, ISTEncoder.front_plan)
 # one embedder call for both node types (tests/test_host.py)
@@ -111,7 +115,8 @@ from .linear import (colsum, linear, linear_f32_act_launch, linear_f32_gate_laun
                      linear_pair, linear_supported, linear_wgrad_dx_gate_supported, linear_wgrad_dx_launch,
                      linear_wgrad_dx_supported, linear_wgrad_launch, linear_wgrad_pair_launch, linear_wgrad_supported,
                      segment_rowsum)
-from .posemb import (mlp_silu_f32, mlp_silu_f32_supported, pos_poly_mlp_f32, pos_poly_mlp_f32_supported, posfreq, posmlp,
-                     posmlp_pair, posmlp_pair_supported, posmlp_supported, segment_minmax)
+from .posemb import (mlp_silu_f32, mlp_silu_f32_covers, mlp_silu_f32_supported, pos_poly_f32_covers, pos_poly_mlp_f32,
+                     pos_poly_mlp_f32_supported, posfreq, posmlp, posmlp_pair, posmlp_pair_supported, posmlp_supported,
+                     segment_minmax)
 from .frontend import (EmbedInput, _EmbedLinear, _gene_table_args, embed_gelu, embed_linear, embed_linear_supported,
                        front_join, l2_normalize, l2_normalize_many, rows_by_id)

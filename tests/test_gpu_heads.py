@@ -663,6 +663,142 @@ def test_positional_embedder_pair_is_one_node_with_the_summed_gradients(cuda, dt
         assert ie._pair_node(emb, pos_a, ba, pos_b, bb, 3, dtype) is None              # (nothing to differentiate)
 
 
+EMBEDDER_FORMS = {     # MLP form -> the switches that lead an embedder call of that storage there, and the ops entry points it makes
+    "fused16": ({}, {"posmlp": 1}),
+    "poly_f32": ({}, {"pos_poly_mlp_f32": 1}),
+    "mlp_f32": ({"POS_POLY_F32": False}, {"posfreq": 1, "mlp_silu_f32": 1}),
+    "composed": ({"FUSED_POSMLP": False, "F32_GATE_EPILOGUE": False}, {"posfreq": 1, "linear": 2}),
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+@pytest.mark.parametrize("n", [1, 31, 1000])           # one row, less than one 32-row tile, several stages + a ragged last one
+def test_embedder_runs_the_planned_route_and_one_tail_serves_every_form(cuda, dtype, n, monkeypatch):
+    """``Positional2dEmbedder._embed`` runs exactly the entry points of the route ``Positional2dEmbedder.route`` names, for every
+    MLP form the storage dtype reaches by switches, and its tail hands out the same thing on each: with ``gelu``, ``out`` =
+    gelu(embedder output); with ``want_pre``, the output itself as ``pre`` (``out`` then a constant) wherever a kernel of the
+    form made both -- every form but the composed one.  The parameter gradients of the three (gelu, want_pre) combinations,
+    the consumer applying gelu' (or the GELU) it owes, agree with each other and with the composed route.  Tolerances as in
+    the tests of the same pairs above and in test_gpu_model.py: 16-bit outputs 2 rel |ref| + 4 rel (rel = 2^-8 bf16, 2^-10
+    f16), 16-bit gradients 3e-2 of the largest entry; fp32 outputs 5e-6, gradients 2e-5 of the largest entry + 1e-6."""
+    import torch.nn.functional as F
+    from segger_amd import ops
+    from segger_amd.ist_encoder import EmbedRoute, Positional2dEmbedder
+    f32 = dtype == torch.float32
+    g = torch.Generator().manual_seed(n)
+    pos = (torch.rand(n, 2, generator=g) * 700 + 3).to(cuda)
+    batch = (2 * torch.sort(torch.randint(0, 2, (n,), generator=g)).values).to(cuda)      # three graphs, the middle one empty
+    torch.manual_seed(3)
+    emb = Positional2dEmbedder(128).to(cuda)
+    if not f32:
+        with torch.no_grad():
+            for p_ in emb.parameters():
+                p_.mul_(3.0)                                 # bigger activations than the default init gives
+    gy = torch.randn(n, 128, device=cuda, generator=torch.Generator(device=cuda).manual_seed(1)).to(dtype)
+    calls = {}
+    for name in ("posmlp", "posmlp_pair", "pos_poly_mlp_f32", "mlp_silu_f32", "posfreq", "linear"):
+        def counted(*a, _real=getattr(ops, name), _name=name, **k):
+            calls[_name] = calls.get(_name, 0) + 1
+            return _real(*a, **k)
+        monkeypatch.setattr(ops, name, counted)
+
+    def run(form, gelu, want_pre):
+        switches, entry_points = EMBEDDER_FORMS[form]
+        with monkeypatch.context() as mp:
+            for name, value in switches.items():
+                mp.setattr(ops, name, value)
+            planned = emb.route(on_gpu=True, batched=True, dtype=dtype, rows=n)
+            assert planned == EmbedRoute("none" if form in ("fused16", "poly_f32") else "posfreq", form)
+            emb.zero_grad(set_to_none=True)
+            calls.clear()
+            r = emb._embed(pos, batch, 3, dtype, gelu=gelu, want_pre=want_pre)
+            assert calls == entry_points, (form, calls)
+        assert r.gelu_applied == gelu and r.out.shape == (n, 128) and r.out.dtype == dtype
+        assert (r.pre is not None) == (want_pre and form != "composed")
+        if r.pre is not None:                                # the consumer multiplies by gelu'(pre) itself
+            assert not r.out.requires_grad and r.pre.shape == (n, 128)
+            r.pre.backward(torch.ops.aten.gelu_backward(gy, r.pre.detach()))
+        else:                                                # ... or still owes the GELU
+            (r.out if gelu else F.gelu(r.out)).backward(gy)
+        act = r.out.detach() if gelu else F.gelu(r.out.detach())
+        return act, None if r.pre is None else r.pre.detach(), [p_.grad.clone() for p_ in emb.parameters()]
+
+    rel = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -10
+
+    def same_out(a, ref):
+        if f32:
+            return bool(((a - ref).abs() < 5e-6).all())
+        return bool(((a.double() - ref.double()).abs() <= 2 * rel * ref.double().abs() + 4 * rel).all())
+
+    def same_grads(got, ref):
+        for a, b in zip(got, ref):
+            scale = b.abs().max().item()
+            if (a - b).abs().max().item() > ((2e-5 * scale + 1e-6) if f32 else 3e-2 * (scale + 1e-6)):
+                return False
+        return True
+
+    ref_act, _, ref_grads = run("composed", False, False)
+    for form in (("poly_f32", "mlp_f32", "composed") if f32 else ("fused16", "composed")):
+        mine = {combo: run(form, *combo) for combo in ((False, False), (True, False), (True, True))}
+        plain = mine[(False, False)]
+        for combo, (act, pre, grads) in mine.items():
+            # (across forms at fp32 only: the 16-bit forms differ by the rounding of z1, which the fp64 comparison above bounds)
+            assert same_out(act, plain[0]) and (not f32 or same_out(act, ref_act)), (form, combo)
+            assert pre is None or same_out(act, F.gelu(pre)), (form, combo)                # out == gelu(pre)
+            assert same_grads(grads, ref_grads), (form, combo)
+            assert same_grads(grads, plain[2]) and same_grads(grads, mine[(True, True)][2]), (form, combo)
+    if f32:
+        # the composed form hands out `pre` as well where the consumer's fp32 GEMM can apply gelu' (F32_GATE_EPILOGUE on):
+        # reached with a bias-free Linear, out = gelu(pre) by torch, a constant
+        emb.mlp[2].bias = None
+        assert emb.route(on_gpu=True, batched=True, dtype=dtype, rows=n) == EmbedRoute("posfreq", "composed")
+        outs = {}
+        for combo in ((False, False), (True, False), (True, True)):
+            emb.zero_grad(set_to_none=True)
+            calls.clear()
+            r = emb._embed(pos, batch, 3, dtype, gelu=combo[0], want_pre=combo[1])
+            assert calls == {"posfreq": 1, "linear": 2} and (r.pre is not None) == combo[1] and r.gelu_applied == combo[0]
+            if r.pre is not None:
+                assert not r.out.requires_grad and torch.equal(r.out, F.gelu(r.pre))
+                r.pre.backward(torch.ops.aten.gelu_backward(gy, r.pre.detach()))
+            else:
+                (r.out if combo[0] else F.gelu(r.out)).backward(gy)
+            outs[combo] = (r.out.detach() if combo[0] else F.gelu(r.out.detach()), [p_.grad.clone() for p_ in emb.parameters()])
+        for act, grads in outs.values():
+            assert same_out(act, outs[(False, False)][0]) and same_grads(grads, outs[(False, False)][1])
+
+
+def test_embedder_kernels_refuse_minmax_they_would_misread(cuda):
+    """``mins`` / ``maxs`` reach the kernels as raw ``float[num_graphs][2]`` pointers: float64, non-contiguous, too few rows for
+    the stated graph count or another device raise ValueError from ops.posfreq, ops.posmlp and ops.pos_poly_mlp_f32 alike,
+    before anything is launched -- the next valid call on the stream gives what it gave before."""
+    from segger_amd import ops
+    from segger_amd.ist_encoder import Positional2dEmbedder
+    n, n_graphs = 4, 3
+    pos = (torch.rand(n, 2, generator=torch.Generator().manual_seed(4)) * 90).to(cuda)
+    batch = torch.tensor([0, 0, 2, 2], device=cuda)
+    emb = Positional2dEmbedder(128).to(cuda)
+    w = (emb.mlp[0].weight, emb.mlp[0].bias, emb.mlp[2].weight, emb.mlp[2].bias)
+    mins, maxs = ops.segment_minmax(pos, batch, n_graphs, keep_empty=True)
+    entries = {"posfreq": lambda lo, hi: ops.posfreq(pos, batch, lo, hi, 256, torch.float32, num_graphs=n_graphs),
+               "posmlp": lambda lo, hi: ops.posmlp(pos, batch, lo, hi, *w, torch.bfloat16, num_graphs=n_graphs),
+               "pos_poly_mlp_f32": lambda lo, hi: ops.pos_poly_mlp_f32(pos, batch, lo, hi, *w, num_graphs=n_graphs)}
+    strided = torch.stack((maxs, maxs), 1)[:, 0]
+    assert strided.shape == maxs.shape and not strided.is_contiguous()
+    bad = {"float64": (mins.double(), maxs), "non-contiguous": (mins, strided), "too few rows": (mins[:n_graphs - 1], maxs),
+           "other device": (mins.cpu(), maxs)}
+    for name, fn in entries.items():
+        for first in (True, False):                          # (first: before the entry's first valid call, nothing cached)
+            for why, (lo, hi) in bad.items():
+                with pytest.raises(ValueError, match="mins / maxs"):
+                    fn(lo, hi)
+            if first:
+                before = fn(mins, maxs).detach().clone()
+        after = fn(mins, maxs).detach()
+        torch.cuda.synchronize()
+        assert torch.equal(before, after), name
+
+
 def test_step_draws_equal_the_separate_launches(cuda):
     """segger_step_draws (all random draws of a training step in one launch: bit planes of the edge views, both triplet
     samplers, the negative boundaries, + the increment of Adam's step counters) against dropout_bits_many, triplet_sample x 2

@@ -414,6 +414,81 @@ def test_front_plan_truth_table(monkeypatch):
     assert plan(bf, 1_000_000) == big
 
 
+def test_embedder_route_truth_table(monkeypatch):
+    """``Positional2dEmbedder.route``: where an embedder call's sinusoid features come from and which form of the MLP runs,
+    from shapes, dtypes and the ``ops`` switches alone (no tensor, no launch, no GPU).  Expected values: the conditions of
+    ``_embed`` as it stood before the route existed -- device features (per-graph min / max kernels) with a batch vector or on
+    the GPU when the width is a multiple of 16, else torch; the one-kernel embedder: FUSED_POSMLP, GPU, biases, 16-bit, 256 ->
+    64; else, at fp32 storage on the GPU with F32_GATE_EPILOGUE, biases and at least one row, one autograd node: the polynomial
+    first layer (POS_POLY_F32, positions without a gradient) or segger_posfreq + the one-node MLP; else composed ops.  The
+    pair node: that one-kernel embedder, batch vectors + graph count, POS_PAIR_NODE, FUSED_POSMLP_BWD, something to
+    differentiate."""
+    import torch
+    from torch.nn import Linear
+    from segger_amd import _lib, ops
+    import segger_amd.ist_encoder as ie
+    R = ie.EmbedRoute
+    bf, f16, f32 = torch.bfloat16, torch.float16, torch.float32
+    emb = ie.Positional2dEmbedder(128)                       # 256 -> 64 -> 64, as the encoder builds it
+    odd = ie.Positional2dEmbedder(128, frequency_embedding_size=250)
+    nobias = ie.Positional2dEmbedder(128)
+    nobias.mlp[2] = Linear(64, 64, bias=False)
+
+    def route(e, dtype, on_gpu=True, batched=True, rows=1000, **kw):
+        return e.route(on_gpu=on_gpu, batched=batched, dtype=dtype, rows=rows, **kw)
+
+    def table():
+        return {(name, str(dt)[6:]): route(e, dt) for name, e in (("emb", emb), ("odd", odd), ("nobias", nobias))
+                for dt in (bf, f16, f32)}
+
+    fused, poly, composed = R("none", "fused16"), R("none", "poly_f32"), R("posfreq", "composed")
+    base = {("emb", "bfloat16"): fused, ("emb", "float16"): fused, ("emb", "float32"): poly,
+            ("odd", "bfloat16"): R("torch", "composed"), ("odd", "float16"): R("torch", "composed"),
+            ("odd", "float32"): R("torch", "composed"),
+            ("nobias", "bfloat16"): composed, ("nobias", "float16"): composed, ("nobias", "float32"): composed}
+    assert table() == base
+    for dt, want in ((bf, fused), (f16, fused), (f32, poly)):
+        assert route(emb, dt, batched=False) == want                       # no batch vector on the GPU: one graph
+        assert route(emb, dt, on_gpu=False, batched=False) == R("torch", "composed")
+        # a batch vector on the CPU still asks for the device's min / max: refused there, as before (no CPU route)
+        assert route(emb, dt, on_gpu=False) == composed
+        assert route(odd, dt, on_gpu=False) == R("torch", "composed")
+    for batch in (torch.zeros(5, dtype=torch.int64), None):               # (and ops.linear has none either)
+        with pytest.raises(_lib.SeggerAmdError, match="no CPU fallback"):
+            emb(torch.rand(5, 2), batch, num_graphs=1)
+    # the fp32 nodes want at least one row; the polynomial one also positions that are constants (segger_posfreq's features
+    # are constants whatever the positions require, so the one-node MLP takes those)
+    assert route(emb, f32, rows=0) == composed and route(emb, f32, rows=1) == poly
+    assert route(emb, f32, pos_grad=True) == R("posfreq", "mlp_f32")
+    assert route(emb, bf, rows=0) == fused and route(emb, f16, pos_grad=True) == fused
+    # each switch off in turn
+    off = {"FUSED_POSMLP": {("emb", "bfloat16"): composed, ("emb", "float16"): composed},
+           "POS_POLY_F32": {("emb", "float32"): R("posfreq", "mlp_f32")},
+           "F32_GATE_EPILOGUE": {("emb", "float32"): composed},
+           "FUSED_POSMLP_BWD": {}, "POS_PAIR_NODE": {}}
+    for name, changed in off.items():
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, name, False)
+            assert table() == {**base, **changed}, name
+            if name == "POS_POLY_F32":
+                assert route(emb, f32, rows=0) == composed and route(emb, f32, pos_grad=True) == R("posfreq", "mlp_f32")
+                mp.setattr(ops, "F32_GATE_EPILOGUE", False)
+                assert route(emb, f32) == composed
+    assert table() == base
+    # the pair node (ops.posmlp_pair) asks the same function
+    pair = lambda e, dt, on_gpu=True, batched=True: ie._pair_node_applies(e, on_gpu, batched, dt)
+    assert pair(emb, bf) and pair(emb, f16)
+    assert not pair(emb, f32) and not pair(emb, bf, on_gpu=False) and not pair(emb, bf, batched=False)
+    assert not pair(odd, bf) and not pair(nobias, bf)
+    with torch.no_grad():
+        assert not pair(emb, bf) and not pair(emb, f16)                    # nothing to differentiate
+    for name in ("POS_PAIR_NODE", "FUSED_POSMLP", "FUSED_POSMLP_BWD"):
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, name, False)
+            assert not pair(emb, bf) and not pair(emb, f16), name
+    assert pair(emb, bf)
+
+
 def test_projection_backward_plan_truth_table(monkeypatch):
     """``ops.linear.backward_plan`` / ``backward_pair_plan``: the kernels of a projection backward from shapes, needs, dtype
     and the ``ops`` switches alone (no tensor, no launch, no GPU).  Expected values: the conditions of the four autograd nodes
