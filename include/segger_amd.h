@@ -1349,6 +1349,72 @@ int segger_contamination_posterior(const int64_t* indptr, const int32_t* indices
                                    int32_t* contamination, int64_t* contaminated, int64_t* total, double* percent,
                                    segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Boundary morphology: the parts of the reference's get_polygon_props (src/segger/geometry/morphology.py, stacked into
+ * X_morphology at data/utils/anndata.py:296-311) for every polygon of a CSR of rings, without geopandas / shapely.  The
+ * kernels behind segger_amd.morphology.  csrc/morphology.hip.  Purely additive: two new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * Input:  ring_offsets [n_polygons + 1] int64 and xy [n_vertices, 2] fp64 (16-byte aligned): polygon p is the single
+ *   exterior ring xy[ring_offsets[p] .. ring_offsets[p + 1]), either orientation; no holes, no multi-part polygons.  A ring
+ *   whose last vertex equals its first bit for bit is closed and the duplicate is ignored: n below counts the vertices
+ *   without it.  Repeated consecutive vertices and vertices collinear with an edge are allowed.
+ *
+ * Output:  props [n_polygons, SEGGER_MORPH_COLS] fp64, the columns
+ *     0 area           |shoelace| / 2                      6 cy
+ *     1 hull_area      area of the convex hull H           7 xmin      the bounds, on the coordinates as given (exact)
+ *     2 rect_area      minimum-area enclosing rectangle    8 ymin
+ *     3 envelope_area  (xmax - xmin) (ymax - ymin)         9 xmax
+ *     4 radius         smallest enclosing circle          10 ymax
+ *     5 cx             area-weighted centroid             11 n_hull    vertices of H, as fp64
+ *   The reference's four columns are area, hull_area / area, rect_area / envelope_area, area / radius^2: the divisions
+ *   are the caller's (IEEE: x / 0 = +-inf, 0 / 0 = NaN; nothing is clamped).
+ *
+ * Arithmetic:  fp64 on coordinates translated to the ring's first vertex (slide coordinates are 10^4 .. 10^5, a cell is
+ *   ~10 across: untranslated shoelace terms cancel), FMA contraction off.  One wave owns one polygon: n <= 64 keeps one
+ *   vertex per lane in registers; 64 < n <= SEGGER_MORPH_MAX_VERTS stages the ring in LDS.  The polygons are binned by
+ *   route on the device (two index lists in the workspace, one integer atomic per wave and route); no floating-point
+ *   atomics; every sum is a per-lane sum over ascending vertices followed by a fixed butterfly: a polygon's row has the
+ *   same bits from call to call, in whatever batch and at whatever position it is computed.
+ *   Hull: gift wrapping from the lowest (x, then y, then index) vertex, counter-clockwise; the next vertex is the most
+ *   clockwise one as seen from the current vertex, ties (collinear with it) go to the larger distance, then to the lower
+ *   index, and a vertex that coincides with the current one never competes: collinear and duplicate vertices are never
+ *   hull vertices, and the march ends at its start after n_hull <= n steps.
+ *   Rectangle: the minimum over the hull's edges e of (max_u - min_u) (max_v - min_v) / |e|^2, u and v the projections of
+ *   the hull vertices on e and on its normal; the lowest edge index wins a tie.
+ *   Circle: exact -- Welzl's iteration over the hull vertices in hull order (no shuffle), support sets of 1, 2 or 3
+ *   vertices, the circumcentre computed relative to the first support vertex, r^2 the largest squared distance from the
+ *   centre to a support vertex; a vertex is outside iff d^2 > r^2 (1 + SEGGER_MORPH_CIRCLE_SLACK), so a support vertex
+ *   never tests as outside its own circle.
+ *   Centroid: first vertex + (sum (x_i + x_j) c_ij, sum (y_i + y_j) c_ij) / (3 sum c_ij), c_ij the shoelace terms; the
+ *   mean of the vertices when the area is 0.
+ *
+ * Degenerate rings are results: n = 0 gives a row of NaN; n = 1, 2, or all vertices collinear or identical give
+ *   area = hull_area = rect_area = 0, radius = half the extent, n_hull = 1 or 2.
+ *
+ * Errors found on the device, without a synchronisation: a ring with ring_offsets[p] < 0, ring_offsets[p + 1] <
+ *   ring_offsets[p] or ring_offsets[p + 1] > n_vertices gets a row of NaN and sets SEGGER_MORPH_ERR_OFFSETS in the error
+ *   word; a ring of more than SEGGER_MORPH_MAX_VERTS vertices gets a row of NaN and SEGGER_MORPH_ERR_CAP (nothing is read
+ *   or written out of bounds for either).  The error word is the int32 at byte 0 of the workspace (0 = none), valid once the
+ *   stream has run; int32 words 1 and 2 are the polygons that took the register and the LDS route.
+ *   The ring lengths live in device memory, so this entry point cannot see the cap without a synchronisation: the cap is
+ *   refused BEFORE the call, by the Python wrapper (segger_amd.morphology.polygon_props raises ValueError naming the first
+ *   such polygon and launches nothing); a C caller that skips that check gets the NaN row and SEGGER_MORPH_ERR_CAP.
+ *
+ * Workspace: 256 bytes + 2 x (4 n_polygons rounded up to 256) bytes, 256-byte aligned.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative n_polygons, n_vertices or
+ * workspace_bytes, 2^31 - 1 polygons or more, and for n_polygons > 0 a NULL pointer (xy may be NULL when n_vertices = 0), a
+ * misaligned pointer, a workspace below segger_morphology_workspace_bytes (which itself returns the negative code for a
+ * count out of range).  n_polygons = 0 returns SEGGER_OK without touching a pointer or the device.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_MORPH_MAX_VERTS 4096           /* 64 KB of fp64 pairs in LDS */
+#define SEGGER_MORPH_COLS 12
+#define SEGGER_MORPH_CIRCLE_SLACK 0x1p-44     /* relative, on squared distances */
+#define SEGGER_MORPH_ERR_OFFSETS 1
+#define SEGGER_MORPH_ERR_CAP 2
+int64_t segger_morphology_workspace_bytes(int64_t n_polygons);
+int segger_polygon_props(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                         double* props /* [P, 12] */, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

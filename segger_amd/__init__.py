@@ -14,5 +14,7 @@ from . import phenograph  # noqa: F401  (the module: its function of the same na
 from .phenograph import knn_bruteforce, jaccard_graph, louvain  # noqa: F401
 from . import validation  # noqa: F401
 from .validation import neighbor_frequencies, reference_table, contamination_posterior, calculate_contamination, contamination_flow  # noqa: F401
+from . import morphology  # noqa: F401
+from .morphology import polygon_props, morphology_features, rings_from_padded  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,0 +1,485 @@
+// segger_polygon_props: area, convex hull, minimum-area rectangle and smallest enclosing circle of every ring of a CSR of
+// polygons -- the parts of the reference's geometry/morphology.py (get_polygon_props), which goes through
+// geopandas / shapely one polygon at a time.  include/segger_amd.h has the contract.
+//
+// Three kernels on one stream, no host synchronisation:
+//   morph_bin_kernel    one thread per polygon: checks its two offsets, drops a closing duplicate vertex, and appends the
+//                       polygon to the list of its route (one integer atomic per wave and route).  A ring with bad offsets
+//                       or more than SEGGER_MORPH_MAX_VERTS vertices gets a row of NaN and a bit in the error word.
+//   morph_short_kernel  n <= 64: one wave per polygon, one vertex per lane, everything in registers (no LDS).
+//   morph_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the translated ring
+//                       staged in LDS (64 KB) next to the hull's index list (8 KB), lanes striding over both.
+// Both polygon kernels are grid-stride loops over their list, whose length they read from the workspace; the order of a
+// list depends on the order of the atomics, the row of a polygon does not: every sum is a per-lane sum in ascending
+// vertex order followed by a 6-level butterfly, so the same input gives the same bits from call to call.
+//
+// Per polygon, in float64 on coordinates translated to the ring's first vertex, with FMA contraction off (a cross
+// product of exactly representable coordinates is then exact, and cross(a, b) = -cross(b, a) to the bit):
+//   1. shoelace area, centroid sums, vertex sums, bounds (bounds on the untranslated coordinates: exact);
+//   2. convex hull by gift wrapping from the lexicographically lowest vertex: each step is one wave-wide arg-max of
+//      "most clockwise as seen from the current vertex", ties broken by the larger distance, then by the lower index; a
+//      vertex that coincides with the current one never competes.  Collinear and duplicate vertices therefore never
+//      enter the hull and the march returns to its start after h <= n steps (n steps is also a hard cap);
+//   3. shoelace over the hull;
+//   4. minimum-area rectangle: lane e takes hull edge e (stride 64) and projects all h hull vertices, broadcast by
+//      readlane or from LDS, on the edge and its normal; the lowest edge index wins a tie;
+//   5. smallest enclosing circle: Welzl's iteration over the hull vertices in hull order, three nested levels (1, 2, 3
+//      support points), each level's scan "first vertex in [lo, hi) outside the circle" one ballot per 64 vertices.  The
+//      radius^2 of a circle is the largest squared distance from its centre to its support points and a vertex is
+//      outside iff d^2 > r^2 (1 + SEGGER_MORPH_CIRCLE_SLACK), so a support point never tests as outside its own circle.
+//      There is no shuffle: the order is the hull order, the result is reproducible, and every scan only moves forward,
+//      so the worst case is h^3 / 64 ballots -- h <= 25 for the 13- and 25-vertex rings that are the bulk of real input;
+//      a long ring whose hull has thousands of vertices (a finely sampled circle) is the slow case.
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): morph_bin_kernel 20 VGPR, no LDS, 8 waves per SIMD;
+// morph_short_kernel 100 VGPR, no LDS, 4 waves per SIMD; morph_long_kernel 104 VGPR, 73728 B LDS (two single-wave
+// workgroups per CU); no scratch in any of them.
+#include <math.h>
+
+#include "common.h"
+#include "post_common.h"
+
+#pragma clang fp contract(off)
+
+namespace segger {
+namespace {
+
+constexpr int kMorphThreads = 256;
+constexpr int kMorphWaves = kMorphThreads / kWave;
+constexpr int kMorphCols = SEGGER_MORPH_COLS;
+constexpr int kWordFlag = 0, kWordShort = 1, kWordLong = 2;        // int32 words at the start of the workspace
+constexpr double kSlack = SEGGER_MORPH_CIRCLE_SLACK;
+
+static_assert(SEGGER_MORPH_MAX_VERTS <= 65536, "the hull's index list is uint16");
+static_assert(SEGGER_MORPH_MAX_VERTS % kWave == 0, "lanes stride over whole chunks");
+
+struct P2 { double x, y; };
+
+__device__ __forceinline__ double shfl_f64(double v, int src) {
+  return __longlong_as_double((long long)shfl64((uint64_t)__double_as_longlong(v), src));
+}
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  return __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(v), mask));
+}
+// lane is the same in every lane of the wave
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+// the same bits in every lane: a + b is commutative, so both partners of a level compute the same sum
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v += shfl_xor_f64(v, m);
+  return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmin(v, shfl_xor_f64(v, m));
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmax(v, shfl_xor_f64(v, m));
+  return v;
+}
+
+// ---------------------------------------------------------------- the two ring / hull stores ---
+// own(i): vertex i from the lane that owns it (i % 64 == lane), callable under any EXEC; at(i): any lane reads any vertex,
+// every lane of the wave active; uni(i): i is the same in every lane.
+struct RegRing {
+  double x, y;                                                       // vertex `lane`, translated
+  __device__ __forceinline__ P2 own(int) const { return P2{x, y}; }
+  __device__ __forceinline__ P2 at(int i) const { return P2{shfl_f64(x, i), shfl_f64(y, i)}; }
+  __device__ __forceinline__ P2 uni(int i) const { return P2{readlane_f64(x, i), readlane_f64(y, i)}; }
+};
+struct RegHull {
+  double x = 0.0, y = 0.0;                                           // hull vertex `lane`
+  __device__ __forceinline__ void push(int k, int, P2 q) {
+    if ((int)(threadIdx.x & (kWave - 1)) == k) { x = q.x; y = q.y; }
+  }
+  __device__ __forceinline__ void publish() const {}
+  __device__ __forceinline__ P2 own(int) const { return P2{x, y}; }
+  __device__ __forceinline__ P2 at(int k) const { return P2{shfl_f64(x, k), shfl_f64(y, k)}; }
+  __device__ __forceinline__ P2 uni(int k) const { return P2{readlane_f64(x, k), readlane_f64(y, k)}; }
+};
+struct LdsRing {
+  const double2* pts;
+  __device__ __forceinline__ P2 own(int i) const { const double2 p = pts[i]; return P2{p.x, p.y}; }
+  __device__ __forceinline__ P2 at(int i) const { return own(i); }
+  __device__ __forceinline__ P2 uni(int i) const { return own(i); }
+};
+struct LdsHull {
+  const double2* pts;
+  uint16_t* idx;
+  __device__ __forceinline__ void push(int k, int i, P2) {
+    if ((threadIdx.x & (kWave - 1)) == 0) idx[k] = (uint16_t)i;
+  }
+  __device__ __forceinline__ void publish() const { __syncthreads(); }       // a workgroup is one wave here
+  __device__ __forceinline__ P2 own(int k) const { const double2 p = pts[idx[k]]; return P2{p.x, p.y}; }
+  __device__ __forceinline__ P2 at(int k) const { return own(k); }
+  __device__ __forceinline__ P2 uni(int k) const { return own(k); }
+};
+
+// ---------------------------------------------------------------- gift wrapping ---
+struct Cand { int i; double dx, dy; };                               // a vertex and its offset from the current hull vertex
+
+// is b ahead of a in the march?  (i < 0: no candidate; neither offset is zero)
+__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
+  if (b.i < 0) return false;
+  if (a.i < 0) return true;
+  const double cr = a.dx * b.dy - a.dy * b.dx;                       // < 0: b is to the right of current -> a
+  if (cr != 0.0) return cr < 0.0;
+  const double da = a.dx * a.dx + a.dy * a.dy, db = b.dx * b.dx + b.dy * b.dy;
+  if (da != db) return db > da;
+  return b.i < a.i;
+}
+
+__device__ __forceinline__ Cand wave_best(Cand c) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {
+    Cand o;
+    o.i = __shfl_xor(c.i, m, kWave);
+    o.dx = shfl_xor_f64(c.dx, m);
+    o.dy = shfl_xor_f64(c.dy, m);
+    if (cand_better(c, o)) c = o;
+  }
+  c.i = __builtin_amdgcn_readfirstlane(c.i);                         // one answer per wave whatever the inputs hold
+  return c;
+}
+
+// ---------------------------------------------------------------- circles ---
+struct Circle { double cx, cy, r2; };
+
+__device__ __forceinline__ double dist2(P2 p, double cx, double cy) {
+  const double dx = p.x - cx, dy = p.y - cy;
+  return dx * dx + dy * dy;
+}
+__device__ __forceinline__ Circle circle1(P2 a) { return Circle{a.x, a.y, 0.0}; }
+__device__ __forceinline__ Circle circle2(P2 a, P2 b) {
+  Circle c;
+  c.cx = a.x + 0.5 * (b.x - a.x);
+  c.cy = a.y + 0.5 * (b.y - a.y);
+  c.r2 = fmax(dist2(a, c.cx, c.cy), dist2(b, c.cx, c.cy));
+  return c;
+}
+__device__ __forceinline__ Circle circle3(P2 a, P2 b, P2 c) {
+  const double bx = b.x - a.x, by = b.y - a.y, cx = c.x - a.x, cy = c.y - a.y;
+  const double d = 2.0 * (bx * cy - by * cx);
+  const double b2 = bx * bx + by * by, c2 = cx * cx + cy * cy;
+  if (d == 0.0) {                                                    // collinear: the circle on the longest of the three sides
+    const double ex = c.x - b.x, ey = c.y - b.y, e2 = ex * ex + ey * ey;
+    if (b2 >= c2 && b2 >= e2) return circle2(a, b);
+    return c2 >= e2 ? circle2(a, c) : circle2(b, c);
+  }
+  Circle o;
+  o.cx = a.x + (cy * b2 - by * c2) / d;
+  o.cy = a.y + (bx * c2 - cx * b2) / d;
+  o.r2 = fmax(dist2(a, o.cx, o.cy), fmax(dist2(b, o.cx, o.cy), dist2(c, o.cx, o.cy)));
+  return o;
+}
+
+// first hull vertex k in [lo, hi) outside the circle, or -1; lo and hi are the same in every lane
+template <class Hull>
+__device__ __forceinline__ int first_outside(const Hull& hull, int lo, int hi, const Circle& c) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const double thr = c.r2 + c.r2 * kSlack;
+  for (int base = lo & ~(kWave - 1); base < hi; base += kWave) {
+    const int k = base + lane;
+    bool out = false;
+    if (k >= lo && k < hi) out = dist2(hull.own(k), c.cx, c.cy) > thr;
+    const unsigned long long m = __ballot(out);
+    if (m) return base + (int)__builtin_ctzll(m);
+  }
+  return -1;
+}
+
+// ---------------------------------------------------------------- one polygon, one wave ---
+// n >= 1 vertices (translated to org); xmin .. ymax are this lane's bounds over the untranslated vertices it owns
+template <class Ring, class Hull>
+__device__ __forceinline__ void polygon_body(const Ring& ring, Hull& hull, int n, P2 org, double xmin, double ymin, double xmax,
+                                             double ymax, double* __restrict__ row) {
+  const int lane = threadIdx.x & (kWave - 1);
+  // 1. shoelace, centroid sums, vertex sums; the start of the march
+  double a2 = 0.0, mx = 0.0, my = 0.0, sx = 0.0, sy = 0.0;
+  int s_i = -1;
+  double s_x = 0.0, s_y = 0.0;
+  for (int base = 0; base < n; base += kWave) {
+    const int i = base + lane;
+    const bool valid = i < n;
+    const int ii = valid ? i : 0;
+    const P2 p = ring.own(ii);
+    const P2 q = ring.at((ii + 1 == n) ? 0 : ii + 1);            // the successor
+    if (valid) {
+      const double cr = p.x * q.y - q.x * p.y;
+      a2 += cr;
+      mx += (p.x + q.x) * cr;
+      my += (p.y + q.y) * cr;
+      sx += p.x;
+      sy += p.y;
+      if (s_i < 0 || p.x < s_x || (p.x == s_x && p.y < s_y)) { s_i = i; s_x = p.x; s_y = p.y; }
+    }
+  }
+  a2 = wave_sum_f64(a2);
+  mx = wave_sum_f64(mx);
+  my = wave_sum_f64(my);
+  sx = wave_sum_f64(sx);
+  sy = wave_sum_f64(sy);
+  xmin = wave_min_f64(xmin);
+  ymin = wave_min_f64(ymin);
+  xmax = wave_max_f64(xmax);
+  ymax = wave_max_f64(ymax);
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {                              // lowest (x, y, index)
+    const int oi = __shfl_xor(s_i, m, kWave);
+    const double ox = shfl_xor_f64(s_x, m), oy = shfl_xor_f64(s_y, m);
+    const bool take = oi >= 0 && (s_i < 0 || ox < s_x || (ox == s_x && (oy < s_y || (oy == s_y && oi < s_i))));
+    if (take) { s_i = oi; s_x = ox; s_y = oy; }
+  }
+  const int start = __builtin_amdgcn_readfirstlane(s_i);
+
+  // 2. the march
+  int h = 0;
+  int cur = start;
+  for (int step = 0; step < n; ++step) {
+    const P2 p = ring.uni(cur);
+    hull.push(h, cur, p);
+    ++h;
+    Cand best{-1, 0.0, 0.0};
+    for (int base = 0; base < n; base += kWave) {
+      const int i = base + lane;
+      if (i < n) {
+        const P2 q = ring.own(i);
+        const Cand c{i, q.x - p.x, q.y - p.y};
+        if ((c.dx != 0.0 || c.dy != 0.0) && cand_better(best, c)) best = c;
+      }
+    }
+    best = wave_best(best);
+    if (best.i < 0 || best.i == start) break;
+    cur = best.i;
+  }
+  hull.publish();
+
+  // 3. hull area, 4. minimum-area rectangle
+  double h2 = 0.0, rect = INFINITY;
+  int rect_k = 0x7fffffff;
+  for (int base = 0; base < h; base += kWave) {
+    const int k = base + lane;
+    const bool valid = k < h;
+    const int kk = valid ? k : 0;
+    const P2 a = hull.own(kk);
+    const P2 b = hull.at((kk + 1 == h) ? 0 : kk + 1);
+    const double ex = b.x - a.x, ey = b.y - a.y;
+    double umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
+    for (int j = 0; j < h; ++j) {
+      const P2 q = hull.uni(j);
+      const double dx = q.x - a.x, dy = q.y - a.y;
+      const double u = dx * ex + dy * ey, v = dy * ex - dx * ey;
+      umin = fmin(umin, u); umax = fmax(umax, u);
+      vmin = fmin(vmin, v); vmax = fmax(vmax, v);
+    }
+    if (valid) {
+      h2 += a.x * b.y - b.x * a.y;
+      const double area = (umax - umin) * (vmax - vmin) / (ex * ex + ey * ey);
+      if (area < rect) { rect = area; rect_k = k; }
+    }
+  }
+  h2 = wave_sum_f64(h2);
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {
+    const double oa = shfl_xor_f64(rect, m);
+    const int ok = __shfl_xor(rect_k, m, kWave);
+    if (oa < rect || (oa == rect && ok < rect_k)) { rect = oa; rect_k = ok; }
+  }
+  if (h < 2) rect = 0.0;
+
+  // 5. smallest enclosing circle of the hull vertices
+  Circle c = circle1(hull.uni(0));
+  for (int i = 1; i < h;) {
+    i = first_outside(hull, i, h, c);
+    if (i < 0) break;
+    const P2 pi = hull.uni(i);
+    c = circle1(pi);
+    for (int j = 0; j < i;) {
+      j = first_outside(hull, j, i, c);
+      if (j < 0) break;
+      const P2 pj = hull.uni(j);
+      c = circle2(pi, pj);
+      for (int k = 0; k < j;) {
+        k = first_outside(hull, k, j, c);
+        if (k < 0) break;
+        c = circle3(pi, pj, hull.uni(k));
+        ++k;
+      }
+      ++j;
+    }
+    ++i;
+  }
+
+  if (lane == 0) {
+    const double nd = (double)n;
+    row[0] = 0.5 * fabs(a2);
+    row[1] = 0.5 * fabs(h2);
+    row[2] = rect;
+    row[3] = (xmax - xmin) * (ymax - ymin);
+    row[4] = sqrt(c.r2);
+    row[5] = org.x + (a2 != 0.0 ? mx / (3.0 * a2) : sx / nd);
+    row[6] = org.y + (a2 != 0.0 ? my / (3.0 * a2) : sy / nd);
+    row[7] = xmin;
+    row[8] = ymin;
+    row[9] = xmax;
+    row[10] = ymax;
+    row[11] = (double)h;
+  }
+}
+
+__device__ __forceinline__ void nan_row(double* __restrict__ row) {
+#pragma unroll
+  for (int c = 0; c < kMorphCols; ++c) row[c] = NAN;
+}
+
+// vertices of ring [b, e) without a closing duplicate (e - b >= 0)
+__device__ __forceinline__ int64_t open_count(const double* __restrict__ xy, int64_t b, int64_t e) {
+  const int64_t n = e - b;
+  if (n < 2) return n;
+  const unsigned long long* u = reinterpret_cast<const unsigned long long*>(xy);
+  return (u[2 * b] == u[2 * (e - 1)] && u[2 * b + 1] == u[2 * (e - 1) + 1]) ? n - 1 : n;
+}
+
+__global__ __launch_bounds__(kMorphThreads) void morph_bin_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
+                                                                  int64_t P, int64_t V, double* __restrict__ props,
+                                                                  int32_t* __restrict__ words, int32_t* __restrict__ list_short,
+                                                                  int32_t* __restrict__ list_long) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t stride = (int64_t)gridDim.x * kMorphThreads;
+  // whole waves iterate together: the ballots below need every lane of a wave in the loop
+  for (int64_t base = (int64_t)blockIdx.x * kMorphThreads + (threadIdx.x & ~(kWave - 1)); base < P; base += stride) {
+    const int64_t p = base + lane;
+    int route = -1;                                                  // 0 short, 1 long, -1 nothing to compute
+    if (p < P) {
+      const int64_t b = off[p], e = off[p + 1];
+      int bad = 0;
+      int64_t n = 0;
+      if (b < 0 || e < b || e > V) bad = SEGGER_MORPH_ERR_OFFSETS;
+      else {
+        n = open_count(xy, b, e);
+        if (n > SEGGER_MORPH_MAX_VERTS) bad = SEGGER_MORPH_ERR_CAP;
+      }
+      if (bad) atomicOr(&words[kWordFlag], bad);
+      if (bad || n == 0) nan_row(props + p * kMorphCols);
+      else route = n > kWave;
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const unsigned long long m = __ballot(route == r);
+      if (m == 0) continue;
+      int pos = 0;
+      if (lane == (int)__builtin_ctzll(m)) pos = atomicAdd(&words[r == 0 ? kWordShort : kWordLong], (int)__popcll(m));
+      pos = __shfl(pos, (int)__builtin_ctzll(m), kWave);
+      if (route == r) (r == 0 ? list_short : list_long)[pos + (int)__popcll(m & ((1ull << lane) - 1))] = (int32_t)p;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kMorphThreads) void morph_short_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
+                                                                    double* __restrict__ props, const int32_t* __restrict__ words,
+                                                                    const int32_t* __restrict__ list) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int count = words[kWordShort];
+  const int n_waves = (int)gridDim.x * kMorphWaves;
+  for (int w = (int)blockIdx.x * kMorphWaves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {             // wave-uniform
+    const int64_t p = list[w];
+    const int64_t b = off[p];
+    const int n = (int)open_count(xy, b, off[p + 1]);                // 1 .. 64: the binning kernel saw the same numbers
+    const double2 first = reinterpret_cast<const double2*>(xy)[b];
+    const double2 mine = lane < n ? reinterpret_cast<const double2*>(xy)[b + lane] : first;
+    RegRing ring{mine.x - first.x, mine.y - first.y};
+    RegHull hull;
+    polygon_body(ring, hull, n, P2{first.x, first.y}, mine.x, mine.y, mine.x, mine.y, props + p * kMorphCols);
+  }
+}
+
+__global__ __launch_bounds__(kWave) void morph_long_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
+                                                           double* __restrict__ props, const int32_t* __restrict__ words,
+                                                           const int32_t* __restrict__ list) {
+  __shared__ double2 pts[SEGGER_MORPH_MAX_VERTS];
+  __shared__ uint16_t hidx[SEGGER_MORPH_MAX_VERTS];
+  const int lane = threadIdx.x;
+  const int count = words[kWordLong];
+  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
+    const int64_t p = list[w];
+    const int64_t b = off[p];
+    const int n = (int)open_count(xy, b, off[p + 1]);                // 65 .. SEGGER_MORPH_MAX_VERTS
+    const double2 first = reinterpret_cast<const double2*>(xy)[b];
+    double xmin = first.x, ymin = first.y, xmax = first.x, ymax = first.y;
+    __syncthreads();                                                 // the previous polygon's reads are done
+    for (int i = lane; i < n; i += kWave) {
+      const double2 v = reinterpret_cast<const double2*>(xy)[b + i];
+      xmin = fmin(xmin, v.x); xmax = fmax(xmax, v.x);
+      ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
+      pts[i] = double2{v.x - first.x, v.y - first.y};
+    }
+    __syncthreads();
+    LdsRing ring{pts};
+    LdsHull hull{pts, hidx};
+    polygon_body(ring, hull, n, P2{first.x, first.y}, xmin, ymin, xmax, ymax, props + p * kMorphCols);
+  }
+}
+
+struct MorphLayout { size_t words, list_short, list_long, total; };
+
+MorphLayout morph_layout(int64_t P) {
+  Carver c;
+  MorphLayout l;
+  l.words = c.take(256);
+  l.list_short = c.take((size_t)P * sizeof(int32_t));
+  l.list_long = c.take((size_t)P * sizeof(int32_t));
+  l.total = c.total();
+  return l;
+}
+
+}  // namespace
+}  // namespace segger
+
+using namespace segger;
+
+extern "C" int64_t segger_morphology_workspace_bytes(int64_t n_polygons) {
+  if (n_polygons < 0 || n_polygons >= 0x7fffffffLL) {
+    set_error("segger_morphology_workspace_bytes: n_polygons = %lld outside 0 .. 2^31 - 2", (long long)n_polygons);
+    return SEGGER_EINVAL;
+  }
+  return (int64_t)morph_layout(n_polygons).total;
+}
+
+extern "C" int segger_polygon_props(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                                    double* props, void* workspace, int64_t workspace_bytes, segger_stream_t stream_) {
+  const char* who = "segger_polygon_props";
+  hipStream_t stream = (hipStream_t)stream_;
+  SEGGER_REQUIRE(n_polygons >= 0 && n_vertices >= 0, "%s: negative n_polygons or n_vertices", who);
+  SEGGER_REQUIRE(n_polygons < 0x7fffffffLL, "%s: 2^31 - 1 polygons or more", who);
+  SEGGER_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", who);
+  if (n_polygons == 0) return SEGGER_OK;
+  SEGGER_REQUIRE(ring_offsets && props && workspace, "%s: NULL pointer", who);
+  SEGGER_REQUIRE(xy || n_vertices == 0, "%s: NULL xy with n_vertices > 0", who);
+  SEGGER_REQUIRE(is_aligned(ring_offsets, 8) && is_aligned(props, 8), "%s: ring_offsets and props must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(xy, 16), "%s: xy must be 16-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  const MorphLayout l = morph_layout(n_polygons);
+  SEGGER_REQUIRE((size_t)workspace_bytes >= l.total, "%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, l.total);
+  int32_t* words = at<int32_t>(workspace, l.words);
+  int32_t* list_short = at<int32_t>(workspace, l.list_short);
+  int32_t* list_long = at<int32_t>(workspace, l.list_long);
+  SEGGER_HIP(hipMemsetAsync(words, 0, 256, stream));
+  const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
+  hipLaunchKernelGGL(morph_bin_kernel, dim3(grid_stride_blocks(n_polygons, kMorphThreads, (int64_t)cus * 8)), dim3(kMorphThreads), 0,
+                     stream, ring_offsets, xy, n_polygons, n_vertices, props, words, list_short, list_long);
+  SEGGER_LAUNCH_CHECK("morph_bin_kernel");
+  hipLaunchKernelGGL(morph_short_kernel, dim3(grid_stride_blocks(n_polygons, kMorphWaves, (int64_t)cus * 8)), dim3(kMorphThreads), 0,
+                     stream, ring_offsets, xy, props, words, list_short);
+  SEGGER_LAUNCH_CHECK("morph_short_kernel");
+  hipLaunchKernelGGL(morph_long_kernel, dim3(grid_stride_blocks(n_polygons, 1, (int64_t)cus * 2)), dim3(kWave), 0, stream,
+                     ring_offsets, xy, props, words, list_long);
+  SEGGER_LAUNCH_CHECK("morph_long_kernel");
+  return SEGGER_OK;
+}

@@ -13,15 +13,16 @@ built.  Everything around the two kernels -- integer sums, the median, ``torch.l
 is torch on the device.  There is no CPU path.
 
 The phenograph clustering (kNN -> Jaccard -> Louvain) is :mod:`segger_amd.phenograph`: cluster labels are computed on
-the device, by a deterministic Louvain that is cuGraph's in objective, not in move order.  Not built: morphology features;
-sklearn's randomized solver, which sklearn's ``auto`` policy picks when ``G > 500`` -- the exact PCA is computed for
+the device, by a deterministic Louvain that is cuGraph's in objective, not in move order.  The morphology features of the
+boundary polygons (``X_morphology``, the other ``cells_representation``) are :mod:`segger_amd.morphology`;
+``anndata_features`` adds them when it is given the rings.  Not built: sklearn's randomized solver, which sklearn's ``auto`` policy picks when ``G > 500`` -- the exact PCA is computed for
 every ``G``; cuML's own sign convention for ``X_pca`` -- sklearn's is used for both embeddings.  scanpy's
 ``normalize_total`` casts integer counts to float32 first; here the normalised values are float64 throughout.
 """
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -185,13 +186,18 @@ def deterministic_sums():
 def anndata_features(expr: Dict[str, Tensor], embedding_size: int = 128, cells_min_counts: int = 10, genes_min_counts: int = 100,
                      cells_clusters_n_neighbors: int = 10, cells_clusters_resolution: float = 2.0,
                      genes_clusters_n_neighbors: int = 5, genes_clusters_resolution: float = 2.0,
-                     out_dtype: torch.dtype = torch.float32) -> Dict[str, Tensor]:
+                     out_dtype: torch.dtype = torch.float32,
+                     boundaries: Optional[Tuple[Tensor, Tensor]] = None) -> Dict[str, Tensor]:
     """Everything :func:`expression_features` returns plus the reference's clusters (``anndata.py:261-291``, the defaults
     of ``data_module.py:138-144``): ``cell_clusters`` int64 over the cells -- the phenograph of ``X_pca`` of the FILTERED
     cells with ``min_size=100``, -1 for a removed cell; ``gene_clusters`` int64 over the kept genes -- the phenograph of
     ``X_corr`` with ``min_size=-1``; ``cell_cluster_similarities`` and ``gene_cluster_similarities`` from
     :func:`cluster_cosine_similarity` (-1 is a cluster like any other there, as in the reference), summed in a fixed order
-    (:func:`deterministic_sums`): the whole result has the same bits from call to call."""
+    (:func:`deterministic_sums`): the whole result has the same bits from call to call.
+
+    ``boundaries = (ring_offsets, xy)``, the polygons of the ``expr`` cells in the order of its rows, adds ``X_morphology``
+    ``[n_cells_present, 4]`` ``out_dtype`` (:func:`segger_amd.morphology.morphology_features`, the reference's
+    ``anndata.py:296-311``); without it the result is what it was, key for key."""
     from .phenograph import phenograph
     out = expression_features(expr, embedding_size, cells_min_counts, genes_min_counts, out_dtype)
     filtered, X_pca, X_corr = out["filtered"], out["X_pca"], out["X_corr"]
@@ -202,4 +208,10 @@ def anndata_features(expr: Dict[str, Tensor], embedding_size: int = 128, cells_m
     with deterministic_sums():                                        # the same tables from call to call
         out["cell_cluster_similarities"] = cluster_cosine_similarity(X_pca, cell_clusters)
         out["gene_cluster_similarities"] = cluster_cosine_similarity(X_corr, out["gene_clusters"])
+    if boundaries is not None:
+        from .morphology import morphology_features
+        X_morphology = morphology_features(boundaries[0], boundaries[1], out_dtype)
+        if int(X_morphology.shape[0]) != int(filtered.numel()):
+            raise ValueError(f"anndata_features: {int(X_morphology.shape[0])} boundary rings for {int(filtered.numel())} cells")
+        out["X_morphology"] = X_morphology
     return out

@@ -11,6 +11,8 @@ and cached on the batch object, so the 4 layers x (forward + backward) reuse it.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import weakref
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -343,3 +345,23 @@ def edge_graph(cache: Optional[dict], key, edge_index: Tensor, n_src: int, n_dst
             g = build_edge_graph(edge_index, n_src, n_dst, known_unique=unique, **kw)
         cache[k] = g
     return g
+
+
+@contextlib.contextmanager
+def graph_capture(graph: "torch.cuda.CUDAGraph", **kw):
+    """``torch.cuda.graph(graph, **kw)`` with Python's garbage collector kept out of the capture.  While a stream is being
+    captured (error mode ``global``) a ``hipFree``, a ``hipGraphExecDestroy`` or an event query from ANY thread is an
+    error, and an automatic collection that happens to fall inside the capture -- on the autograd thread as soon as any
+    allocation crosses the collector's threshold -- runs the destructors of whatever dead cycle holds device objects (an
+    earlier trainer's ``CUDAGraph`` and its pool, for one); the error is raised inside a destructor and ends the process
+    with an abort.  torch >= 2.9 no longer collects on entering ``torch.cuda.graph`` (``force_cudagraph_gc``), so: collect
+    once before the capture, and no automatic collection until it has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()

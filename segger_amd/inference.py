@@ -24,7 +24,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .graph import EdgeCSR, EdgeGraph, batch_cache, build_edge_graph, edge_graph, padded_view_segments
+from .graph import EdgeCSR, EdgeGraph, batch_cache, build_edge_graph, edge_graph, graph_capture, padded_view_segments
 from .hetero import HeteroBatch, TX_BD, TX_NB_BD, TX_TX
 
 _EDGE_TYPES = (TX_TX, TX_BD, TX_NB_BD)
@@ -149,7 +149,7 @@ class GraphedPredictor:
                 self._run()                              # warm-up on a side stream (lazy inits, allocator)
             torch.cuda.current_stream().wait_stream(s)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with graph_capture(self.graph):
                 self._run()
         self.graph.replay()
 

@@ -76,7 +76,8 @@ def transcripts_graph(pos: Tensor, max_k: int, max_dist: float = math.inf) -> Te
 
 def prediction_graph_uniform(tx_pos: Tensor, bd_pos: Tensor, max_k: int, max_dist: float = math.inf) -> Tensor:
     """``setup_prediction_graph(mode='uniform')`` (``neighbors.py:213-221``): kNN from boundary centroids
-    (queries) into the transcripts (points); row 0 = query (boundary) id, row 1 = transcript id."""
+    (queries) into the transcripts (points); row 0 = query (boundary) id, row 1 = transcript id.  For polygon boundaries
+    ``segger_amd.morphology.polygon_props(ring_offsets, xy)["centroid"]`` is the reference's ``bd.geometry.centroid``."""
     nbr, _ = knn_grid(tx_pos, max_k, max_dist, query=bd_pos)
     ei, _ = knn_to_edge_index(nbr, padding_value=int(tx_pos.shape[0]))
     return ei

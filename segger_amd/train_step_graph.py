@@ -42,7 +42,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .graph import EdgeCSR, EdgeGraph, batch_cache, edge_graph, padded_view_segments
+from .graph import EdgeCSR, EdgeGraph, batch_cache, edge_graph, graph_capture, padded_view_segments
 from .hetero import TX_BD, TX_TX
 from .ist_encoder import StagedInputs, rows_by_gene
 
@@ -460,15 +460,15 @@ class GraphedTrainStep:
             self.graph = torch.cuda.CUDAGraph()
             with ops.pack_scope(aliases):                     # ... of this step's own packs only
                 if not self.split:
-                    with torch.cuda.graph(self.graph):
+                    with graph_capture(self.graph):
                         self._run()
                 else:                                         # forward + backward (+ pack) | <exchange> | Adam
-                    with torch.cuda.graph(self.graph):
+                    with graph_capture(self.graph):
                         self._run_grads()
                         if self.grad_bucket is not None:      # gradients -> the bucket's flat buffer; .grad = its slices
                             self.grad_bucket.pack()
                     self.graph_opt = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph_opt, pool=self.graph.pool()):
+                    with graph_capture(self.graph_opt, pool=self.graph.pool()):
                         self._opt_step()
             # the graph holds raw pointers into these buffers: they must outlive it whatever happens to the cache
             self._pack_refs = [(pk, pk.w, pk.b, pk._wt) for pk in ops.packs_of(aliases)]
