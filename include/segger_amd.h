@@ -1415,6 +1415,92 @@ int64_t segger_morphology_workspace_bytes(int64_t n_polygons);
 int segger_polygon_props(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
                          double* props /* [P, 12] */, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Points in buffered polygons: every (point, polygon) pair for which the point lies in the polygon grown by a distance
+ * d >= 0 of its own -- the reference's points_in_polygons (src/segger/geometry/query.py, a cuSpatial quadtree join) over
+ * polygons.buffer(d), which builds the ("tx", "neighbors", "bd") prediction graph of the default mode
+ * (src/segger/data/utils/neighbors.py:223-238).  The kernels behind segger_amd.geometry.  csrc/polygon_join.hip.  Purely
+ * additive: three new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * The predicate.  For a point t, a ring P (as segger_polygon_props takes it: a CSR of single exterior rings in fp64, either
+ *   orientation, a closing duplicate of the first vertex dropped) and a distance d >= 0:
+ *     parity(t, P)  the crossing-number test with the half-open rule: an edge (a, b) counts when a.y <= t.y < b.y or
+ *                   b.y <= t.y < a.y, and the crossing lies strictly to the right of t;
+ *     dist2(t, P)   the smallest squared distance from t to a closed edge segment of the ring;
+ *     SEGGER_PJOIN_CONTAINS    dist2 < d d || (parity && dist2 > 0)   the open set: a point on the ring itself is out when
+ *                              d == 0 and in when d > 0;
+ *     SEGGER_PJOIN_INTERSECTS  dist2 <= d d || parity                 the closed set (what the reference's
+ *                              ISTPreprocessor.assign_transcripts_to_boundaries uses through sjoin).
+ *   A ring with fewer than 3 vertices (after the closing duplicate is dropped) matches nothing under either predicate.
+ *   This is the EXACT offset of the polygon, its Minkowski sum with a disc of radius d.  GEOS, through which the
+ *   reference's buffer() goes, replaces each round corner by a polyline (geopandas: 16 segments per quarter circle), so
+ *   the two sets differ in slivers at convex corners, at most d (1 - cos(pi / 64)) ~ 0.0012 d wide.  UNVERIFIED: neither
+ *   shapely nor GEOS was available where this was written; the arc vertices of GEOS are not reproduced.
+ *
+ * Arithmetic:  fp64 throughout, the point and the vertices translated to the ring's first vertex before any product (slide
+ *   coordinates are 10^4 .. 10^5, a cell is ~10 across), FMA contraction off.  Per edge (a, b):  e = b - a, w = t - a,
+ *   cr = e.x w.y - e.y w.x, dot = w.x e.x + w.y e.y, len2 = e.x e.x + e.y e.y;  the edge counts for the parity when
+ *   (a.y <= t.y && !(b.y <= t.y) && cr > 0) or (!(a.y <= t.y) && b.y <= t.y && cr < 0);  its squared distance is |w|^2 when
+ *   dot <= 0 or len2 == 0, |t - b|^2 when dot >= len2, and cr cr / len2 otherwise;  dist2 is the minimum over the edges.
+ *   With coordinates that are exact after the translation, cr is exact: the parity and "on the ring" (dist2 == 0) are.
+ *
+ * The points are binned into a uniform grid the caller describes (origin x0, y0, cell side, nx x ny cells; points outside
+ *   are clamped into the border cells) by a stable keys sort (key = cell << 32 | point id); the kernels read a cell-ordered
+ *   fp64 copy of the coordinates and the ids.  One wave owns one polygon: n <= 64 keeps one vertex per lane and broadcasts
+ *   the edges across the wave; 64 < n <= SEGGER_MORPH_MAX_VERTS stages the ring in LDS; the polygons are binned by route on
+ *   the device (one integer atomic per wave and route).  The wave walks the cells that overlap the ring's bounds grown by
+ *   d (1 + 2^-20) + 2^-40 max|bound| (the margin covers the rounding; the cell range is clamped to the grid), 64 points at a
+ *   time.  The grid decides the speed and nothing else: the pairs are the same for every grid.
+ *
+ * Two calls:
+ *   segger_polygon_join_count  bins the points, counts the matches of every polygon and scans the counts on the device:
+ *       pair_offsets [n_polygons + 1] int64, pair_offsets[p + 1] - pair_offsets[p] = the matches of polygon p and
+ *       pair_offsets[n_polygons] their total.
+ *   segger_polygon_join_fill   the same traversal again, with the same inputs and the workspace as the count call left
+ *       it: writes the point ids of polygon p to point_index_out[pair_offsets[p] .. pair_offsets[p + 1]).  The slot of a
+ *       pair is the polygon's offset + the number of matches before it in the traversal (ballot + prefix popcount), not
+ *       an atomic: within a polygon the ids come in (cell row, cell, point id) order, the same from call to call.  Nothing
+ *       is written at or beyond capacity entries, nor outside the polygon's own range.
+ *   No floating-point atomics anywhere.
+ *
+ * Errors found on the device, without a synchronisation (the int32 at byte 0 of the workspace, 0 = none, valid once the
+ *   stream has run; int32 words 1 and 2 are the polygons that took the register and the LDS route):
+ *     SEGGER_PJOIN_ERR_OFFSETS  ring_offsets[p] < 0, ring_offsets[p + 1] < ring_offsets[p] or ring_offsets[p + 1] > n_vertices;
+ *     SEGGER_PJOIN_ERR_CAP      a ring of more than SEGGER_MORPH_MAX_VERTS vertices (the Python wrapper refuses it before
+ *                               the call, naming the polygon, as it does for segger_polygon_props);
+ *     SEGGER_PJOIN_ERR_BUFFER   a negative, infinite or NaN buffer[p];
+ *     SEGGER_PJOIN_ERR_FILL     the fill found other counts than pair_offsets holds, or more pairs than capacity.
+ *   A polygon with one of the first three matches nothing; nothing is read or written out of bounds for any of them.
+ *
+ * Workspace: segger_polygon_join_workspace_bytes(n_points, n_polygons, nx, ny) = 256 + up(8 N) + up(16 N) +
+ *   up(4 (nx ny + 1)) + 2 up(4 n_polygons) + the radix sort's storage, with N = max(n_points, 1) and up() rounding up to
+ *   256; the sort's storage depends on N and nx ny only.  256-byte aligned.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative n_points, n_polygons, n_vertices,
+ *   workspace_bytes or capacity, 2^31 - 1 points or polygons or more, nx or ny < 1 or nx ny >= 2^31 - 1, a cell side that is
+ *   not positive and finite, an origin that is not finite, an unknown predicate, and for n_points > 0 and n_polygons > 0 a
+ *   NULL pointer (buffer may be NULL = no buffer; xy may be NULL when n_vertices = 0), a misaligned pointer (points and xy:
+ *   16 bytes), a workspace below segger_polygon_join_workspace_bytes (which itself returns the negative code for sizes out
+ *   of range).  n_points = 0 or n_polygons = 0 returns SEGGER_OK without touching a pointer or the device: pair_offsets
+ *   is NOT written, the caller knows it is all zeros.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_PJOIN_CONTAINS 0
+#define SEGGER_PJOIN_INTERSECTS 1
+#define SEGGER_PJOIN_ERR_OFFSETS 1
+#define SEGGER_PJOIN_ERR_CAP 2
+#define SEGGER_PJOIN_ERR_BUFFER 4
+#define SEGGER_PJOIN_ERR_FILL 8
+int64_t segger_polygon_join_workspace_bytes(int64_t n_points, int64_t n_polygons, int32_t nx, int32_t ny);
+int segger_polygon_join_count(const double* points /* [N, 2] */, int64_t n_points, const int64_t* ring_offsets,
+                              const double* xy, int64_t n_polygons, int64_t n_vertices,
+                              const double* buffer /* [P] fp64 or NULL = 0 */, int32_t predicate, double x0, double y0,
+                              double cell, int32_t nx, int32_t ny, int64_t* pair_offsets /* [P + 1] */, void* workspace,
+                              int64_t workspace_bytes, segger_stream_t stream);
+int segger_polygon_join_fill(const double* points, int64_t n_points, const int64_t* ring_offsets, const double* xy,
+                             int64_t n_polygons, int64_t n_vertices, const double* buffer, int32_t predicate, double x0,
+                             double y0, double cell, int32_t nx, int32_t ny, const int64_t* pair_offsets,
+                             int64_t* point_index_out, int64_t capacity, void* workspace, int64_t workspace_bytes,
+                             segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

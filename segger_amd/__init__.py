@@ -16,5 +16,8 @@ from . import validation  # noqa: F401
 from .validation import neighbor_frequencies, reference_table, contamination_posterior, calculate_contamination, contamination_flow  # noqa: F401
 from . import morphology  # noqa: F401
 from .morphology import polygon_props, morphology_features, rings_from_padded  # noqa: F401
+from . import geometry  # noqa: F401
+from .geometry import points_in_polygons  # noqa: F401
+from .neighbors import prediction_graph_shape  # noqa: F401
 
 __version__ = "0.1.0"

@@ -22,6 +22,8 @@ FEATURES_MAX_COLS, FEATURES_MAX_K = 32768, 256
 KNN_BF_MAX_D, KNN_BF_MAX_K, KNN_BF_MAX_SLABS = 256, 64, 32                  # SEGGER_KNN_BF_*: the range of segger_knn_bruteforce
 CONTAM_MAX_TYPES, CONTAM_MAX_K, CONTAM_MAX_REF_GENES, CONTAM_LDS_BYTES = 256, 64, 32768, 65536   # SEGGER_CONTAM_*
 MORPH_MAX_VERTS, MORPH_COLS, MORPH_ERR_OFFSETS, MORPH_ERR_CAP = 4096, 12, 1, 2                       # SEGGER_MORPH_*
+PJOIN_CONTAINS, PJOIN_INTERSECTS = 0, 1                                                                # SEGGER_PJOIN_*
+PJOIN_ERR_OFFSETS, PJOIN_ERR_CAP, PJOIN_ERR_BUFFER, PJOIN_ERR_FILL = 1, 2, 4, 8
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -360,6 +362,11 @@ EXPORTS = {
                                                  vp, vp, vp, vp, vp, vp, vp, vp]),
     "segger_morphology_workspace_bytes": (C.c_int64, [C.c_int64]),
     "segger_polygon_props": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]),
+    "segger_polygon_join_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "segger_polygon_join_count": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_double, C.c_double,
+                                            C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]),
+    "segger_polygon_join_fill": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_double, C.c_double,
+                                           C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

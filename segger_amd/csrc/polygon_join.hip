@@ -1,0 +1,475 @@
+// segger_polygon_join_count / _fill: every (point, polygon) pair for which the point lies in the polygon grown by a
+// per-polygon distance d -- the reference's points_in_polygons (src/segger/geometry/query.py, a cuSpatial quadtree join)
+// over polygons.buffer(d) (src/segger/data/utils/neighbors.py:223-238).  include/segger_amd.h has the contract and the
+// predicate; this is the exact offset of the ring (Minkowski sum with a disc), not GEOS's polyline approximation of it.
+//
+// Six kernels and one radix sort on one stream, no host synchronisation:
+//   pjoin_keys_kernel   one thread per point: key = cell << 32 | point id (cells clamped to the nx x ny grid);
+//   (rocprim keys sort: stable by construction, the id is part of the key)
+//   pjoin_cells_kernel  one thread per sorted position: cell_start[] and the cell-ordered float64 copy of the points (the
+//                       ids stay in the low words of the sorted keys);
+//   pjoin_bin_kernel    one thread per polygon: checks its two offsets and its distance, drops a closing duplicate vertex,
+//                       zeroes its count and appends it to the list of its route (one integer atomic per wave and route);
+//   pjoin_short_kernel  n <= 64: one wave per polygon, one vertex per lane, edges broadcast by readlane, no LDS;
+//   pjoin_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the translated ring
+//                       staged in LDS (64 KB), every lane reading the same edge (an LDS broadcast);
+//   pjoin_scan_kernel   one workgroup: counts -> pair_offsets, in place.
+// The two polygon kernels are templates on "count" / "fill" over ONE traversal (polygon_body): the wave walks the rows of
+// grid cells that overlap the ring's bounds grown by d and a rounding margin, each row one contiguous span of the
+// cell-ordered points, 64 points at a time, one point per lane, and loops over the edges accumulating the crossing parity
+// and the smallest squared distance.  A match's slot is the polygon's offset + the matches before it in the traversal (a
+// running count + ballot + prefix popcount): no atomic decides a slot, so the list of a polygon is in (cell row, cell,
+// point id) order whatever the scheduling, and the same call gives the same bytes.
+//
+// Arithmetic: float64, the point and the vertices translated to the ring's first vertex, FMA contraction off, so with
+// coordinates that are exactly representable after the translation the cross product, and with it the parity and "on the
+// ring" (dist2 == 0), are exact.  Per edge (a, b) and point t:  e = b - a, w = t - a, cr = e.x w.y - e.y w.x,
+// dot = w.e, len2 = e.e;  dist2 = |w|^2 if dot <= 0 or len2 == 0, |t - b|^2 if dot >= len2, cr cr / len2 otherwise.
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no scratch in any kernel of this unit (the sort is
+// instantiated with NoScratchSortConfig); pjoin_long_kernel holds 65536 B of LDS, two single-wave workgroups per CU.
+#include <math.h>
+
+#include "common.h"
+#include "post_common.h"
+#include "sort_config.h"
+
+#pragma clang fp contract(off)
+
+namespace segger {
+namespace {
+
+constexpr int kPjThreads = 256;
+constexpr int kPjWaves = kPjThreads / kWave;
+constexpr int kScanThreads = 1024;
+constexpr int kWordFlag = 0, kWordShort = 1, kWordLong = 2;          // int32 words at the start of the workspace
+
+struct PjGrid { double x0, y0, inv_cell; int nx, ny; };
+
+// the cell of a coordinate, clamped into 0 .. n - 1 (NaN -> 0): monotone in v, which is what the walk relies on
+__device__ __forceinline__ int cell_of(double v, double origin, double inv_cell, int n) {
+  const double c = floor((v - origin) * inv_cell);
+  return (int)fmin(fmax(c, 0.0), (double)(n - 1));
+}
+
+// lane is the same in every lane of the wave
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  return __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(v), mask));
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmin(v, shfl_xor_f64(v, m));
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmax(v, shfl_xor_f64(v, m));
+  return v;
+}
+
+struct P2 { double x, y; };
+
+// uni(i): vertex i, i the same in every lane
+struct RegRing {
+  double x, y;                                                       // vertex `lane`, translated
+  __device__ __forceinline__ P2 uni(int i) const { return P2{readlane_f64(x, i), readlane_f64(y, i)}; }
+};
+struct LdsRing {
+  const double2* pts;
+  __device__ __forceinline__ P2 uni(int i) const { const double2 p = pts[i]; return P2{p.x, p.y}; }
+};
+
+// ---------------------------------------------------------------- the points ---
+__global__ __launch_bounds__(kPjThreads) void pjoin_keys_kernel(const double* __restrict__ pts, int64_t n, PjGrid g,
+                                                                unsigned long long* __restrict__ keys) {
+  const int64_t stride = (int64_t)gridDim.x * kPjThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kPjThreads + threadIdx.x; i < n; i += stride) {
+    const double2 p = reinterpret_cast<const double2*>(pts)[i];
+    const int cx = cell_of(p.x, g.x0, g.inv_cell, g.nx), cy = cell_of(p.y, g.y0, g.inv_cell, g.ny);
+    keys[i] = ((unsigned long long)((int64_t)cy * g.nx + cx) << 32) | (unsigned long long)i;
+  }
+}
+
+__global__ __launch_bounds__(kPjThreads) void pjoin_cells_kernel(const unsigned long long* __restrict__ keys_sorted,
+                                                                 const double* __restrict__ pts, int64_t n, int64_t n_cells,
+                                                                 int32_t* __restrict__ cell_start, double2* __restrict__ sorted_pts) {
+  const int64_t stride = (int64_t)gridDim.x * kPjThreads;
+  for (int64_t s = (int64_t)blockIdx.x * kPjThreads + threadIdx.x; s < n; s += stride) {
+    const unsigned long long key = keys_sorted[s];
+    sorted_pts[s] = reinterpret_cast<const double2*>(pts)[key & 0xffffffffull];
+    const int64_t k = (int64_t)(key >> 32);                          // < n_cells: the keys kernel clamped it
+    const int64_t kprev = s > 0 ? (int64_t)(keys_sorted[s - 1] >> 32) : -1;
+    for (int64_t c = kprev + 1; c <= k; ++c) cell_start[c] = (int32_t)s;
+    if (s == n - 1)
+      for (int64_t c = k + 1; c <= n_cells; ++c) cell_start[c] = (int32_t)n;
+  }
+}
+
+// ---------------------------------------------------------------- the polygons ---
+// vertices of ring [b, e) without a closing duplicate (e - b >= 0)
+__device__ __forceinline__ int64_t open_count(const double* __restrict__ xy, int64_t b, int64_t e) {
+  const int64_t n = e - b;
+  if (n < 2) return n;
+  const unsigned long long* u = reinterpret_cast<const unsigned long long*>(xy);
+  return (u[2 * b] == u[2 * (e - 1)] && u[2 * b + 1] == u[2 * (e - 1) + 1]) ? n - 1 : n;
+}
+
+__global__ __launch_bounds__(kPjThreads) void pjoin_bin_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
+                                                               const double* __restrict__ buffer, int64_t P, int64_t V,
+                                                               int64_t* __restrict__ pair_offsets, int32_t* __restrict__ words,
+                                                               int32_t* __restrict__ list_short, int32_t* __restrict__ list_long) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t stride = (int64_t)gridDim.x * kPjThreads;
+  // whole waves iterate together: the ballots below need every lane of a wave in the loop
+  for (int64_t base = (int64_t)blockIdx.x * kPjThreads + (threadIdx.x & ~(kWave - 1)); base < P; base += stride) {
+    const int64_t p = base + lane;
+    int route = -1;                                                  // 0 short, 1 long, -1 matches nothing
+    if (p < P) {
+      const int64_t b = off[p], e = off[p + 1];
+      int bad = 0;
+      int64_t n = 0;
+      if (b < 0 || e < b || e > V) bad = SEGGER_PJOIN_ERR_OFFSETS;
+      else {
+        n = open_count(xy, b, e);
+        if (n > SEGGER_MORPH_MAX_VERTS) bad = SEGGER_PJOIN_ERR_CAP;
+      }
+      if (buffer && !(buffer[p] >= 0.0 && buffer[p] < INFINITY)) bad |= SEGGER_PJOIN_ERR_BUFFER;
+      if (bad) atomicOr(&words[kWordFlag], bad);
+      pair_offsets[p + 1] = 0;                                       // the count; the polygon kernels overwrite theirs
+      if (p == 0) pair_offsets[0] = 0;
+      if (!bad && n >= 3) route = n > kWave;
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const unsigned long long m = __ballot(route == r);
+      if (m == 0) continue;
+      int pos = 0;
+      if (lane == (int)__builtin_ctzll(m)) pos = atomicAdd(&words[r == 0 ? kWordShort : kWordLong], (int)__popcll(m));
+      pos = __shfl(pos, (int)__builtin_ctzll(m), kWave);
+      if (route == r) (r == 0 ? list_short : list_long)[pos + (int)__popcll(m & ((1ull << lane) - 1))] = (int32_t)p;
+    }
+  }
+}
+
+struct JoinArgs {
+  const int64_t* off;
+  const double* xy;
+  const double* buffer;                                              // [P] or NULL = 0
+  int predicate;
+  PjGrid g;
+  const int32_t* cell_start;
+  const double2* pts;                                                // cell-ordered
+  const unsigned long long* keys;                                    // cell-ordered; the low word is the point id
+  int64_t* pair_offsets;                                             // count: [p + 1] is written; fill: read
+  int64_t* out;                                                      // fill: the point ids
+  int64_t capacity;
+  int32_t* words;
+};
+
+// One polygon, one wave, every lane active.  n >= 3 vertices translated to org; xmin .. ymax are the ring's bounds on the
+// coordinates as given (the same in every lane).
+template <bool kFill, class Ring>
+__device__ __forceinline__ void polygon_body(const Ring& ring, int n, P2 org, double xmin, double ymin, double xmax, double ymax,
+                                             int64_t p, const JoinArgs& a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const double d = a.buffer ? a.buffer[p] : 0.0;
+  const double dd = d * d;
+  // Every matching point has dist2 <= d^2 or lies inside the ring, so in exact arithmetic it is within the bounds grown by
+  // d.  The margin covers the rounding of dist2, of the translation and of the subtraction below (a few ulp of the
+  // coordinates: 2^-40 of them is four thousand ulp); cell_of is monotone, so a point inside the grown bounds is in a
+  // walked cell whatever the grid, and the result does not depend on the grid.
+  const double m = d + d * 0x1p-20 + 0x1p-40 * fmax(fmax(fabs(xmin), fabs(xmax)), fmax(fabs(ymin), fabs(ymax)));
+  // (readfirstlane: the values are the same in every lane already; it tells the compiler so, and the loops become scalar)
+  const int cx0 = __builtin_amdgcn_readfirstlane(cell_of(xmin - m, a.g.x0, a.g.inv_cell, a.g.nx));
+  const int cx1 = __builtin_amdgcn_readfirstlane(cell_of(xmax + m, a.g.x0, a.g.inv_cell, a.g.nx));
+  const int cy0 = __builtin_amdgcn_readfirstlane(cell_of(ymin - m, a.g.y0, a.g.inv_cell, a.g.ny));
+  const int cy1 = __builtin_amdgcn_readfirstlane(cell_of(ymax + m, a.g.y0, a.g.inv_cell, a.g.ny));
+  int64_t begin = 0, end = 0;
+  if (kFill) {
+    begin = a.pair_offsets[p];
+    end = a.pair_offsets[p + 1];
+    if (end > a.capacity) end = a.capacity;                          // nothing is ever written at or beyond either
+  }
+  int64_t found = 0;
+  for (int cy = cy0; cy <= cy1; ++cy) {
+    const int64_t row = (int64_t)cy * a.g.nx;
+    const int s0 = __builtin_amdgcn_readfirstlane(a.cell_start[row + cx0]);
+    const int s1 = __builtin_amdgcn_readfirstlane(a.cell_start[row + cx1 + 1]);
+    for (int sb = s0; sb < s1; sb += kWave) {
+      const int s = sb + lane;
+      const bool valid = s < s1;
+      const double2 t = a.pts[valid ? s : s0];
+      const double px = t.x - org.x, py = t.y - org.y;
+      bool inside = false;
+      double best = INFINITY;
+      P2 va = ring.uni(0);
+      for (int j = 0; j < n; ++j) {
+        const P2 vb = ring.uni(j + 1 == n ? 0 : j + 1);
+        const double ex = vb.x - va.x, ey = vb.y - va.y;
+        const double wx = px - va.x, wy = py - va.y;
+        const double cr = ex * wy - ey * wx;
+        const double dot = wx * ex + wy * ey;
+        const double len2 = ex * ex + ey * ey;
+        const bool a_below = va.y <= py, b_below = vb.y <= py;       // the half-open rule
+        inside ^= (a_below && !b_below && cr > 0.0) || (!a_below && b_below && cr < 0.0);
+        double d2;
+        if (dot <= 0.0 || len2 == 0.0) d2 = wx * wx + wy * wy;
+        else if (dot >= len2) {
+          const double ux = px - vb.x, uy = py - vb.y;
+          d2 = ux * ux + uy * uy;
+        } else d2 = cr * cr / len2;
+        best = fmin(best, d2);
+        va = vb;
+      }
+      const bool hit = valid && (a.predicate == SEGGER_PJOIN_CONTAINS ? (best < dd || (inside && best > 0.0))
+                                                                      : (best <= dd || inside));
+      const unsigned long long mask = __ballot(hit);
+      if (kFill && hit) {
+        const int64_t slot = begin + found + (int64_t)__popcll(mask & ((1ull << lane) - 1));
+        if (slot >= 0 && slot < end) a.out[slot] = (int64_t)(a.keys[s] & 0xffffffffull);
+      }
+      found += (int64_t)__popcll(mask);
+    }
+  }
+  if (lane == 0) {
+    if (!kFill) a.pair_offsets[p + 1] = found;
+    else if (begin + found != a.pair_offsets[p + 1] || begin + found > a.capacity) atomicOr(&a.words[kWordFlag], SEGGER_PJOIN_ERR_FILL);
+  }
+}
+
+template <bool kFill>
+__global__ __launch_bounds__(kPjThreads) void pjoin_short_kernel(JoinArgs a, const int32_t* __restrict__ list) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int count = a.words[kWordShort];
+  const int n_waves = (int)gridDim.x * kPjWaves;
+  for (int w = (int)blockIdx.x * kPjWaves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {                // wave-uniform
+    const int64_t p = list[w];
+    const int64_t b = a.off[p];
+    const int n = __builtin_amdgcn_readfirstlane((int)open_count(a.xy, b, a.off[p + 1]));    // 3 .. 64, as the binning kernel saw
+    const double2 first = reinterpret_cast<const double2*>(a.xy)[b];
+    const double2 mine = lane < n ? reinterpret_cast<const double2*>(a.xy)[b + lane] : first;
+    RegRing ring{mine.x - first.x, mine.y - first.y};
+    polygon_body<kFill>(ring, n, P2{first.x, first.y}, wave_min_f64(mine.x), wave_min_f64(mine.y), wave_max_f64(mine.x),
+                        wave_max_f64(mine.y), p, a);
+  }
+}
+
+template <bool kFill>
+__global__ __launch_bounds__(kWave) void pjoin_long_kernel(JoinArgs a, const int32_t* __restrict__ list) {
+  __shared__ double2 pts[SEGGER_MORPH_MAX_VERTS];
+  const int lane = threadIdx.x;
+  const int count = a.words[kWordLong];
+  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
+    const int64_t p = list[w];
+    const int64_t b = a.off[p];
+    const int n = __builtin_amdgcn_readfirstlane((int)open_count(a.xy, b, a.off[p + 1]));    // 65 .. SEGGER_MORPH_MAX_VERTS
+    const double2 first = reinterpret_cast<const double2*>(a.xy)[b];
+    double xmin = first.x, ymin = first.y, xmax = first.x, ymax = first.y;
+    __syncthreads();                                                 // the previous polygon's reads are done
+    for (int i = lane; i < n; i += kWave) {
+      const double2 v = reinterpret_cast<const double2*>(a.xy)[b + i];
+      xmin = fmin(xmin, v.x); xmax = fmax(xmax, v.x);
+      ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
+      pts[i] = double2{v.x - first.x, v.y - first.y};
+    }
+    __syncthreads();
+    LdsRing ring{pts};
+    polygon_body<kFill>(ring, n, P2{first.x, first.y}, wave_min_f64(xmin), wave_min_f64(ymin), wave_max_f64(xmax),
+                        wave_max_f64(ymax), p, a);
+  }
+}
+
+// pair_offsets[1 .. P] holds the counts; afterwards pair_offsets[p] = the counts of the polygons before p
+__global__ __launch_bounds__(kScanThreads) void pjoin_scan_kernel(int64_t* __restrict__ pair_offsets, int64_t P) {
+  __shared__ int64_t wave_total[kScanThreads / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < P; base += kScanThreads) {
+    const int64_t i = base + threadIdx.x;
+    int64_t v = i < P ? pair_offsets[i + 1] : 0;
+#pragma unroll
+    for (int s = 1; s < kWave; s <<= 1) {                            // inclusive scan of the wave
+      const int64_t o = (int64_t)shfl64((uint64_t)v, lane >= s ? lane - s : lane);
+      if (lane >= s) v += o;
+    }
+    if (lane == kWave - 1) wave_total[wave] = v;
+    __syncthreads();
+    int64_t before = carry, all = carry;
+    for (int w = 0; w < kScanThreads / kWave; ++w) {
+      const int64_t t = wave_total[w];
+      if (w < wave) before += t;
+      all += t;
+    }
+    if (i < P) pair_offsets[i + 1] = before + v;
+    carry = all;
+    __syncthreads();                                                 // wave_total is rewritten by the next chunk
+  }
+}
+
+struct PjLayout {
+  size_t words, keys, pts, cell_start, list_short, list_long, temp, total;
+  size_t temp_bytes;
+  int key_bits;
+};
+
+// with n_points, n_polygons and n_cells below 2^31 every term is below 2^36 bytes: nothing here can overflow
+PjLayout pj_layout(int64_t N, int64_t P, int64_t n_cells) {
+  PjLayout l;
+  l.key_bits = 32 + bit_length((unsigned long long)(n_cells > 1 ? n_cells - 1 : 1));
+  const size_t n = (size_t)(N > 0 ? N : 1);
+  Carver c;
+  l.words = c.take(256);
+  l.keys = c.take(n * 8);                                            // sorted keys: cell << 32 | point id
+  l.pts = c.take(n * 16);                                            // cell-ordered points; before that, the unsorted keys
+  l.cell_start = c.take((size_t)(n_cells + 1) * 4);
+  l.list_short = c.take((size_t)P * 4);
+  l.list_long = c.take((size_t)P * 4);
+  size_t t = 0;
+  unsigned long long* k64 = nullptr;
+  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, t, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
+  l.temp_bytes = t;
+  l.temp = c.take(t > 0 ? t : 1);
+  l.total = c.total();
+  return l;
+}
+
+int pj_check_sizes(const char* who, int64_t N, int64_t P, int32_t nx, int32_t ny) {
+  SEGGER_REQUIRE(N >= 0 && P >= 0, "%s: negative n_points or n_polygons", who);
+  SEGGER_REQUIRE(N < 0x7fffffffLL && P < 0x7fffffffLL, "%s: 2^31 - 1 points or polygons, or more", who);
+  SEGGER_REQUIRE(nx >= 1 && ny >= 1 && (int64_t)nx * ny < 0x7fffffffLL, "%s: bad grid: nx, ny >= 1 and nx * ny < 2^31 - 1", who);
+  return SEGGER_OK;
+}
+
+struct PjCall {
+  const double* points; int64_t N; const int64_t* ring_offsets; const double* xy; int64_t P, V; const double* buffer;
+  int32_t predicate; double x0, y0, cell; int32_t nx, ny; const int64_t* pair_offsets; void* workspace; int64_t workspace_bytes;
+};
+
+// everything both entry points reject; *empty = nothing to do (no pointer was looked at)
+int pj_check(const char* who, const PjCall& c, bool* empty) {
+  *empty = false;
+  const int rc = pj_check_sizes(who, c.N, c.P, c.nx, c.ny);
+  if (rc != SEGGER_OK) return rc;
+  SEGGER_REQUIRE(c.V >= 0, "%s: negative n_vertices", who);
+  SEGGER_REQUIRE(c.workspace_bytes >= 0, "%s: negative workspace_bytes", who);
+  SEGGER_REQUIRE(c.predicate == SEGGER_PJOIN_CONTAINS || c.predicate == SEGGER_PJOIN_INTERSECTS,
+                 "%s: predicate %d is neither SEGGER_PJOIN_CONTAINS nor SEGGER_PJOIN_INTERSECTS", who, (int)c.predicate);
+  SEGGER_REQUIRE(c.cell > 0.0 && c.cell < INFINITY && c.x0 - c.x0 == 0.0 && c.y0 - c.y0 == 0.0,
+                 "%s: bad grid: the origin must be finite and the cell side positive and finite", who);
+  if (c.N == 0 || c.P == 0) { *empty = true; return SEGGER_OK; }
+  SEGGER_REQUIRE(c.points && c.ring_offsets && c.pair_offsets && c.workspace, "%s: NULL pointer", who);
+  SEGGER_REQUIRE(c.xy || c.V == 0, "%s: NULL xy with n_vertices > 0", who);
+  SEGGER_REQUIRE(is_aligned(c.ring_offsets, 8) && is_aligned(c.pair_offsets, 8) && is_aligned(c.buffer, 8),
+                 "%s: ring_offsets, pair_offsets and buffer must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(c.points, 16) && is_aligned(c.xy, 16), "%s: points and xy must be 16-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(c.workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  const size_t need = pj_layout(c.N, c.P, (int64_t)c.nx * c.ny).total;
+  SEGGER_REQUIRE((size_t)c.workspace_bytes >= need, "%s: workspace %lld < %zu bytes", who, (long long)c.workspace_bytes, need);
+  return SEGGER_OK;
+}
+
+JoinArgs join_args(const PjCall& c, const PjLayout& l, int64_t* pair_offsets, int64_t* out, int64_t capacity) {
+  JoinArgs a;
+  a.off = c.ring_offsets;
+  a.xy = c.xy;
+  a.buffer = c.buffer;
+  a.predicate = c.predicate;
+  a.g = PjGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny};
+  a.cell_start = at<int32_t>(c.workspace, l.cell_start);
+  a.pts = at<double2>(c.workspace, l.pts);
+  a.keys = at<unsigned long long>(c.workspace, l.keys);
+  a.pair_offsets = pair_offsets;
+  a.out = out;
+  a.capacity = capacity;
+  a.words = at<int32_t>(c.workspace, l.words);
+  return a;
+}
+
+template <bool kFill>
+int launch_polygons(const PjCall& c, const PjLayout& l, const JoinArgs& a, hipStream_t stream) {
+  const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
+  hipLaunchKernelGGL((pjoin_short_kernel<kFill>), dim3(grid_stride_blocks(c.P, kPjWaves, (int64_t)cus * 8)), dim3(kPjThreads), 0,
+                     stream, a, (const int32_t*)at<int32_t>(c.workspace, l.list_short));
+  SEGGER_LAUNCH_CHECK("pjoin_short_kernel");
+  hipLaunchKernelGGL((pjoin_long_kernel<kFill>), dim3(grid_stride_blocks(c.P, 1, (int64_t)cus * 2)), dim3(kWave), 0, stream, a,
+                     (const int32_t*)at<int32_t>(c.workspace, l.list_long));
+  SEGGER_LAUNCH_CHECK("pjoin_long_kernel");
+  return SEGGER_OK;
+}
+
+}  // namespace
+}  // namespace segger
+
+using namespace segger;
+
+extern "C" int64_t segger_polygon_join_workspace_bytes(int64_t n_points, int64_t n_polygons, int32_t nx, int32_t ny) {
+  const int rc = pj_check_sizes("segger_polygon_join_workspace_bytes", n_points, n_polygons, nx, ny);
+  if (rc != SEGGER_OK) return rc;
+  return (int64_t)pj_layout(n_points, n_polygons, (int64_t)nx * ny).total;
+}
+
+extern "C" int segger_polygon_join_count(const double* points, int64_t n_points, const int64_t* ring_offsets, const double* xy,
+                                         int64_t n_polygons, int64_t n_vertices, const double* buffer, int32_t predicate,
+                                         double x0, double y0, double cell, int32_t nx, int32_t ny, int64_t* pair_offsets,
+                                         void* workspace, int64_t workspace_bytes, segger_stream_t stream_) {
+  const char* who = "segger_polygon_join_count";
+  hipStream_t stream = (hipStream_t)stream_;
+  const PjCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
+                 pair_offsets, workspace, workspace_bytes};
+  bool empty = false;
+  const int rc = pj_check(who, c, &empty);
+  if (rc != SEGGER_OK || empty) return rc;
+  const int64_t n_cells = (int64_t)nx * ny;
+  const PjLayout l = pj_layout(n_points, n_polygons, n_cells);
+  const JoinArgs a = join_args(c, l, pair_offsets, nullptr, 0);
+  unsigned long long* keys_in = at<unsigned long long>(workspace, l.pts);      // dead once sorted: the points go there
+  unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
+  const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
+  SEGGER_HIP(hipMemsetAsync(a.words, 0, 256, stream));
+  hipLaunchKernelGGL(pjoin_keys_kernel, dim3(grid_stride_blocks(n_points, kPjThreads, (int64_t)cus * 32)), dim3(kPjThreads), 0,
+                     stream, points, n_points, a.g, keys_in);
+  SEGGER_LAUNCH_CHECK("pjoin_keys_kernel");
+  size_t temp_bytes = l.temp_bytes;
+  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, l.temp), temp_bytes, keys_in, keys, (size_t)n_points,
+                                                           0, (unsigned)l.key_bits, stream));
+  hipLaunchKernelGGL(pjoin_cells_kernel, dim3(grid_stride_blocks(n_points, kPjThreads, (int64_t)cus * 32)), dim3(kPjThreads), 0,
+                     stream, (const unsigned long long*)keys, points, n_points, n_cells, at<int32_t>(workspace, l.cell_start),
+                     at<double2>(workspace, l.pts));
+  SEGGER_LAUNCH_CHECK("pjoin_cells_kernel");
+  hipLaunchKernelGGL(pjoin_bin_kernel, dim3(grid_stride_blocks(n_polygons, kPjThreads, (int64_t)cus * 8)), dim3(kPjThreads), 0,
+                     stream, ring_offsets, xy, buffer, n_polygons, n_vertices, pair_offsets, a.words,
+                     at<int32_t>(workspace, l.list_short), at<int32_t>(workspace, l.list_long));
+  SEGGER_LAUNCH_CHECK("pjoin_bin_kernel");
+  const int rc2 = launch_polygons<false>(c, l, a, stream);
+  if (rc2 != SEGGER_OK) return rc2;
+  hipLaunchKernelGGL(pjoin_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, pair_offsets, n_polygons);
+  SEGGER_LAUNCH_CHECK("pjoin_scan_kernel");
+  return SEGGER_OK;
+}
+
+extern "C" int segger_polygon_join_fill(const double* points, int64_t n_points, const int64_t* ring_offsets, const double* xy,
+                                        int64_t n_polygons, int64_t n_vertices, const double* buffer, int32_t predicate,
+                                        double x0, double y0, double cell, int32_t nx, int32_t ny, const int64_t* pair_offsets,
+                                        int64_t* point_index_out, int64_t capacity, void* workspace, int64_t workspace_bytes,
+                                        segger_stream_t stream_) {
+  const char* who = "segger_polygon_join_fill";
+  hipStream_t stream = (hipStream_t)stream_;
+  const PjCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
+                 pair_offsets, workspace, workspace_bytes};
+  bool empty = false;
+  const int rc = pj_check(who, c, &empty);
+  if (rc != SEGGER_OK) return rc;
+  SEGGER_REQUIRE(capacity >= 0, "%s: negative capacity", who);
+  if (empty || capacity == 0) return SEGGER_OK;
+  SEGGER_REQUIRE(point_index_out, "%s: NULL pointer", who);
+  SEGGER_REQUIRE(is_aligned(point_index_out, 8), "%s: point_index_out must be 8-byte aligned", who);
+  const PjLayout l = pj_layout(n_points, n_polygons, (int64_t)nx * ny);
+  const JoinArgs a = join_args(c, l, const_cast<int64_t*>(pair_offsets), point_index_out, capacity);
+  return launch_polygons<true>(c, l, a, stream);
+}

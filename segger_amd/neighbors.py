@@ -6,7 +6,9 @@ Restates reference ``src/segger/data/utils/neighbors.py``:
   -> :func:`knn_grid` over the HIP kernel ``segger_knn_grid`` (exact, uniform grid);
 * ``knn_to_edge_index`` (``:54-92``): dense neighbour table with padding -> COO ``edge_index`` whose
   row 0 is the QUERY point (source) and row 1 the neighbour (target);
-* ``setup_transcripts_graph`` (``:166-180``) -> :func:`transcripts_graph`.
+* ``setup_transcripts_graph`` (``:166-180``) -> :func:`transcripts_graph`;
+* ``setup_prediction_graph`` (``:200-241``): ``mode="uniform"`` -> :func:`prediction_graph_uniform`, the shape-based
+  modes ``"cell"`` (the default) and ``"nucleus"`` -> :func:`prediction_graph_shape`.
 """
 from __future__ import annotations
 
@@ -81,3 +83,29 @@ def prediction_graph_uniform(tx_pos: Tensor, bd_pos: Tensor, max_k: int, max_dis
     nbr, _ = knn_grid(tx_pos, max_k, max_dist, query=bd_pos)
     ei, _ = knn_to_edge_index(nbr, padding_value=int(tx_pos.shape[0]))
     return ei
+
+
+def prediction_graph_shape(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, buffer_ratio: float = 0.05) -> Tensor:
+    """``setup_prediction_graph(mode='cell' | 'nucleus')`` (``neighbors.py:223-238``), the reference's default
+    (``ISTDataModule.prediction_graph_mode = "cell"``, ``prediction_graph_buffer_ratio = 0.05``): every boundary polygon
+    is grown by ``d = sqrt(area / pi) * buffer_ratio`` and every transcript is joined to every grown polygon that contains
+    it.  ``area`` comes from :func:`segger_amd.morphology.polygon_props` and ``d`` is float64 torch; the join is
+    :func:`segger_amd.geometry.points_in_polygons` with ``predicate="contains"``, whose docstring says where the exact
+    offset used here differs from GEOS's ``buffer`` (slivers at convex corners ~ 0.0012 d wide; unverified against GEOS).
+
+    ``tx_pos`` is ``[N, 2]`` (float32 positions are converted to float64, which is exact); ``ring_offsets`` / ``xy`` are
+    the CSR of rings.  Returns the ``TX_NB_BD`` edge index ``[2, E]`` int64 in the reference's direction: row 0 the
+    transcript (``index_query``), row 1 the polygon (``index_match``), sorted by (transcript, polygon).
+
+    The reference selects the rows of one ``boundary_type`` (cell or nucleus) before the call -- pass only those rings --
+    and ignores ``max_k`` in this mode, so there is no such argument.  ``buffer_ratio < 0`` is a ``ValueError``: GEOS's
+    erosion (a negative buffer) is not built."""
+    from .geometry import points_in_polygons
+    from .morphology import polygon_props
+    buffer_ratio = float(buffer_ratio)
+    if not (buffer_ratio >= 0.0 and math.isfinite(buffer_ratio)):
+        raise ValueError(f"prediction_graph_shape: buffer_ratio must be finite and >= 0 (erosion is not built), got {buffer_ratio}")
+    area = polygon_props(ring_offsets, xy)["area"]
+    d = torch.sqrt(area / math.pi) * buffer_ratio
+    d = torch.where(area.isnan(), torch.zeros_like(d), d)           # an empty ring has no area and matches nothing
+    return points_in_polygons(tx_pos, ring_offsets, xy, buffer=d, predicate="contains")
