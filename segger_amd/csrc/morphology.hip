@@ -2,16 +2,15 @@
 // polygons -- the parts of the reference's geometry/morphology.py (get_polygon_props), which goes through
 // geopandas / shapely one polygon at a time.  include/segger_amd.h has the contract.
 //
-// Three kernels on one stream, no host synchronisation:
-//   morph_bin_kernel    one thread per polygon: checks its two offsets, drops a closing duplicate vertex, and appends the
-//                       polygon to the list of its route (one integer atomic per wave and route).  A ring with bad offsets
-//                       or more than SEGGER_MORPH_MAX_VERTS vertices gets a row of NaN and a bit in the error word.
-//   morph_short_kernel  n <= 64: one wave per polygon, one vertex per lane, everything in registers (no LDS).
-//   morph_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the translated ring
-//                       staged in LDS (64 KB) next to the hull's index list (8 KB), lanes striding over both.
-// Both polygon kernels are grid-stride loops over their list, whose length they read from the workspace; the order of a
-// list depends on the order of the atomics, the row of a polygon does not: every sum is a per-lane sum in ascending
-// vertex order followed by a 6-level butterfly, so the same input gives the same bits from call to call.
+// Three kernels on one stream, no host synchronisation; rings.h has the ring layer they share with polygon_join.hip (the
+// open vertex count, the two routes and their lists, the loaders):
+//   morph_bin_kernel    one thread per polygon: a ring that cannot be computed (bad offsets, above the cap) or is empty
+//                       gets a row of NaN, and the first two a bit in the error word; the others go to their route's list.
+//   morph_short_kernel  n <= 64: one wave per polygon, ring and hull in registers (no LDS).
+//   morph_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the ring in LDS (64 KB)
+//                       next to the hull's index list (8 KB), lanes striding over both.
+// The order of a list depends on the order of the atomics, the row of a polygon does not: every sum is a per-lane sum in
+// ascending vertex order followed by a 6-level butterfly, so the same input gives the same bits from call to call.
 //
 // Per polygon, in float64 on coordinates translated to the ring's first vertex, with FMA contraction off (a cross
 // product of exactly representable coordinates is then exact, and cross(a, b) = -cross(b, a) to the bit):
@@ -32,12 +31,13 @@
 //      a long ring whose hull has thousands of vertices (a finely sampled circle) is the slow case.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): morph_bin_kernel 20 VGPR, no LDS, 8 waves per SIMD;
-// morph_short_kernel 100 VGPR, no LDS, 4 waves per SIMD; morph_long_kernel 104 VGPR, 73728 B LDS (two single-wave
+// morph_short_kernel 94 VGPR, no LDS, 5 waves per SIMD; morph_long_kernel 104 VGPR, 73728 B LDS (two single-wave
 // workgroups per CU); no scratch in any of them.
 #include <math.h>
 
 #include "common.h"
 #include "post_common.h"
+#include "rings.h"
 
 #pragma clang fp contract(off)
 
@@ -47,53 +47,12 @@ namespace {
 constexpr int kMorphThreads = 256;
 constexpr int kMorphWaves = kMorphThreads / kWave;
 constexpr int kMorphCols = SEGGER_MORPH_COLS;
-constexpr int kWordFlag = 0, kWordShort = 1, kWordLong = 2;        // int32 words at the start of the workspace
 constexpr double kSlack = SEGGER_MORPH_CIRCLE_SLACK;
 
 static_assert(SEGGER_MORPH_MAX_VERTS <= 65536, "the hull's index list is uint16");
-static_assert(SEGGER_MORPH_MAX_VERTS % kWave == 0, "lanes stride over whole chunks");
 
-struct P2 { double x, y; };
-
-__device__ __forceinline__ double shfl_f64(double v, int src) {
-  return __longlong_as_double((long long)shfl64((uint64_t)__double_as_longlong(v), src));
-}
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-  return __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(v), mask));
-}
-// lane is the same in every lane of the wave
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-// the same bits in every lane: a + b is commutative, so both partners of a level compute the same sum
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) v += shfl_xor_f64(v, m);
-  return v;
-}
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) v = fmin(v, shfl_xor_f64(v, m));
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) v = fmax(v, shfl_xor_f64(v, m));
-  return v;
-}
-
-// ---------------------------------------------------------------- the two ring / hull stores ---
-// own(i): vertex i from the lane that owns it (i % 64 == lane), callable under any EXEC; at(i): any lane reads any vertex,
-// every lane of the wave active; uni(i): i is the same in every lane.
-struct RegRing {
-  double x, y;                                                       // vertex `lane`, translated
-  __device__ __forceinline__ P2 own(int) const { return P2{x, y}; }
-  __device__ __forceinline__ P2 at(int i) const { return P2{shfl_f64(x, i), shfl_f64(y, i)}; }
-  __device__ __forceinline__ P2 uni(int i) const { return P2{readlane_f64(x, i), readlane_f64(y, i)}; }
-};
+// ---------------------------------------------------------------- the two hull stores ---
+// push(k, i, q): hull vertex k is ring vertex i = q; own / at / uni as the ring stores of rings.h
 struct RegHull {
   double x = 0.0, y = 0.0;                                           // hull vertex `lane`
   __device__ __forceinline__ void push(int k, int, P2 q) {
@@ -103,12 +62,6 @@ struct RegHull {
   __device__ __forceinline__ P2 own(int) const { return P2{x, y}; }
   __device__ __forceinline__ P2 at(int k) const { return P2{shfl_f64(x, k), shfl_f64(y, k)}; }
   __device__ __forceinline__ P2 uni(int k) const { return P2{readlane_f64(x, k), readlane_f64(y, k)}; }
-};
-struct LdsRing {
-  const double2* pts;
-  __device__ __forceinline__ P2 own(int i) const { const double2 p = pts[i]; return P2{p.x, p.y}; }
-  __device__ __forceinline__ P2 at(int i) const { return own(i); }
-  __device__ __forceinline__ P2 uni(int i) const { return own(i); }
 };
 struct LdsHull {
   const double2* pts;
@@ -339,64 +292,36 @@ __device__ __forceinline__ void nan_row(double* __restrict__ row) {
   for (int c = 0; c < kMorphCols; ++c) row[c] = NAN;
 }
 
-// vertices of ring [b, e) without a closing duplicate (e - b >= 0)
-__device__ __forceinline__ int64_t open_count(const double* __restrict__ xy, int64_t b, int64_t e) {
-  const int64_t n = e - b;
-  if (n < 2) return n;
-  const unsigned long long* u = reinterpret_cast<const unsigned long long*>(xy);
-  return (u[2 * b] == u[2 * (e - 1)] && u[2 * b + 1] == u[2 * (e - 1) + 1]) ? n - 1 : n;
-}
-
 __global__ __launch_bounds__(kMorphThreads) void morph_bin_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
                                                                   int64_t P, int64_t V, double* __restrict__ props,
                                                                   int32_t* __restrict__ words, int32_t* __restrict__ list_short,
                                                                   int32_t* __restrict__ list_long) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t stride = (int64_t)gridDim.x * kMorphThreads;
-  // whole waves iterate together: the ballots below need every lane of a wave in the loop
+  // whole waves iterate together: append_by_route needs every lane of a wave in the loop
   for (int64_t base = (int64_t)blockIdx.x * kMorphThreads + (threadIdx.x & ~(kWave - 1)); base < P; base += stride) {
     const int64_t p = base + lane;
-    int route = -1;                                                  // 0 short, 1 long, -1 nothing to compute
+    int route = -1;                                                  // -1: nothing to compute
     if (p < P) {
-      const int64_t b = off[p], e = off[p + 1];
-      int bad = 0;
-      int64_t n = 0;
-      if (b < 0 || e < b || e > V) bad = SEGGER_MORPH_ERR_OFFSETS;
-      else {
-        n = open_count(xy, b, e);
-        if (n > SEGGER_MORPH_MAX_VERTS) bad = SEGGER_MORPH_ERR_CAP;
-      }
-      if (bad) atomicOr(&words[kWordFlag], bad);
-      if (bad || n == 0) nan_row(props + p * kMorphCols);
-      else route = n > kWave;
+      const RingClass c = classify_ring(off, xy, p, V);
+      if (c.bad) atomicOr(&words[kWordFlag], c.bad);
+      if (c.bad || c.n == 0) nan_row(props + p * kMorphCols);
+      else route = ring_route(c.n);
     }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const unsigned long long m = __ballot(route == r);
-      if (m == 0) continue;
-      int pos = 0;
-      if (lane == (int)__builtin_ctzll(m)) pos = atomicAdd(&words[r == 0 ? kWordShort : kWordLong], (int)__popcll(m));
-      pos = __shfl(pos, (int)__builtin_ctzll(m), kWave);
-      if (route == r) (r == 0 ? list_short : list_long)[pos + (int)__popcll(m & ((1ull << lane) - 1))] = (int32_t)p;
-    }
+    append_by_route(route, p, words, list_short, list_long);
   }
 }
 
 __global__ __launch_bounds__(kMorphThreads) void morph_short_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
                                                                     double* __restrict__ props, const int32_t* __restrict__ words,
                                                                     const int32_t* __restrict__ list) {
-  const int lane = threadIdx.x & (kWave - 1);
   const int count = words[kWordShort];
   const int n_waves = (int)gridDim.x * kMorphWaves;
   for (int w = (int)blockIdx.x * kMorphWaves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {             // wave-uniform
     const int64_t p = list[w];
-    const int64_t b = off[p];
-    const int n = (int)open_count(xy, b, off[p + 1]);                // 1 .. 64: the binning kernel saw the same numbers
-    const double2 first = reinterpret_cast<const double2*>(xy)[b];
-    const double2 mine = lane < n ? reinterpret_cast<const double2*>(xy)[b + lane] : first;
-    RegRing ring{mine.x - first.x, mine.y - first.y};
+    const ShortRing s = load_short_ring(off, xy, p);
     RegHull hull;
-    polygon_body(ring, hull, n, P2{first.x, first.y}, mine.x, mine.y, mine.x, mine.y, props + p * kMorphCols);
+    polygon_body(s.ring, hull, s.n, s.first, s.mine.x, s.mine.y, s.mine.x, s.mine.y, props + p * kMorphCols);
   }
 }
 
@@ -405,38 +330,14 @@ __global__ __launch_bounds__(kWave) void morph_long_kernel(const int64_t* __rest
                                                            const int32_t* __restrict__ list) {
   __shared__ double2 pts[SEGGER_MORPH_MAX_VERTS];
   __shared__ uint16_t hidx[SEGGER_MORPH_MAX_VERTS];
-  const int lane = threadIdx.x;
   const int count = words[kWordLong];
   for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
     const int64_t p = list[w];
-    const int64_t b = off[p];
-    const int n = (int)open_count(xy, b, off[p + 1]);                // 65 .. SEGGER_MORPH_MAX_VERTS
-    const double2 first = reinterpret_cast<const double2*>(xy)[b];
-    double xmin = first.x, ymin = first.y, xmax = first.x, ymax = first.y;
-    __syncthreads();                                                 // the previous polygon's reads are done
-    for (int i = lane; i < n; i += kWave) {
-      const double2 v = reinterpret_cast<const double2*>(xy)[b + i];
-      xmin = fmin(xmin, v.x); xmax = fmax(xmax, v.x);
-      ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
-      pts[i] = double2{v.x - first.x, v.y - first.y};
-    }
-    __syncthreads();
+    const LongRing r = stage_long_ring(off, xy, p, pts);
     LdsRing ring{pts};
     LdsHull hull{pts, hidx};
-    polygon_body(ring, hull, n, P2{first.x, first.y}, xmin, ymin, xmax, ymax, props + p * kMorphCols);
+    polygon_body(ring, hull, r.n, r.first, r.xmin, r.ymin, r.xmax, r.ymax, props + p * kMorphCols);
   }
-}
-
-struct MorphLayout { size_t words, list_short, list_long, total; };
-
-MorphLayout morph_layout(int64_t P) {
-  Carver c;
-  MorphLayout l;
-  l.words = c.take(256);
-  l.list_short = c.take((size_t)P * sizeof(int32_t));
-  l.list_long = c.take((size_t)P * sizeof(int32_t));
-  l.total = c.total();
-  return l;
 }
 
 }  // namespace
@@ -449,7 +350,9 @@ extern "C" int64_t segger_morphology_workspace_bytes(int64_t n_polygons) {
     set_error("segger_morphology_workspace_bytes: n_polygons = %lld outside 0 .. 2^31 - 2", (long long)n_polygons);
     return SEGGER_EINVAL;
   }
-  return (int64_t)morph_layout(n_polygons).total;
+  Carver c;                                                          // the workspace is the ring lists and nothing else
+  take_ring_lists(c, n_polygons);
+  return (int64_t)c.total();
 }
 
 extern "C" int segger_polygon_props(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
@@ -460,18 +363,16 @@ extern "C" int segger_polygon_props(const int64_t* ring_offsets, const double* x
   SEGGER_REQUIRE(n_polygons < 0x7fffffffLL, "%s: 2^31 - 1 polygons or more", who);
   SEGGER_REQUIRE(workspace_bytes >= 0, "%s: negative workspace_bytes", who);
   if (n_polygons == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(ring_offsets && props && workspace, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(xy || n_vertices == 0, "%s: NULL xy with n_vertices > 0", who);
-  SEGGER_REQUIRE(is_aligned(ring_offsets, 8) && is_aligned(props, 8), "%s: ring_offsets and props must be 8-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(xy, 16), "%s: xy must be 16-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
-  const MorphLayout l = morph_layout(n_polygons);
-  SEGGER_REQUIRE((size_t)workspace_bytes >= l.total, "%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, l.total);
+  Carver c;
+  const RingLists l = take_ring_lists(c, n_polygons);
+  const int rc = check_ring_call(who, ring_offsets, xy, n_vertices, workspace, workspace_bytes, c.total(),
+                                 OtherPointers{props != nullptr, is_aligned(props, 8), true, "ring_offsets and props", "xy"});
+  if (rc != SEGGER_OK) return rc;
   int32_t* words = at<int32_t>(workspace, l.words);
   int32_t* list_short = at<int32_t>(workspace, l.list_short);
   int32_t* list_long = at<int32_t>(workspace, l.list_long);
-  SEGGER_HIP(hipMemsetAsync(words, 0, 256, stream));
-  const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
+  SEGGER_HIP(hipMemsetAsync(words, 0, kRingWordsBytes, stream));
+  const int cus = cu_count_or_default();
   hipLaunchKernelGGL(morph_bin_kernel, dim3(grid_stride_blocks(n_polygons, kMorphThreads, (int64_t)cus * 8)), dim3(kMorphThreads), 0,
                      stream, ring_offsets, xy, n_polygons, n_vertices, props, words, list_short, list_long);
   SEGGER_LAUNCH_CHECK("morph_bin_kernel");

@@ -8,11 +8,11 @@
 //   (rocprim keys sort: stable by construction, the id is part of the key)
 //   pjoin_cells_kernel  one thread per sorted position: cell_start[] and the cell-ordered float64 copy of the points (the
 //                       ids stay in the low words of the sorted keys);
-//   pjoin_bin_kernel    one thread per polygon: checks its two offsets and its distance, drops a closing duplicate vertex,
-//                       zeroes its count and appends it to the list of its route (one integer atomic per wave and route);
-//   pjoin_short_kernel  n <= 64: one wave per polygon, one vertex per lane, edges broadcast by readlane, no LDS;
-//   pjoin_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the translated ring
-//                       staged in LDS (64 KB), every lane reading the same edge (an LDS broadcast);
+//   pjoin_bin_kernel    one thread per polygon: checks its ring (rings.h) and its distance, zeroes its count and appends
+//                       a ring of 3 or more vertices to the list of its route;
+//   pjoin_short_kernel  n <= 64: one wave per polygon, the ring in registers, edges broadcast by readlane, no LDS;
+//   pjoin_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the ring in LDS (64 KB),
+//                       every lane reading the same edge (an LDS broadcast);
 //   pjoin_scan_kernel   one workgroup: counts -> pair_offsets, in place.
 // The two polygon kernels are templates on "count" / "fill" over ONE traversal (polygon_body): the wave walks the rows of
 // grid cells that overlap the ring's bounds grown by d and a rounding margin, each row one contiguous span of the
@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "post_common.h"
+#include "rings.h"
 #include "sort_config.h"
 
 #pragma clang fp contract(off)
@@ -42,7 +43,6 @@ namespace {
 constexpr int kPjThreads = 256;
 constexpr int kPjWaves = kPjThreads / kWave;
 constexpr int kScanThreads = 1024;
-constexpr int kWordFlag = 0, kWordShort = 1, kWordLong = 2;          // int32 words at the start of the workspace
 
 struct PjGrid { double x0, y0, inv_cell; int nx, ny; };
 
@@ -51,39 +51,6 @@ __device__ __forceinline__ int cell_of(double v, double origin, double inv_cell,
   const double c = floor((v - origin) * inv_cell);
   return (int)fmin(fmax(c, 0.0), (double)(n - 1));
 }
-
-// lane is the same in every lane of the wave
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-  return __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(v), mask));
-}
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) v = fmin(v, shfl_xor_f64(v, m));
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) v = fmax(v, shfl_xor_f64(v, m));
-  return v;
-}
-
-struct P2 { double x, y; };
-
-// uni(i): vertex i, i the same in every lane
-struct RegRing {
-  double x, y;                                                       // vertex `lane`, translated
-  __device__ __forceinline__ P2 uni(int i) const { return P2{readlane_f64(x, i), readlane_f64(y, i)}; }
-};
-struct LdsRing {
-  const double2* pts;
-  __device__ __forceinline__ P2 uni(int i) const { const double2 p = pts[i]; return P2{p.x, p.y}; }
-};
 
 // ---------------------------------------------------------------- the points ---
 __global__ __launch_bounds__(kPjThreads) void pjoin_keys_kernel(const double* __restrict__ pts, int64_t n, PjGrid g,
@@ -112,48 +79,26 @@ __global__ __launch_bounds__(kPjThreads) void pjoin_cells_kernel(const unsigned 
 }
 
 // ---------------------------------------------------------------- the polygons ---
-// vertices of ring [b, e) without a closing duplicate (e - b >= 0)
-__device__ __forceinline__ int64_t open_count(const double* __restrict__ xy, int64_t b, int64_t e) {
-  const int64_t n = e - b;
-  if (n < 2) return n;
-  const unsigned long long* u = reinterpret_cast<const unsigned long long*>(xy);
-  return (u[2 * b] == u[2 * (e - 1)] && u[2 * b + 1] == u[2 * (e - 1) + 1]) ? n - 1 : n;
-}
-
 __global__ __launch_bounds__(kPjThreads) void pjoin_bin_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
                                                                const double* __restrict__ buffer, int64_t P, int64_t V,
                                                                int64_t* __restrict__ pair_offsets, int32_t* __restrict__ words,
                                                                int32_t* __restrict__ list_short, int32_t* __restrict__ list_long) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t stride = (int64_t)gridDim.x * kPjThreads;
-  // whole waves iterate together: the ballots below need every lane of a wave in the loop
+  // whole waves iterate together: append_by_route needs every lane of a wave in the loop
   for (int64_t base = (int64_t)blockIdx.x * kPjThreads + (threadIdx.x & ~(kWave - 1)); base < P; base += stride) {
     const int64_t p = base + lane;
-    int route = -1;                                                  // 0 short, 1 long, -1 matches nothing
+    int route = -1;                                                  // -1: matches nothing
     if (p < P) {
-      const int64_t b = off[p], e = off[p + 1];
-      int bad = 0;
-      int64_t n = 0;
-      if (b < 0 || e < b || e > V) bad = SEGGER_PJOIN_ERR_OFFSETS;
-      else {
-        n = open_count(xy, b, e);
-        if (n > SEGGER_MORPH_MAX_VERTS) bad = SEGGER_PJOIN_ERR_CAP;
-      }
+      const RingClass c = classify_ring(off, xy, p, V);
+      int bad = c.bad;
       if (buffer && !(buffer[p] >= 0.0 && buffer[p] < INFINITY)) bad |= SEGGER_PJOIN_ERR_BUFFER;
       if (bad) atomicOr(&words[kWordFlag], bad);
       pair_offsets[p + 1] = 0;                                       // the count; the polygon kernels overwrite theirs
       if (p == 0) pair_offsets[0] = 0;
-      if (!bad && n >= 3) route = n > kWave;
+      if (!bad && c.n >= 3) route = ring_route(c.n);
     }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const unsigned long long m = __ballot(route == r);
-      if (m == 0) continue;
-      int pos = 0;
-      if (lane == (int)__builtin_ctzll(m)) pos = atomicAdd(&words[r == 0 ? kWordShort : kWordLong], (int)__popcll(m));
-      pos = __shfl(pos, (int)__builtin_ctzll(m), kWave);
-      if (route == r) (r == 0 ? list_short : list_long)[pos + (int)__popcll(m & ((1ull << lane) - 1))] = (int32_t)p;
-    }
+    append_by_route(route, p, words, list_short, list_long);
   }
 }
 
@@ -245,43 +190,26 @@ __device__ __forceinline__ void polygon_body(const Ring& ring, int n, P2 org, do
 
 template <bool kFill>
 __global__ __launch_bounds__(kPjThreads) void pjoin_short_kernel(JoinArgs a, const int32_t* __restrict__ list) {
-  const int lane = threadIdx.x & (kWave - 1);
   const int count = a.words[kWordShort];
   const int n_waves = (int)gridDim.x * kPjWaves;
   for (int w = (int)blockIdx.x * kPjWaves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {                // wave-uniform
     const int64_t p = list[w];
-    const int64_t b = a.off[p];
-    const int n = __builtin_amdgcn_readfirstlane((int)open_count(a.xy, b, a.off[p + 1]));    // 3 .. 64, as the binning kernel saw
-    const double2 first = reinterpret_cast<const double2*>(a.xy)[b];
-    const double2 mine = lane < n ? reinterpret_cast<const double2*>(a.xy)[b + lane] : first;
-    RegRing ring{mine.x - first.x, mine.y - first.y};
-    polygon_body<kFill>(ring, n, P2{first.x, first.y}, wave_min_f64(mine.x), wave_min_f64(mine.y), wave_max_f64(mine.x),
-                        wave_max_f64(mine.y), p, a);
+    const ShortRing s = load_short_ring(a.off, a.xy, p);             // 3 .. 64 vertices
+    polygon_body<kFill>(s.ring, s.n, s.first, wave_min_f64(s.mine.x), wave_min_f64(s.mine.y), wave_max_f64(s.mine.x),
+                        wave_max_f64(s.mine.y), p, a);
   }
 }
 
 template <bool kFill>
 __global__ __launch_bounds__(kWave) void pjoin_long_kernel(JoinArgs a, const int32_t* __restrict__ list) {
   __shared__ double2 pts[SEGGER_MORPH_MAX_VERTS];
-  const int lane = threadIdx.x;
   const int count = a.words[kWordLong];
   for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
     const int64_t p = list[w];
-    const int64_t b = a.off[p];
-    const int n = __builtin_amdgcn_readfirstlane((int)open_count(a.xy, b, a.off[p + 1]));    // 65 .. SEGGER_MORPH_MAX_VERTS
-    const double2 first = reinterpret_cast<const double2*>(a.xy)[b];
-    double xmin = first.x, ymin = first.y, xmax = first.x, ymax = first.y;
-    __syncthreads();                                                 // the previous polygon's reads are done
-    for (int i = lane; i < n; i += kWave) {
-      const double2 v = reinterpret_cast<const double2*>(a.xy)[b + i];
-      xmin = fmin(xmin, v.x); xmax = fmax(xmax, v.x);
-      ymin = fmin(ymin, v.y); ymax = fmax(ymax, v.y);
-      pts[i] = double2{v.x - first.x, v.y - first.y};
-    }
-    __syncthreads();
+    const LongRing r = stage_long_ring(a.off, a.xy, p, pts);
     LdsRing ring{pts};
-    polygon_body<kFill>(ring, n, P2{first.x, first.y}, wave_min_f64(xmin), wave_min_f64(ymin), wave_max_f64(xmax),
-                        wave_max_f64(ymax), p, a);
+    polygon_body<kFill>(ring, r.n, r.first, wave_min_f64(r.xmin), wave_min_f64(r.ymin), wave_max_f64(r.xmax), wave_max_f64(r.ymax),
+                        p, a);
   }
 }
 
@@ -313,7 +241,8 @@ __global__ __launch_bounds__(kScanThreads) void pjoin_scan_kernel(int64_t* __res
 }
 
 struct PjLayout {
-  size_t words, keys, pts, cell_start, list_short, list_long, temp, total;
+  RingLists rings;
+  size_t keys, pts, cell_start, temp, total;
   size_t temp_bytes;
   int key_bits;
 };
@@ -324,12 +253,10 @@ PjLayout pj_layout(int64_t N, int64_t P, int64_t n_cells) {
   l.key_bits = 32 + bit_length((unsigned long long)(n_cells > 1 ? n_cells - 1 : 1));
   const size_t n = (size_t)(N > 0 ? N : 1);
   Carver c;
-  l.words = c.take(256);
+  l.rings = take_ring_lists(c, P);
   l.keys = c.take(n * 8);                                            // sorted keys: cell << 32 | point id
   l.pts = c.take(n * 16);                                            // cell-ordered points; before that, the unsorted keys
   l.cell_start = c.take((size_t)(n_cells + 1) * 4);
-  l.list_short = c.take((size_t)P * 4);
-  l.list_long = c.take((size_t)P * 4);
   size_t t = 0;
   unsigned long long* k64 = nullptr;
   (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, t, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
@@ -363,15 +290,10 @@ int pj_check(const char* who, const PjCall& c, bool* empty) {
   SEGGER_REQUIRE(c.cell > 0.0 && c.cell < INFINITY && c.x0 - c.x0 == 0.0 && c.y0 - c.y0 == 0.0,
                  "%s: bad grid: the origin must be finite and the cell side positive and finite", who);
   if (c.N == 0 || c.P == 0) { *empty = true; return SEGGER_OK; }
-  SEGGER_REQUIRE(c.points && c.ring_offsets && c.pair_offsets && c.workspace, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(c.xy || c.V == 0, "%s: NULL xy with n_vertices > 0", who);
-  SEGGER_REQUIRE(is_aligned(c.ring_offsets, 8) && is_aligned(c.pair_offsets, 8) && is_aligned(c.buffer, 8),
-                 "%s: ring_offsets, pair_offsets and buffer must be 8-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(c.points, 16) && is_aligned(c.xy, 16), "%s: points and xy must be 16-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(c.workspace, 256), "%s: workspace must be 256-byte aligned", who);
   const size_t need = pj_layout(c.N, c.P, (int64_t)c.nx * c.ny).total;
-  SEGGER_REQUIRE((size_t)c.workspace_bytes >= need, "%s: workspace %lld < %zu bytes", who, (long long)c.workspace_bytes, need);
-  return SEGGER_OK;
+  return check_ring_call(who, c.ring_offsets, c.xy, c.V, c.workspace, c.workspace_bytes, need,
+                         OtherPointers{c.points && c.pair_offsets, is_aligned(c.pair_offsets, 8) && is_aligned(c.buffer, 8),
+                                       is_aligned(c.points, 16), "ring_offsets, pair_offsets and buffer", "points and xy"});
 }
 
 JoinArgs join_args(const PjCall& c, const PjLayout& l, int64_t* pair_offsets, int64_t* out, int64_t capacity) {
@@ -387,18 +309,18 @@ JoinArgs join_args(const PjCall& c, const PjLayout& l, int64_t* pair_offsets, in
   a.pair_offsets = pair_offsets;
   a.out = out;
   a.capacity = capacity;
-  a.words = at<int32_t>(c.workspace, l.words);
+  a.words = at<int32_t>(c.workspace, l.rings.words);
   return a;
 }
 
 template <bool kFill>
 int launch_polygons(const PjCall& c, const PjLayout& l, const JoinArgs& a, hipStream_t stream) {
-  const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
+  const int cus = cu_count_or_default();
   hipLaunchKernelGGL((pjoin_short_kernel<kFill>), dim3(grid_stride_blocks(c.P, kPjWaves, (int64_t)cus * 8)), dim3(kPjThreads), 0,
-                     stream, a, (const int32_t*)at<int32_t>(c.workspace, l.list_short));
+                     stream, a, (const int32_t*)at<int32_t>(c.workspace, l.rings.list_short));
   SEGGER_LAUNCH_CHECK("pjoin_short_kernel");
   hipLaunchKernelGGL((pjoin_long_kernel<kFill>), dim3(grid_stride_blocks(c.P, 1, (int64_t)cus * 2)), dim3(kWave), 0, stream, a,
-                     (const int32_t*)at<int32_t>(c.workspace, l.list_long));
+                     (const int32_t*)at<int32_t>(c.workspace, l.rings.list_long));
   SEGGER_LAUNCH_CHECK("pjoin_long_kernel");
   return SEGGER_OK;
 }
@@ -430,8 +352,8 @@ extern "C" int segger_polygon_join_count(const double* points, int64_t n_points,
   const JoinArgs a = join_args(c, l, pair_offsets, nullptr, 0);
   unsigned long long* keys_in = at<unsigned long long>(workspace, l.pts);      // dead once sorted: the points go there
   unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
-  const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
-  SEGGER_HIP(hipMemsetAsync(a.words, 0, 256, stream));
+  const int cus = cu_count_or_default();
+  SEGGER_HIP(hipMemsetAsync(a.words, 0, kRingWordsBytes, stream));
   hipLaunchKernelGGL(pjoin_keys_kernel, dim3(grid_stride_blocks(n_points, kPjThreads, (int64_t)cus * 32)), dim3(kPjThreads), 0,
                      stream, points, n_points, a.g, keys_in);
   SEGGER_LAUNCH_CHECK("pjoin_keys_kernel");
@@ -444,7 +366,7 @@ extern "C" int segger_polygon_join_count(const double* points, int64_t n_points,
   SEGGER_LAUNCH_CHECK("pjoin_cells_kernel");
   hipLaunchKernelGGL(pjoin_bin_kernel, dim3(grid_stride_blocks(n_polygons, kPjThreads, (int64_t)cus * 8)), dim3(kPjThreads), 0,
                      stream, ring_offsets, xy, buffer, n_polygons, n_vertices, pair_offsets, a.words,
-                     at<int32_t>(workspace, l.list_short), at<int32_t>(workspace, l.list_long));
+                     at<int32_t>(workspace, l.rings.list_short), at<int32_t>(workspace, l.rings.list_long));
   SEGGER_LAUNCH_CHECK("pjoin_bin_kernel");
   const int rc2 = launch_polygons<false>(c, l, a, stream);
   if (rc2 != SEGGER_OK) return rc2;

@@ -27,6 +27,9 @@ inline unsigned grid_stride_blocks(int64_t n_items, int threads, int64_t max_blo
   return (unsigned)(blocks < 1 ? 1 : (blocks < max_blocks ? blocks : max_blocks));
 }
 
+// the compute units that size a persistent grid; a guess where the device does not say
+inline int cu_count_or_default() { return device_cu_count() > 0 ? device_cu_count() : 256; }
+
 // The regions of a workspace, first to last: every region starts on a 256-byte boundary of a 256-byte aligned base.
 struct Carver {
   size_t off = 0;

@@ -1,0 +1,172 @@
+// The ring layer shared by the units that read a CSR of float64 rings (morphology.hip, polygon_join.hip; included after
+// post_common.h).  Polygon p is xy[off[p] .. off[p + 1]), either orientation; a closing duplicate of its first vertex is
+// dropped, bit for bit.  A ring of n <= 64 open vertices takes the register route (one wave, vertex `lane` in lane `lane`),
+// one of 64 < n <= SEGGER_MORPH_MAX_VERTS the LDS route (one single-wave workgroup, 64 KB); both hold the ring translated to
+// its first vertex.  A binning kernel classifies every polygon and appends it to the list of its route; the polygon kernels
+// read the list lengths from the workspace words and load what the binning kernel counted.  One definition each: the units
+// agree on "entries", "open vertices" and "route" because they run the same code, and a fix is made here and nowhere else.
+//
+// Floating point: this header sets `#pragma clang fp contract(off)` itself, to the end of the including unit.  The loaders
+// only subtract, but wave_sum_f64's additions are inlined next to the callers' products, which must not fuse with them.
+#pragma once
+#include <math.h>
+
+#include "post_common.h"
+
+#pragma clang fp contract(off)
+
+namespace segger {
+
+static_assert(SEGGER_MORPH_ERR_OFFSETS == SEGGER_PJOIN_ERR_OFFSETS, "classify_ring returns bits that both units OR into their word");
+static_assert(SEGGER_MORPH_ERR_CAP == SEGGER_PJOIN_ERR_CAP, "classify_ring returns bits that both units OR into their word");
+static_assert(SEGGER_MORPH_MAX_VERTS % kWave == 0, "lanes stride over whole chunks");
+
+constexpr int kWordFlag = 0, kWordShort = 1, kWordLong = 2;          // int32 words at the start of the workspace
+constexpr size_t kRingWordsBytes = 256;                              // the words' region, zeroed before the binning kernel
+
+struct P2 { double x, y; };
+
+// ---------------------------------------------------------------- float64 across the wave ---
+__device__ __forceinline__ double shfl_f64(double v, int src) {
+  return __longlong_as_double((long long)shfl64((uint64_t)__double_as_longlong(v), src));
+}
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  return __longlong_as_double((long long)shfl_xor64((uint64_t)__double_as_longlong(v), mask));
+}
+// lane is the same in every lane of the wave
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+// the same bits in every lane: a + b is commutative, so both partners of a level compute the same sum
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v += shfl_xor_f64(v, m);
+  return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmin(v, shfl_xor_f64(v, m));
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmax(v, shfl_xor_f64(v, m));
+  return v;
+}
+
+// ---------------------------------------------------------------- the two ring stores ---
+// own(i): vertex i from the lane that owns it (i % 64 == lane), callable under any EXEC; at(i): any lane reads any vertex,
+// every lane of the wave active; uni(i): i is the same in every lane.
+struct RegRing {
+  double x, y;                                                       // vertex `lane`, translated
+  __device__ __forceinline__ P2 own(int) const { return P2{x, y}; }
+  __device__ __forceinline__ P2 at(int i) const { return P2{shfl_f64(x, i), shfl_f64(y, i)}; }
+  __device__ __forceinline__ P2 uni(int i) const { return P2{readlane_f64(x, i), readlane_f64(y, i)}; }
+};
+struct LdsRing {
+  const double2* pts;
+  __device__ __forceinline__ P2 own(int i) const { const double2 p = pts[i]; return P2{p.x, p.y}; }
+  __device__ __forceinline__ P2 at(int i) const { return own(i); }
+  __device__ __forceinline__ P2 uni(int i) const { return own(i); }
+};
+
+// ---------------------------------------------------------------- binning: classify, append ---
+// vertices of ring [b, e) without a closing duplicate (e - b >= 0)
+__device__ __forceinline__ int64_t open_count(const double* __restrict__ xy, int64_t b, int64_t e) {
+  const int64_t n = e - b;
+  if (n < 2) return n;
+  const unsigned long long* u = reinterpret_cast<const unsigned long long*>(xy);
+  return (u[2 * b] == u[2 * (e - 1)] && u[2 * b + 1] == u[2 * (e - 1) + 1]) ? n - 1 : n;
+}
+
+// polygon p < P of a CSR over V vertices: its open vertex count, and SEGGER_MORPH_ERR_OFFSETS or _CAP if it cannot be
+// computed (n means nothing then; with bad offsets no vertex was read)
+struct RingClass { int64_t n; int bad; };
+__device__ __forceinline__ RingClass classify_ring(const int64_t* __restrict__ off, const double* __restrict__ xy, int64_t p, int64_t V) {
+  const int64_t b = off[p], e = off[p + 1];
+  if (b < 0 || e < b || e > V) return RingClass{0, SEGGER_MORPH_ERR_OFFSETS};
+  const int64_t n = open_count(xy, b, e);
+  return RingClass{n, n > SEGGER_MORPH_MAX_VERTS ? SEGGER_MORPH_ERR_CAP : 0};
+}
+
+// the route of a ring of 1 <= n <= SEGGER_MORPH_MAX_VERTS open vertices: 0 short (registers), 1 long (LDS)
+__device__ __forceinline__ int ring_route(int64_t n) { return n > kWave; }
+
+// Appends p to the list of its route (0, 1; anything else: to none): one integer atomic per wave and route.  Whole waves
+// call this together: the ballots need every lane of the wave here, so the caller's loop iterates by waves, not by threads.
+__device__ __forceinline__ void append_by_route(int route, int64_t p, int32_t* __restrict__ words, int32_t* __restrict__ list_short,
+                                                int32_t* __restrict__ list_long) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const unsigned long long m = __ballot(route == r);
+    if (m == 0) continue;
+    int pos = 0;
+    if (lane == (int)__builtin_ctzll(m)) pos = atomicAdd(&words[r == 0 ? kWordShort : kWordLong], (int)__popcll(m));
+    pos = __shfl(pos, (int)__builtin_ctzll(m), kWave);
+    if (route == r) (r == 0 ? list_short : list_long)[pos + (int)__popcll(m & ((1ull << lane) - 1))] = (int32_t)p;
+  }
+}
+
+// ---------------------------------------------------------------- the polygon kernels: load a listed ring ---
+// Register route, one wave, p the same in every lane: vertex `lane` (the first vertex in the lanes beyond n), translated
+// in `ring` and as given in `mine`.  n is what the binning kernel counted, 1 .. 64; readfirstlane tells the compiler what
+// is true already, that it is the same in every lane, so the loops over it become scalar.
+struct ShortRing { RegRing ring; int n; P2 first, mine; };
+__device__ __forceinline__ ShortRing load_short_ring(const int64_t* __restrict__ off, const double* __restrict__ xy, int64_t p) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t b = off[p];
+  const int n = __builtin_amdgcn_readfirstlane((int)open_count(xy, b, off[p + 1]));
+  const double2 first = reinterpret_cast<const double2*>(xy)[b];
+  const double2 mine = lane < n ? reinterpret_cast<const double2*>(xy)[b + lane] : first;
+  return ShortRing{RegRing{mine.x - first.x, mine.y - first.y}, n, P2{first.x, first.y}, P2{mine.x, mine.y}};
+}
+
+// LDS route, a workgroup of one wave: the translated ring into pts[SEGGER_MORPH_MAX_VERTS], between two barriers (the
+// previous ring's readers are done; this ring is visible).  n is 65 .. SEGGER_MORPH_MAX_VERTS; xmin .. ymax are this lane's
+// bounds over the vertices it copied, as given.
+struct LongRing { int n; P2 first; double xmin, ymin, xmax, ymax; };
+__device__ __forceinline__ LongRing stage_long_ring(const int64_t* __restrict__ off, const double* __restrict__ xy, int64_t p,
+                                                    double2* __restrict__ pts) {
+  const int64_t b = off[p];
+  const int n = __builtin_amdgcn_readfirstlane((int)open_count(xy, b, off[p + 1]));
+  const double2 first = reinterpret_cast<const double2*>(xy)[b];
+  LongRing r{n, P2{first.x, first.y}, first.x, first.y, first.x, first.y};
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += kWave) {
+    const double2 v = reinterpret_cast<const double2*>(xy)[b + i];
+    r.xmin = fmin(r.xmin, v.x); r.xmax = fmax(r.xmax, v.x);
+    r.ymin = fmin(r.ymin, v.y); r.ymax = fmax(r.ymax, v.y);
+    pts[i] = double2{v.x - first.x, v.y - first.y};
+  }
+  __syncthreads();
+  return r;
+}
+
+// ---------------------------------------------------------------- host: workspace and arguments ---
+// the head of a ring consumer's workspace: the words, then one int32 list per route, each long enough for every polygon
+struct RingLists { size_t words, list_short, list_long; };
+inline RingLists take_ring_lists(Carver& c, int64_t n_polygons) {
+  const size_t list_bytes = (size_t)n_polygons * sizeof(int32_t);
+  return RingLists{c.take(kRingWordsBytes), c.take(list_bytes), c.take(list_bytes)};      // a braced list: left to right
+}
+
+// What an entry point rejects about the pointers of a non-empty call: the ring's own (ring_offsets, xy, workspace) and, in
+// the same order and the same messages, the unit's further ones: whether the required ones are there, whether they are
+// aligned, and how the two alignment messages name the lot ("ring_offsets and ...", "... xy").
+struct OtherPointers { bool present, aligned8, aligned16; const char *names8, *names16; };
+inline int check_ring_call(const char* who, const int64_t* ring_offsets, const double* xy, int64_t n_vertices, const void* workspace,
+                           int64_t workspace_bytes, size_t need, const OtherPointers& o) {
+  SEGGER_REQUIRE(ring_offsets && workspace && o.present, "%s: NULL pointer", who);
+  SEGGER_REQUIRE(xy || n_vertices == 0, "%s: NULL xy with n_vertices > 0", who);
+  SEGGER_REQUIRE(is_aligned(ring_offsets, 8) && o.aligned8, "%s: %s must be 8-byte aligned", who, o.names8);
+  SEGGER_REQUIRE(is_aligned(xy, 16) && o.aligned16, "%s: %s must be 16-byte aligned", who, o.names16);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  SEGGER_REQUIRE((size_t)workspace_bytes >= need, "%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, need);
+  return SEGGER_OK;
+}
+
+}  // namespace segger

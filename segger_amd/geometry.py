@@ -37,7 +37,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .morphology import _rings
+from .rings import raise_ring_errors, ring_csr
 
 __all__ = ["points_in_polygons"]
 
@@ -74,7 +74,7 @@ def points_in_polygons(points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer:
         raise ValueError(f"{who}: points is a floating-point [n_points, 2] tensor")
     if not points_per_cell > 0 or not math.isfinite(points_per_cell):
         raise ValueError(f"{who}: points_per_cell must be positive and finite")
-    ring_offsets, xy, n_polygons, n_vertices = _rings(ring_offsets, xy)
+    ring_offsets, xy, n_polygons, n_vertices = ring_csr(who, ring_offsets, xy)
     if points.device != xy.device:
         raise ValueError(f"{who}: points and the rings are on different devices")
     n_points = int(points.shape[0])
@@ -131,13 +131,7 @@ def points_in_polygons(points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer:
     point_id = torch.empty(total, dtype=torch.int64, device=dev)
     if total > 0:
         L.call("segger_polygon_join_fill", dev, *args, point_id.data_ptr(), total, ws.data_ptr(), ws_bytes)
-    flag = int(ws[:4].view(torch.int32))                                                # the third
-    if flag & L.PJOIN_ERR_OFFSETS:
-        bad = (ring_offsets[:-1] < 0) | (ring_offsets[1:] < ring_offsets[:-1]) | (ring_offsets[1:] > n_vertices)
-        raise ValueError(f"{who}: ring_offsets of polygon {int(bad.nonzero()[0])} are negative, descending or beyond the "
-                         f"{n_vertices} vertices")
-    if flag:
-        raise ValueError(f"{who}: the device reported error word {flag}")
+    raise_ring_errors(who, int(ws[:4].view(torch.int32)), ring_offsets, n_vertices)          # the third
     # polygon-major -> sorted by (point, polygon): within a point the stable sort keeps the polygons ascending
     polygon_id = torch.repeat_interleave(torch.arange(n_polygons, dtype=torch.int64, device=dev),
                                          pair_offsets[1:] - pair_offsets[:-1], output_size=total)

@@ -26,40 +26,17 @@ Polygons are single exterior rings: no holes, no multi-part polygons, no bufferi
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict
 
 import torch
 from torch import Tensor
 
 from . import _lib as L
+from .rings import raise_ring_errors, ring_csr, rings_from_padded
 
 __all__ = ["polygon_props", "morphology_features", "rings_from_padded"]
 
 _COLS = ("area", "hull_area", "rect_area", "envelope_area", "radius")
-
-
-def _rings(ring_offsets: Tensor, xy: Tensor) -> Tuple[Tensor, Tensor, int, int]:
-    if not isinstance(ring_offsets, Tensor) or not isinstance(xy, Tensor):
-        raise ValueError("polygon_props: ring_offsets and xy are tensors")
-    if ring_offsets.dim() != 1 or ring_offsets.numel() < 1 or ring_offsets.dtype not in (torch.int64, torch.int32):
-        raise ValueError("polygon_props: ring_offsets is an int64 (or int32) vector of n_polygons + 1 entries")
-    if xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_floating_point():
-        raise ValueError("polygon_props: xy is a floating-point [n_vertices, 2] tensor")
-    if ring_offsets.device != xy.device:
-        raise ValueError("polygon_props: ring_offsets and xy are on different devices")
-    n_polygons, n_vertices = int(ring_offsets.numel()) - 1, int(xy.shape[0])
-    ring_offsets = ring_offsets.detach().to(torch.int64).contiguous()
-    xy = xy.detach().to(torch.float64).contiguous()
-    if n_polygons > 0:
-        # the cap is refused here, before the call: the ring lengths are device memory the C entry point cannot read
-        # without a synchronisation (a closing duplicate vertex does not count, hence the + 1)
-        longest, where = (ring_offsets[1:] - ring_offsets[:-1]).max(dim=0)
-        longest, where = int(longest), int(where)
-        if longest > L.MORPH_MAX_VERTS + 1 or (longest == L.MORPH_MAX_VERTS + 1 and not torch.equal(
-                xy[int(ring_offsets[where])], xy[int(ring_offsets[where + 1]) - 1])):
-            raise ValueError(f"polygon_props: polygon {where} has {longest} vertices, more than SEGGER_MORPH_MAX_VERTS = "
-                             f"{L.MORPH_MAX_VERTS}")
-    return ring_offsets, xy, n_polygons, n_vertices
 
 
 def polygon_props(ring_offsets: Tensor, xy: Tensor) -> Dict[str, Tensor]:
@@ -74,7 +51,7 @@ def polygon_props(ring_offsets: Tensor, xy: Tensor) -> Dict[str, Tensor]:
     extent as ``radius``.  Raises ``ValueError`` for bad shapes or dtypes, for a ring above ``SEGGER_MORPH_MAX_VERTS``
     (naming the polygon, before anything is launched) and for offsets the device found descending or out of range.  Waits
     for the device twice (the longest ring, the error word)."""
-    ring_offsets, xy, n_polygons, n_vertices = _rings(ring_offsets, xy)
+    ring_offsets, xy, n_polygons, n_vertices = ring_csr("polygon_props", ring_offsets, xy)
     L.need_device("polygon_props", ring_offsets, xy, hint="tests/morphology_cases.py holds the CPU oracle")
     dev = xy.device
     props = torch.empty(n_polygons, L.MORPH_COLS, dtype=torch.float64, device=dev)
@@ -82,13 +59,7 @@ def polygon_props(ring_offsets: Tensor, xy: Tensor) -> Dict[str, Tensor]:
         ws, ws_bytes = L.workspace("segger_morphology_workspace_bytes", dev, n_polygons)
         L.call("segger_polygon_props", dev, ring_offsets.data_ptr(), xy.data_ptr(), n_polygons, n_vertices, props.data_ptr(),
                ws.data_ptr(), ws_bytes)
-        flag = int(ws[:4].view(torch.int32))
-        if flag & L.MORPH_ERR_OFFSETS:
-            bad = (ring_offsets[:-1] < 0) | (ring_offsets[1:] < ring_offsets[:-1]) | (ring_offsets[1:] > n_vertices)
-            raise ValueError(f"polygon_props: ring_offsets of polygon {int(bad.nonzero()[0])} are negative, descending or beyond "
-                             f"the {n_vertices} vertices")
-        if flag:
-            raise ValueError(f"polygon_props: the device reported error word {flag}")
+        raise_ring_errors("polygon_props", int(ws[:4].view(torch.int32)), ring_offsets, n_vertices)
     out = {name: props[:, c] for c, name in enumerate(_COLS)}
     out["convexity"] = out["hull_area"] / out["area"]
     out["elongation"] = out["rect_area"] / out["envelope_area"]
@@ -106,17 +77,3 @@ def morphology_features(ring_offsets: Tensor, xy: Tensor, out_dtype: torch.dtype
     ``cells_representation="morphology"``."""
     p = polygon_props(ring_offsets, xy)
     return torch.stack([p["area"], p["convexity"], p["elongation"], p["circularity"]], dim=1).to(out_dtype)
-
-
-def rings_from_padded(vertices: Tensor, counts: Tensor) -> Tuple[Tensor, Tensor]:
-    """``(ring_offsets, xy)`` from padded rings: ``vertices`` ``[P, L, 2]`` of which row ``p`` uses its first
-    ``counts[p]`` entries (Xenium's boundaries are fixed 13- or 25-vertex rings).  Plain torch on the tensors' device."""
-    if vertices.dim() != 3 or vertices.shape[2] != 2 or counts.dim() != 1 or counts.numel() != vertices.shape[0]:
-        raise ValueError("rings_from_padded: vertices is [P, L, 2] and counts [P]")
-    counts = counts.to(torch.int64)
-    if counts.numel() and (int(counts.min()) < 0 or int(counts.max()) > vertices.shape[1]):
-        raise ValueError("rings_from_padded: counts outside 0 .. L")
-    ring_offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=vertices.device)
-    torch.cumsum(counts, 0, out=ring_offsets[1:])
-    used = torch.arange(vertices.shape[1], device=vertices.device)[None, :] < counts[:, None]
-    return ring_offsets, vertices[used]
