@@ -720,10 +720,54 @@ static const int kMinStagesPerBlock = [] {
   return v >= 4 && v <= 1024 ? v : 32;
 }();
 
+// ---- the instantiated shapes ------------------------------------------------------------------------------------------
+// A new shape is added to one of these three lists and nowhere else: the *_supported queries, the checks of the entry
+// points and the dispatchers below are all generated from them.
+#define SEGGER_WGRAD_SHAPES(X) /* (M, K): dW / db */                                                                    \
+  X(384, 256) X(384, 128) X(384, 64) X(192, 256) X(192, 128) X(192, 64) X(128, 256) X(128, 128) X(128, 64)              \
+  X(64, 256) X(64, 128) X(64, 64)
+constexpr int kDxK = 128;
+#define SEGGER_WGRAD_DX_SHAPES(X) /* M: dX as well, K = kDxK */ X(384) X(192) X(128) X(64)
+// (MA, MB, K, NW, DX): two sides in one launch -- the pairs of the default encoder: a hetero layer ([lin_l | lin_r | lin_l]
+// of the transcripts + lin_r of the boundaries; the first layer reads K = 256 and has no one-pass data gradient) and
+// lin_last of both node types
+#define SEGGER_WGRAD_PAIR_SHAPES(X)                                                                                     \
+  X(384, 128, 128, 8, true) X(384, 128, 256, 8, false) X(64, 64, 128, 4, true) X(384, 128, 128, 8, false)               \
+  X(64, 64, 128, 4, false)
+
+constexpr int waves_for(int m) { return m % 128 == 0 ? 8 : 4; }
+
 bool shape_ok(int m, int k) {
-  return (m == 384 || m == 192 || m == 128 || m == 64) && (k == 256 || k == 128 || k == 64);
+#define X(MM, KK) || (m == MM && k == KK)
+  return false SEGGER_WGRAD_SHAPES(X);
+#undef X
 }
-int waves_for(int m) { return m % 128 == 0 ? 8 : 4; }
+bool dx_shape_ok(int m, int k) {
+#define X(MM) || m == MM
+  return k == kDxK && (false SEGGER_WGRAD_DX_SHAPES(X));
+#undef X
+}
+bool dx_gate_ok(int m, int k) {          // WgGeo::GATE_OK of the instantiated shapes
+#define X(MM) || (m == MM && WgGeo<MM, kDxK, waves_for(MM)>::GATE_OK)
+  return k == kDxK && (false SEGGER_WGRAD_DX_SHAPES(X));
+#undef X
+}
+
+// What an entry point asks of wgrad_kernel: dW / db; those and dX (optionally times gelu'(gate)); dW / db against the
+// X operand generated from one coordinate per row (the positional embedder's first layer, one shape)
+enum class WgradForm { kPlain, kDx, kGen };
+constexpr const char* kFormLabel[] = {"wgrad_kernel", "wgrad_kernel (dX)", "wgrad_kernel (generated operand)"};
+
+bool form_supported(WgradForm form, int m, int k, int dtype) {
+  const bool b16 = dtype == SEGGER_BF16 || dtype == SEGGER_F16;
+  switch (form) {
+    case WgradForm::kPlain: return shape_ok(m, k) && (b16 || dtype == SEGGER_F32);
+    case WgradForm::kDx:    return dx_shape_ok(m, k) && b16;
+    case WgradForm::kGen:   return m == kPbD && k == kPbF && b16;
+  }
+  return false;
+}
+
 // workgroups per CU the register and LDS footprints allow (accumulator registers per lane = M*K / (64*NW);
 // LDS = 4 ring slots of the stage image rounded up to whole 1 KiB chunks per wave)
 int blocks_per_cu(int m, int k, bool dx = false) {
@@ -741,289 +785,54 @@ int blocks_per_cu(int m, int k, bool dx = false) {
   const int b = by_regs < by_lds ? by_regs : by_lds;
   return b < 1 ? 1 : b;
 }
+// persistent grid over 16-row stages: at least kMinStagesPerBlock stages per workgroup, 1 .. cap workgroups
+int64_t persistent_grid(int64_t n_rows, int64_t cap) {
+  const int64_t want = ceil_div(ceil_div(n_rows, kStageRows), kMinStagesPerBlock);
+  return want < 1 ? 1 : (want < cap ? want : cap);
+}
 int64_t grid_for(int64_t n_rows, int m, int k, bool dx = false) {
-  const int64_t stages = (n_rows + kStageRows - 1) / kStageRows;
-  const int64_t cap = (int64_t)kNumCu * blocks_per_cu(m, k, dx);
-  const int64_t want = (stages + kMinStagesPerBlock - 1) / kMinStagesPerBlock;
-  return want < cap ? (want < 1 ? 1 : want) : cap;
+  return persistent_grid(n_rows, (int64_t)kNumCu * blocks_per_cu(m, k, dx));
 }
+// the fused positional backward: 2 workgroups per CU (VALU-bound on the regenerated features; every workgroup leaves an
+// 82 KB partial)
+int64_t posmlp_bwd_grid(int64_t n_rows) { return persistent_grid(n_rows, 2 * kNumCu); }
 
-template <typename T, int M, int K>
+template <typename T, int M, int K, bool GEN, bool DX>
 void launch_wgrad(const WgradParams& p, int64_t grid, hipStream_t stream) {
-  constexpr int NW = M % 128 == 0 ? 8 : 4;
-  hipLaunchKernelGGL((wgrad_kernel<T, M, K, NW>), dim3((unsigned)grid), dim3(NW * 64), 0, stream, p);
+  constexpr int NW = waves_for(M);
+  hipLaunchKernelGGL((wgrad_kernel<T, M, K, NW, GEN, DX>), dim3((unsigned)grid), dim3(NW * 64), 0, stream, p);
 }
 
-int reduce_partials(float* partial, int64_t grid, int m_out, int k_in, float* grad_w, float* grad_b, hipStream_t stream);
-
-template <typename T, int M, int K>
-void launch_wgrad_dx(const WgradParams& p, int64_t grid, hipStream_t stream) {
-  constexpr int NW = M % 128 == 0 ? 8 : 4;
-  hipLaunchKernelGGL((wgrad_kernel<T, M, K, NW, false, true>), dim3((unsigned)grid), dim3(NW * 64), 0, stream, p);
-}
-
-bool dx_shape_ok(int m, int k) { return k == 128 && (m == 384 || m == 192 || m == 128 || m == 64); }
-bool dx_gate_ok(int m, int k) {          // WgGeo::GATE_OK of the instantiated shapes
-  return k == 128 && ((m == 384 && WgGeo<384, 128, 8>::GATE_OK) || (m == 128 && WgGeo<128, 128, 8>::GATE_OK));
-}
-
+// -> false: no kernel of that form and shape (form_supported said otherwise)
 template <typename T>
-int dispatch_wgrad_dx(const WgradParams& p, int m, int64_t grid, hipStream_t stream) {
-  switch (m) {
-    case 384: launch_wgrad_dx<T, 384, 128>(p, grid, stream); return SEGGER_OK;
-    case 192: launch_wgrad_dx<T, 192, 128>(p, grid, stream); return SEGGER_OK;
-    case 128: launch_wgrad_dx<T, 128, 128>(p, grid, stream); return SEGGER_OK;
-    case 64:  launch_wgrad_dx<T, 64, 128>(p, grid, stream); return SEGGER_OK;
+bool dispatch_wgrad(WgradForm form, const WgradParams& p, int m, int k, int64_t grid, hipStream_t stream) {
+#define PLAIN(MM, KK) if (m == MM && k == KK) { launch_wgrad<T, MM, KK, false, false>(p, grid, stream); return true; }
+#define WITH_DX(MM) if (m == MM && k == kDxK) { launch_wgrad<T, MM, kDxK, false, true>(p, grid, stream); return true; }
+  switch (form) {
+    case WgradForm::kPlain: SEGGER_WGRAD_SHAPES(PLAIN) break;
+    case WgradForm::kDx:    SEGGER_WGRAD_DX_SHAPES(WITH_DX) break;
+    case WgradForm::kGen:   launch_wgrad<T, kPbD, kPbF, true, false>(p, grid, stream); return true;
   }
-  set_error("segger_linear_wgrad_dx: m_out=%d not supported", m);
-  return SEGGER_EUNSUPPORTED;
+#undef PLAIN
+#undef WITH_DX
+  return false;
 }
 
+// -> false: no paired kernel for these two shapes
 template <typename T>
-int dispatch_wgrad(const WgradParams& p, int m, int k, int64_t grid, hipStream_t stream) {
-#define CASE(MM, KK) if (m == MM && k == KK) { launch_wgrad<T, MM, KK>(p, grid, stream); return SEGGER_OK; }
-  CASE(384, 256) CASE(384, 128) CASE(384, 64)
-  CASE(192, 256) CASE(192, 128) CASE(192, 64)
-  CASE(128, 256) CASE(128, 128) CASE(128, 64)
-  CASE(64, 256) CASE(64, 128) CASE(64, 64)
-#undef CASE
-  set_error("segger_linear_wgrad: m_out=%d k_in=%d not supported", m, k);
-  return SEGGER_EUNSUPPORTED;
-}
-
-}  // namespace
-}  // namespace segger
-
-using namespace segger;
-
-extern "C" int segger_linear_wgrad_supported(int32_t m_out, int32_t k_in, int32_t dtype) {
-  return shape_ok(m_out, k_in) && (dtype == SEGGER_BF16 || dtype == SEGGER_F16 || dtype == SEGGER_F32);
-}
-
-extern "C" size_t segger_linear_wgrad_workspace_bytes(int64_t n_rows, int32_t m_out, int32_t k_in) {
-  if (n_rows <= 0 || !shape_ok(m_out, k_in)) return 16;
-  const size_t b16 = (size_t)(grid_for(n_rows, m_out, k_in) + kRedGroups) * ((size_t)m_out * k_in + m_out) * sizeof(float);
-  size_t b32 = wgrad_f32_workspace_bytes(n_rows, m_out, k_in);             // (the fp32 kernels' slab counts)
-  if (wgrad_f32_split_shape_ok(m_out, k_in)) {
-    const size_t bs = (size_t)(wgrad_f32_split_grid(n_rows, m_out, k_in) + kRedGroups) * ((size_t)m_out * k_in + m_out) * sizeof(float);
-    b32 = bs > b32 ? bs : b32;
-  }
-  return b16 > b32 ? b16 : b32;
-}
-
-extern "C" int segger_linear_wgrad_dx_supported(int32_t m_out, int32_t k_in, int32_t dtype) {
-  return dx_shape_ok(m_out, k_in) && (dtype == SEGGER_BF16 || dtype == SEGGER_F16);
-}
-
-extern "C" int segger_linear_wgrad_dx_gate_supported(int32_t m_out, int32_t k_in, int32_t dtype) {
-  return segger_linear_wgrad_dx_supported(m_out, k_in, dtype) && dx_gate_ok(m_out, k_in);
-}
-
-extern "C" int segger_linear_wgrad_dx(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, const void* w_t,
-                                      int64_t n_rows, int32_t m_out, int32_t k_in, int32_t dtype, float* grad_w,
-                                      float* grad_b, void* dx, int64_t ld_dx, const void* gelu_gate, int64_t ld_gate,
-                                      void* workspace, size_t workspace_bytes, segger_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SEGGER_REQUIRE(n_rows >= 0 && m_out > 0 && k_in > 0, "segger_linear_wgrad_dx: bad sizes");
-  SEGGER_REQUIRE(grad_w != nullptr, "segger_linear_wgrad_dx: grad_w is NULL");
-  if (!segger_linear_wgrad_dx_supported(m_out, k_in, dtype)) {
-    set_error("segger_linear_wgrad_dx: m_out=%d k_in=%d dtype=%d not supported (m_out in {64,128,192,384}, k_in 128, "
-              "bf16/f16)", m_out, k_in, dtype);
-    return SEGGER_EUNSUPPORTED;
-  }
-  if (n_rows == 0) {
-    SEGGER_HIP(hipMemsetAsync(grad_w, 0, (size_t)m_out * k_in * sizeof(float), stream));
-    if (grad_b) SEGGER_HIP(hipMemsetAsync(grad_b, 0, (size_t)m_out * sizeof(float), stream));
-    return SEGGER_OK;
-  }
-  SEGGER_REQUIRE(dy && x && w_t && dx, "segger_linear_wgrad_dx: NULL pointer");
-  SEGGER_REQUIRE(is_aligned(dy, 16) && is_aligned(x, 16) && is_aligned(w_t, 16) && is_aligned(dx, 16),
-                 "segger_linear_wgrad_dx: pointers must be 16-byte aligned");
-  SEGGER_REQUIRE(ld_dy >= m_out && ld_x >= k_in && ld_dx >= k_in && (ld_dy * 2) % 16 == 0 && (ld_x * 2) % 16 == 0 &&
-                     (ld_dx * 2) % 16 == 0, "segger_linear_wgrad_dx: bad leading dimension");
-  if (gelu_gate) {
-    SEGGER_REQUIRE(dx_gate_ok(m_out, k_in), "segger_linear_wgrad_dx: the gate form covers m_out in {128, 384} (k_in 128)");
-    SEGGER_REQUIRE(is_aligned(gelu_gate, 16) && ld_gate >= k_in && (ld_gate * 2) % 16 == 0,
-                   "segger_linear_wgrad_dx: gate rows must be 16-byte aligned");
-  }
-  const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in);     // (the dX form never uses more slabs)
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("segger_linear_wgrad_dx: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
-  const int64_t grid = grid_for(n_rows, m_out, k_in, true);
-  const int64_t stages = (n_rows + kStageRows - 1) / kStageRows;
-  {
-    const int64_t span = ((stages + grid - 1) / grid) * kStageRows * (ld_dy > ld_x ? ld_dy : ld_x) * 2;
-    SEGGER_REQUIRE(span < (int64_t)kOutOfRange, "segger_linear_wgrad_dx: a workgroup's row slab exceeds 1 GiB");
-  }
-  {
-    const int64_t span_g = ((stages + grid - 1) / grid) * kStageRows * ld_gate * 2;
-    SEGGER_REQUIRE(!gelu_gate || span_g < (int64_t)kOutOfRange, "segger_linear_wgrad_dx: a workgroup's row slab exceeds 1 GiB");
-  }
-  WgradParams p{dy, ld_dy, x, ld_x, n_rows, stages, (stages + grid - 1) / grid, static_cast<float*>(workspace), nullptr, 0.f,
-                w_t, dx, ld_dx, gelu_gate, ld_gate};
-  const int rc = dtype == SEGGER_BF16 ? dispatch_wgrad_dx<bf16_t>(p, m_out, grid, stream)
-                                      : dispatch_wgrad_dx<f16_t>(p, m_out, grid, stream);
-  if (rc != SEGGER_OK) return rc;
-  SEGGER_LAUNCH_CHECK("wgrad_kernel (dX)");
-  return reduce_partials(p.partial, grid, m_out, k_in, grad_w, grad_b, stream);
-}
-
-extern "C" int segger_linear_wgrad(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t n_rows,
-                                   int32_t m_out, int32_t k_in, int32_t dtype, float* grad_w, float* grad_b,
-                                   void* workspace, size_t workspace_bytes, segger_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SEGGER_REQUIRE(n_rows >= 0 && m_out > 0 && k_in > 0, "segger_linear_wgrad: bad sizes");
-  SEGGER_REQUIRE(grad_w != nullptr, "segger_linear_wgrad: grad_w is NULL");
-  if (!segger_linear_wgrad_supported(m_out, k_in, dtype)) {
-    set_error("segger_linear_wgrad: m_out=%d k_in=%d dtype=%d not supported (m_out in {64,128,192,384}, k_in in "
-              "{64,128,256}, bf16/f16)", m_out, k_in, dtype);
-    return SEGGER_EUNSUPPORTED;
-  }
-  if (n_rows == 0) {
-    SEGGER_HIP(hipMemsetAsync(grad_w, 0, (size_t)m_out * k_in * sizeof(float), stream));
-    if (grad_b) SEGGER_HIP(hipMemsetAsync(grad_b, 0, (size_t)m_out * sizeof(float), stream));
-    return SEGGER_OK;
-  }
-  SEGGER_REQUIRE(dy && x, "segger_linear_wgrad: NULL input");
-  SEGGER_REQUIRE(is_aligned(dy, 16) && is_aligned(x, 16), "segger_linear_wgrad: inputs must be 16-byte aligned");
-  const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("segger_linear_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
-  if (dtype == SEGGER_F32) {       // fp32 storage: exact-fp32 MFMA kernel (csrc/linear_f32.hip), same partial sums
-    SEGGER_REQUIRE(ld_dy >= m_out && ld_x >= k_in, "segger_linear_wgrad: bad leading dimension");
-    int64_t slabs = 0;
-    const int rc32 = wgrad_f32_launch(dy, ld_dy, x, ld_x, n_rows, m_out, k_in, static_cast<float*>(workspace), &slabs, stream);
-    if (rc32 != SEGGER_OK) return rc32;
-    return reduce_partials(static_cast<float*>(workspace), slabs, m_out, k_in, grad_w, grad_b, stream);
-  }
-  SEGGER_REQUIRE(ld_dy >= m_out && ld_x >= k_in && (ld_dy * 2) % 16 == 0 && (ld_x * 2) % 16 == 0,
-                 "segger_linear_wgrad: bad leading dimension");
-  const int64_t grid = grid_for(n_rows, m_out, k_in);
-  {
-    // buffer resources address one workgroup's slab with 32-bit offsets
-    const int64_t stages = (n_rows + kStageRows - 1) / kStageRows;
-    const int64_t span = ((stages + grid - 1) / grid) * kStageRows * (ld_dy > ld_x ? ld_dy : ld_x) * 2;
-    SEGGER_REQUIRE(span < (int64_t)kOutOfRange, "segger_linear_wgrad: a workgroup's row slab exceeds 1 GiB");
-  }
-  WgradParams p{dy, ld_dy, x, ld_x, n_rows, (n_rows + kStageRows - 1) / kStageRows, 0, static_cast<float*>(workspace)};
-  p.stages_per_block = (p.n_stages + grid - 1) / grid;
-  const int rc = dtype == SEGGER_BF16 ? dispatch_wgrad<bf16_t>(p, m_out, k_in, grid, stream)
-                                      : dispatch_wgrad<f16_t>(p, m_out, k_in, grid, stream);
-  if (rc != SEGGER_OK) return rc;
-  SEGGER_LAUNCH_CHECK("wgrad_kernel");
-  return reduce_partials(p.partial, grid, m_out, k_in, grad_w, grad_b, stream);
-}
-
-// ---- two backward passes in one launch -----------------------------------------------------------------------------
-namespace segger {
-namespace {
-template <typename T>
-bool launch_wgrad_pair(const WgradParams& a, int ma, int64_t grid_a, const WgradParams& b, int mb, int64_t grid_b, int k,
-                       bool dx, hipStream_t stream) {
+bool dispatch_wgrad_pair(const WgradParams& a, int ma, int64_t grid_a, const WgradParams& b, int mb, int64_t grid_b, int k,
+                         bool dx, hipStream_t stream) {
   const dim3 grid((unsigned)(grid_a + grid_b));
 #define PAIR(MA, MB, KK, NWW, DXX)                                                                                     \
   if (ma == MA && mb == MB && k == KK && dx == DXX) {                                                                  \
     hipLaunchKernelGGL((wgrad_pair_kernel<T, MA, MB, KK, NWW, DXX>), grid, dim3(NWW * 64), 0, stream, a, b, (int)grid_b); \
     return true;                                                                                                       \
   }
-  // the pairs of the default encoder: a hetero layer ([lin_l | lin_r | lin_l] of the transcripts + lin_r of the
-  // boundaries; the first layer reads K = 256 and has no one-pass data gradient) and lin_last of both node types
-  PAIR(384, 128, 128, 8, true) PAIR(384, 128, 256, 8, false) PAIR(64, 64, 128, 4, true)
-  PAIR(384, 128, 128, 8, false) PAIR(64, 64, 128, 4, false)
+  SEGGER_WGRAD_PAIR_SHAPES(PAIR)
 #undef PAIR
   return false;
 }
-}  // namespace
-}  // namespace segger
 
-extern "C" int segger_linear_wgrad_f32_split(const float* dy, int64_t ld_dy, const float* x, int64_t ld_x, int64_t n_rows,
-                                             int32_t m_out, int32_t k_in, float* grad_w, float* grad_b, void* workspace,
-                                             size_t workspace_bytes, segger_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SEGGER_REQUIRE(n_rows >= 0 && grad_w != nullptr, "segger_linear_wgrad_f32_split: bad sizes or NULL grad_w");
-  if (!wgrad_f32_split_shape_ok(m_out, k_in)) {
-    set_error("segger_linear_wgrad_f32_split: m_out=%d k_in=%d not supported", m_out, k_in);
-    return SEGGER_EUNSUPPORTED;
-  }
-  if (n_rows == 0) {
-    SEGGER_HIP(hipMemsetAsync(grad_w, 0, (size_t)m_out * k_in * sizeof(float), stream));
-    if (grad_b) SEGGER_HIP(hipMemsetAsync(grad_b, 0, (size_t)m_out * sizeof(float), stream));
-    return SEGGER_OK;
-  }
-  SEGGER_REQUIRE(dy && x && is_aligned(dy, 16) && is_aligned(x, 16) && ld_dy >= m_out && ld_x >= k_in && ld_dy % 4 == 0 && ld_x % 4 == 0,
-                 "segger_linear_wgrad_f32_split: rows must be 16-byte aligned");
-  const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("segger_linear_wgrad_f32_split: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
-  int64_t slabs = 0;
-  const int rc = wgrad_f32_split_launch(dy, ld_dy, x, ld_x, n_rows, m_out, k_in, static_cast<float*>(workspace), &slabs, stream);
-  if (rc != SEGGER_OK) return rc;
-  return reduce_partials(static_cast<float*>(workspace), slabs, m_out, k_in, grad_w, grad_b, stream);
-}
-
-extern "C" int segger_linear_wgrad_pair(const segger_wgrad_args* a, const segger_wgrad_args* b, int32_t k_in, int32_t dtype,
-                                        segger_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SEGGER_REQUIRE(a && b, "segger_linear_wgrad_pair: NULL args");
-  const segger_wgrad_args* both[2] = {a, b};
-  const bool dx = a->w_t != nullptr;
-  auto separately = [&]() -> int {
-    for (const segger_wgrad_args* q : both) {
-      const int rc = q->w_t ? segger_linear_wgrad_dx(q->dy, q->ld_dy, q->x, q->ld_x, q->w_t, q->n_rows, q->m_out, k_in, dtype,
-                                                     q->grad_w, q->grad_b, q->dx, q->ld_dx, nullptr, 0, q->workspace,
-                                                     q->workspace_bytes, stream_)
-                            : segger_linear_wgrad(q->dy, q->ld_dy, q->x, q->ld_x, q->n_rows, q->m_out, k_in, dtype, q->grad_w,
-                                                  q->grad_b, q->workspace, q->workspace_bytes, stream_);
-      if (rc != SEGGER_OK) return rc;
-    }
-    return SEGGER_OK;
-  };
-  if ((dtype != SEGGER_BF16 && dtype != SEGGER_F16) || (b->w_t != nullptr) != dx || a->n_rows <= 0 || b->n_rows <= 0)
-    return separately();
-  WgradParams p[2];
-  int64_t grid[2];
-  for (int i = 0; i < 2; ++i) {
-    const segger_wgrad_args* q = both[i];
-    const bool ok = dx ? segger_linear_wgrad_dx_supported(q->m_out, k_in, dtype) : segger_linear_wgrad_supported(q->m_out, k_in, dtype);
-    if (!ok) return separately();
-    SEGGER_REQUIRE(q->grad_w != nullptr, "segger_linear_wgrad_pair: grad_w is NULL");
-    SEGGER_REQUIRE(q->dy && q->x && (!dx || q->dx), "segger_linear_wgrad_pair: NULL pointer");
-    SEGGER_REQUIRE(is_aligned(q->dy, 16) && is_aligned(q->x, 16) && is_aligned(q->w_t, 16) && is_aligned(q->dx, 16),
-                   "segger_linear_wgrad_pair: pointers must be 16-byte aligned");
-    SEGGER_REQUIRE(q->ld_dy >= q->m_out && q->ld_x >= k_in && (q->ld_dy * 2) % 16 == 0 && (q->ld_x * 2) % 16 == 0 &&
-                       (!dx || (q->ld_dx >= k_in && (q->ld_dx * 2) % 16 == 0)), "segger_linear_wgrad_pair: bad leading dimension");
-    const size_t need = segger_linear_wgrad_workspace_bytes(q->n_rows, q->m_out, k_in);
-    if (q->workspace == nullptr || q->workspace_bytes < need) {
-      set_error("segger_linear_wgrad_pair: workspace %zu < %zu bytes", q->workspace_bytes, need);
-      return SEGGER_EWORKSPACE;
-    }
-    grid[i] = grid_for(q->n_rows, q->m_out, k_in, dx);
-    const int64_t stages = (q->n_rows + kStageRows - 1) / kStageRows;
-    const int64_t span = ((stages + grid[i] - 1) / grid[i]) * kStageRows * (q->ld_dy > q->ld_x ? q->ld_dy : q->ld_x) * 2;
-    SEGGER_REQUIRE(span < (int64_t)kOutOfRange, "segger_linear_wgrad_pair: a workgroup's row slab exceeds 1 GiB");
-    p[i] = WgradParams{q->dy, q->ld_dy, q->x, q->ld_x, q->n_rows, stages, (stages + grid[i] - 1) / grid[i],
-                       static_cast<float*>(q->workspace), nullptr, 0.f, q->w_t, q->dx, q->ld_dx, nullptr, 0};
-  }
-  const bool launched = dtype == SEGGER_BF16
-      ? launch_wgrad_pair<bf16_t>(p[0], a->m_out, grid[0], p[1], b->m_out, grid[1], k_in, dx, stream)
-      : launch_wgrad_pair<f16_t>(p[0], a->m_out, grid[0], p[1], b->m_out, grid[1], k_in, dx, stream);
-  if (!launched) return separately();
-  SEGGER_LAUNCH_CHECK("wgrad_pair_kernel");
-  for (int i = 0; i < 2; ++i) {
-    const int rc = reduce_partials(p[i].partial, grid[i], both[i]->m_out, k_in, both[i]->grad_w, both[i]->grad_b, stream);
-    if (rc != SEGGER_OK) return rc;
-  }
-  return SEGGER_OK;
-}
-
-namespace segger {
-namespace {
 int reduce_partials(float* partial, int64_t grid, int m_out, int k_in, float* grad_w, float* grad_b, hipStream_t stream) {
   const int64_t width = (int64_t)m_out * k_in + m_out;
   if (defer_reduce(ReduceSeg{partial, grid, width, (int64_t)m_out * k_in, grad_w, grad_b, partial + grid * width}, stream))
@@ -1042,52 +851,227 @@ int reduce_partials(float* partial, int64_t grid, int m_out, int k_in, float* gr
   SEGGER_LAUNCH_CHECK("wgrad_reduce_kernel");
   return SEGGER_OK;
 }
+
+// the result over no rows: dW = 0, and db = 0 where it is wanted
+int zero_wgrad(float* grad_w, float* grad_b, int m_out, int k_in, hipStream_t stream) {
+  SEGGER_HIP(hipMemsetAsync(grad_w, 0, (size_t)m_out * k_in * sizeof(float), stream));
+  if (grad_b) SEGGER_HIP(hipMemsetAsync(grad_b, 0, (size_t)m_out * sizeof(float), stream));
+  return SEGGER_OK;
+}
+
+int require_workspace(const char* who, const void* workspace, size_t have, size_t need) {
+  return workspace != nullptr && have >= need ? SEGGER_OK : workspace_too_small(who, have, need);
+}
+
+// fp32 storage: the exact-fp32 MFMA kernel (csrc/linear_f32.hip) or the six bf16 partial products
+// (csrc/linear_f32_split.hip) leave the same partial sums, summed as the 16-bit kernels' are
+int wgrad_f32(bool split, const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t n_rows, int m_out, int k_in,
+              float* grad_w, float* grad_b, void* workspace, hipStream_t stream) {
+  float* partial = static_cast<float*>(workspace);
+  int64_t slabs = 0;
+  const int rc = split ? wgrad_f32_split_launch(static_cast<const float*>(dy), ld_dy, static_cast<const float*>(x), ld_x,
+                                                n_rows, m_out, k_in, partial, &slabs, stream)
+                       : wgrad_f32_launch(dy, ld_dy, x, ld_x, n_rows, m_out, k_in, partial, &slabs, stream);
+  if (rc != SEGGER_OK) return rc;
+  return reduce_partials(partial, slabs, m_out, k_in, grad_w, grad_b, stream);
+}
+
+// ---- one request, one planner ------------------------------------------------------------------------------------------
+// One side of a weight-gradient call as its entry point received it.  The form decides which fields are read: kPlain
+// dy / x; kDx also w_t, dx and the optional gate; kGen dy and pn (x is generated).
+struct WgradRequest {
+  const char* who;                 // the entry point, for messages
+  WgradForm form;
+  int k_in, dtype;
+  segger_wgrad_args a;
+  const void* gate = nullptr; int64_t ld_gate = 0;     // kDx, optional
+  const float* pn = nullptr; float log_max_period = 0.f;   // kGen
+};
+struct WgradPlan {
+  bool empty;                      // n_rows == 0: nothing to launch, the result is zero_wgrad()
+  WgradParams p;                   // 16-bit dtypes; fp32 (kPlain only) goes to wgrad_f32(), which plans its own slabs
+  int64_t grid;
+};
+
+// Every host check of a weight-gradient call, in one order for every entry point, then the kernel's parameters and grid.
+int plan_wgrad(const WgradRequest& r, WgradPlan* out) {
+  const segger_wgrad_args& a = r.a;
+  const int m = a.m_out, k = r.k_in;
+  const bool dx = r.form == WgradForm::kDx, gen = r.form == WgradForm::kGen, f32 = r.dtype == SEGGER_F32;
+  SEGGER_REQUIRE(a.n_rows >= 0 && m > 0 && k > 0, "%s: bad sizes (negative n_rows, m_out or k_in not positive)", r.who);
+  SEGGER_REQUIRE(a.grad_w != nullptr, "%s: grad_w is NULL", r.who);
+  if (!form_supported(r.form, m, k, r.dtype)) {
+    set_error("%s: m_out=%d k_in=%d dtype=%d not supported", r.who, m, k, r.dtype);
+    return SEGGER_EUNSUPPORTED;
+  }
+  *out = WgradPlan{};
+  if (a.n_rows == 0) { out->empty = true; return SEGGER_OK; }
+
+  // the operands this form reads (the others may hold anything)
+  const void* x = gen ? static_cast<const void*>(r.pn) : a.x;
+  const int64_t ld_x = gen ? 0 : a.ld_x;
+  const void* gate = dx ? r.gate : nullptr;
+  const auto ld_ok = [&](int64_t ld, int64_t width) { return ld >= width && (f32 || (ld * 2) % 16 == 0); };
+  SEGGER_REQUIRE(a.dy && x && (!dx || (a.w_t && a.dx)), "%s: NULL pointer", r.who);
+  SEGGER_REQUIRE(is_aligned(a.dy, 16) && is_aligned(x, 16) && (!dx || (is_aligned(a.w_t, 16) && is_aligned(a.dx, 16))),
+                 "%s: pointers must be 16-byte aligned", r.who);
+  SEGGER_REQUIRE(ld_ok(a.ld_dy, m) && (gen || ld_ok(ld_x, k)) && (!dx || ld_ok(a.ld_dx, k)),
+                 "%s: bad leading dimension (shorter than a row, or rows not 16-byte aligned)", r.who);
+  if (gate) {
+    SEGGER_REQUIRE(dx_gate_ok(m, k), "%s: the gate form does not cover m_out=%d k_in=%d", r.who, m, k);
+    SEGGER_REQUIRE(is_aligned(gate, 16) && ld_ok(r.ld_gate, k), "%s: gate rows must be 16-byte aligned", r.who);
+  }
+  const int rc = require_workspace(r.who, a.workspace, a.workspace_bytes, segger_linear_wgrad_workspace_bytes(a.n_rows, m, k));
+  if (rc != SEGGER_OK || f32) return rc;              // (the dX form never uses more slabs than the size query counts)
+
+  const int64_t grid = grid_for(a.n_rows, m, k, dx);
+  const int64_t stages = ceil_div(a.n_rows, kStageRows), stages_per_block = ceil_div(stages, grid);
+  // buffer resources address one workgroup's slab of dY, X and the gate with 32-bit offsets
+  int64_t ld_max = a.ld_dy > ld_x ? a.ld_dy : ld_x;
+  if (gate && r.ld_gate > ld_max) ld_max = r.ld_gate;
+  SEGGER_REQUIRE(stages_per_block * kStageRows * ld_max * 2 < (int64_t)kOutOfRange, "%s: a workgroup's row slab exceeds 1 GiB",
+                 r.who);
+  WgradParams& p = out->p;
+  p.dy = a.dy;  p.ld_dy = a.ld_dy;
+  p.x = gen ? nullptr : a.x;  p.ld_x = ld_x;
+  p.n_rows = a.n_rows;  p.n_stages = stages;  p.stages_per_block = stages_per_block;
+  p.partial = static_cast<float*>(a.workspace);
+  if (gen) { p.pn = r.pn;  p.log_max_period = r.log_max_period; }
+  if (dx) { p.wt = a.w_t;  p.dx = a.dx;  p.ld_dx = a.ld_dx;  p.gate = gate;  p.ld_gate = r.ld_gate; }
+  out->grid = grid;
+  return SEGGER_OK;
+}
+
+// a single-sided entry point behind its request: plan, dispatch, check the launch, sum the partials
+int run_wgrad(const WgradRequest& r, hipStream_t stream) {
+  const segger_wgrad_args& a = r.a;
+  WgradPlan plan;
+  const int rc = plan_wgrad(r, &plan);
+  if (rc != SEGGER_OK) return rc;
+  if (plan.empty) return zero_wgrad(a.grad_w, a.grad_b, a.m_out, r.k_in, stream);
+  if (r.dtype == SEGGER_F32)
+    return wgrad_f32(false, a.dy, a.ld_dy, a.x, a.ld_x, a.n_rows, a.m_out, r.k_in, a.grad_w, a.grad_b, a.workspace, stream);
+  const bool launched = r.dtype == SEGGER_BF16 ? dispatch_wgrad<bf16_t>(r.form, plan.p, a.m_out, r.k_in, plan.grid, stream)
+                                               : dispatch_wgrad<f16_t>(r.form, plan.p, a.m_out, r.k_in, plan.grid, stream);
+  if (!launched) {
+    set_error("%s: m_out=%d k_in=%d not supported", r.who, a.m_out, r.k_in);
+    return SEGGER_EUNSUPPORTED;
+  }
+  SEGGER_LAUNCH_CHECK(kFormLabel[(int)r.form]);
+  return reduce_partials(plan.p.partial, plan.grid, a.m_out, r.k_in, a.grad_w, a.grad_b, stream);
+}
+
 }  // namespace
 }  // namespace segger
 
-extern "C" int segger_posmlp_wgrad(const void* dz1, int64_t ld_dz1, const float* pn, int64_t n_rows, float max_period,
-                                   int32_t dtype, float* grad_w0, float* grad_b0, void* workspace, size_t workspace_bytes,
-                                   segger_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  constexpr int M = 64, K = 256;
-  SEGGER_REQUIRE(n_rows >= 0, "segger_posmlp_wgrad: negative size");
-  SEGGER_REQUIRE(dtype == SEGGER_BF16 || dtype == SEGGER_F16, "segger_posmlp_wgrad: bf16 / f16 only");
-  SEGGER_REQUIRE(grad_w0 != nullptr, "segger_posmlp_wgrad: grad_w0 is NULL");
-  if (n_rows == 0) {
-    SEGGER_HIP(hipMemsetAsync(grad_w0, 0, (size_t)M * K * sizeof(float), stream));
-    if (grad_b0) SEGGER_HIP(hipMemsetAsync(grad_b0, 0, (size_t)M * sizeof(float), stream));
-    return SEGGER_OK;
-  }
-  SEGGER_REQUIRE(dz1 && pn, "segger_posmlp_wgrad: NULL input");
-  SEGGER_REQUIRE(is_aligned(dz1, 16) && is_aligned(pn, 16) && ld_dz1 >= M && (ld_dz1 * 2) % 16 == 0,
-                 "segger_posmlp_wgrad: dz1 rows and pn must be 16-byte aligned");
-  const size_t need = segger_linear_wgrad_workspace_bytes(n_rows, M, K);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("segger_posmlp_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
-  const int64_t grid = grid_for(n_rows, M, K);
-  const int64_t stages = (n_rows + kStageRows - 1) / kStageRows;
-  SEGGER_REQUIRE(((stages + grid - 1) / grid) * kStageRows * ld_dz1 * 2 < (int64_t)kOutOfRange,
-                 "segger_posmlp_wgrad: a workgroup's row slab exceeds 1 GiB");
-  WgradParams p{dz1, ld_dz1, nullptr, 0, n_rows, stages, (stages + grid - 1) / grid, static_cast<float*>(workspace), pn,
-                logf(max_period)};
-  if (dtype == SEGGER_BF16)
-    hipLaunchKernelGGL((wgrad_kernel<bf16_t, M, K, 4, true>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-  else
-    hipLaunchKernelGGL((wgrad_kernel<f16_t, M, K, 4, true>), dim3((unsigned)grid), dim3(256), 0, stream, p);
-  SEGGER_LAUNCH_CHECK("wgrad_kernel (generated operand)");
-  return reduce_partials(p.partial, grid, M, K, grad_w0, grad_b0, stream);
+using namespace segger;
 
+extern "C" int segger_linear_wgrad_supported(int32_t m_out, int32_t k_in, int32_t dtype) {
+  return form_supported(WgradForm::kPlain, m_out, k_in, dtype);
 }
 
-// grid of the fused positional backward: 2 workgroups per CU (VALU-bound on the regenerated features; every workgroup
-// leaves an 82 KB partial), at least kMinStagesPerBlock stages each
-static int64_t posmlp_bwd_grid(int64_t n_rows) {
-  const int64_t stages = (n_rows + kStageRows - 1) / kStageRows;
-  const int64_t want = (stages + kMinStagesPerBlock - 1) / kMinStagesPerBlock;
-  const int64_t cap = 2 * kNumCu;
-  return want < cap ? (want < 1 ? 1 : want) : cap;
+extern "C" size_t segger_linear_wgrad_workspace_bytes(int64_t n_rows, int32_t m_out, int32_t k_in) {
+  if (n_rows <= 0 || !shape_ok(m_out, k_in)) return 16;
+  const size_t b16 = (size_t)(grid_for(n_rows, m_out, k_in) + kRedGroups) * ((size_t)m_out * k_in + m_out) * sizeof(float);
+  size_t b32 = wgrad_f32_workspace_bytes(n_rows, m_out, k_in);             // (the fp32 kernels' slab counts)
+  if (wgrad_f32_split_shape_ok(m_out, k_in)) {
+    const size_t bs = (size_t)(wgrad_f32_split_grid(n_rows, m_out, k_in) + kRedGroups) * ((size_t)m_out * k_in + m_out) * sizeof(float);
+    b32 = bs > b32 ? bs : b32;
+  }
+  return b16 > b32 ? b16 : b32;
+}
+
+extern "C" int segger_linear_wgrad_dx_supported(int32_t m_out, int32_t k_in, int32_t dtype) {
+  return form_supported(WgradForm::kDx, m_out, k_in, dtype);
+}
+
+extern "C" int segger_linear_wgrad_dx_gate_supported(int32_t m_out, int32_t k_in, int32_t dtype) {
+  return segger_linear_wgrad_dx_supported(m_out, k_in, dtype) && dx_gate_ok(m_out, k_in);
+}
+
+extern "C" int segger_linear_wgrad(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int64_t n_rows,
+                                   int32_t m_out, int32_t k_in, int32_t dtype, float* grad_w, float* grad_b,
+                                   void* workspace, size_t workspace_bytes, segger_stream_t stream) {
+  WgradRequest r{"segger_linear_wgrad", WgradForm::kPlain, k_in, dtype};
+  r.a.dy = dy;  r.a.ld_dy = ld_dy;  r.a.x = x;  r.a.ld_x = ld_x;  r.a.n_rows = n_rows;  r.a.m_out = m_out;
+  r.a.grad_w = grad_w;  r.a.grad_b = grad_b;  r.a.workspace = workspace;  r.a.workspace_bytes = workspace_bytes;
+  return run_wgrad(r, (hipStream_t)stream);
+}
+
+extern "C" int segger_linear_wgrad_dx(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, const void* w_t,
+                                      int64_t n_rows, int32_t m_out, int32_t k_in, int32_t dtype, float* grad_w,
+                                      float* grad_b, void* dx, int64_t ld_dx, const void* gelu_gate, int64_t ld_gate,
+                                      void* workspace, size_t workspace_bytes, segger_stream_t stream) {
+  WgradRequest r{"segger_linear_wgrad_dx", WgradForm::kDx, k_in, dtype};
+  r.a.dy = dy;  r.a.ld_dy = ld_dy;  r.a.x = x;  r.a.ld_x = ld_x;  r.a.n_rows = n_rows;  r.a.m_out = m_out;
+  r.a.grad_w = grad_w;  r.a.grad_b = grad_b;  r.a.workspace = workspace;  r.a.workspace_bytes = workspace_bytes;
+  r.a.w_t = w_t;  r.a.dx = dx;  r.a.ld_dx = ld_dx;  r.gate = gelu_gate;  r.ld_gate = ld_gate;
+  return run_wgrad(r, (hipStream_t)stream);
+}
+
+extern "C" int segger_posmlp_wgrad(const void* dz1, int64_t ld_dz1, const float* pn, int64_t n_rows, float max_period,
+                                   int32_t dtype, float* grad_w0, float* grad_b0, void* workspace, size_t workspace_bytes,
+                                   segger_stream_t stream) {
+  SEGGER_REQUIRE(dtype == SEGGER_BF16 || dtype == SEGGER_F16, "segger_posmlp_wgrad: bf16 / f16 only");
+  WgradRequest r{"segger_posmlp_wgrad", WgradForm::kGen, kPbF, dtype};
+  r.a.dy = dz1;  r.a.ld_dy = ld_dz1;  r.a.n_rows = n_rows;  r.a.m_out = kPbD;
+  r.a.grad_w = grad_w0;  r.a.grad_b = grad_b0;  r.a.workspace = workspace;  r.a.workspace_bytes = workspace_bytes;
+  r.pn = pn;  r.log_max_period = logf(max_period);
+  return run_wgrad(r, (hipStream_t)stream);
+}
+
+extern "C" int segger_linear_wgrad_f32_split(const float* dy, int64_t ld_dy, const float* x, int64_t ld_x, int64_t n_rows,
+                                             int32_t m_out, int32_t k_in, float* grad_w, float* grad_b, void* workspace,
+                                             size_t workspace_bytes, segger_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SEGGER_REQUIRE(n_rows >= 0 && grad_w != nullptr, "segger_linear_wgrad_f32_split: bad sizes or NULL grad_w");
+  if (!wgrad_f32_split_shape_ok(m_out, k_in)) {
+    set_error("segger_linear_wgrad_f32_split: m_out=%d k_in=%d not supported", m_out, k_in);
+    return SEGGER_EUNSUPPORTED;
+  }
+  if (n_rows == 0) return zero_wgrad(grad_w, grad_b, m_out, k_in, stream);
+  SEGGER_REQUIRE(dy && x && is_aligned(dy, 16) && is_aligned(x, 16) && ld_dy >= m_out && ld_x >= k_in && ld_dy % 4 == 0 && ld_x % 4 == 0,
+                 "segger_linear_wgrad_f32_split: rows must be 16-byte aligned");
+  const int rc = require_workspace("segger_linear_wgrad_f32_split", workspace, workspace_bytes,
+                                   segger_linear_wgrad_workspace_bytes(n_rows, m_out, k_in));
+  if (rc != SEGGER_OK) return rc;
+  return wgrad_f32(true, dy, ld_dy, x, ld_x, n_rows, m_out, k_in, grad_w, grad_b, workspace, stream);
+}
+
+// ---- two backward passes in one launch -----------------------------------------------------------------------------
+extern "C" int segger_linear_wgrad_pair(const segger_wgrad_args* a, const segger_wgrad_args* b, int32_t k_in, int32_t dtype,
+                                        segger_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SEGGER_REQUIRE(a && b, "segger_linear_wgrad_pair: NULL args");
+  const segger_wgrad_args* both[2] = {a, b};
+  const bool dx = a->w_t != nullptr;
+  auto separately = [&]() -> int {                     // each side as its own entry point would run it
+    for (const segger_wgrad_args* q : both) {
+      const int rc = q->w_t ? run_wgrad(WgradRequest{"segger_linear_wgrad_dx", WgradForm::kDx, k_in, dtype, *q}, stream)
+                            : run_wgrad(WgradRequest{"segger_linear_wgrad", WgradForm::kPlain, k_in, dtype, *q}, stream);
+      if (rc != SEGGER_OK) return rc;
+    }
+    return SEGGER_OK;
+  };
+  if ((dtype != SEGGER_BF16 && dtype != SEGGER_F16) || (b->w_t != nullptr) != dx || a->n_rows <= 0 || b->n_rows <= 0)
+    return separately();
+  WgradPlan plan[2];
+  for (int i = 0; i < 2; ++i) {
+    const WgradRequest r{"segger_linear_wgrad_pair", dx ? WgradForm::kDx : WgradForm::kPlain, k_in, dtype, *both[i]};
+    const int rc = plan_wgrad(r, &plan[i]);
+    if (rc == SEGGER_EUNSUPPORTED) return separately();          // (each side's own entry point words the refusal)
+    if (rc != SEGGER_OK) return rc;
+  }
+  const bool launched = dtype == SEGGER_BF16
+      ? dispatch_wgrad_pair<bf16_t>(plan[0].p, a->m_out, plan[0].grid, plan[1].p, b->m_out, plan[1].grid, k_in, dx, stream)
+      : dispatch_wgrad_pair<f16_t>(plan[0].p, a->m_out, plan[0].grid, plan[1].p, b->m_out, plan[1].grid, k_in, dx, stream);
+  if (!launched) return separately();
+  SEGGER_LAUNCH_CHECK("wgrad_pair_kernel");
+  for (int i = 0; i < 2; ++i) {
+    const int rc = reduce_partials(plan[i].p.partial, plan[i].grid, both[i]->m_out, k_in, both[i]->grad_w, both[i]->grad_b, stream);
+    if (rc != SEGGER_OK) return rc;
+  }
+  return SEGGER_OK;
 }
 
 extern "C" size_t segger_posmlp_bwd_pair_workspace_bytes(int64_t n_rows_a, int64_t n_rows_b) {
@@ -1107,18 +1091,13 @@ extern "C" int segger_posmlp_bwd_pair(const void* g_a, int64_t ld_ga, const void
   SEGGER_REQUIRE(dtype == SEGGER_BF16 || dtype == SEGGER_F16, "segger_posmlp_bwd: bf16 / f16 only");
   SEGGER_REQUIRE(grad_w0 && grad_b0 && grad_w2 && grad_b2, "segger_posmlp_bwd: NULL output");
   if (n_rows_a == 0 && n_rows_b == 0) {
-    SEGGER_HIP(hipMemsetAsync(grad_w0, 0, (size_t)kPbD * kPbF * sizeof(float), stream));
-    SEGGER_HIP(hipMemsetAsync(grad_b0, 0, (size_t)kPbD * sizeof(float), stream));
-    SEGGER_HIP(hipMemsetAsync(grad_w2, 0, (size_t)kPbD * kPbD * sizeof(float), stream));
-    SEGGER_HIP(hipMemsetAsync(grad_b2, 0, (size_t)kPbD * sizeof(float), stream));
-    return SEGGER_OK;
+    const int rc0 = zero_wgrad(grad_w0, grad_b0, kPbD, kPbF, stream);
+    return rc0 != SEGGER_OK ? rc0 : zero_wgrad(grad_w2, grad_b2, kPbD, kPbD, stream);
   }
   SEGGER_REQUIRE(w2_t && is_aligned(w2_t, 16), "segger_posmlp_bwd: NULL / misaligned W2^T");
-  const size_t need = segger_posmlp_bwd_pair_workspace_bytes(n_rows_a, n_rows_b);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("segger_posmlp_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
+  int rc = require_workspace("segger_posmlp_bwd", workspace, workspace_bytes,
+                             segger_posmlp_bwd_pair_workspace_bytes(n_rows_a, n_rows_b));
+  if (rc != SEGGER_OK) return rc;
   const int64_t grid_a = n_rows_a > 0 ? posmlp_bwd_grid(n_rows_a) : 0, grid_b = n_rows_b > 0 ? posmlp_bwd_grid(n_rows_b) : 0;
   const int64_t grid = grid_a + grid_b;
   float* part2 = static_cast<float*>(workspace);
@@ -1138,7 +1117,7 @@ extern "C" int segger_posmlp_bwd_pair(const void* g_a, int64_t ld_ga, const void
     return SEGGER_OK;
   };
   PosBwdParams pa, pb;
-  int rc = side(g_a, ld_ga, z1_a, pn_a, n_rows_a, grid_a, 0, pa);
+  rc = side(g_a, ld_ga, z1_a, pn_a, n_rows_a, grid_a, 0, pa);
   if (rc != SEGGER_OK) return rc;
   rc = side(g_b, ld_gb, z1_b, pn_b, n_rows_b, grid_b, grid_a, pb);
   if (rc != SEGGER_OK) return rc;

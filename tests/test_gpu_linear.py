@@ -654,3 +654,58 @@ def test_linear_backward_needs_only_what_is_asked(cuda, dtype):
                 assert torch.equal(t, ref), (asked, i)
             else:
                 assert t is None, (asked, i)
+
+
+def test_wgrad_over_no_rows_is_zero(cuda):
+    """n = 0 on every weight-gradient launcher (plain bf16 / fp32, with the data gradient, generated operand): dW and db come
+    back exactly zero in their shapes, dX as [0, K] -- the outputs are allocated uninitialised, the zeros are the library's."""
+    import importlib
+    from segger_amd import ops
+    posemb = importlib.import_module("segger_amd.ops.posemb")
+    m, k = 384, 128
+    for dtype in (torch.bfloat16, torch.float32):
+        gw, gb = ops.linear_wgrad_launch(torch.ones(4, m, device=cuda, dtype=dtype)[:0], torch.ones(4, k, device=cuda, dtype=dtype)[:0])
+        assert gw.shape == (m, k) and gb.shape == (m,) and gw.dtype == gb.dtype == torch.float32
+        assert not gw.any() and not gb.any()
+        gw, none = ops.linear_wgrad_launch(torch.ones(4, m, device=cuda, dtype=dtype)[:0], torch.ones(4, k, device=cuda, dtype=dtype)[:0],
+                                           want_bias=False)
+        assert none is None and gw.shape == (m, k) and not gw.any()
+    gy, x = torch.ones(4, m, device=cuda).bfloat16()[:0], torch.ones(4, k, device=cuda).bfloat16()[:0]
+    gx, gw, gb = ops.linear_wgrad_dx_launch(gy, x, torch.ones(k, m, device=cuda).bfloat16())
+    assert gx.shape == (0, k) and gx.dtype == torch.bfloat16 and gw.shape == (m, k) and gb.shape == (m,)
+    assert not gw.any() and not gb.any()
+    gw0, gb0 = posemb._posmlp_wgrad_launch(torch.ones(4, 64, device=cuda).bfloat16()[:0], torch.ones(4, device=cuda)[:0], 10000.0)
+    assert gw0.shape == (64, 256) and gb0.shape == (64,) and gw0.dtype == gb0.dtype == torch.float32
+    assert not gw0.any() and not gb0.any()
+
+
+@pytest.mark.parametrize("dtype,na,nb,dx", [(torch.bfloat16, 17, 0, True), (torch.bfloat16, 17, 0, False), (torch.bfloat16, 0, 17, True),
+                                            (torch.bfloat16, 0, 17, False), (torch.float32, 17, 33, False)])
+def test_wgrad_pair_sides_that_take_two_launches(cuda, monkeypatch, dtype, na, nb, dx):
+    """``linear_wgrad_pair_launch`` (K = 128, M = 384 / 128) where the library answers with one launch per side: an empty side
+    (its dW / db are zeros, its dX [0, K]), with and without the data gradients, and fp32 storage (which has no one-pass data
+    gradient).  Each side against the single-side launcher on the same inputs, bit for bit as in
+    test_linear_pair_equals_two_launches (slab-ordered sums, no atomics).  The C entry runs an fp32 side on the exact-fp32
+    kernel, so the single-side launcher is held to that kernel too (by default it takes the bf16 x 3 split at this shape)."""
+    from segger_amd import ops
+    monkeypatch.setattr(ops, "F32_SPLIT_WGRAD", False)
+    k = 128
+    g = torch.Generator(device=cuda).manual_seed(na + 2 * nb)
+    sides = []
+    for n, m in ((na, 384), (nb, 128)):
+        gy = (torch.randn(n + 1, m, device=cuda, generator=g) + 0.1).to(dtype)[:n]
+        x = torch.randn(n + 1, k, device=cuda, generator=g).to(dtype)[:n]
+        wt = (torch.randn(k, m, device=cuda, generator=g) / m ** 0.5).to(dtype) if dx else None
+        sides.append((gy, x, wt, True))
+    got = ops.linear_wgrad_pair_launch(sides, dx)
+    for (gy, x, wt, _), (gx, gw, gb) in zip(sides, got):
+        n, m = gy.shape
+        if dx:
+            rx, rw, rb = ops.linear_wgrad_dx_launch(gy, x, wt)
+            assert gx.shape == (n, k) and torch.equal(gx, rx)
+        else:
+            rw, rb = ops.linear_wgrad_launch(gy, x)
+            assert gx is None
+        assert gw.shape == (m, k) and gb.shape == (m,) and torch.equal(gw, rw) and torch.equal(gb, rb)
+        if n == 0:
+            assert not gw.any() and not gb.any()
