@@ -325,21 +325,20 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const T* __restrict__ y, in
 template <typename T, bool BWD>
 int launch_l2norm(const void* y, int64_t ld_y, const void* gz, int64_t ld_gz, int64_t n, int C, float eps, void* out,
                   int64_t ld_out, hipStream_t stream, const void* gz2 = nullptr, int64_t ld_gz2 = 0) {
-#define GO(LPC)                                                                                                      \
-  {                                                                                                                  \
-    const int64_t rpb = 4 * (64 / LPC);                                                                              \
-    hipLaunchKernelGGL((l2norm_kernel<T, LPC, BWD>), dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, stream,    \
-                       (const T*)y, ld_y, (const T*)gz, ld_gz, n, eps, (T*)out, ld_out, (const T*)gz2, ld_gz2);      \
-  }
+  auto go = [&](auto lpc) {
+    constexpr int LPC = decltype(lpc)::value;
+    const int64_t rpb = 4 * (64 / LPC);
+    hipLaunchKernelGGL((l2norm_kernel<T, LPC, BWD>), dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, stream,
+                       (const T*)y, ld_y, (const T*)gz, ld_gz, n, eps, (T*)out, ld_out, (const T*)gz2, ld_gz2);
+  };
   switch (C) {
-    case 8: GO(1) break;
-    case 16: GO(2) break;
-    case 32: GO(4) break;
-    case 64: GO(8) break;
-    case 128: GO(16) break;
+    case 8: go(int_c<1>{}); break;
+    case 16: go(int_c<2>{}); break;
+    case 32: go(int_c<4>{}); break;
+    case 64: go(int_c<8>{}); break;
+    case 128: go(int_c<16>{}); break;
     default: set_error("segger_l2norm: channels=%d not supported (8,16,32,64,128)", C); return SEGGER_EUNSUPPORTED;
   }
-#undef GO
   SEGGER_LAUNCH_CHECK("l2norm_kernel");
   return SEGGER_OK;
 }
@@ -385,8 +384,6 @@ __global__ __launch_bounds__(256) void l2norm_many_kernel(L2Batch b) {
   for (int k = 0; k < 8; ++k) gr[k] = (gr[k] - v[k] * inv * dot) * inv;
   Vec8<T>::store(out, gr);
 }
-
-size_t esize(int dtype) { return dtype == SEGGER_F32 ? 4 : 2; }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -471,14 +468,6 @@ static int colsum_blocks(int64_t n) {
 
 using namespace segger;
 
-#define DISPATCH_DTYPE(dtype, EXPR_F32, EXPR_BF16, EXPR_F16)           \
-  switch (dtype) {                                                      \
-    case SEGGER_F32: EXPR_F32; break;                                   \
-    case SEGGER_BF16: EXPR_BF16; break;                                 \
-    case SEGGER_F16: EXPR_F16; break;                                   \
-    default: set_error("unknown dtype %d", dtype); return SEGGER_EINVAL; \
-  }
-
 extern "C" int segger_posfreq(const float* pos, const int64_t* batch, const float* mins, const float* maxs, int64_t n,
                               int32_t freq_dim, float eps, float max_period, void* out, int32_t dtype, segger_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -491,11 +480,12 @@ extern "C" int segger_posfreq(const float* pos, const int64_t* batch, const floa
   const int64_t nb = (items + 255) / 256;
   SEGGER_REQUIRE(nb < 0x7fffffffLL, "segger_posfreq: too many rows");
   const float lmp = logf(max_period);
-#define GO(T) hipLaunchKernelGGL((posfreq_kernel<T>), dim3((unsigned)nb), dim3(256), half * sizeof(float), stream, pos, batch, mins, maxs, n, freq_dim, eps, lmp, (T*)out)
-  DISPATCH_DTYPE(dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
+return dispatch_dtype(dtype, "segger_posfreq", [&](auto t) -> int {
+  using T = elem_t<decltype(t)>;
+  hipLaunchKernelGGL((posfreq_kernel<T>), dim3((unsigned)nb), dim3(256), half * sizeof(float), stream, pos, batch, mins, maxs, n, freq_dim, eps, lmp, (T*)out);
   SEGGER_LAUNCH_CHECK("posfreq_kernel");
   return SEGGER_OK;
+});
 }
 
 extern "C" int segger_embed_gelu_fwd(const float* table, const int32_t* ids, const void* pe, int64_t ld_pe, int64_t n,
@@ -511,11 +501,12 @@ extern "C" int segger_embed_gelu_fwd(const float* table, const int32_t* ids, con
   const int64_t items = n * (2 * D / 8);
   const int64_t nb = (items + 255) / 256;
   SEGGER_REQUIRE(nb < 0x7fffffffLL, "segger_embed_gelu_fwd: too many rows");
-#define GO(T) hipLaunchKernelGGL((embed_gelu_fwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, table, ids, (const T*)pe, ld_pe, n, D, (T*)out, ld_out)
-  DISPATCH_DTYPE(dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
+return dispatch_dtype(dtype, "segger_embed_gelu_fwd", [&](auto t) -> int {
+  using T = elem_t<decltype(t)>;
+  hipLaunchKernelGGL((embed_gelu_fwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, table, ids, (const T*)pe, ld_pe, n, D, (T*)out, ld_out);
   SEGGER_LAUNCH_CHECK("embed_gelu_fwd_kernel");
   return SEGGER_OK;
+});
 }
 
 static int64_t emb_max_chunks(int64_t n, int32_t G) {
@@ -529,29 +520,35 @@ extern "C" size_t segger_embed_gelu_bwd_workspace_bytes(int64_t n, int32_t n_row
   return (size_t)emb_max_chunks(n, n_rows_table) * (size_t)D * sizeof(float) + ((size_t)n_rows_table + 1) * sizeof(int) + 32;
 }
 
-// gtable = gelu'(table) * (rows of gx0[:, :D] summed per id): plan + gather + finish (see emb_gather_kernel)
+// out[s] = the sum of the rows of x[:, :D] that seg_rows lists for segment s, times gelu'(table[s]) where there is a table:
+// plan + gather + finish (see emb_gather_kernel).  The embedding-table gradient (segments = genes) and segger_segment_rowsum.
+static int segment_sums(const char* who, const void* x, int64_t ld, int64_t n, int32_t n_segments, int32_t D, const float* table,
+                        float* out, const int64_t* seg_ptr, const int32_t* seg_rows, void* workspace, size_t workspace_bytes,
+                        int32_t dtype, hipStream_t stream) {
+  const size_t need = segger_embed_gelu_bwd_workspace_bytes(n, n_segments, D);
+  if (!workspace || workspace_bytes < need) return workspace_too_small(who, workspace_bytes, need);
+  const int64_t gd = (int64_t)n_segments * D;
+  const int64_t max_chunks = emb_max_chunks(n, n_segments);
+  SEGGER_REQUIRE(max_chunks < 0x7fffffffLL, "%s: too many rows", who);
+  float* partial = static_cast<float*>(workspace);
+  int* chunk_ptr = reinterpret_cast<int*>(static_cast<char*>(workspace) + (((size_t)max_chunks * D * sizeof(float) + 15) & ~(size_t)15));
+  hipLaunchKernelGGL(emb_plan_kernel, dim3(1), dim3(256), 0, stream, seg_ptr, (int)n_segments, chunk_ptr);
+  const int P = D / 8, R = 256 / P > 0 ? 256 / P : 1;
+  const size_t lds = (size_t)R * D * sizeof(float);
+  return dispatch_dtype(dtype, who, [&](auto t) -> int {
+    using T = elem_t<decltype(t)>;
+    hipLaunchKernelGGL((emb_gather_kernel<T>), dim3((unsigned)max_chunks), dim3((unsigned)(P * R)), lds, stream, (const T*)x, ld, seg_ptr, seg_rows, chunk_ptr, (int)n_segments, D, partial);
+    hipLaunchKernelGGL(emb_finish_kernel, dim3((unsigned)((gd + 255) / 256)), dim3(256), 0, stream, partial, chunk_ptr, table, (int)n_segments, D, out);
+    return SEGGER_OK;
+  });
+}
+
 static int embed_table_grad(const void* gx0, int64_t ld_g, const float* table, int64_t n, int32_t n_rows_table, int32_t D,
                             float* gtable, const int64_t* gene_ptr, const int32_t* gene_rows, void* workspace,
                             size_t workspace_bytes, int32_t dtype, hipStream_t stream) {
   SEGGER_REQUIRE(table && gene_ptr && gene_rows, "embedding-table gradient: table / gene_ptr / gene_rows required");
-  const size_t need = segger_embed_gelu_bwd_workspace_bytes(n, n_rows_table, D);
-  if (!workspace || workspace_bytes < need) {
-    set_error("embedding-table gradient: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
-  const int64_t gd = (int64_t)n_rows_table * D;
-  const int64_t max_chunks = emb_max_chunks(n, n_rows_table);
-  SEGGER_REQUIRE(max_chunks < 0x7fffffffLL, "embedding-table gradient: too many rows");
-  float* partial = static_cast<float*>(workspace);
-  int* chunk_ptr = reinterpret_cast<int*>(static_cast<char*>(workspace) + (((size_t)max_chunks * D * sizeof(float) + 15) & ~(size_t)15));
-  hipLaunchKernelGGL(emb_plan_kernel, dim3(1), dim3(256), 0, stream, gene_ptr, (int)n_rows_table, chunk_ptr);
-  const int P = D / 8, R = 256 / P > 0 ? 256 / P : 1;
-  const size_t lds = (size_t)R * D * sizeof(float);
-#define GO(T) hipLaunchKernelGGL((emb_gather_kernel<T>), dim3((unsigned)max_chunks), dim3((unsigned)(P * R)), lds, stream, (const T*)gx0, ld_g, gene_ptr, gene_rows, chunk_ptr, (int)n_rows_table, D, partial)
-  DISPATCH_DTYPE(dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
-  hipLaunchKernelGGL(emb_finish_kernel, dim3((unsigned)((gd + 255) / 256)), dim3(256), 0, stream, partial, chunk_ptr, table, (int)n_rows_table, D, gtable);
-  return SEGGER_OK;
+  return segment_sums("embedding-table gradient", gx0, ld_g, n, n_rows_table, D, table, gtable, gene_ptr, gene_rows, workspace,
+                      workspace_bytes, dtype, stream);
 }
 
 extern "C" int segger_embed_gelu_bwd(const void* gx0, int64_t ld_g, const float* table, const void* pe, int64_t ld_pe,
@@ -569,16 +566,16 @@ extern "C" int segger_embed_gelu_bwd(const void* gx0, int64_t ld_g, const float*
   SEGGER_REQUIRE(gx0 && pe && gpe, "segger_embed_gelu_bwd: NULL pointer");
   SEGGER_REQUIRE(is_aligned(gx0, 16) && is_aligned(pe, 16) && is_aligned(gpe, 16), "segger_embed_gelu_bwd: 16-byte alignment required");
   SEGGER_REQUIRE((ld_g * esize(dtype)) % 16 == 0 && ld_g >= 2 * D, "segger_embed_gelu_bwd: bad leading dimension of gx0");
-  {
-    const int64_t items = n * (D / 8);
-    const int64_t nb = (items + 255) / 256;
-    SEGGER_REQUIRE(nb < 0x7fffffffLL, "segger_embed_gelu_bwd: too many rows");
-#define GO(T) hipLaunchKernelGGL((embed_gelu_bwd_pe_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, (const T*)gx0, ld_g, (const T*)pe, ld_pe, n, D, (T*)gpe, ld_gpe)
-    DISPATCH_DTYPE(dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
-  }
+  const int64_t nb = (n * (D / 8) + 255) / 256;
+  SEGGER_REQUIRE(nb < 0x7fffffffLL, "segger_embed_gelu_bwd: too many rows");
+  int rc = dispatch_dtype(dtype, "segger_embed_gelu_bwd", [&](auto t) -> int {
+    using T = elem_t<decltype(t)>;
+    hipLaunchKernelGGL((embed_gelu_bwd_pe_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, (const T*)gx0, ld_g, (const T*)pe, ld_pe, n, D, (T*)gpe, ld_gpe);
+    return SEGGER_OK;
+  });
+  if (rc != SEGGER_OK) return rc;
   if (gtable) {
-    const int rc = embed_table_grad(gx0, ld_g, table, n, n_rows_table, D, gtable, gene_ptr, gene_rows, workspace, workspace_bytes,
+    rc = embed_table_grad(gx0, ld_g, table, n, n_rows_table, D, gtable, gene_ptr, gene_rows, workspace, workspace_bytes,
                                     dtype, stream);
     if (rc != SEGGER_OK) return rc;
   }
@@ -626,11 +623,12 @@ extern "C" int segger_front_join_fwd(const segger_front_join_args* a, segger_str
   if (items == 0) return SEGGER_OK;
   const int64_t nb = (items + 255) / 256;
   SEGGER_REQUIRE(nb < 0x7fffffffLL, "segger_front_join_fwd: too many rows");
-#define GO(T) hipLaunchKernelGGL((front_join_fwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, p)
-  DISPATCH_DTYPE(a->dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
+return dispatch_dtype(a->dtype, "segger_front_join_fwd", [&](auto t) -> int {
+  using T = elem_t<decltype(t)>;
+  hipLaunchKernelGGL((front_join_fwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, p);
   SEGGER_LAUNCH_CHECK("front_join_fwd_kernel");
   return SEGGER_OK;
+});
 }
 
 extern "C" int segger_front_join_bwd(const segger_front_join_args* a, segger_stream_t stream_) {
@@ -642,10 +640,12 @@ extern "C" int segger_front_join_bwd(const segger_front_join_args* a, segger_str
   if (items > 0) {
     const int64_t nb = (items + 255) / 256;
     SEGGER_REQUIRE(nb < 0x7fffffffLL, "segger_front_join_bwd: too many rows");
-#define GO(T) hipLaunchKernelGGL((front_join_bwd_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, p)
-    DISPATCH_DTYPE(a->dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
-    SEGGER_LAUNCH_CHECK("front_join_bwd_kernel");
+    const int rc1 = dispatch_dtype(a->dtype, "segger_front_join_bwd", [&](auto t) -> int {
+      hipLaunchKernelGGL((front_join_bwd_kernel<elem_t<decltype(t)>>), dim3((unsigned)nb), dim3(256), 0, stream, p);
+      SEGGER_LAUNCH_CHECK("front_join_bwd_kernel");
+      return SEGGER_OK;
+    });
+    if (rc1 != SEGGER_OK) return rc1;
   }
   if (a->g_table) {
     if (a->n_tx == 0) {
@@ -677,23 +677,9 @@ extern "C" int segger_segment_rowsum(const void* x, int64_t ld, int64_t n, int32
   }
   SEGGER_REQUIRE(x && seg_ptr && seg_rows, "segger_segment_rowsum: NULL pointer");
   SEGGER_REQUIRE(is_aligned(x, 16) && ld >= D && (ld * esize(dtype)) % 16 == 0, "segger_segment_rowsum: bad pointer / leading dimension");
-  const size_t need = segger_segment_rowsum_workspace_bytes(n, n_segments, D);
-  if (!workspace || workspace_bytes < need) {
-    set_error("segger_segment_rowsum: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
-  const int64_t max_chunks = emb_max_chunks(n, n_segments);
-  SEGGER_REQUIRE(max_chunks < 0x7fffffffLL, "segger_segment_rowsum: too many rows");
-  float* partial = static_cast<float*>(workspace);
-  int* chunk_ptr = reinterpret_cast<int*>(static_cast<char*>(workspace) + (((size_t)max_chunks * D * sizeof(float) + 15) & ~(size_t)15));
-  hipLaunchKernelGGL(emb_plan_kernel, dim3(1), dim3(256), 0, stream, seg_ptr, (int)n_segments, chunk_ptr);
-  const int P = D / 8, R = 256 / P > 0 ? 256 / P : 1;
-  const size_t lds = (size_t)R * D * sizeof(float);
-#define GO(T) hipLaunchKernelGGL((emb_gather_kernel<T>), dim3((unsigned)max_chunks), dim3((unsigned)(P * R)), lds, stream, (const T*)x, ld, seg_ptr, seg_rows, chunk_ptr, (int)n_segments, D, partial)
-  DISPATCH_DTYPE(dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
-  hipLaunchKernelGGL(emb_finish_kernel, dim3((unsigned)((gd + 255) / 256)), dim3(256), 0, stream, partial, chunk_ptr,
-                     (const float*)nullptr, (int)n_segments, D, out);
+  const int rc = segment_sums("segger_segment_rowsum", x, ld, n, n_segments, D, nullptr, out, seg_ptr, seg_rows, workspace,
+                              workspace_bytes, dtype, stream);
+  if (rc != SEGGER_OK) return rc;
   SEGGER_LAUNCH_CHECK("segment_rowsum kernels");
   return SEGGER_OK;
 }
@@ -713,22 +699,20 @@ extern "C" int segger_colsum(const void* x, int64_t ld, int64_t n, int32_t cols,
   }
   SEGGER_REQUIRE(x && is_aligned(x, 16) && ld >= cols && (ld * esize(dtype)) % 16 == 0, "segger_colsum: bad pointer / leading dimension");
   const size_t need = segger_colsum_workspace_bytes(n, cols);
-  if (!workspace || workspace_bytes < need) {
-    set_error("segger_colsum: workspace %zu < %zu bytes", workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
+  if (!workspace || workspace_bytes < need) return workspace_too_small("segger_colsum", workspace_bytes, need);
   const int nparts = colsum_blocks(n);
   const int64_t rpb = (n + nparts - 1) / nparts;
   const int P = cols / 8, R = 256 / P > 0 ? 256 / P : 1;
   SEGGER_REQUIRE(P <= 256, "segger_colsum: cols must be <= 2048");
   const size_t lds = (size_t)R * cols * sizeof(float);    // <= 256/P * P*8 * 4 = 8 KiB
   float* partial = static_cast<float*>(workspace);
-#define GO(T) hipLaunchKernelGGL((colsum_partial_kernel<T>), dim3((unsigned)nparts), dim3((unsigned)(P * R)), lds, stream, (const T*)x, ld, n, cols, rpb, partial)
-  DISPATCH_DTYPE(dtype, GO(float), GO(bf16_t), GO(f16_t))
-#undef GO
-  hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, stream, partial, nparts, cols, out);
-  SEGGER_LAUNCH_CHECK("colsum kernels");
-  return SEGGER_OK;
+  return dispatch_dtype(dtype, "segger_colsum", [&](auto t) -> int {
+    using T = elem_t<decltype(t)>;
+    hipLaunchKernelGGL((colsum_partial_kernel<T>), dim3((unsigned)nparts), dim3((unsigned)(P * R)), lds, stream, (const T*)x, ld, n, cols, rpb, partial);
+    hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, stream, partial, nparts, cols, out);
+    SEGGER_LAUNCH_CHECK("colsum kernels");
+    return SEGGER_OK;
+  });
 }
 
 extern "C" int segger_l2norm_fwd(const void* y, int64_t ld_y, int64_t n, int32_t channels, float eps, void* z, int64_t ld_z,
@@ -737,11 +721,9 @@ extern "C" int segger_l2norm_fwd(const void* y, int64_t ld_y, int64_t n, int32_t
   if (n == 0) return SEGGER_OK;
   SEGGER_REQUIRE(y && z && is_aligned(y, 16) && is_aligned(z, 16), "segger_l2norm_fwd: NULL or misaligned pointer");
   SEGGER_REQUIRE((ld_y * esize(dtype)) % 16 == 0 && (ld_z * esize(dtype)) % 16 == 0, "segger_l2norm_fwd: bad leading dimension");
-  DISPATCH_DTYPE(dtype,
-                 return (launch_l2norm<float, false>(y, ld_y, nullptr, 0, n, channels, eps, z, ld_z, (hipStream_t)stream)),
-                 return (launch_l2norm<bf16_t, false>(y, ld_y, nullptr, 0, n, channels, eps, z, ld_z, (hipStream_t)stream)),
-                 return (launch_l2norm<f16_t, false>(y, ld_y, nullptr, 0, n, channels, eps, z, ld_z, (hipStream_t)stream)))
-  return SEGGER_OK;
+  return dispatch_dtype(dtype, "segger_l2norm_fwd", [&](auto t) {
+    return launch_l2norm<elem_t<decltype(t)>, false>(y, ld_y, nullptr, 0, n, channels, eps, z, ld_z, (hipStream_t)stream);
+  });
 }
 
 extern "C" int segger_l2norm_bwd2(const void* y, int64_t ld_y, const void* gz, int64_t ld_gz, const void* gz2, int64_t ld_gz2,
@@ -754,11 +736,9 @@ extern "C" int segger_l2norm_bwd2(const void* y, int64_t ld_y, const void* gz, i
   const size_t es = esize(dtype);
   SEGGER_REQUIRE((ld_y * es) % 16 == 0 && (ld_gz * es) % 16 == 0 && (ld_gy * es) % 16 == 0 && (!gz2 || (ld_gz2 * es) % 16 == 0),
                  "segger_l2norm_bwd: bad leading dimension");
-  DISPATCH_DTYPE(dtype,
-                 return (launch_l2norm<float, true>(y, ld_y, gz, ld_gz, n, channels, eps, gy, ld_gy, (hipStream_t)stream, gz2, ld_gz2)),
-                 return (launch_l2norm<bf16_t, true>(y, ld_y, gz, ld_gz, n, channels, eps, gy, ld_gy, (hipStream_t)stream, gz2, ld_gz2)),
-                 return (launch_l2norm<f16_t, true>(y, ld_y, gz, ld_gz, n, channels, eps, gy, ld_gy, (hipStream_t)stream, gz2, ld_gz2)))
-  return SEGGER_OK;
+  return dispatch_dtype(dtype, "segger_l2norm_bwd", [&](auto t) {
+    return launch_l2norm<elem_t<decltype(t)>, true>(y, ld_y, gz, ld_gz, n, channels, eps, gy, ld_gy, (hipStream_t)stream, gz2, ld_gz2);
+  });
 }
 
 extern "C" int segger_l2norm_bwd(const void* y, int64_t ld_y, const void* gz, int64_t ld_gz, int64_t n, int32_t channels,
@@ -792,11 +772,10 @@ extern "C" int segger_l2norm_many(const segger_l2norm_seg* segs, int32_t n_segs,
   }
   b.first_block[b.n] = (int32_t)blocks;
   if (blocks == 0) return SEGGER_OK;
-#define GO(T, LPC) hipLaunchKernelGGL((l2norm_many_kernel<T, LPC>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, b)
-#define BY_C(T) switch (lpc) { case 1: GO(T, 1); break; case 2: GO(T, 2); break; case 4: GO(T, 4); break; case 8: GO(T, 8); break; default: GO(T, 16); break; }
-  DISPATCH_DTYPE(dtype, BY_C(float), BY_C(bf16_t), BY_C(f16_t))
-#undef BY_C
-#undef GO
-  SEGGER_LAUNCH_CHECK("l2norm_many_kernel");
-  return SEGGER_OK;
+  return dispatch_dtype(dtype, "segger_l2norm_many", [&](auto t) -> int {
+    auto go = [&](auto n) { hipLaunchKernelGGL((l2norm_many_kernel<elem_t<decltype(t)>, decltype(n)::value>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, b); };
+    switch (lpc) { case 1: go(int_c<1>{}); break; case 2: go(int_c<2>{}); break; case 4: go(int_c<4>{}); break; case 8: go(int_c<8>{}); break; default: go(int_c<16>{}); break; }
+    SEGGER_LAUNCH_CHECK("l2norm_many_kernel");
+    return SEGGER_OK;
+  });
 }

@@ -66,7 +66,6 @@ int launch(Pass pass, GatParams& p, int dtype, int heads, int channels, bool wpr
   return table[(int)pass][dtype](p, heads, channels, wpr, stream);
 }
 
-size_t elem_size(int dtype) { return dtype == SEGGER_F32 ? 4 : 2; }
 
 // vectorised (specialised) kernels need 16-byte aligned rows; the generic kernels load element-wise
 thread_local bool g_need_align = true;
@@ -74,10 +73,10 @@ thread_local bool g_need_align = true;
 int check_rows(const char* name, const void* ptr, int64_t ld, int dtype, int hc) {
   SEGGER_REQUIRE(ptr != nullptr, "gatv2: %s is NULL", name);
   SEGGER_REQUIRE(ld >= hc, "gatv2: ld of %s (%lld) < heads*channels (%d)", name, (long long)ld, hc);
-  SEGGER_REQUIRE(ld * (int64_t)elem_size(dtype) < 0xffffffffLL, "gatv2: row stride of %s exceeds 4 GiB", name);
+  SEGGER_REQUIRE(ld * (int64_t)esize(dtype) < 0xffffffffLL, "gatv2: row stride of %s exceeds 4 GiB", name);
   if (g_need_align) {
     SEGGER_REQUIRE(is_aligned(ptr, 16), "gatv2: %s is not 16-byte aligned", name);
-    SEGGER_REQUIRE((ld * (int64_t)elem_size(dtype)) % 16 == 0, "gatv2: row stride of %s is not a multiple of 16 bytes", name);
+    SEGGER_REQUIRE((ld * (int64_t)esize(dtype)) % 16 == 0, "gatv2: row stride of %s is not a multiple of 16 bytes", name);
   }
   return SEGGER_OK;
 }
@@ -281,7 +280,7 @@ void bwd_src_params(const segger_gatv2_bwd_args* a, BwdState& s) {
 // destination pass (rows are 16-byte aligned multiples of 16 bytes: checked above.  hipMemset2DAsync measured 0.19 ms
 // for 1M x 256 B at pitch 768; this kernel 0.05 ms)
 int bwd_zero_fill(const segger_gatv2_bwd_args* a, const BwdState& s, hipStream_t stream) {
-  const size_t es = elem_size(a->dtype);
+  const size_t es = esize(a->dtype);
   const int64_t pieces = (int64_t)a->heads * a->channels * es / 16, total = s.n_src * pieces;
   hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
                      static_cast<char*>(a->grad_xl), (int64_t)a->ld_gxl * (int64_t)es, pieces, total);

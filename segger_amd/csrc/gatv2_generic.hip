@@ -6,6 +6,7 @@
 // written for coverage rather than speed.  grad_att / grad_bias are accumulated with
 // fp32 atomics into buffers the launcher zero-fills.
 #include "gatv2_launch.h"
+#include "post_common.h"
 
 namespace segger {
 namespace {
@@ -268,12 +269,7 @@ int gatv2_launch_generic(int pass, GatParams& p, int dtype, int heads, int chann
     SEGGER_HIP(hipMemsetAsync(grad_att, 0, (size_t)heads * channels * sizeof(float), stream));
     if (grad_bias) SEGGER_HIP(hipMemsetAsync(grad_bias, 0, (size_t)heads * channels * sizeof(float), stream));
   }
-  switch (dtype) {
-    case SEGGER_F32: return launch_generic<float>(pass, q, stream);
-    case SEGGER_BF16: return launch_generic<bf16_t>(pass, q, stream);
-    case SEGGER_F16: return launch_generic<f16_t>(pass, q, stream);
-    default: set_error("gatv2: unknown dtype %d", dtype); return SEGGER_EINVAL;
-  }
+  return dispatch_dtype(dtype, "gatv2", [&](auto t) { return launch_generic<elem_t<decltype(t)>>(pass, q, stream); });
 }
 
 }  // namespace segger

@@ -120,11 +120,11 @@ int launch_argmax(const ArgmaxParams& p, hipStream_t stream) {
   };
   const bool vec_ok = (C % 8 == 0) && is_aligned(p.zs, 16) && is_aligned(p.zd, 16) &&
                       (p.ld_zs * sizeof(T)) % 16 == 0 && (p.ld_zd * sizeof(T)) % 16 == 0;
-  if (vec_ok && C == 8) go(std::integral_constant<int, 1>{});
-  else if (vec_ok && C == 16) go(std::integral_constant<int, 2>{});
-  else if (vec_ok && C == 32) go(std::integral_constant<int, 4>{});
-  else if (vec_ok && C == 64) go(std::integral_constant<int, 8>{});
-  else if (vec_ok && C == 128) go(std::integral_constant<int, 16>{});
+  if (vec_ok && C == 8) go(int_c<1>{});
+  else if (vec_ok && C == 16) go(int_c<2>{});
+  else if (vec_ok && C == 32) go(int_c<4>{});
+  else if (vec_ok && C == 64) go(int_c<8>{});
+  else if (vec_ok && C == 128) go(int_c<16>{});
   else {
     const int64_t nb = (p.n_rows + 3) / 4;
     hipLaunchKernelGGL((edge_cos_argmax_generic_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, p);
@@ -184,8 +184,9 @@ __device__ __forceinline__ void grad_add2(void* base, bool packed, int64_t elem,
   }
 }
 
-// one wave per edge-slot batch: lanes stride the channels (any C); a wave handles
-// kTripletEdgesPerWave edges one after another
+// the per-edge kernels (triplet, C64, BCE, metric): a block of 4 waves takes this many consecutive edges, 16 at a time
+// -- one edge per 16-lane group, whose lanes share the channels -- so every group handles 4 edges in turn; it is also
+// the unit of the forward's partial sums (one float per block: segger_triplet_partial_count)
 constexpr int kTripletEdgesPerBlock = 64;
 
 template <typename T, bool BWD>
@@ -762,12 +763,8 @@ extern "C" int segger_edge_cos_argmax(const segger_edge_argmax_args* a, segger_s
   SEGGER_REQUIRE(a->max_sim && a->max_eid && a->seg_idx, "segger_edge_cos_argmax: NULL output");
   ArgmaxParams p{g.indptr, g.col, g.eid, g.n_rows, g.n_edges, a->z_src, a->ld_zs, a->z_dst, a->ld_zd, a->channels,
                  a->eps, a->use_min_similarity, a->min_similarity, a->dst_index, a->max_sim, a->max_eid, a->seg_idx, a->sim};
-  switch (a->dtype) {
-    case SEGGER_F32:  return launch_argmax<float>(p, (hipStream_t)stream);
-    case SEGGER_BF16: return launch_argmax<bf16_t>(p, (hipStream_t)stream);
-    case SEGGER_F16:  return launch_argmax<f16_t>(p, (hipStream_t)stream);
-    default: set_error("segger_edge_cos_argmax: unknown dtype %d", a->dtype); return SEGGER_EINVAL;
-  }
+  return dispatch_dtype(a->dtype, "segger_edge_cos_argmax",
+                        [&](auto t) { return launch_argmax<elem_t<decltype(t)>>(p, (hipStream_t)stream); });
 }
 
 extern "C" int64_t segger_triplet_partial_count(int64_t n_edges) { return n_edges > 0 ? triplet_blocks(n_edges) : 0; }
@@ -776,30 +773,59 @@ extern "C" size_t segger_triplet_workspace_bytes(int64_t n_edges) {
   return (size_t)(n_edges > 0 ? triplet_blocks(n_edges) : 1) * sizeof(float) + 16;
 }
 
-static int triplet_common(const segger_triplet_args* a, bool bwd, hipStream_t stream) {
+// ---- the host layer of segger_triplet_fwd / _bwd and segger_metric_fwd / _bwd: plan_triplet holds every check and chooses
+// the route, run_triplet launches what the plan says ------------------------------------------------------------------------
+namespace segger {
+namespace {
+enum class TripletRoute {
+  kEdge,         // triplet_kernel: one triplet per 16-lane group, any C
+  kEdgeC64Fwd,   // triplet_c64_kernel: C == 64 and rows that admit 4-channel vector loads, forward only
+  kGrouped,      // triplet_grouped_kernel: unique anchors, one walk over the triplets grouped by positive row (backward)
+  kBceEdge,      // bce_edge_kernel
+  kBceGrouped,   // bce_grouped_kernel: as kGrouped
+};
+struct TripletPlan {
+  TripletParams p;
+  TripletRoute route;
+  bool bwd;
+  bool pos_first;      // kEdge, backward: triplet_pos_kernel WRITES grad_b first, the per-triplet kernel then adds the negatives
+  unsigned grid;       // blocks of kTripletEdgesPerBlock triplets, or (grouped routes) rows of z_b; 0: no triplets at all
+  int kp;              // grouped routes: channels / 32
+  float* loss;         // forward: loss = finish_scale * (sum of the partial sums), 1/n or 0.5/n (BCE: the mean over 2 n logits);
+  float finish_scale;  // NULL and 0: the partial sums stay in the workspace (segger_loss_combine_partials_fwd)
+};
+
+// rows that admit 4-byte pair loads: an even channel count, rows that start on 4 bytes, 8-byte aligned matrices
+bool pair_rows_ok(const segger_triplet_args* a, size_t es) {
+  return a->channels % 2 == 0 && (a->ld_za * es) % 4 == 0 && (a->ld_zb * es) % 4 == 0 && is_aligned(a->z_a, 8) && is_aligned(a->z_b, 8);
+}
+
+// the forward's workspace: one partial sum per block of kTripletEdgesPerBlock items
+int partials_fit(const char* who, const void* workspace, size_t have, int64_t n) {
+  const size_t need = segger_triplet_workspace_bytes(n);
+  return (!workspace || have < need) ? workspace_too_small(who, have, need) : SEGGER_OK;
+}
+
+int plan_triplet(const segger_triplet_args* a, bool bwd, TripletPlan* plan) {
   SEGGER_REQUIRE(a != nullptr, "segger_triplet: args is NULL");
   SEGGER_REQUIRE(a->n_edges >= 0 && a->channels > 0, "segger_triplet: bad sizes");
   SEGGER_REQUIRE(a->n_edges < 0x7fffffffLL * kTripletEdgesPerBlock, "segger_triplet: too many edges");
-  if (a->n_edges == 0) {
-    // torch: mean over zero elements is NaN; segger never calls the loss with no edges
-    // (lightning_model.py:173 guards num_bd <= 1 only).  We return 0.
-    if (!bwd && a->loss) SEGGER_HIP(hipMemsetAsync(a->loss, 0, sizeof(float), stream));
-    return SEGGER_OK;
-  }
+  *plan = TripletPlan{};
+  plan->bwd = bwd;
+  plan->loss = bwd ? nullptr : static_cast<float*>(a->loss);
+  if (a->n_edges == 0) return SEGGER_OK;            // (before any pointer is looked at)
   SEGGER_REQUIRE(a->src && a->pos && a->neg && a->z_a && a->z_b, "segger_triplet: NULL input");
   SEGGER_REQUIRE(a->ld_za >= a->channels && a->ld_zb >= a->channels, "segger_triplet: ld < channels");
   SEGGER_REQUIRE(a->n_a > 0 && a->n_b > 0, "segger_triplet: n_a / n_b (rows of z_a / z_b) must be positive");
-  const int64_t nb = triplet_blocks(a->n_edges);
-  TripletParams p{a->src, a->pos, a->neg, a->n_edges, a->z_a, a->ld_za, a->z_b, a->ld_zb, a->n_a, a->n_b, a->channels, a->margin, a->eps,
-                  static_cast<float*>(a->workspace), 0.f, nullptr, a->grad_a, a->grad_b,
-                  a->grad_a_packed, a->grad_b_packed, bwd ? a->contrib : nullptr,
-                  bwd ? a->pos_indptr : nullptr, bwd ? a->pos_eid : nullptr, 0, bwd ? a->grad_a_rows : nullptr};
+  TripletParams& p = plan->p;
+  p.src = a->src; p.pos = a->pos; p.neg = a->neg; p.n_edges = a->n_edges;
+  p.za = a->z_a; p.ld_za = a->ld_za; p.n_a = a->n_a; p.zb = a->z_b; p.ld_zb = a->ld_zb; p.n_b = a->n_b;
+  p.channels = a->channels; p.margin = a->margin; p.eps = a->eps;
+  p.partial = static_cast<float*>(a->workspace);
+  p.ga = a->grad_a; p.gb = a->grad_b; p.ga_packed = a->grad_a_packed; p.gb_packed = a->grad_b_packed;
   if (!bwd) {
-    const size_t need = segger_triplet_workspace_bytes(a->n_edges);
-    if (!a->workspace || a->workspace_bytes < need) {
-      set_error("segger_triplet_fwd: workspace %zu < %zu bytes", a->workspace_bytes, need);
-      return SEGGER_EWORKSPACE;
-    }
+    const int rc = partials_fit("segger_triplet_fwd", a->workspace, a->workspace_bytes, a->n_edges);
+    if (rc != SEGGER_OK) return rc;
   } else {
     SEGGER_REQUIRE(a->grad_a && (a->grad_b || a->contrib), "segger_triplet_bwd: NULL gradient buffer");
     SEGGER_REQUIRE(!a->contrib || (a->channels % 2 == 0 && a->grad_a != a->grad_b),
@@ -811,109 +837,97 @@ static int triplet_common(const segger_triplet_args* a, bool bwd, hipStream_t st
     SEGGER_REQUIRE(!a->grad_a_rows || (a->channels % 2 == 0 && !a->contrib && a->loss_kind == SEGGER_LOSS_TRIPLET &&
                                        a->n_edges == a->n_a && is_aligned(a->grad_a_rows, 8)),
                    "segger_triplet_bwd: grad_a_rows needs an even channel count, one triplet per row of z_a, no contrib");
-    p.scale = a->grad_scale / (float)a->n_edges;
-    p.scale_dev = a->grad_scale_dev;
+    p.contrib = a->contrib; p.pos_indptr = a->pos_indptr; p.pos_eid = a->pos_eid; p.ga_rows = a->grad_a_rows;
+    p.scale = a->grad_scale / (float)a->n_edges; p.scale_dev = a->grad_scale_dev;
     if (p.pos_indptr) {
       SEGGER_REQUIRE(p.pos_eid && a->grad_b && a->grad_b != a->grad_a && !a->grad_b_packed && !a->contrib,
                      "segger_triplet_bwd: pos_indptr needs pos_eid and a separate fp32 grad_b (no contrib)");
       p.skip_pos = 1;
     }
   }
-  dim3 grid((unsigned)nb), block(256);
-  if (a->loss_kind == SEGGER_LOSS_BCE) {
+  const size_t es = esize(a->dtype);
+  const bool bce = a->loss_kind == SEGGER_LOSS_BCE;
+  const bool one_walk = bwd && a->anchor_unique && p.pos_indptr;   // unique anchors, triplets grouped by positive row
+  const bool walk_ok = a->channels % 32 == 0 && a->channels <= 128 && is_aligned(a->grad_a, 8);
+  if (bce) {
     // BCE head: mean over the 2 n logits; 4-byte pair loads
-    const size_t es1 = a->dtype == SEGGER_F32 ? 4 : 2;
-    SEGGER_REQUIRE(a->channels % 2 == 0 && (a->ld_za * es1) % 4 == 0 && (a->ld_zb * es1) % 4 == 0 &&
-                       ((uintptr_t)a->z_a % 8) == 0 && ((uintptr_t)a->z_b % 8) == 0,
-                   "segger_triplet (BCE): even channel count and 8-byte aligned rows");
+    SEGGER_REQUIRE(pair_rows_ok(a, es), "segger_triplet (BCE): even channel count and 8-byte aligned rows");
     SEGGER_REQUIRE(!a->contrib, "segger_triplet (BCE): contrib is a triplet-loss option");
     p.scale *= 0.5f;
-    const bool grouped = bwd && a->anchor_unique && p.pos_indptr && a->channels % 32 == 0 && a->channels <= 128 &&
-                         ((uintptr_t)a->grad_a % 8) == 0;
     p.skip_pos = 0;                                     // (the two-kernel positive route is a triplet-loss option)
-#define BCE(T)                                                                                                    \
-    do {                                                                                                          \
-      if (grouped) {                                                                                              \
-        const dim3 gg((unsigned)a->n_b);                                                                          \
-        switch (a->channels / 32) {                                                                               \
-          case 1: hipLaunchKernelGGL((bce_grouped_kernel<T, 1>), gg, block, 0, stream, p); break;                 \
-          case 2: hipLaunchKernelGGL((bce_grouped_kernel<T, 2>), gg, block, 0, stream, p); break;                 \
-          case 3: hipLaunchKernelGGL((bce_grouped_kernel<T, 3>), gg, block, 0, stream, p); break;                 \
-          default: hipLaunchKernelGGL((bce_grouped_kernel<T, 4>), gg, block, 0, stream, p); break;                \
-        }                                                                                                         \
-      } else if (bwd) hipLaunchKernelGGL((bce_edge_kernel<T, true>), grid, block, 0, stream, p);                  \
-      else hipLaunchKernelGGL((bce_edge_kernel<T, false>), grid, block, 0, stream, p);                            \
-    } while (0)
-    SEGGER_REQUIRE(a->n_b < 0x7fffffffLL, "segger_triplet (BCE): too many rows in z_b");
-    switch (a->dtype) {
-      case SEGGER_F32:  BCE(float); break;
-      case SEGGER_BF16: BCE(bf16_t); break;
-      case SEGGER_F16:  BCE(f16_t); break;
-      default: set_error("segger_triplet: unknown dtype %d", a->dtype); return SEGGER_EINVAL;
-    }
-#undef BCE
-    SEGGER_LAUNCH_CHECK("bce kernels");
-    if (!bwd && a->loss) {
-      hipLaunchKernelGGL(triplet_finish_kernel, dim3(1), dim3(256), 0, stream, p.partial, nb, 0.5f / (float)a->n_edges, a->loss);
-      SEGGER_LAUNCH_CHECK("triplet_finish_kernel");
-    }
-    return SEGGER_OK;
-  }
-  if (bwd && a->anchor_unique && p.pos_indptr) {
+    plan->route = one_walk && walk_ok ? TripletRoute::kBceGrouped : TripletRoute::kBceEdge;
+  } else if (one_walk) {
     // one walk over the groups does everything (see triplet_grouped_kernel); grad_b is accumulated into
-    const size_t es0 = a->dtype == SEGGER_F32 ? 4 : 2;
-    SEGGER_REQUIRE(a->channels % 32 == 0 && a->channels <= 128 && (a->ld_za * es0) % 4 == 0 && (a->ld_zb * es0) % 4 == 0 &&
-                       ((uintptr_t)a->z_a % 8) == 0 && ((uintptr_t)a->z_b % 8) == 0 && ((uintptr_t)a->grad_a % 8) == 0,
+    SEGGER_REQUIRE(walk_ok && pair_rows_ok(a, es),
                    "segger_triplet_bwd: anchor_unique needs C in {32, 64, 96, 128} and 8-byte aligned rows");
-    SEGGER_REQUIRE(a->n_b < 0x7fffffffLL, "segger_triplet_bwd: too many rows in z_b");
-    const dim3 ggrid((unsigned)a->n_b);
-#define GROUPED(T)                                                                                         \
-    switch (a->channels / 32) {                                                                            \
-      case 1: hipLaunchKernelGGL((triplet_grouped_kernel<T, 1>), ggrid, block, 0, stream, p); break;       \
-      case 2: hipLaunchKernelGGL((triplet_grouped_kernel<T, 2>), ggrid, block, 0, stream, p); break;       \
-      case 3: hipLaunchKernelGGL((triplet_grouped_kernel<T, 3>), ggrid, block, 0, stream, p); break;       \
-      default: hipLaunchKernelGGL((triplet_grouped_kernel<T, 4>), ggrid, block, 0, stream, p); break;      \
-    }
-    switch (a->dtype) {
-      case SEGGER_F32:  GROUPED(float); break;
-      case SEGGER_BF16: GROUPED(bf16_t); break;
-      case SEGGER_F16:  GROUPED(f16_t); break;
-      default: set_error("segger_triplet: unknown dtype %d", a->dtype); return SEGGER_EINVAL;
-    }
-#undef GROUPED
-    SEGGER_LAUNCH_CHECK("triplet_grouped_kernel");
-    return SEGGER_OK;
+    plan->route = TripletRoute::kGrouped;
+  } else {
+    // C == 64 with rows that admit 4-channel vector loads -> the vectorised kernel.  Forward only: in the backward the
+    // lane-strided pair layout of triplet_kernel keeps each atomic instruction on consecutive dwords; the 4-channel
+    // layout measured 60 % slower (0.71 vs 0.44 ms)
+    const bool c64 = a->channels == 64 && (a->ld_za * es) % (4 * es) == 0 && (a->ld_zb * es) % (4 * es) == 0 &&
+                     is_aligned(a->z_a, 4 * es) && is_aligned(a->z_b, 4 * es);
+    plan->route = c64 && !bwd ? TripletRoute::kEdgeC64Fwd : TripletRoute::kEdge;
+    plan->pos_first = bwd && p.skip_pos;
   }
-  // C == 64 with rows that admit 4-channel vector loads -> the vectorised kernel
-  const size_t es = a->dtype == SEGGER_F32 ? 4 : 2;
-  const bool c64 = a->channels == 64 && (a->ld_za * es) % (4 * es) == 0 && (a->ld_zb * es) % (4 * es) == 0 &&
-                   ((uintptr_t)a->z_a % (4 * es)) == 0 && ((uintptr_t)a->z_b % (4 * es)) == 0;
-#define LAUNCH(T)                                                                                \
-  do {                                                                                           \
-    if (bwd && p.skip_pos)   /* first: it WRITES grad_b; the per-triplet kernel then adds the negatives */            \
-      hipLaunchKernelGGL((triplet_pos_kernel<T>), dim3((unsigned)((a->n_b + 3) / 4)), block, 0, stream, p);   \
-    if (c64 && !bwd) {   /* backward: the lane-strided pair layout of triplet_kernel keeps each atomic   */ \
-      /* instruction on consecutive dwords; the 4-channel layout measured 60 % slower (0.71 vs 0.44 ms) */   \
-      hipLaunchKernelGGL((triplet_c64_kernel<T, false>), grid, block, 0, stream, p);             \
-    } else {                                                                                     \
-      if (bwd) hipLaunchKernelGGL((triplet_kernel<T, true>), grid, block, 0, stream, p);         \
-      else     hipLaunchKernelGGL((triplet_kernel<T, false>), grid, block, 0, stream, p);        \
-    }                                                                                            \
-  } while (0)
-  switch (a->dtype) {
-    case SEGGER_F32:  LAUNCH(float); break;
-    case SEGGER_BF16: LAUNCH(bf16_t); break;
-    case SEGGER_F16:  LAUNCH(f16_t); break;
-    default: set_error("segger_triplet: unknown dtype %d", a->dtype); return SEGGER_EINVAL;
-  }
-#undef LAUNCH
-  SEGGER_LAUNCH_CHECK("triplet_kernel");
-  if (!bwd && a->loss) {      // loss == NULL: the per-block partial sums stay in the workspace (segger_loss_combine_partials_fwd)
-    hipLaunchKernelGGL(triplet_finish_kernel, dim3(1), dim3(256), 0, stream, p.partial, nb, 1.0f / (float)a->n_edges, a->loss);
-    SEGGER_LAUNCH_CHECK("triplet_finish_kernel");
-  }
+  const bool grouped = plan->route == TripletRoute::kGrouped || plan->route == TripletRoute::kBceGrouped;
+  SEGGER_REQUIRE(!(bce || grouped) || a->n_b < 0x7fffffffLL, "%s: too many rows in z_b",
+                 bce ? "segger_triplet (BCE)" : "segger_triplet_bwd");
+  plan->grid = (unsigned)(grouped ? a->n_b : triplet_blocks(a->n_edges));
+  plan->kp = a->channels / 32;
+  plan->finish_scale = plan->loss ? (bce ? 0.5f : 1.0f) / (float)a->n_edges : 0.f;
   return SEGGER_OK;
 }
+
+// f(int_c<KP>{}) for a grouped kernel's channel count: KP = C / 32 in 1..4 (plan_triplet)
+template <typename F>
+void with_kp(int kp, F&& f) {
+  if (kp == 1) f(int_c<1>{}); else if (kp == 2) f(int_c<2>{}); else if (kp == 3) f(int_c<3>{}); else f(int_c<4>{});
+}
+
+// loss[0] = scale * (partial[0] + ... + partial[nb - 1])
+int finish_partials(const float* partial, int64_t nb, float scale, float* loss, hipStream_t stream) {
+  hipLaunchKernelGGL(triplet_finish_kernel, dim3(1), dim3(256), 0, stream, partial, nb, scale, loss);
+  SEGGER_LAUNCH_CHECK("triplet_finish_kernel");
+  return SEGGER_OK;
+}
+
+int run_triplet(const TripletPlan& plan, int dtype, hipStream_t stream) {
+  const TripletParams& p = plan.p;
+  if (plan.grid == 0) {
+    // torch: mean over zero elements is NaN; segger never calls the loss with no edges
+    // (lightning_model.py:173 guards num_bd <= 1 only).  We return 0.
+    if (plan.loss) SEGGER_HIP(hipMemsetAsync(plan.loss, 0, sizeof(float), stream));
+    return SEGGER_OK;
+  }
+  const dim3 grid(plan.grid);
+  const int rc = dispatch_dtype(dtype, "segger_triplet", [&](auto t) -> int {
+    using T = elem_t<decltype(t)>;
+    auto go = [&](void (*kernel)(TripletParams), dim3 blocks) { hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, stream, p); };
+    switch (plan.route) {
+      case TripletRoute::kEdge:
+        if (plan.pos_first) go(triplet_pos_kernel<T>, dim3((unsigned)((p.n_b + 3) / 4)));
+        go(plan.bwd ? triplet_kernel<T, true> : triplet_kernel<T, false>, grid);
+        break;
+      case TripletRoute::kEdgeC64Fwd: go(triplet_c64_kernel<T, false>, grid); break;
+      case TripletRoute::kGrouped: with_kp(plan.kp, [&](auto k) { go(triplet_grouped_kernel<T, decltype(k)::value>, grid); }); break;
+      case TripletRoute::kBceEdge: go(plan.bwd ? bce_edge_kernel<T, true> : bce_edge_kernel<T, false>, grid); break;
+      case TripletRoute::kBceGrouped: with_kp(plan.kp, [&](auto k) { go(bce_grouped_kernel<T, decltype(k)::value>, grid); }); break;
+    }
+    SEGGER_LAUNCH_CHECK("segger_triplet kernels");
+    return SEGGER_OK;
+  });
+  if (rc != SEGGER_OK || plan.finish_scale == 0.f) return rc;
+  return finish_partials(p.partial, triplet_blocks(p.n_edges), plan.finish_scale, plan.loss, stream);
+}
+
+int triplet_common(const segger_triplet_args* a, bool bwd, hipStream_t stream) {
+  TripletPlan plan;
+  const int rc = plan_triplet(a, bwd, &plan);
+  return rc != SEGGER_OK ? rc : run_triplet(plan, a->dtype, stream);
+}
+}  // namespace
+}  // namespace segger
 
 // ---- the weighted sum of the step's losses and its gradient, as one tiny launch each way --------------------------------
 namespace segger {
@@ -933,11 +947,7 @@ __global__ void loss_combine_kernel(const float* __restrict__ raw, const float* 
     for (int i = 0; i < n; ++i) graw[i] = (gout[n] * b[i] + gout[i]) * a[i];
   }
 }
-}  // namespace
-}  // namespace segger
 
-namespace segger {
-namespace {
 struct CombineParts { const float* partial[16]; int64_t n_partial[16]; float scale[16]; };
 // one workgroup: term i = scale[i] * (sum of its partial sums, in a fixed order), then the combination of loss_combine_kernel
 __global__ __launch_bounds__(256) void loss_combine_parts_kernel(CombineParts c, const float* __restrict__ a,
@@ -1037,57 +1047,56 @@ extern "C" int segger_sample_negatives(const int64_t* pos, int64_t n, int64_t n_
   return SEGGER_OK;
 }
 
-static int metric_common(const void* z, int64_t ld_z, int64_t n, int32_t channels, int32_t dtype, const int64_t* pos,
-                         const int64_t* neg, const float* d_pos, const float* d_neg, const float* w, float eps,
-                         float* loss, void* workspace, size_t workspace_bytes, const float* scale_dev, float* grad_z,
-                         bool bwd, hipStream_t stream) {
-  SEGGER_REQUIRE(n >= 0 && channels > 0 && ld_z >= channels, "segger_metric: bad sizes");
-  if (n == 0) {
-    if (!bwd && loss) SEGGER_HIP(hipMemsetAsync(loss, 0, sizeof(float), stream));
+namespace segger {
+namespace {
+// what segger_metric_fwd and _bwd ask for: the forward fills p.partial (its workspace), workspace_bytes and loss, the
+// backward p.scale_dev and p.gz
+struct MetricRequest { MetricParams p; int dtype; bool bwd; size_t workspace_bytes; float* loss; };
+
+int metric_common(const MetricRequest& r, hipStream_t stream) {
+  const MetricParams& p = r.p;
+  SEGGER_REQUIRE(p.n >= 0 && p.channels > 0 && p.ld >= p.channels, "segger_metric: bad sizes");
+  if (p.n == 0) {
+    if (!r.bwd && r.loss) SEGGER_HIP(hipMemsetAsync(r.loss, 0, sizeof(float), stream));
     return SEGGER_OK;
   }
-  SEGGER_REQUIRE(z && pos && neg && d_pos && d_neg && w, "segger_metric: NULL input");
-  const int64_t nb = triplet_blocks(n);
-  MetricParams p{z, ld_z, n, channels, pos, neg, d_pos, d_neg, w, eps, static_cast<float*>(workspace), scale_dev, grad_z};
-  if (!bwd) {
-    const size_t need = segger_triplet_workspace_bytes(n);
-    if (!workspace || workspace_bytes < need) {
-      set_error("segger_metric_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
-      return SEGGER_EWORKSPACE;
-    }
+  SEGGER_REQUIRE(p.z && p.pos && p.neg && p.dpos && p.dneg && p.w, "segger_metric: NULL input");
+  if (!r.bwd) {
+    const int rc = partials_fit("segger_metric_fwd", p.partial, r.workspace_bytes, p.n);
+    if (rc != SEGGER_OK) return rc;
   } else {
-    SEGGER_REQUIRE(grad_z != nullptr, "segger_metric_bwd: grad_z is NULL");
+    SEGGER_REQUIRE(p.gz != nullptr, "segger_metric_bwd: grad_z is NULL");
   }
-  dim3 grid((unsigned)nb), block(256);
-#define LAUNCH_M(T)                                                                                \
-  do {                                                                                             \
-    if (bwd) hipLaunchKernelGGL((metric_kernel<T, true>), grid, block, 0, stream, p);              \
-    else     hipLaunchKernelGGL((metric_kernel<T, false>), grid, block, 0, stream, p);             \
-  } while (0)
-  switch (dtype) {
-    case SEGGER_F32:  LAUNCH_M(float); break;
-    case SEGGER_BF16: LAUNCH_M(bf16_t); break;
-    case SEGGER_F16:  LAUNCH_M(f16_t); break;
-    default: set_error("segger_metric: unknown dtype %d", dtype); return SEGGER_EINVAL;
-  }
-#undef LAUNCH_M
-  SEGGER_LAUNCH_CHECK("metric_kernel");
-  if (!bwd && loss) {         // loss == NULL: partial sums only, as segger_triplet_fwd
-    hipLaunchKernelGGL(triplet_finish_kernel, dim3(1), dim3(256), 0, stream, p.partial, nb, 1.0f, loss);
-    SEGGER_LAUNCH_CHECK("triplet_finish_kernel");
-  }
-  return SEGGER_OK;
+  const int64_t nb = triplet_blocks(p.n);
+  const dim3 grid((unsigned)nb), block(256);
+  const int rc = dispatch_dtype(r.dtype, "segger_metric", [&](auto t) -> int {
+    using T = elem_t<decltype(t)>;
+    if (r.bwd) hipLaunchKernelGGL((metric_kernel<T, true>), grid, block, 0, stream, p);
+    else       hipLaunchKernelGGL((metric_kernel<T, false>), grid, block, 0, stream, p);
+    SEGGER_LAUNCH_CHECK("metric_kernel");
+    return SEGGER_OK;
+  });
+  if (rc != SEGGER_OK || r.bwd || !r.loss) return rc;         // loss == NULL: partial sums only, as segger_triplet_fwd
+  return finish_partials(p.partial, nb, 1.0f, r.loss, stream);
 }
+}  // namespace
+}  // namespace segger
 
 extern "C" int segger_metric_fwd(const void* z, int64_t ld_z, int64_t n, int32_t channels, int32_t dtype, const int64_t* pos,
                                  const int64_t* neg, const float* d_pos, const float* d_neg, const float* w, float eps,
                                  float* loss, void* workspace, size_t workspace_bytes, segger_stream_t stream) {
-  return metric_common(z, ld_z, n, channels, dtype, pos, neg, d_pos, d_neg, w, eps, loss, workspace, workspace_bytes,
-                       nullptr, nullptr, false, (hipStream_t)stream);
+  MetricRequest r{};
+  r.p.z = z; r.p.ld = ld_z; r.p.n = n; r.p.channels = channels; r.dtype = dtype;
+  r.p.pos = pos; r.p.neg = neg; r.p.dpos = d_pos; r.p.dneg = d_neg; r.p.w = w; r.p.eps = eps;
+  r.p.partial = static_cast<float*>(workspace); r.workspace_bytes = workspace_bytes; r.loss = loss;
+  return metric_common(r, (hipStream_t)stream);
 }
 extern "C" int segger_metric_bwd(const void* z, int64_t ld_z, int64_t n, int32_t channels, int32_t dtype, const int64_t* pos,
                                  const int64_t* neg, const float* d_pos, const float* d_neg, const float* w, float eps,
                                  const float* grad_scale_dev, float* grad_z, segger_stream_t stream) {
-  return metric_common(z, ld_z, n, channels, dtype, pos, neg, d_pos, d_neg, w, eps, nullptr, nullptr, 0, grad_scale_dev,
-                       grad_z, true, (hipStream_t)stream);
+  MetricRequest r{};
+  r.p.z = z; r.p.ld = ld_z; r.p.n = n; r.p.channels = channels; r.dtype = dtype;
+  r.p.pos = pos; r.p.neg = neg; r.p.dpos = d_pos; r.p.dneg = d_neg; r.p.w = w; r.p.eps = eps;
+  r.bwd = true; r.p.scale_dev = grad_scale_dev; r.p.gz = grad_z;
+  return metric_common(r, (hipStream_t)stream);
 }

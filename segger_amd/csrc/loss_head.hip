@@ -574,7 +574,7 @@ int fill_params(const segger_loss_head_args* a, bool bwd, LossHeadParams* out) {
   SEGGER_REQUIRE(a->n_tx >= 0 && a->n_bd >= 0 && a->n_sg >= 0, "segger_loss_head: negative size");
   SEGGER_REQUIRE(a->channels == 32 || a->channels == 64 || a->channels == 128, "segger_loss_head: channels must be 32, 64 or 128");
   SEGGER_REQUIRE(a->dtype == SEGGER_F32 || a->dtype == SEGGER_BF16 || a->dtype == SEGGER_F16, "segger_loss_head: unknown dtype %d", a->dtype);
-  const size_t es = a->dtype == SEGGER_F32 ? 4 : 2;
+  const size_t es = esize(a->dtype);
   const size_t row_align = (size_t)(a->channels / 16) * es >= 16 ? 16 : (size_t)(a->channels / 16) * es;
   SEGGER_REQUIRE(a->n_tx == 0 || (a->z_tx && ((uintptr_t)a->z_tx % 16) == 0 && ((size_t)a->ld_ztx * es) % row_align == 0 && a->ld_ztx >= a->channels),
                  "segger_loss_head: z_tx NULL, misaligned or ld < channels");
@@ -590,10 +590,7 @@ int fill_params(const segger_loss_head_args* a, bool bwd, LossHeadParams* out) {
   const int64_t nb_sg = bwd ? (a->n_sg > 0 ? a->n_bd : 0) : blocks_of(a->n_sg);
   SEGGER_REQUIRE(nb_tx + nb_bd + nb_sg < 0x7fffffffLL, "segger_loss_head: too many blocks");
   const size_t need = segger_loss_head_workspace_bytes(a->n_tx, a->n_bd, a->n_sg);
-  if (!a->workspace || a->workspace_bytes < need) {
-    set_error("segger_loss_head: workspace %zu < %zu bytes", a->workspace_bytes, need);
-    return SEGGER_EWORKSPACE;
-  }
+  if (!a->workspace || a->workspace_bytes < need) return workspace_too_small("segger_loss_head", a->workspace_bytes, need);
   LossHeadParams p{};
   p.ztx = a->z_tx; p.ld_ztx = a->ld_ztx; p.n_tx = a->n_tx;
   p.zbd = a->z_bd; p.ld_zbd = a->ld_zbd; p.n_bd = a->n_bd;
@@ -638,25 +635,18 @@ int launch(const segger_loss_head_args* a, hipStream_t stream) {
   if (rc != SEGGER_OK) return rc;
   const int64_t grid = (int64_t)p.nb_tx + p.nb_bd + p.nb_sg + ((BWD && p.defer) ? 1 : 0);
   if (grid == 0) return SEGGER_OK;
-#define GO(T, CPL)                                                                                              \
-  do {                                                                                                          \
-    if (BWD) hipLaunchKernelGGL((loss_head_bwd_kernel<T, CPL>), dim3((unsigned)grid), dim3(256), 0, stream, p); \
-    else     hipLaunchKernelGGL((loss_head_fwd_kernel<T, CPL>), dim3((unsigned)grid), dim3(256), 0, stream, p); \
-  } while (0)
-#define BY_C(T)                                       \
-  switch (a->channels) {                              \
-    case 32: GO(T, 2); break;                         \
-    case 64: GO(T, 4); break;                         \
-    default: GO(T, 8); break;                         \
-  }
-  switch (a->dtype) {
-    case SEGGER_F32:  BY_C(float); break;
-    case SEGGER_BF16: BY_C(bf16_t); break;
-    default:          BY_C(f16_t); break;
-  }
-#undef BY_C
-#undef GO
-  SEGGER_LAUNCH_CHECK("loss_head kernel");
+  const int rc2 = dispatch_dtype(a->dtype, "segger_loss_head", [&](auto t) -> int {
+    auto go = [&](auto cpl) {                            // channels per lane: C / 16 (fill_params: C is 32, 64 or 128)
+      using T = elem_t<decltype(t)>;
+      constexpr int CPL = decltype(cpl)::value;
+      if (BWD) hipLaunchKernelGGL((loss_head_bwd_kernel<T, CPL>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+      else     hipLaunchKernelGGL((loss_head_fwd_kernel<T, CPL>), dim3((unsigned)grid), dim3(256), 0, stream, p);
+    };
+    if (a->channels == 32) go(int_c<2>{}); else if (a->channels == 64) go(int_c<4>{}); else go(int_c<8>{});
+    SEGGER_LAUNCH_CHECK("loss_head kernel");
+    return SEGGER_OK;
+  });
+  if (rc2 != SEGGER_OK) return rc2;
   if (!BWD && !p.defer) {
     hipLaunchKernelGGL(loss_head_finish_kernel, dim3(1), dim3(256), 0, stream, p);
     SEGGER_LAUNCH_CHECK("loss_head_finish_kernel");

@@ -1,8 +1,9 @@
 // Host-side scaffolding shared by the translation units (included after common.h): the predicates that decide whether a
-// pointer may be dereferenced, the rule that places the scratch arrays inside a caller's workspace, and the whole-wave
-// integer helpers of the post-processing kernels.  One definition each: a fix to the carving rule or to an alignment
-// check is made here and nowhere else.
+// pointer may be dereferenced, the rule that places the scratch arrays inside a caller's workspace, the step from a dtype
+// code to an element type, and the whole-wave integer helpers of the post-processing kernels.  One definition each: a
+// fix to the carving rule or to an alignment check is made here and nowhere else.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace segger {
@@ -47,6 +48,26 @@ inline T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<c
 inline int workspace_too_small(const char* who, size_t have, size_t need) {
   set_error("%s: workspace %zu < %zu bytes", who, have, need);
   return SEGGER_EWORKSPACE;
+}
+
+// ---------------------------------------------------------------- host: element types ---
+inline size_t esize(int dtype) { return dtype == SEGGER_F32 ? sizeof(float) : sizeof(bf16_t); }
+
+// a generic lambda's compile-time arguments: `using T = elem_t<decltype(t)>;`, `constexpr int N = decltype(n)::value;`
+template <typename T> struct dtype_tag { using type = T; };
+template <typename Tag> using elem_t = typename Tag::type;
+template <int N> using int_c = std::integral_constant<int, N>;
+
+// The one place a SEGGER_* dtype code becomes an element type: returns f(dtype_tag<float | bf16_t | f16_t>{}), or refuses
+// any other code in `who`'s name.  The translation units that support fewer types on purpose keep their own switch.
+template <typename F>
+int dispatch_dtype(int dtype, const char* who, F&& f) {
+  switch (dtype) {
+    case SEGGER_F32:  return f(dtype_tag<float>{});
+    case SEGGER_BF16: return f(dtype_tag<bf16_t>{});
+    case SEGGER_F16:  return f(dtype_tag<f16_t>{});
+    default: set_error("%s: unknown dtype %d", who, dtype); return SEGGER_EINVAL;
+  }
 }
 
 // ---------------------------------------------------------------- device: whole-wave integer sums ---

@@ -1065,3 +1065,125 @@ def test_edge_cos_argmax_at_c2_size(oracle, cuda, dtype):
         # assignments may differ from float64 only where the two best candidates (or the threshold) are within tol
         differ = seg.cpu() != seg_ref
         assert float(differ.float().mean()) < 1e-4, float(differ.float().mean())
+
+
+def _edge_loss_and_grads(ops, kind, z_tx, z_bd, src, dst, neg, cuda, groups=None, unique=False):
+    da, db = z_tx.to(cuda).requires_grad_(True), z_bd.to(cuda).requires_grad_(True)
+    if kind == "triplet":
+        loss = ops.triplet_edge_loss(da, db, src.to(cuda), dst.to(cuda), neg.to(cuda), 0.4, pos_groups=groups, anchors_unique=unique)
+    else:
+        loss = ops.bce_edge_loss(da, db, src.to(cuda), dst.to(cuda), neg.to(cuda), pos_groups=groups, anchors_unique=unique)
+    (loss * 0.37).backward()
+    return loss.item(), da.grad.cpu().double(), db.grad.cpu().double()
+
+
+def _edge_loss_oracle(oracle, kind, z_tx, z_bd, src, dst, neg):
+    """float64, straight from the formulas (oracle.segmentation_loss returns 0 for a single boundary)."""
+    a, b = z_tx.double().requires_grad_(True), z_bd.double().requires_grad_(True)
+    if kind == "triplet":
+        ref = oracle.triplet_margin_loss(a[src], b[dst], b[neg], 0.4)
+    else:
+        logits = torch.cat([(a[src] * b[dst]).sum(-1), (a[src] * b[neg]).sum(-1)])
+        labels = torch.cat([torch.ones(src.numel()), torch.zeros(src.numel())]).double()
+        ref = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels)
+    (ref * 0.37).backward()
+    return ref.item(), a.grad, b.grad
+
+
+def _edge_loss_inputs(kind, n_tx, n_bd, E, C, dtype, seed, unique=False):
+    g = torch.Generator().manual_seed(seed)
+    if kind == "triplet":
+        z_tx = torch.nn.functional.normalize(torch.randn(n_tx, C, generator=g), dim=-1).to(dtype)
+        z_bd = torch.nn.functional.normalize(torch.randn(n_bd, C, generator=g), dim=-1).to(dtype)
+    else:                                                  # (not normalised: logits of a few units either way)
+        z_tx, z_bd = torch.randn(n_tx, C, generator=g).to(dtype), (torch.randn(n_bd, C, generator=g) * 0.5).to(dtype)
+    src = torch.randperm(n_tx, generator=g)[:E] if unique else torch.randint(0, n_tx, (E,), generator=g)
+    dst = torch.randint(0, n_bd, (E,), generator=g)
+    if n_bd > 4:
+        dst[dst == 3] = 4                                  # a boundary that is nobody's positive
+    neg = (dst + torch.randint(1, n_bd, (E,), generator=g)) % n_bd if n_bd > 1 else dst.clone()
+    return z_tx, z_bd, src, dst, neg
+
+
+def _edge_loss_tolerances(kind, dtype, ref):
+    """Those of test_triplet_edge_loss / test_bce_edge_loss for the same dtype and quantity."""
+    if kind == "triplet":
+        return 1e-5, ((1e-5, 1e-7) if dtype == torch.float32 else (1e-2, 2e-6))
+    return 2e-5 * max(1.0, abs(ref)), ((1e-5, 1e-7) if dtype == torch.float32 else (1e-2, 4e-6))
+
+
+@pytest.mark.parametrize("dtype,packed", [(torch.float32, False), (torch.bfloat16, False), (torch.bfloat16, True),
+                                          (torch.float16, False), (torch.float16, True)])
+@pytest.mark.parametrize("kind", ["triplet", "bce"])
+def test_one_walk_over_the_groups_at_96_channels(oracle, cuda, dtype, packed, kind, monkeypatch):
+    """C = 96: three 32-channel pieces per lane pair, the one width of the grouped walk (triplet_grouped_kernel /
+    bce_grouped_kernel, KP = 3) between the widths the model uses; anchor rows stored as fp32 or as packed pairs in the
+    embeddings' dtype.  Against the float64 oracle, tolerances of the neighbouring tests."""
+    from segger_amd import ops
+    from segger_amd.graph import csr_from_coo
+    monkeypatch.setattr(ops, "_CONTRIB_MIN_EDGES", 0 if packed else 1 << 60)
+    z_tx, z_bd, src, dst, neg = _edge_loss_inputs(kind, 400, 12, 300, 96, dtype, 96, unique=True)
+    ref, ga, gb = _edge_loss_oracle(oracle, kind, z_tx, z_bd, src, dst, neg)
+    groups = csr_from_coo(dst.to(cuda), src.to(cuda), 12, 400, validate=False)
+    loss, da, db = _edge_loss_and_grads(ops, kind, z_tx, z_bd, src, dst, neg, cuda, groups, unique=True)
+    ltol, (rtol, atol) = _edge_loss_tolerances(kind, dtype, ref)
+    assert abs(loss - ref) < ltol
+    assert torch.allclose(da, ga, rtol=rtol, atol=atol) and torch.allclose(db, gb, rtol=rtol, atol=atol)
+    free = torch.ones(400, dtype=torch.bool); free[src] = False
+    assert not da[free].any()
+
+
+@pytest.mark.parametrize("E", [1, 63, 64, 65, 129])
+@pytest.mark.parametrize("kind,C", [("triplet", 64), ("triplet", 20), ("bce", 32)])
+def test_per_edge_kernels_at_the_edges_of_their_64_edge_blocks(oracle, cuda, kind, C, E):
+    """The per-edge kernels take 64 edges per block and leave one partial sum per block: one edge, one short of a block,
+    a block, one more, two blocks and one (C = 64: the vectorised forward kernel; 20: the lane-strided one)."""
+    from segger_amd import ops
+    z_tx, z_bd, src, dst, neg = _edge_loss_inputs(kind, 40, 9, E, C, torch.float32, 7 + E)
+    ref, ga, gb = _edge_loss_oracle(oracle, kind, z_tx, z_bd, src, dst, neg)
+    loss, da, db = _edge_loss_and_grads(ops, kind, z_tx, z_bd, src, dst, neg, cuda)
+    ltol, (rtol, atol) = _edge_loss_tolerances(kind, torch.float32, ref)
+    assert abs(loss - ref) < ltol
+    assert torch.allclose(da, ga, rtol=rtol, atol=atol) and torch.allclose(db, gb, rtol=rtol, atol=atol)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("n_bd", [1, 4, 5])
+def test_positive_rows_kernel_at_the_edges_of_its_4_row_blocks(oracle, cuda, dtype, n_bd):
+    """Triplets grouped by positive row, anchors not unique: triplet_pos_kernel WRITES every row of grad_b (an
+    uninitialised buffer), four rows per block -- one row, one block, one block and a row -- and the per-triplet kernel
+    adds the negatives.  Against the float64 oracle and the atomics route on the same input."""
+    from segger_amd import ops
+    from segger_amd.graph import csr_from_coo
+    z_tx, z_bd, src, dst, neg = _edge_loss_inputs("triplet", 50, n_bd, 130, 32, dtype, 40 + n_bd)
+    ref, ga, gb = _edge_loss_oracle(oracle, "triplet", z_tx, z_bd, src, dst, neg)
+    groups = csr_from_coo(dst.to(cuda), src.to(cuda), n_bd, 50, validate=False)
+    loss, da, db = _edge_loss_and_grads(ops, "triplet", z_tx, z_bd, src, dst, neg, cuda, groups)
+    ltol, (rtol, atol) = _edge_loss_tolerances("triplet", dtype, ref)
+    assert abs(loss - ref) < ltol
+    assert torch.allclose(da, ga, rtol=rtol, atol=atol) and torch.allclose(db, gb, rtol=rtol, atol=atol)
+    loss2, da2, db2 = _edge_loss_and_grads(ops, "triplet", z_tx, z_bd, src, dst, neg, cuda)
+    assert loss2 == loss and torch.allclose(da2, da, rtol=rtol, atol=atol) and torch.allclose(db2, db, rtol=rtol, atol=1e-6)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("n", [1, 64, 65, 129])
+def test_metric_loss_every_dtype_at_the_edges_of_a_block(oracle, cuda, dtype, n):
+    """segger_metric_fwd / _bwd on their own (the model reaches them at fp32 only): MetricLoss over given triplets with
+    weights 1 / n against the float64 oracle on the same (already rounded) embeddings.  The loss is an fp32 sum of O(1):
+    the 1e-5 of the triplet loss; the gradient is accumulated in fp32 and rounded once to the embeddings' dtype, as the
+    boundary side of the triplet loss: its tolerances."""
+    from segger_amd import ops
+    g = torch.Generator().manual_seed(50 + n)
+    z = torch.randn(n, 32, generator=g).to(dtype)
+    pos, neg = torch.randint(0, n, (n,), generator=g), torch.randint(0, n, (n,), generator=g)
+    dp, dn = torch.rand(n, generator=g), torch.rand(n, generator=g)
+    a = z.double().requires_grad_(True)
+    ref = oracle.bd_metric_loss(a, pos, neg, dp.double(), dn.double())
+    (ref * 0.37).backward()
+    d = z.to(cuda).requires_grad_(True)
+    loss = ops.metric_loss(d, pos.to(cuda), neg.to(cuda), dp.to(cuda), dn.to(cuda), torch.full((n,), 1.0 / n, device=cuda))
+    (loss * 0.37).backward()
+    assert abs(loss.item() - ref.item()) < 1e-5
+    rtol, atol = (1e-5, 1e-7) if dtype == torch.float32 else (1e-2, 2e-6)
+    assert torch.allclose(d.grad.cpu().double(), a.grad, rtol=rtol, atol=atol)
