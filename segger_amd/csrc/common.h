@@ -45,11 +45,45 @@ inline int device_cu_count() {
   return n;
 }
 
-// ------------------------------------------------- fp32 projections (csrc/linear_f32.hip) ---
-int linear_f32_launch(const void* x, int64_t ldx, const void* w, const float* bias, void* y, int64_t ldy, int64_t n_rows,
-                      int k_in, int m_out, hipStream_t stream, const float* rowbias = nullptr, const int32_t* rowidx = nullptr,
-                      int64_t ld_rb = 0, const float* gate = nullptr, int64_t ld_gate = 0, int gate_kind = 0,
-                      float* y_act = nullptr, int64_t ld_yact = 0, int act_kind = 0);
+// ------------------------------------------------- forward projections: one request, one route plan ---
+// The shapes the kernel families are instantiated for: segger_linear_supported, the planner's refusals and the executors'
+// else-if dispatch are generated from these lists, so a new shape is added here and nowhere else.
+#define SEGGER_FWD_K_LIST(X) X(64) X(128) X(256) X(384)            /* chunked K: 16-bit, its equal-K pair, exact fp32 */
+#define SEGGER_FWD_RES_LIST(X) X(128, 6) X(128, 2) X(128, 1) X(64, 6) X(64, 2) X(64, 1)      /* 16-bit W-resident (K, M / 64) */
+#define SEGGER_FWD_F32_EPILOGUE_K_LIST(X) X(64) X(128) X(256)      /* exact fp32 with row bias, gate or second output */
+#define SEGGER_FWD_SPLIT_WRES_LIST(X) /* planes, W-resident (K, M, GATE kind, BIAS) */ \
+  X(384, 128, 1, false) X(384, 128, 2, false) X(384, 128, 0, false) X(384, 128, 0, true) X(128, 384, 0, true) X(128, 384, 0, false)
+
+// One forward projection y = x W^T (+ bias) (+ rowbias[rowidx]) (* act'(gate)) (and y_act = act(y)) as its entry point
+// received it.  An entry point fills the fields its form has; plan_fwd (csrc/linear.hip) holds every check.
+enum class FwdGate { kNone, kSilu16, kF32 };   // SiLU' in the 16-bit chunked kernel | GELU' / SiLU' (gate_kind) at fp32
+struct FwdRequest {
+  const char* who = "";            // the entry point, for messages
+  int dtype = SEGGER_F32;
+  int64_t n_rows = 0;  int k_in = 0, m_out = 0;
+  const void* x = nullptr;  int64_t ldx = 0;
+  const void* w = nullptr;  bool w_planes = false;      // [m_out, k_in] in dtype | bf16 x 3 planes [3][m_out][k_in] (fp32 only)
+  const float* bias = nullptr;
+  void* y = nullptr;  int64_t ldy = 0;
+  bool has_rowbias = false;  const void* rowbias = nullptr;  const int32_t* rowidx = nullptr;  int64_t ld_rb = 0;
+  FwdGate gate_form = FwdGate::kNone;  const void* gate = nullptr;  int64_t ld_gate = 0;  int gate_kind = 0;
+  bool has_act = false;  float* y_act = nullptr;  int64_t ld_yact = 0;  int act_kind = 0;
+  // a call without rows answers for its sizes and kinds, and as its entry point always has:
+  bool shape_before_empty = false; // for the shape too (the planes' own entries, a 16-bit pair side)
+  bool pair_side = false;          // a 16-bit pair side: for all but NULL pointers as well; its k_in <= 0 is an unsupported shape
+};
+enum class FwdRoute {
+  kNone,                                          // n_rows == 0: nothing to launch
+  kRes16, kChunk16, kRowBias16, kSiluGrad16,      // csrc/linear.hip: W-resident persistent | chunked (+ row bias | * SiLU')
+  kExactF32, kKSliceF32,                          // csrc/linear_f32.hip
+  kSplit                                          // csrc/linear_f32_split.hip: chunked or W-resident, as its executor's switch says
+};
+struct FwdPlan { FwdRoute route;  int64_t grid; };      // grid: workgroups of the route's kernel
+int plan_fwd(const FwdRequest& q, FwdPlan* plan);                                       // csrc/linear.hip
+int launch_fwd_f32(const FwdRequest& q, const FwdPlan& plan, hipStream_t stream);       // csrc/linear_f32.hip
+int launch_fwd_f32_split(const FwdRequest& q, const FwdPlan& plan, hipStream_t stream); // csrc/linear_f32_split.hip
+
+// ------------------------------------------------- fp32 weight gradients (csrc/linear_f32.hip) ---
 size_t wgrad_f32_workspace_bytes(int64_t n_rows, int m_out, int k_in);
 // csrc/linear_f32_split.hip: the same weight gradient as six bf16 partial products (same partial-sum layout)
 bool wgrad_f32_split_shape_ok(int m, int k);

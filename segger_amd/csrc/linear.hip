@@ -14,6 +14,7 @@
 //   * D = W_tile * X_tile^T  (v_mfma_f32_32x32x16): a lane owns one DATA ROW and
 //     4-column groups, so the epilogue packs 4 bf16 -> ds_write_b64 into a wave-private
 //     LDS tile and streams it out as full 128-byte row segments (16 B per lane).
+#include <algorithm>
 #include "common.h"
 #include "post_common.h"
 
@@ -335,104 +336,166 @@ __global__ __launch_bounds__(kResWaves * 64, 1) void linear_res_kernel(LinearPar
   if (tile < n_tiles) do_tile(std::false_type{}, tile);
 }
 
-template <typename T>
-int launch_linear_res(const LinearParams& p, int k_in, hipStream_t stream, bool* done) {
-  *done = false;
-  const int n_cu = device_cu_count();           // per device (common.h)
-  const int64_t n_tiles = (p.n_rows + 31) / 32;
-  // worth it only when every wave of the persistent grid gets a few tiles
-  if (n_cu <= 0 || p.rowbias || p.gate || n_tiles < (int64_t)n_cu * kResWaves * 2) return SEGGER_OK;
-  dim3 grid((unsigned)n_cu), block(kResWaves * 64);
-#define RES_CASE(KK, NN) \
-  if (k_in == KK && p.m_out == NN * kChunk) { \
-    hipLaunchKernelGGL((linear_res_kernel<T, KK, NN>), grid, block, 0, stream, p, n_tiles); \
-    SEGGER_LAUNCH_CHECK("linear_res_kernel"); *done = true; return SEGGER_OK; }
-  RES_CASE(128, 6) RES_CASE(128, 2) RES_CASE(128, 1) RES_CASE(64, 6) RES_CASE(64, 2) RES_CASE(64, 1)
-#undef RES_CASE
-  return SEGGER_OK;
+// ---- host: the entry points fill a FwdRequest, plan_fwd checks and routes, one executor per unit launches -------
+#define K_IS(KK) || k == KK
+#define K_TEXT(KK) " " #KK
+#define RES_IS(KK, NN) || (k == KK && m == NN * kChunk)
+bool chunked_k(int k) { return false SEGGER_FWD_K_LIST(K_IS); }
+bool f32_epilogue_k(int k) { return false SEGGER_FWD_F32_EPILOGUE_K_LIST(K_IS); }
+bool resident_shape(int k, int m) { return false SEGGER_FWD_RES_LIST(RES_IS); }
+bool out_width_ok(int m) { return m > 0 && m % kChunk == 0; }
+// (no list where one kernel serves: the planes' chunked <128> / <384>, the row bias' two K, the SiLU' K, the K-slice, 384 + 128)
+bool split_shape(int k, int m) { return (k == 128 && out_width_ok(m)) || (k == 384 && m == 128); }
+
+LinearParams params_16(const FwdRequest& q) {
+  LinearParams p{};
+  p.x = q.x;  p.ldx = q.ldx;  p.w = q.w;  p.bias = q.bias;
+  p.y = q.y;  p.ldy = q.ldy;  p.n_rows = q.n_rows;  p.m_out = q.m_out;
+  if (q.has_rowbias) { p.rowbias = q.rowbias;  p.rowidx = q.rowidx;  p.ld_rb = q.ld_rb; }
+  if (q.gate_form == FwdGate::kSilu16) { p.gate = q.gate;  p.ld_gate = q.ld_gate; }
+  return p;
 }
 
 template <typename T>
-int launch_linear(const LinearParams& p, int k_in, hipStream_t stream) {
-  bool done = false;
-  const int rc = launch_linear_res<T>(p, k_in, stream, &done);
-  if (rc != SEGGER_OK || done) return rc;
-  const int64_t nb = (p.n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
-  if (nb > 0x7fffffffLL) { set_error("segger_linear_fwd: too many rows"); return SEGGER_EUNSUPPORTED; }
-  dim3 grid((unsigned)nb), block(256);
-  if (p.gate) {
-    if (k_in != 64) {
-      set_error("segger_linear_fwd_silu_grad: k_in=%d not supported (64)", k_in);
-      return SEGGER_EUNSUPPORTED;
-    }
+int launch_fwd_16(const FwdRequest& q, const FwdPlan& plan, hipStream_t stream) {
+  const LinearParams p = params_16(q);
+  const dim3 grid((unsigned)plan.grid), block(256);
+#define RES(KK, NN) else if (q.k_in == KK && q.m_out == NN * kChunk) hipLaunchKernelGGL( \
+    (linear_res_kernel<T, KK, NN>), grid, dim3(kResWaves * 64), 0, stream, p, ceil_div(q.n_rows, 32));
+#define CHUNKED(KK) else if (q.k_in == KK) hipLaunchKernelGGL((linear_fwd_kernel<T, KK>), grid, block, 0, stream, p);
+  if (plan.route == FwdRoute::kRes16) { if (false) {} SEGGER_FWD_RES_LIST(RES) }
+  else if (plan.route == FwdRoute::kSiluGrad16)
     hipLaunchKernelGGL((linear_fwd_kernel<T, 64, false, true>), grid, block, 0, stream, p);
-    SEGGER_LAUNCH_CHECK("linear_fwd_kernel (silu')");
-    return SEGGER_OK;
-  }
-  if (p.rowbias) {
-    switch (k_in) {
-      case 64:  hipLaunchKernelGGL((linear_fwd_kernel<T, 64, true>), grid, block, 0, stream, p); break;
-      case 128: hipLaunchKernelGGL((linear_fwd_kernel<T, 128, true>), grid, block, 0, stream, p); break;
-      default:
-        set_error("segger_linear_fwd_rowbias: k_in=%d not supported (64, 128)", k_in);
-        return SEGGER_EUNSUPPORTED;
-    }
-    SEGGER_LAUNCH_CHECK("linear_fwd_kernel (row bias)");
-    return SEGGER_OK;
-  }
-  switch (k_in) {
-    case 64:  hipLaunchKernelGGL((linear_fwd_kernel<T, 64>), grid, block, 0, stream, p); break;
-    case 128: hipLaunchKernelGGL((linear_fwd_kernel<T, 128>), grid, block, 0, stream, p); break;
-    case 256: hipLaunchKernelGGL((linear_fwd_kernel<T, 256>), grid, block, 0, stream, p); break;
-    case 384: hipLaunchKernelGGL((linear_fwd_kernel<T, 384>), grid, block, 0, stream, p); break;
-    default:
-      set_error("segger_linear_fwd: k_in=%d not supported (64, 128, 256, 384)", k_in);
-      return SEGGER_EUNSUPPORTED;
-  }
-  SEGGER_LAUNCH_CHECK("linear_fwd_kernel");
+  else if (plan.route == FwdRoute::kRowBias16 && q.k_in == 64)
+    hipLaunchKernelGGL((linear_fwd_kernel<T, 64, true>), grid, block, 0, stream, p);
+  else if (plan.route == FwdRoute::kRowBias16) hipLaunchKernelGGL((linear_fwd_kernel<T, 128, true>), grid, block, 0, stream, p);
+  else { if (false) {} SEGGER_FWD_K_LIST(CHUNKED) }
+#undef RES
+#undef CHUNKED
+  SEGGER_LAUNCH_CHECK("linear_fwd_kernel / linear_res_kernel");
   return SEGGER_OK;
 }
 
+// both sides' 128-row blocks in one grid, b's first (two plain chunked projections of one K, or of the two-width pair)
 template <typename T>
-int launch_linear_pair(const LinearParams& a, const LinearParams& b, int k_in, hipStream_t stream, int k_b = 0) {
-  if (k_b == 0) k_b = k_in;
-  bool done = false;
-  int rc = launch_linear_res<T>(a, k_in, stream, &done);       // a large `a` goes its own (persistent) way
-  if (rc != SEGGER_OK) return rc;
-  if (done) return launch_linear<T>(b, k_b, stream);
-  if (k_b != k_in) {
-    // different input widths (a first layer's two data gradients: 384 and 128 columns of dY): the pairs instantiated
-    const int64_t na = (a.n_rows + kRowsPerBlock - 1) / kRowsPerBlock, nb = (b.n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    if (k_in == 384 && k_b == 128 && na > 0 && nb > 0 && na + nb <= 0x7fffffffLL) {
-      hipLaunchKernelGGL((linear_fwd_pair_kernel<T, 384, 128>), dim3((unsigned)(na + nb)), dim3(256), 0, stream, a, b, (int)nb);
-      SEGGER_LAUNCH_CHECK("linear_fwd_pair_kernel");
-      return SEGGER_OK;
-    }
-    rc = launch_linear<T>(a, k_in, stream);
-    return rc != SEGGER_OK ? rc : launch_linear<T>(b, k_b, stream);
-  }
-  const int64_t nb_a = (a.n_rows + kRowsPerBlock - 1) / kRowsPerBlock, nb_b = (b.n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
-  if (nb_a + nb_b > 0x7fffffffLL) { set_error("segger_linear_fwd_pair: too many rows"); return SEGGER_EUNSUPPORTED; }
-  if (nb_a == 0) return launch_linear<T>(b, k_in, stream);
-  if (nb_b == 0) return launch_linear<T>(a, k_in, stream);
-  dim3 grid((unsigned)(nb_a + nb_b)), block(256);
-  switch (k_in) {
-    case 64:  hipLaunchKernelGGL((linear_fwd_pair_kernel<T, 64>), grid, block, 0, stream, a, b, (int)nb_b); break;
-    case 128: hipLaunchKernelGGL((linear_fwd_pair_kernel<T, 128>), grid, block, 0, stream, a, b, (int)nb_b); break;
-    case 256: hipLaunchKernelGGL((linear_fwd_pair_kernel<T, 256>), grid, block, 0, stream, a, b, (int)nb_b); break;
-    case 384: hipLaunchKernelGGL((linear_fwd_pair_kernel<T, 384>), grid, block, 0, stream, a, b, (int)nb_b); break;
-    default:
-      set_error("segger_linear_fwd_pair: k_in=%d not supported (64, 128, 256, 384)", k_in);
-      return SEGGER_EUNSUPPORTED;
-  }
+int launch_fwd_pair_16(const FwdRequest& qa, const FwdRequest& qb, int64_t nb_a, int64_t nb_b, hipStream_t stream) {
+  const LinearParams a = params_16(qa), b = params_16(qb);
+  const dim3 grid((unsigned)(nb_a + nb_b)), block(256);
+#define SAME(KK) else if (qa.k_in == KK) hipLaunchKernelGGL((linear_fwd_pair_kernel<T, KK>), grid, block, 0, stream, a, b, (int)nb_b);
+  if (qa.k_in != qb.k_in) hipLaunchKernelGGL((linear_fwd_pair_kernel<T, 384, 128>), grid, block, 0, stream, a, b, (int)nb_b);
+  SEGGER_FWD_K_LIST(SAME)
+#undef SAME
   SEGGER_LAUNCH_CHECK("linear_fwd_pair_kernel");
   return SEGGER_OK;
 }
 
+int launch_fwd(const FwdRequest& q, const FwdPlan& plan, hipStream_t stream) {
+  switch (plan.route) {
+    case FwdRoute::kNone: return SEGGER_OK;
+    case FwdRoute::kExactF32: case FwdRoute::kKSliceF32: return launch_fwd_f32(q, plan, stream);
+    case FwdRoute::kSplit: return launch_fwd_f32_split(q, plan, stream);
+    default: return q.dtype == SEGGER_BF16 ? launch_fwd_16<bf16_t>(q, plan, stream) : launch_fwd_16<f16_t>(q, plan, stream);
+  }
+}
+
+int run_fwd(const FwdRequest& q, segger_stream_t stream) {
+  FwdPlan plan;
+  const int rc = plan_fwd(q, &plan);
+  return rc != SEGGER_OK ? rc : launch_fwd(q, plan, (hipStream_t)stream);
+}
+
+// The pair: both sides are planned before anything runs.  One joint launch where both are plain chunked 16-bit projections
+// of one K (or 384 beside 128); otherwise each side goes its own planned way, a side without rows nowhere.
+int run_fwd_pair(const FwdRequest& a, const FwdRequest& b, hipStream_t stream) {
+  FwdPlan pa, pb;
+  int rc = plan_fwd(a, &pa);
+  if (rc == SEGGER_OK) rc = plan_fwd(b, &pb);
+  if (rc != SEGGER_OK) return rc;
+  const int64_t nb_a = ceil_div(a.n_rows, kRowsPerBlock), nb_b = ceil_div(b.n_rows, kRowsPerBlock);
+  const bool b_plain16 = pb.route == FwdRoute::kChunk16 || pb.route == FwdRoute::kRes16;   // (beside a small a, b is not asked)
+  const bool k_joint = a.k_in == b.k_in || (a.k_in == 384 && b.k_in == 128);
+  if (pa.route == FwdRoute::kChunk16 && b_plain16 && k_joint && nb_a + nb_b <= 0x7fffffffLL)
+    return a.dtype == SEGGER_BF16 ? launch_fwd_pair_16<bf16_t>(a, b, nb_a, nb_b, stream)
+                                  : launch_fwd_pair_16<f16_t>(a, b, nb_a, nb_b, stream);
+  rc = launch_fwd(a, pa, stream);
+  return rc != SEGGER_OK ? rc : launch_fwd(b, pb, stream);
+}
+
 }  // namespace
+
+// Every host check of a forward projection, once and in this order: sizes; act_kind / gate_kind; the shape (in the called
+// entry's name); NULL pointers; 16-byte alignment; leading dimensions; the row bias table; then the route, its grid and the
+// row count.  What a call without rows still answers for is the request's to say (shape_before_empty, pair_side: common.h).
+// The element size (esize, post_common.h) is all that differs between the storage widths.
+int plan_fwd(const FwdRequest& q, FwdPlan* plan) {
+  const int k = q.k_in, m = q.m_out;
+  const bool f32 = q.dtype == SEGGER_F32, sixteen = q.dtype == SEGGER_BF16 || q.dtype == SEGGER_F16, none = q.n_rows == 0;
+  const bool gate_f32 = q.gate_form == FwdGate::kF32, silu16 = q.gate_form == FwdGate::kSilu16;
+  const bool f32_only = q.w_planes || gate_f32 || q.has_act;
+  // (the fp32-only forms leave k_in and m_out, a 16-bit pair side k_in, to the shape: unsupported, not a bad argument)
+  SEGGER_REQUIRE(q.n_rows >= 0 && (f32_only || (m > 0 && (k > 0 || q.pair_side))),
+                 "%s: bad sizes (negative n_rows, k_in or m_out not positive)", q.who);
+  SEGGER_REQUIRE(!q.has_act || q.act_kind == 1 || q.act_kind == 2, "%s: act_kind 1 (GELU) or 2 (SiLU)", q.who);
+  SEGGER_REQUIRE(!gate_f32 || q.gate_kind == 1 || q.gate_kind == 2, "%s: gate_kind 1 (GELU) or 2 (SiLU)", q.who);
+  *plan = FwdPlan{FwdRoute::kNone, ceil_div(q.n_rows, kRowsPerBlock)};      // (the grid of every route but the persistent one)
+  if (none && !q.shape_before_empty) return SEGGER_OK;
+  SEGGER_REQUIRE(!silu16 || (k == 64 && out_width_ok(m) && sixteen), "%s: k_in 64, m_out %% 64 == 0, bf16 / f16", q.who);
+  const bool f32_epilogue = gate_f32 || q.has_act || (f32 && q.has_rowbias);
+  const bool k_ok = f32_epilogue ? f32_epilogue_k(k) : q.has_rowbias ? (k == 64 || k == 128) : chunked_k(k);
+  if (!(q.w_planes ? split_shape(k, m) : (f32 || sixteen) && out_width_ok(m) && k_ok)) {
+    set_error("%s: k_in=%d m_out=%d dtype=%d not supported (m_out %% 64 == 0; k_in" SEGGER_FWD_K_LIST(K_TEXT) ", with a row bias 64 128,"
+              " with an fp32 epilogue" SEGGER_FWD_F32_EPILOGUE_K_LIST(K_TEXT) "; planes 128 -> any, 384 -> 128)", q.who, k, m, q.dtype);
+    return SEGGER_EUNSUPPORTED;
+  }
+  if (none && !q.pair_side) return SEGGER_OK;
+  // (an operand that the form does not have is NULL in the request: aligned, and its leading dimension is not asked)
+  SEGGER_REQUIRE(none || (q.x && q.w && q.y && (q.gate_form == FwdGate::kNone || q.gate) && (!q.has_act || q.y_act)),
+                 "%s: NULL pointer", q.who);
+  SEGGER_REQUIRE(!q.has_rowbias || (q.rowbias && q.rowidx), "%s: the rowbias table and rowidx go together", q.who);
+  SEGGER_REQUIRE(is_aligned(q.x, 16) && is_aligned(q.w, 16) && is_aligned(q.y, 16) && is_aligned(q.gate, 16) &&
+                     is_aligned(q.y_act, 16) && (!f32 || is_aligned(q.bias, 16)),
+                 "%s: pointers (at fp32 the bias too) must be 16-byte aligned", q.who);
+  const int64_t es = (int64_t)esize(q.dtype);
+  const auto ld_ok = [&](int64_t ld, int64_t width, int bytes) { return ld >= width && (ld * es) % bytes == 0; };
+  SEGGER_REQUIRE(ld_ok(q.ldx, k, 16) && ld_ok(q.ldy, m, 16) && (!q.gate || ld_ok(q.ld_gate, m, silu16 ? 8 : 16)) &&
+                     (!q.y_act || ld_ok(q.ld_yact, m, 16)),
+                 "%s: bad leading dimension (shorter than a row, or rows not 16-byte aligned)", q.who);
+  SEGGER_REQUIRE(!q.has_rowbias || (is_aligned(q.rowbias, 16) && ld_ok(q.ld_rb, m, 16)),
+                 "%s: the rowbias table needs 16-byte aligned rows of at least m_out elements", q.who);
+  if (none) return SEGGER_OK;
+  // the persistent form is worth it only when every wave of its grid gets a few 32-row tiles
+  const bool plain16 = sixteen && !silu16 && !q.has_rowbias;
+  const int n_cu = plain16 && resident_shape(k, m) ? device_cu_count() : 0;           // per device (common.h)
+  const bool res = n_cu > 0 && ceil_div(q.n_rows, 32) >= (int64_t)n_cu * kResWaves * 2;
+  if (res) plan->grid = n_cu;
+  plan->route = q.w_planes ? FwdRoute::kSplit
+              : f32 ? (k == 384 && (m == 128 || m == 256) ? FwdRoute::kKSliceF32 : FwdRoute::kExactF32)
+              : silu16 ? FwdRoute::kSiluGrad16 : q.has_rowbias ? FwdRoute::kRowBias16 : res ? FwdRoute::kRes16 : FwdRoute::kChunk16;
+  if (plan->grid > 0x7fffffffLL) {
+    set_error("%s: too many rows", q.who);
+    return q.w_planes ? SEGGER_EINVAL : SEGGER_EUNSUPPORTED;                 // (as either family has always answered)
+  }
+  return SEGGER_OK;
+}
+
 }  // namespace segger
 
 using namespace segger;
+
+extern "C" int segger_linear_supported(int32_t k_in, int32_t m_out, int32_t dtype) {
+  return chunked_k(k_in) && out_width_ok(m_out) && (dtype == SEGGER_BF16 || dtype == SEGGER_F16 || dtype == SEGGER_F32);
+}
+
+extern "C" int segger_linear_fwd_f32_split_supported(int32_t k_in, int32_t m_out) { return split_shape(k_in, m_out); }
+
+// the fields every form has; an entry point adds its own by name
+static FwdRequest request(const char* who, int32_t dtype, int64_t n_rows, int32_t k_in, int32_t m_out, const void* x, int64_t ldx,
+                          const void* w, const float* bias, void* y, int64_t ldy) {
+  FwdRequest q;
+  q.who = who;  q.dtype = dtype;  q.n_rows = n_rows;  q.k_in = k_in;  q.m_out = m_out;
+  q.x = x;  q.ldx = ldx;  q.w = w;  q.bias = bias;  q.y = y;  q.ldy = ldy;
+  return q;
+}
 
 extern "C" int segger_linear_fwd_pair(const segger_linear_args* a, const segger_linear_args* b, int32_t k_in, int32_t dtype,
                                       segger_stream_t stream) {
@@ -442,90 +505,61 @@ extern "C" int segger_linear_fwd_pair(const segger_linear_args* a, const segger_
 extern "C" int segger_linear_fwd_pair_k(const segger_linear_args* a, int32_t k_a, const segger_linear_args* b, int32_t k_b,
                                         int32_t dtype, segger_stream_t stream) {
   SEGGER_REQUIRE(a && b, "segger_linear_fwd_pair: NULL args");
-  const segger_linear_args* both[2] = {a, b};
-  const int32_t ks[2] = {k_a, k_b};
-  if (dtype == SEGGER_F32) {      // fp32 storage: two launches of the exact-fp32 kernel
-    for (int i = 0; i < 2; ++i) {
-      const segger_linear_args* q = both[i];
-      const int rc = segger_linear_fwd(q->x, q->ldx, q->w, q->bias, q->y, q->ldy, q->n_rows, ks[i], q->m_out, dtype, stream);
-      if (rc != SEGGER_OK) return rc;
-    }
-    return SEGGER_OK;
-  }
-  LinearParams p[2];
-  for (int i = 0; i < 2; ++i) {
-    const segger_linear_args* q = both[i];
-    const int32_t k_in = ks[i];
-    SEGGER_REQUIRE(q->n_rows >= 0 && q->m_out > 0, "segger_linear_fwd_pair: bad sizes");
-    if (!segger_linear_supported(k_in, q->m_out, dtype)) {
-      set_error("segger_linear_fwd_pair: k_in=%d m_out=%d dtype=%d not supported", k_in, q->m_out, dtype);
-      return SEGGER_EUNSUPPORTED;
-    }
-    SEGGER_REQUIRE(q->n_rows == 0 || (q->x && q->w && q->y), "segger_linear_fwd_pair: NULL pointer");
-    SEGGER_REQUIRE(is_aligned(q->x, 16) && is_aligned(q->w, 16) && is_aligned(q->y, 16), "segger_linear_fwd_pair: pointers must be 16-byte aligned");
-    SEGGER_REQUIRE(q->ldx >= k_in && q->ldy >= q->m_out && (q->ldx * 2) % 16 == 0 && (q->ldy * 2) % 16 == 0,
-                   "segger_linear_fwd_pair: bad leading dimension");
-    p[i] = LinearParams{q->x, q->ldx, q->w, q->bias, q->y, q->ldy, q->n_rows, q->m_out, nullptr, nullptr, 0, nullptr, 0};
-  }
-  return dtype == SEGGER_BF16 ? launch_linear_pair<bf16_t>(p[0], p[1], k_a, (hipStream_t)stream, k_b)
-                              : launch_linear_pair<f16_t>(p[0], p[1], k_a, (hipStream_t)stream, k_b);
-}
-
-extern "C" int segger_linear_supported(int32_t k_in, int32_t m_out, int32_t dtype) {
-  const bool k_ok = k_in == 64 || k_in == 128 || k_in == 256 || k_in == 384;
-  return k_ok && m_out > 0 && m_out % kChunk == 0 && (dtype == SEGGER_BF16 || dtype == SEGGER_F16 || dtype == SEGGER_F32);
+  const char* who = "segger_linear_fwd_pair";
+  FwdRequest qa = request(who, dtype, a->n_rows, k_a, a->m_out, a->x, a->ldx, a->w, a->bias, a->y, a->ldy);
+  FwdRequest qb = request(who, dtype, b->n_rows, k_b, b->m_out, b->x, b->ldx, b->w, b->bias, b->y, b->ldy);
+  qa.shape_before_empty = qa.pair_side = qb.shape_before_empty = qb.pair_side = dtype != SEGGER_F32;   // (fp32: as two plain calls)
+  return run_fwd_pair(qa, qb, (hipStream_t)stream);
 }
 
 extern "C" int segger_linear_fwd(const void* x, int64_t ldx, const void* w, const float* bias, void* y, int64_t ldy,
                                  int64_t n_rows, int32_t k_in, int32_t m_out, int32_t dtype, segger_stream_t stream) {
-  return segger_linear_fwd_rowbias(x, ldx, w, bias, nullptr, 0, nullptr, y, ldy, n_rows, k_in, m_out, dtype, stream);
+  return run_fwd(request("segger_linear_fwd", dtype, n_rows, k_in, m_out, x, ldx, w, bias, y, ldy), stream);
+}
+
+extern "C" int segger_linear_fwd_rowbias(const void* x, int64_t ldx, const void* w, const float* bias, const void* rowbias,
+                                         int64_t ld_rb, const int32_t* rowidx, void* y, int64_t ldy, int64_t n_rows,
+                                         int32_t k_in, int32_t m_out, int32_t dtype, segger_stream_t stream) {
+  FwdRequest q = request("segger_linear_fwd_rowbias", dtype, n_rows, k_in, m_out, x, ldx, w, bias, y, ldy);
+  q.has_rowbias = rowbias || rowidx;  q.rowbias = rowbias;  q.rowidx = rowidx;  q.ld_rb = ld_rb;
+  return run_fwd(q, stream);
 }
 
 extern "C" int segger_linear_fwd_silu_grad(const void* x, int64_t ldx, const void* w, const void* gate, int64_t ld_gate,
                                            void* y, int64_t ldy, int64_t n_rows, int32_t k_in, int32_t m_out,
                                            int32_t dtype, segger_stream_t stream) {
-  SEGGER_REQUIRE(n_rows >= 0 && k_in > 0 && m_out > 0, "segger_linear_fwd_silu_grad: bad sizes");
-  if (n_rows == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(segger_linear_supported(k_in, m_out, dtype) && k_in == 64 && dtype != SEGGER_F32,
-                 "segger_linear_fwd_silu_grad: k_in 64, m_out %% 64 == 0, bf16 / f16");
-  SEGGER_REQUIRE(x && w && y && gate, "segger_linear_fwd_silu_grad: NULL pointer");
-  SEGGER_REQUIRE(is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16) && is_aligned(gate, 16),
-                 "segger_linear_fwd_silu_grad: pointers must be 16-byte aligned");
-  SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && ld_gate >= m_out && (ldx * 2) % 16 == 0 && (ldy * 2) % 16 == 0 &&
-                     (ld_gate * 2) % 8 == 0, "segger_linear_fwd_silu_grad: bad leading dimension");
-  LinearParams p{x, ldx, w, nullptr, y, ldy, n_rows, m_out, nullptr, nullptr, 0, gate, ld_gate};
-  return dtype == SEGGER_BF16 ? launch_linear<bf16_t>(p, k_in, (hipStream_t)stream)
-                              : launch_linear<f16_t>(p, k_in, (hipStream_t)stream);
+  FwdRequest q = request("segger_linear_fwd_silu_grad", dtype, n_rows, k_in, m_out, x, ldx, w, nullptr, y, ldy);
+  q.gate_form = FwdGate::kSilu16;  q.gate = gate;  q.ld_gate = ld_gate;
+  return run_fwd(q, stream);
 }
 
-extern "C" int segger_linear_fwd_rowbias(const void* x, int64_t ldx, const void* w, const float* bias,
-                                         const void* rowbias, int64_t ld_rb, const int32_t* rowidx, void* y, int64_t ldy,
-                                         int64_t n_rows, int32_t k_in, int32_t m_out, int32_t dtype,
-                                         segger_stream_t stream) {
-  SEGGER_REQUIRE(n_rows >= 0 && k_in > 0 && m_out > 0, "segger_linear_fwd: bad sizes");
-  if (n_rows == 0) return SEGGER_OK;
-  if (!segger_linear_supported(k_in, m_out, dtype)) {
-    set_error("segger_linear_fwd: k_in=%d m_out=%d dtype=%d not supported (k_in in {64,128,256,384}, "
-              "m_out %% 64 == 0, bf16/f16)", k_in, m_out, dtype);
-    return SEGGER_EUNSUPPORTED;
-  }
-  SEGGER_REQUIRE(x && w && y, "segger_linear_fwd: NULL pointer");
-  SEGGER_REQUIRE(is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16), "segger_linear_fwd: pointers must be 16-byte aligned");
-  if (dtype == SEGGER_F32) {       // fp32 storage: exact-fp32 MFMA kernel (csrc/linear_f32.hip); plain projection only
-    SEGGER_REQUIRE(!rowbias == !rowidx, "segger_linear_fwd_rowbias: rowbias and rowidx go together");
-    SEGGER_REQUIRE(!rowbias || (is_aligned(rowbias, 16) && ld_rb >= m_out && ld_rb % 4 == 0),
-                   "segger_linear_fwd_rowbias: the fp32 table needs 16-byte aligned rows of at least m_out elements");
-    SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && (!bias || is_aligned(bias, 16)),
-                   "segger_linear_fwd: fp32 rows (and the bias) must be 16-byte aligned");
-    return linear_f32_launch(x, ldx, w, bias, y, ldy, n_rows, k_in, m_out, (hipStream_t)stream,
-                             static_cast<const float*>(rowbias), rowidx, ld_rb);
-  }
-  SEGGER_REQUIRE(ldx >= k_in && ldy >= m_out && (ldx * 2) % 16 == 0 && (ldy * 2) % 16 == 0,
-                 "segger_linear_fwd: bad leading dimension");
-  SEGGER_REQUIRE(!rowbias == !rowidx, "segger_linear_fwd_rowbias: rowbias and rowidx go together");
-  SEGGER_REQUIRE(!rowbias || (is_aligned(rowbias, 16) && ld_rb >= m_out && ld_rb % 8 == 0),
-                 "segger_linear_fwd_rowbias: the table needs 16-byte aligned rows of at least m_out elements");
-  LinearParams p{x, ldx, w, bias, y, ldy, n_rows, m_out, rowbias, rowidx, ld_rb, nullptr, 0};
-  return dtype == SEGGER_BF16 ? launch_linear<bf16_t>(p, k_in, (hipStream_t)stream)
-                              : launch_linear<f16_t>(p, k_in, (hipStream_t)stream);
+extern "C" int segger_linear_fwd_f32_split(const float* x, int64_t ldx, const void* w3, const float* bias, float* y, int64_t ldy,
+                                           int64_t n_rows, int32_t k_in, int32_t m_out, segger_stream_t stream) {
+  FwdRequest q = request("segger_linear_fwd_f32_split", SEGGER_F32, n_rows, k_in, m_out, x, ldx, w3, bias, y, ldy);
+  q.w_planes = q.shape_before_empty = true;
+  return run_fwd(q, stream);
+}
+
+extern "C" int segger_linear_fwd_f32_split_rowbias(const float* x, int64_t ldx, const void* w3, const float* rowbias, int64_t ld_rb,
+                                                   const int32_t* rowidx, float* y, int64_t ldy, int64_t n_rows, int32_t k_in,
+                                                   int32_t m_out, segger_stream_t stream) {
+  FwdRequest q = request("segger_linear_fwd_f32_split_rowbias", SEGGER_F32, n_rows, k_in, m_out, x, ldx, w3, nullptr, y, ldy);
+  q.w_planes = q.shape_before_empty = q.has_rowbias = true;  q.rowbias = rowbias;  q.rowidx = rowidx;  q.ld_rb = ld_rb;
+  return run_fwd(q, stream);
+}
+
+extern "C" int segger_linear_fwd_f32_act(const float* x, int64_t ldx, const float* w, const float* bias, float* y, int64_t ldy,
+                                         float* y_act, int64_t ld_yact, int32_t act_kind, int64_t n_rows, int32_t k_in,
+                                         int32_t m_out, segger_stream_t stream) {
+  FwdRequest q = request("segger_linear_fwd_f32_act", SEGGER_F32, n_rows, k_in, m_out, x, ldx, w, bias, y, ldy);
+  q.has_act = true;  q.y_act = y_act;  q.ld_yact = ld_yact;  q.act_kind = act_kind;
+  return run_fwd(q, stream);
+}
+
+extern "C" int segger_linear_fwd_f32_gate(const float* x, int64_t ldx, const void* w, int32_t w_is_planes, const float* gate,
+                                          int64_t ld_gate, int32_t gate_kind, float* y, int64_t ldy, int64_t n_rows, int32_t k_in,
+                                          int32_t m_out, segger_stream_t stream) {
+  FwdRequest q = request("segger_linear_fwd_f32_gate", SEGGER_F32, n_rows, k_in, m_out, x, ldx, w, nullptr, y, ldy);
+  q.w_planes = w_is_planes != 0;  q.gate_form = FwdGate::kF32;  q.gate = gate;  q.ld_gate = ld_gate;  q.gate_kind = gate_kind;
+  return run_fwd(q, stream);
 }

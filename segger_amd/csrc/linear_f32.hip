@@ -352,32 +352,23 @@ void launch_wgrad_f32(const WgF32Params& p, int64_t grid, hipStream_t stream) {
 
 }  // namespace
 
-// (declared in common.h for csrc/linear.hip and csrc/linear_wgrad.hip, which dispatch on the dtype)
-int linear_f32_launch(const void* x, int64_t ldx, const void* w, const float* bias, void* y, int64_t ldy, int64_t n_rows,
-                      int k_in, int m_out, hipStream_t stream, const float* rowbias, const int32_t* rowidx, int64_t ld_rb,
-                      const float* gate, int64_t ld_gate, int gate_kind, float* y_act, int64_t ld_yact, int act_kind) {
-  LinF32Params p{static_cast<const float*>(x), ldx, static_cast<const float*>(w), bias, static_cast<float*>(y), ldy,
-                 n_rows, m_out, rowbias, rowidx, ld_rb, gate, ld_gate, gate_kind, y_act, ld_yact, act_kind};
-  if (y_act && k_in == 384) { set_error("segger_linear_fwd_f32_act: k_in 64, 128 or 256"); return SEGGER_EUNSUPPORTED; }
-  if (gate && k_in == 384) { set_error("segger_linear_fwd_f32_gate: k_in 64, 128 or 256 on the exact kernel"); return SEGGER_EUNSUPPORTED; }
-  if (rowbias && k_in == 384) { set_error("segger_linear_fwd_rowbias (fp32): k_in 64, 128 or 256"); return SEGGER_EUNSUPPORTED; }
-  const int64_t nb = (n_rows + 127) / 128;
-  if (nb > 0x7fffffffLL) { set_error("segger_linear_fwd: too many rows"); return SEGGER_EUNSUPPORTED; }
-  dim3 grid((unsigned)nb), block(256);
-  if (k_in == 384 && (m_out == 128 || m_out == 256)) {   // the data gradients of the stacked projections
-    if (m_out == 128) hipLaunchKernelGGL((linear_f32_kslice_kernel<384, 128>), grid, block, 0, stream, p);
-    else              hipLaunchKernelGGL((linear_f32_kslice_kernel<384, 256>), grid, block, 0, stream, p);
-    SEGGER_LAUNCH_CHECK("linear_f32_kslice_kernel");
-    return SEGGER_OK;
-  }
-  switch (k_in) {
-    case 64:  hipLaunchKernelGGL((linear_f32_kernel<64>), grid, block, 0, stream, p); break;
-    case 128: hipLaunchKernelGGL((linear_f32_kernel<128>), grid, block, 0, stream, p); break;
-    case 256: hipLaunchKernelGGL((linear_f32_kernel<256>), grid, block, 0, stream, p); break;
-    case 384: hipLaunchKernelGGL((linear_f32_kernel<384>), grid, block, 0, stream, p); break;
-    default: set_error("segger_linear_fwd: k_in=%d not supported (64, 128, 256, 384)", k_in); return SEGGER_EUNSUPPORTED;
-  }
-  SEGGER_LAUNCH_CHECK("linear_f32_kernel");
+// The executor of the two exact-fp32 routes: plan_fwd (csrc/linear.hip) has made every check and chosen route and grid.
+int launch_fwd_f32(const FwdRequest& q, const FwdPlan& plan, hipStream_t stream) {
+  LinF32Params p{};
+  p.x = static_cast<const float*>(q.x);  p.ldx = q.ldx;
+  p.w = static_cast<const float*>(q.w);  p.bias = q.bias;
+  p.y = static_cast<float*>(q.y);  p.ldy = q.ldy;  p.n_rows = q.n_rows;  p.m_out = q.m_out;
+  if (q.has_rowbias) { p.rowbias = static_cast<const float*>(q.rowbias);  p.rowidx = q.rowidx;  p.ld_rb = q.ld_rb; }
+  if (q.gate_form == FwdGate::kF32) { p.gate = static_cast<const float*>(q.gate);  p.ld_gate = q.ld_gate;  p.gate_kind = q.gate_kind; }
+  if (q.has_act) { p.y_act = q.y_act;  p.ld_yact = q.ld_yact;  p.act_kind = q.act_kind; }
+  const dim3 grid((unsigned)plan.grid), block(256);
+  const bool kslice = plan.route == FwdRoute::kKSliceF32;     // the data gradients of the stacked projections: 384 -> 128 | 256
+#define EXACT(KK) else if (q.k_in == KK) hipLaunchKernelGGL((linear_f32_kernel<KK>), grid, block, 0, stream, p);
+  if (kslice && q.m_out == 128) hipLaunchKernelGGL((linear_f32_kslice_kernel<384, 128>), grid, block, 0, stream, p);
+  else if (kslice) hipLaunchKernelGGL((linear_f32_kslice_kernel<384, 256>), grid, block, 0, stream, p);
+  SEGGER_FWD_K_LIST(EXACT)
+#undef EXACT
+  SEGGER_LAUNCH_CHECK("linear_f32_kernel / linear_f32_kslice_kernel");
   return SEGGER_OK;
 }
 

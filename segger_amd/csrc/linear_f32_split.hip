@@ -79,6 +79,9 @@ constexpr int kWS = kKS * 2 + 16;              // LDS row stride of a staged pla
 #ifndef SEGGER_FS_K384_WAVES
 #define SEGGER_FS_K384_WAVES 1            // K = 384: one wave per SIMD (512 registers): next slice's rows AND next W chunk in flight
 #endif
+#ifndef SEGGER_FS_WRES
+#define SEGGER_FS_WRES 1                  // the two K * M = 49152 shapes on the W-resident kernel (linear_f32_split_wres_kernel)
+#endif
 template <int K>
 __global__ __launch_bounds__(256, K == 128 ? 2 : SEGGER_FS_K384_WAVES) void linear_f32_split_kernel(SplitParams p) {
   constexpr int NS = K / kKS;                  // k slices
@@ -1044,13 +1047,20 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
 
 } }  // namespace segger::(anonymous)
 
+// one matrix of a plane split: the refusal in `who`'s name, or its element count through *n
+static int check_planes_job(const char* who, const float* w, int32_t rows, int32_t cols, const void* planes, int64_t* n) {
+  *n = (int64_t)rows * cols;
+  SEGGER_REQUIRE(rows >= 0 && cols >= 0, "%s: negative size", who);
+  SEGGER_REQUIRE(*n == 0 || (w && planes), "%s: NULL pointer", who);
+  SEGGER_REQUIRE(*n < (int64_t)0x7fffffff * 256, "%s: matrix too large", who);
+  return SEGGER_OK;
+}
+
 extern "C" int segger_f32_split_planes(const float* w, int32_t rows, int32_t cols, int32_t transpose, void* planes,
                                        segger_stream_t stream) {
-  SEGGER_REQUIRE(rows >= 0 && cols >= 0, "segger_f32_split_planes: negative size");
-  const int64_t n = (int64_t)rows * cols;
-  if (n == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(w && planes, "segger_f32_split_planes: NULL pointer");
-  SEGGER_REQUIRE(n < (int64_t)0x7fffffff * 256, "segger_f32_split_planes: matrix too large");
+  int64_t n = 0;
+  const int rc = check_planes_job("segger_f32_split_planes", w, rows, cols, planes, &n);
+  if (rc != SEGGER_OK || n == 0) return rc;
   hipLaunchKernelGGL(f32_split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, rows, cols,
                      transpose, static_cast<bf16_t*>(planes));
   SEGGER_LAUNCH_CHECK("f32_split_planes_kernel");
@@ -1063,10 +1073,9 @@ extern "C" int segger_f32_split_planes_many(const segger_planes_job* jobs, int32
   int64_t most = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const segger_planes_job& j = jobs[i];
-    SEGGER_REQUIRE(j.rows >= 0 && j.cols >= 0, "segger_f32_split_planes_many: negative size");
-    const int64_t n = (int64_t)j.rows * j.cols;
-    SEGGER_REQUIRE(n == 0 || (j.w && j.planes), "segger_f32_split_planes_many: NULL pointer");
-    SEGGER_REQUIRE(n < (int64_t)0x7fffffff * 256, "segger_f32_split_planes_many: matrix too large");
+    int64_t n = 0;
+    const int rc = check_planes_job("segger_f32_split_planes_many", j.w, j.rows, j.cols, j.planes, &n);
+    if (rc != SEGGER_OK) return rc;
     all.job[i] = j;
     if (n > most) most = n;
   }
@@ -1079,96 +1088,30 @@ extern "C" int segger_f32_split_planes_many(const segger_planes_job* jobs, int32
 
 extern "C" int segger_linear_wgrad_f32_split_supported(int32_t m_out, int32_t k_in) { return wgrad_f32_split_shape_ok(m_out, k_in); }
 
-extern "C" int segger_linear_fwd_f32_split_supported(int32_t k_in, int32_t m_out) {
-  return (k_in == 128 && m_out > 0 && m_out % kCH == 0) || (k_in == 384 && m_out == 128);
-}
+namespace segger {
 
-static int split_fwd_launch(const float* x, int64_t ldx, const void* w3, const float* bias, const float* rowbias, int64_t ld_rb,
-                            const int32_t* rowidx, float* y, int64_t ldy, int64_t n_rows, int32_t k_in, int32_t m_out,
-                            segger_stream_t stream, const float* gate = nullptr, int64_t ld_gate = 0, int gate_kind = 0);
-
-extern "C" int segger_linear_fwd_f32_split(const float* x, int64_t ldx, const void* w3, const float* bias, float* y, int64_t ldy,
-                                           int64_t n_rows, int32_t k_in, int32_t m_out, segger_stream_t stream) {
-  return split_fwd_launch(x, ldx, w3, bias, nullptr, 0, nullptr, y, ldy, n_rows, k_in, m_out, stream);
-}
-
-extern "C" int segger_linear_fwd_f32_split_rowbias(const float* x, int64_t ldx, const void* w3, const float* rowbias, int64_t ld_rb,
-                                                   const int32_t* rowidx, float* y, int64_t ldy, int64_t n_rows, int32_t k_in,
-                                                   int32_t m_out, segger_stream_t stream) {
-  SEGGER_REQUIRE(n_rows == 0 || (rowbias && rowidx && is_aligned(rowbias, 16) && ld_rb >= m_out && ld_rb % 4 == 0),
-                 "segger_linear_fwd_f32_split_rowbias: table NULL, misaligned or ld < m_out");
-  return split_fwd_launch(x, ldx, w3, nullptr, rowbias, ld_rb, rowidx, y, ldy, n_rows, k_in, m_out, stream);
-}
-
-extern "C" int segger_linear_fwd_f32_act(const float* x, int64_t ldx, const float* w, const float* bias, float* y, int64_t ldy,
-                                         float* y_act, int64_t ld_yact, int32_t act_kind, int64_t n_rows, int32_t k_in,
-                                         int32_t m_out, segger_stream_t stream) {
-  SEGGER_REQUIRE(n_rows >= 0 && (act_kind == 1 || act_kind == 2), "segger_linear_fwd_f32_act: act_kind 1 (GELU) or 2 (SiLU)");
-  if (n_rows == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(x && w && y && y_act && is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16) && is_aligned(y_act, 16) && (!bias || is_aligned(bias, 16)) &&
-                     ldx >= k_in && ldy >= m_out && ld_yact >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && ld_yact % 4 == 0,
-                 "segger_linear_fwd_f32_act: NULL pointer or rows not 16-byte aligned");
-  if (!((k_in == 64 || k_in == 128 || k_in == 256) && m_out > 0 && m_out % 64 == 0)) {
-    set_error("segger_linear_fwd_f32_act: k_in=%d m_out=%d not supported (k_in 64 / 128 / 256, m_out %% 64 == 0)", k_in, m_out);
-    return SEGGER_EUNSUPPORTED;
-  }
-  return linear_f32_launch(x, ldx, w, bias, y, ldy, n_rows, k_in, m_out, (hipStream_t)stream, nullptr, nullptr, 0, nullptr, 0, 0,
-                           y_act, ld_yact, act_kind);
-}
-
-extern "C" int segger_linear_fwd_f32_gate(const float* x, int64_t ldx, const void* w, int32_t w_is_planes, const float* gate,
-                                          int64_t ld_gate, int32_t gate_kind, float* y, int64_t ldy, int64_t n_rows, int32_t k_in,
-                                          int32_t m_out, segger_stream_t stream) {
-  SEGGER_REQUIRE(n_rows >= 0 && (gate_kind == 1 || gate_kind == 2), "segger_linear_fwd_f32_gate: gate_kind 1 (GELU) or 2 (SiLU)");
-  if (n_rows == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(x && w && y && gate && is_aligned(x, 16) && is_aligned(w, 16) && is_aligned(y, 16) && is_aligned(gate, 16) && ldx >= k_in &&
-                     ldy >= m_out && ld_gate >= m_out && ldx % 4 == 0 && ldy % 4 == 0 && ld_gate % 4 == 0,
-                 "segger_linear_fwd_f32_gate: NULL pointer or rows not 16-byte aligned");
-  if (w_is_planes) return split_fwd_launch(x, ldx, w, nullptr, nullptr, 0, nullptr, y, ldy, n_rows, k_in, m_out, stream, gate, ld_gate, gate_kind);
-  if (!((k_in == 64 || k_in == 128 || k_in == 256) && m_out > 0 && m_out % 64 == 0)) {
-    set_error("segger_linear_fwd_f32_gate: k_in=%d m_out=%d not supported (k_in 64 / 128 / 256, m_out %% 64 == 0)", k_in, m_out);
-    return SEGGER_EUNSUPPORTED;
-  }
-  return linear_f32_launch(x, ldx, w, nullptr, y, ldy, n_rows, k_in, m_out, (hipStream_t)stream, nullptr, nullptr, 0, gate, ld_gate,
-                           gate_kind);
-}
-
-static int split_fwd_launch(const float* x, int64_t ldx, const void* w3, const float* bias, const float* rowbias, int64_t ld_rb,
-                            const int32_t* rowidx, float* y, int64_t ldy, int64_t n_rows, int32_t k_in, int32_t m_out,
-                            segger_stream_t stream, const float* gate, int64_t ld_gate, int gate_kind) {
-  SEGGER_REQUIRE(n_rows >= 0, "segger_linear_fwd_f32_split: negative size");
-  if (!segger_linear_fwd_f32_split_supported(k_in, m_out)) {
-    set_error("segger_linear_fwd_f32_split: k_in=%d m_out=%d not supported (128 -> multiple of 64, 384 -> 128)", k_in, m_out);
-    return SEGGER_EUNSUPPORTED;
-  }
-  if (n_rows == 0) return SEGGER_OK;
-  SEGGER_REQUIRE(x && w3 && y, "segger_linear_fwd_f32_split: NULL pointer");
-  SEGGER_REQUIRE(is_aligned(x, 16) && is_aligned(w3, 16) && is_aligned(y, 16) && (!bias || is_aligned(bias, 16)) && ldx >= k_in && ldy >= m_out &&
-                     ldx % 4 == 0 && ldy % 4 == 0, "segger_linear_fwd_f32_split: rows (and the bias) must be 16-byte aligned");
-  const int64_t nb = (n_rows + 127) / 128;
-  SEGGER_REQUIRE(nb <= 0x7fffffffLL, "segger_linear_fwd_f32_split: too many rows");
-  SplitParams p{x, ldx, static_cast<const bf16_t*>(w3), bias, y, ldy, n_rows, m_out, rowbias, rowidx, ld_rb, gate, ld_gate, gate_kind};
-#ifndef SEGGER_FS_WRES
-#define SEGGER_FS_WRES 1                   // the two K * M = 49152 shapes on the W-resident kernel
-#endif
-  const int64_t n_tiles = (n_rows + 31) / 32;
-  const unsigned wres_grid = (unsigned)std::min<int64_t>(n_tiles, device_cu_count());
-  // (the W-resident kernels address x, y and the gate with 31-bit byte offsets)
-  // (SEGGER_AMD_F32_WRES=0 in the environment: the chunked kernels for every shape -- A/B runs without a rebuild)
+// The planes' executor (plan_fwd, csrc/linear.hip, has made every check).  W-resident: a listed case whose x, y and gate fit
+// that kernel's 31-bit byte offsets, unless SEGGER_FS_WRES or SEGGER_AMD_F32_WRES=0 in the environment (read once) says no.
+int launch_fwd_f32_split(const FwdRequest& q, const FwdPlan& plan, hipStream_t stream) {
+  SplitParams p{};
+  p.x = static_cast<const float*>(q.x);  p.ldx = q.ldx;
+  p.w3 = static_cast<const bf16_t*>(q.w);  p.bias = q.bias;
+  p.y = static_cast<float*>(q.y);  p.ldy = q.ldy;  p.n_rows = q.n_rows;  p.m_out = q.m_out;
+  if (q.has_rowbias) { p.rowbias = static_cast<const float*>(q.rowbias);  p.rowidx = q.rowidx;  p.ld_rb = q.ld_rb; }
+  if (q.gate_form == FwdGate::kF32) { p.gate = static_cast<const float*>(q.gate);  p.ld_gate = q.ld_gate;  p.gate_kind = q.gate_kind; }
   static const bool wres_env = [] { const char* e = getenv("SEGGER_AMD_F32_WRES"); return !(e && e[0] == '0'); }();
-  const bool wres_ok = SEGGER_FS_WRES && wres_env && !rowbias && n_rows * ldx * 4 < 0x7ffff000LL && n_rows * ldy * 4 < 0x7ffff000LL &&
-                       (!gate || n_rows * ld_gate * 4 < 0x7ffff000LL);
-#define WRES(KK, MM, GG, BB) hipLaunchKernelGGL((linear_f32_split_wres_kernel<KK, MM, GG, BB>), dim3(wres_grid), dim3(256), 0, \
-                                                (hipStream_t)stream, p, (int)n_tiles)
-  if (wres_ok && k_in == 384 && m_out == 128 && !bias && gate && gate_kind == 1) WRES(384, 128, 1, false);
-  else if (wres_ok && k_in == 384 && m_out == 128 && !bias && gate) WRES(384, 128, 2, false);
-  else if (wres_ok && k_in == 384 && m_out == 128 && !bias) WRES(384, 128, 0, false);
-  else if (wres_ok && k_in == 384 && m_out == 128 && !gate) WRES(384, 128, 0, true);
-  else if (wres_ok && k_in == 128 && m_out == 384 && !gate && bias) WRES(128, 384, 0, true);
-  else if (wres_ok && k_in == 128 && m_out == 384 && !gate) WRES(128, 384, 0, false);
+  const auto fits = [&](int64_t ld) { return p.n_rows * ld * 4 < 0x7ffff000LL; };
+  const bool wres = SEGGER_FS_WRES && wres_env && !p.rowbias && fits(p.ldx) && fits(p.ldy) && (!p.gate || fits(p.ld_gate));
+  const int64_t n_tiles = ceil_div(p.n_rows, 32);
+  const dim3 grid((unsigned)plan.grid), wres_grid((unsigned)std::min<int64_t>(n_tiles, device_cu_count())), block(256);
+#define WRES(KK, MM, GG, BB) else if (wres && q.k_in == KK && p.m_out == MM && p.gate_kind == GG && (p.bias != nullptr) == BB) \
+    hipLaunchKernelGGL((linear_f32_split_wres_kernel<KK, MM, GG, BB>), wres_grid, block, 0, stream, p, (int)n_tiles);
+  if (false) {} SEGGER_FWD_SPLIT_WRES_LIST(WRES)
+  else if (q.k_in == 128) hipLaunchKernelGGL((linear_f32_split_kernel<128>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((linear_f32_split_kernel<384>), grid, block, 0, stream, p);
 #undef WRES
-  else if (k_in == 128) hipLaunchKernelGGL((linear_f32_split_kernel<128>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((linear_f32_split_kernel<384>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p);
   SEGGER_LAUNCH_CHECK("linear_f32_split_kernel");
   return SEGGER_OK;
 }
+
+}  // namespace segger

@@ -709,3 +709,216 @@ def test_wgrad_pair_sides_that_take_two_launches(cuda, monkeypatch, dtype, na, n
         assert gw.shape == (m, k) and gb.shape == (m,) and torch.equal(gw, rw) and torch.equal(gb, rb)
         if n == 0:
             assert not gw.any() and not gb.any()
+
+
+# ---- the forward entry points called directly: what the route plan (plan_fwd, csrc/linear.hip) decides ----------------------
+def _entry(name, device, *args):
+    from segger_amd import _lib
+    with _lib.on_device(device):
+        rc = getattr(_lib.load(), name)(*args, _lib.stream_ptr(device))
+    _lib.check(rc, name)
+
+
+def _side(x, w, b, y):
+    from segger_amd import _lib
+    a = _lib.LinearArgs()
+    a.x, a.ldx, a.w, a.bias = x.data_ptr(), x.shape[1], w.data_ptr(), _lib.ptr(b)
+    a.y, a.ldy, a.n_rows, a.m_out = y.data_ptr(), y.shape[1], x.shape[0], w.shape[0]
+    return a
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_linear_forward_entries_over_no_rows_leave_the_output_alone(cuda, dtype):
+    """n_rows = 0 on each of the nine forward entry points: SEGGER_OK, nothing launched -- a sentinel-filled y (and y_act)
+    stays as it was.  The pair with (0, 0), (0, 17) and (17, 0) rows: the side with rows equals its single launch bit for bit."""
+    import ctypes as C
+    from segger_amd import ops
+    from segger_amd._lib import DTYPE_CODE
+    code, f32 = DTYPE_CODE[dtype], dtype == torch.float32
+    k, m = 128, 128
+    g = torch.Generator(device=cuda).manual_seed(5)
+    x = torch.randn(8, k, device=cuda, generator=g).to(dtype)
+    w = (torch.randn(m, k, device=cuda, generator=g) / k ** 0.5).to(dtype)
+    b = torch.randn(m, device=cuda, generator=g)
+    tab = torch.randn(4, m, device=cuda, generator=g).to(dtype)
+    ids = torch.zeros(8, dtype=torch.int32, device=cuda)
+    y = torch.full((8, m), 7.0, device=cuda, dtype=dtype)
+    ya = torch.full((8, m), 7.0, device=cuda, dtype=dtype)
+    P = lambda t: t.data_ptr()
+    _entry("segger_linear_fwd", cuda, P(x), k, P(w), P(b), P(y), m, 0, k, m, code)
+    _entry("segger_linear_fwd_rowbias", cuda, P(x), k, P(w), P(b), P(tab), m, P(ids), P(y), m, 0, k, m, code)
+    if f32:
+        w3 = ops.f32_split_planes(w)
+        _entry("segger_linear_fwd_f32_split", cuda, P(x), k, P(w3), P(b), P(y), m, 0, k, m)
+        _entry("segger_linear_fwd_f32_split_rowbias", cuda, P(x), k, P(w3), P(tab), m, P(ids), P(y), m, 0, k, m)
+        _entry("segger_linear_fwd_f32_act", cuda, P(x), k, P(w), P(b), P(y), m, P(ya), m, 1, 0, k, m)
+        for planes, wq in ((0, w), (1, w3)):
+            _entry("segger_linear_fwd_f32_gate", cuda, P(x), k, P(wq), planes, P(x), k, 2, P(y), m, 0, k, m)
+    else:
+        w64 = w[:, :64].contiguous()
+        _entry("segger_linear_fwd_silu_grad", cuda, P(x), k, P(w64), P(ya), m, P(y), m, 0, 64, m, code)
+    for na, nb in ((0, 0), (0, 17), (17, 0)):
+        xs = [torch.randn(n + 1, k, device=cuda, generator=g).to(dtype)[:n] for n in (na, nb)]
+        ys = [torch.full((n + 4, m), 7.0, device=cuda, dtype=dtype) for n in (na, nb)]
+        sides = [_side(xi, w, b, yi[:xi.shape[0]]) for xi, yi in zip(xs, ys)]
+        _entry("segger_linear_fwd_pair", cuda, C.byref(sides[0]), C.byref(sides[1]), k, code)
+        _entry("segger_linear_fwd_pair_k", cuda, C.byref(sides[0]), k, C.byref(sides[1]), k, code)
+        for xi, yi in zip(xs, ys):
+            n = xi.shape[0]
+            assert bool((yi[n:] == 7.0).all())
+            if n:
+                assert torch.equal(yi[:n], ops.linear_fwd_launch(xi, w, b))
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all()) and bool((ya == 7.0).all())
+
+
+@pytest.mark.parametrize("dtype,ka,kb", [(torch.bfloat16, 384, 128), (torch.float16, 384, 128), (torch.bfloat16, 256, 128),
+                                         (torch.bfloat16, 128, 128), (torch.float32, 128, 128), (torch.float32, 384, 128)])
+def test_linear_pair_k_equals_two_launches(cuda, dtype, ka, kb):
+    """segger_linear_fwd_pair_k itself (a first layer's two data gradients), every (na, nb) of {1, 127, 129}: the joint
+    kernel of widths (384, 128), two launches for (256, 128), the equal-width joint kernel, fp32 storage (two launches of
+    the exact kernel) -- each side bit for bit what its single launch gives."""
+    from segger_amd import ops
+    g = torch.Generator(device=cuda).manual_seed(ka + kb)
+    m = 128
+    wa = (torch.randn(m, ka, device=cuda, generator=g) / ka ** 0.5).to(dtype)
+    wb = (torch.randn(m, kb, device=cuda, generator=g) / kb ** 0.5).to(dtype)
+    for na in (1, 127, 129):
+        for nb in (1, 127, 129):
+            xa = torch.randn(na, ka, device=cuda, generator=g).to(dtype)
+            xb = torch.randn(nb, kb, device=cuda, generator=g).to(dtype)
+            ya, yb = ops.linear_fwd_pair_launch(xa, wa, xb, wb)
+            assert torch.equal(ya, ops.linear_fwd_launch(xa, wa, None)), (na, nb)
+            assert torch.equal(yb, ops.linear_fwd_launch(xb, wb, None)), (na, nb)
+
+
+def test_linear_pair_k_with_a_persistent_side(cuda):
+    """Side a at 262 144 rows of 128 -> 64 takes the persistent W-resident launch of its own and b goes alone."""
+    from segger_amd import ops
+    g = torch.Generator(device=cuda).manual_seed(3)
+    wa = (torch.randn(64, 128, device=cuda, generator=g) / 128 ** 0.5).bfloat16()
+    wb = (torch.randn(64, 128, device=cuda, generator=g) / 128 ** 0.5).bfloat16()
+    xa = torch.randn(262_144, 128, device=cuda, generator=g).bfloat16()
+    xb = torch.randn(129, 128, device=cuda, generator=g).bfloat16()
+    ya, yb = ops.linear_fwd_pair_launch(xa, wa, xb, wb)
+    assert torch.equal(ya, ops.linear_fwd_launch(xa, wa, None)) and torch.equal(yb, ops.linear_fwd_launch(xb, wb, None))
+    assert torch.equal(ya[5000:10_000], ops.linear_fwd_launch(xa[5000:10_000], wa, None))       # (the chunked kernel)
+
+
+@pytest.mark.parametrize("n", [33, 4133])
+@pytest.mark.parametrize("k,m,gate,bias", [(384, 128, "gelu", False), (384, 128, "silu", False), (384, 128, None, False),
+                                            (384, 128, None, True), (128, 384, None, True), (128, 384, None, False),
+                                            (128, 384, "gelu", False), (128, 384, "silu", False)])
+def test_linear_fp32_split_every_w_resident_case_and_the_chunked_one_beside_it(cuda, monkeypatch, k, m, gate, bias, n):
+    """The six W-resident plane kernels (K, M, gate kind, bias) through segger_linear_fwd_f32_split / _f32_gate, and the
+    chunked kernel that serves 128 -> 384 with a gate.  (No entry point passes a bias AND a gate, so the other chunked
+    neighbour, 384 -> 128 with both, cannot be reached.)  Without a gate: the bound of
+    test_linear_fp32_split_within_the_exact_kernels_error; with one: that of test_linear_f32_gate_epilogue."""
+    from segger_amd import ops
+    monkeypatch.setattr(ops, "F32_SPLIT", True)
+    g = torch.Generator(device=cuda).manual_seed(k + m + n)
+    x = torch.randn(n, k, device=cuda, generator=g)
+    w = torch.randn(m, k, device=cuda, generator=g) / k ** 0.5
+    bound = x.double().abs() @ w.double().abs().t()
+    if gate is None:
+        b = torch.randn(m, device=cuda, generator=g) if bias else None
+        y = ops.linear_f32_split_launch(x, ops.f32_split_planes(w), b)
+        y_exact = ops.linear_fwd_launch(x, w, b)
+        ref = x.double() @ w.double().t()
+        if bias:
+            ref, bound = ref + b.double(), bound + b.double().abs()
+        e_split = ((y.double() - ref).abs() / bound).max().item()
+        e_exact = ((y_exact.double() - ref).abs() / bound).max().item()
+        print("split", e_split, "exact", e_exact)
+        assert e_split <= max(2 * e_exact, 2.0 ** -23), (e_split, e_exact)
+        assert e_split <= 4 * 2.0 ** -24 * k ** 0.5
+    else:
+        gt = torch.randn(n, m, device=cuda, generator=g) * 2
+        y = ops.linear_f32_gate_launch(x, w, gt, gate)
+        gd = gt.double().requires_grad_(True)
+        act = torch.nn.functional.gelu(gd) if gate == "gelu" else torch.nn.functional.silu(gd)
+        (dact,) = torch.autograd.grad(act.sum(), gd)
+        ref = (x.double() @ w.double().t()) * dact
+        err = ((y.double() - ref).abs() / (bound + 1e-6)).max().item()
+        print("gate", err)
+        assert err < 2e-5
+
+
+@pytest.mark.parametrize("n", [1, 127, 129])
+def test_linear_rowbias_silu_grad_and_act_entries_against_fp64(cuda, n):
+    """The entry points that only module-level tests reached, called directly at every K they serve, against fp64 on the
+    rounded inputs.  16 bit (segger_linear_fwd_rowbias at K = 64 / 128, segger_linear_fwd_silu_grad at K = 64): one rounding
+    of an fp32 result, the bound of test_linear_forward.  fp32 (segger_linear_fwd_rowbias and segger_linear_fwd_f32_act at
+    K = 64 / 128 / 256): the bound of test_linear_forward_fp32 with the table row among the summed terms; y_act against the
+    activation of the kernel's own y: the epilogue's GELU is within 4e-7 absolutely (csrc/common.h), its SiLU is a
+    reciprocal and an exp2 of a few ulp each, and the result is rounded once: 2e-6 |act| + 4e-7.  segger_linear_fwd_f32_split_rowbias
+    (K = 128 and 384 -> 128): the bound of test_linear_fp32_split_within_the_exact_kernels_error against the exact kernel's row-bias form."""
+    from segger_amd import ops
+    from segger_amd._lib import DTYPE_CODE
+    P = lambda t: t.data_ptr()
+    g = torch.Generator(device=cuda).manual_seed(n)
+    m, n_tab = 128, 5
+    ids = torch.randint(0, n_tab, (n,), device=cuda, generator=g, dtype=torch.int32)
+    for dtype in (torch.bfloat16, torch.float16):
+        code, rel = DTYPE_CODE[dtype], (2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -10)
+        for k in (64, 128):
+            x = torch.randn(n, k, device=cuda, generator=g).to(dtype)
+            w = (torch.randn(m, k, device=cuda, generator=g) / k ** 0.5).to(dtype)
+            b = torch.randn(m, device=cuda, generator=g)
+            tab = torch.randn(n_tab, m, device=cuda, generator=g).to(dtype)
+            y = torch.empty(n, m, device=cuda, dtype=dtype)
+            _entry("segger_linear_fwd_rowbias", cuda, P(x), k, P(w), P(b), P(tab), m, P(ids), P(y), m, n, k, m, code)
+            ref = x.double() @ w.double().t() + b.double() + tab.double()[ids.long()]
+            assert ((y.double() - ref).abs() <= rel * ref.abs() + 1e-3).all(), (dtype, k)
+        x = torch.randn(n, 64, device=cuda, generator=g).to(dtype)
+        w = (torch.randn(m, 64, device=cuda, generator=g) / 8).to(dtype)
+        z = (torch.randn(n, m, device=cuda, generator=g) * 2).to(dtype)
+        y = torch.empty(n, m, device=cuda, dtype=dtype)
+        _entry("segger_linear_fwd_silu_grad", cuda, P(x), 64, P(w), P(z), m, P(y), m, n, 64, m, code)
+        zd = z.double().requires_grad_(True)
+        (dz,) = torch.autograd.grad(torch.nn.functional.silu(zd).sum(), zd)
+        ref = (x.double() @ w.double().t()) * dz
+        assert ((y.double() - ref).abs() <= rel * ref.abs() + 1e-3).all(), dtype
+    for k in (64, 128, 256):
+        x = torch.randn(n, k, device=cuda, generator=g)
+        w = torch.randn(m, k, device=cuda, generator=g) / k ** 0.5
+        b = torch.randn(m, device=cuda, generator=g)
+        tab = torch.randn(n_tab, m, device=cuda, generator=g)
+        rows = tab.double()[ids.long()]
+        y = torch.empty(n, m, device=cuda)
+        _entry("segger_linear_fwd_rowbias", cuda, P(x), k, P(w), P(b), P(tab), m, P(ids), P(y), m, n, k, m, 0)
+        ref = x.double() @ w.double().t() + b.double() + rows
+        terms = x.double().abs() @ w.double().abs().t() + b.double().abs() + rows.abs()
+        assert bool(((y.double() - ref).abs() <= 2e-6 * terms + 1e-7).all()), k
+        if k == 128:
+            ys = torch.empty(n, m, device=cuda)
+            _entry("segger_linear_fwd_rowbias", cuda, P(x), k, P(w), None, P(tab), m, P(ids), P(y), m, n, k, m, 0)
+            _entry("segger_linear_fwd_f32_split_rowbias", cuda, P(x), k, P(ops.f32_split_planes(w)), P(tab), m, P(ids), P(ys), m,
+                   n, k, m)
+            ref0, terms0 = ref - b.double(), terms - b.double().abs()
+            e_split = ((ys.double() - ref0).abs() / terms0).max().item()
+            e_exact = ((y.double() - ref0).abs() / terms0).max().item()
+            assert e_split <= max(2 * e_exact, 2.0 ** -23) and e_split <= 4 * 2.0 ** -24 * k ** 0.5, (e_split, e_exact)
+        for kind, fn in ((1, torch.nn.functional.gelu), (2, torch.nn.functional.silu)):
+            y, ya = torch.empty(n, m, device=cuda), torch.empty(n, m, device=cuda)
+            _entry("segger_linear_fwd_f32_act", cuda, P(x), k, P(w), P(b), P(y), m, P(ya), m, kind, n, k, m)
+            ref = x.double() @ w.double().t() + b.double()
+            terms = x.double().abs() @ w.double().abs().t() + b.double().abs()
+            assert bool(((y.double() - ref).abs() <= 2e-6 * terms + 1e-7).all()), (k, kind)
+            act = fn(y.double())
+            assert bool(((ya.double() - act).abs() <= 2e-6 * act.abs() + 4e-7).all()), (k, kind)
+    # the planes' other shape, 384 -> 128 (the K-slice form of the chunked plane kernel) with the row bias: the exact kernels
+    # refuse a row bias at K = 384, so the exact error is that of the exact K-slice kernel plus the table rows added in fp32
+    k = 384
+    x = torch.randn(n, k, device=cuda, generator=g)
+    w = torch.randn(m, k, device=cuda, generator=g) / k ** 0.5
+    tab = torch.randn(n_tab, m, device=cuda, generator=g)
+    ys = torch.empty(n, m, device=cuda)
+    _entry("segger_linear_fwd_f32_split_rowbias", cuda, P(x), k, P(ops.f32_split_planes(w)), P(tab), m, P(ids), P(ys), m, n, k, m)
+    y_exact = ops.linear_fwd_launch(x, w, None) + tab[ids.long()]
+    ref = x.double() @ w.double().t() + tab.double()[ids.long()]
+    terms = x.double().abs() @ w.double().abs().t() + tab.double()[ids.long()].abs()
+    e_split = ((ys.double() - ref).abs() / terms).max().item()
+    e_exact = ((y_exact.double() - ref).abs() / terms).max().item()
+    print("split rowbias 384", e_split, "exact", e_exact)
+    assert e_split <= max(2 * e_exact, 2.0 ** -23) and e_split <= 4 * 2.0 ** -24 * k ** 0.5, (e_split, e_exact)
