@@ -1501,6 +1501,74 @@ int segger_polygon_join_fill(const double* points, int64_t n_points, const int64
                              int64_t* point_index_out, int64_t capacity, void* workspace, int64_t workspace_bytes,
                              segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Cell boundary polygons: one ring per segmented cell, the convex hull of the cell's transcripts -- the reference's
+ * generate_boundaries / cell_boundary with method="convex_hull" (src/segger/export/boundary.py:157-217), optionally rounded
+ * by Chaikin corner cutting (boundary.py:42-54).  The reference's DEFAULT method, "delaunay" (boundary.py:57-154, a
+ * sequential pruning of a Delaunay triangulation), is NOT built.  The kernels behind segger_amd.boundaries.
+ * csrc/boundaries.hip.  Purely additive: two new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * Input:  xy [n_rows, 2] fp64 (16-byte aligned), cell [n_rows] int32, keep [n_rows] bytes or NULL (= all ones), and the
+ *   cell id domain n_cells.  Row i is COUNTED iff 0 <= cell[i] < n_cells, keep[i] != 0 and both coordinates are finite.  A
+ *   negative cell id means "unassigned" and is skipped silently, as is a row with keep[i] == 0 whatever else it holds.  A
+ *   row with keep[i] != 0 and cell[i] >= n_cells adds one to counters[4], one with an id inside the domain and a NaN or
+ *   infinite coordinate adds one to counters[5]; neither is used anywhere.  -0.0 is read as +0.0.
+ *
+ * Output, for the K cells that get a polygon, in ascending cell id:
+ *     ring_offsets   [K + 1] int64   ring q is xy_out[ring_offsets[q] .. ring_offsets[q + 1]), open (no closing duplicate)
+ *     xy_out         [V, 2] fp64     the rings; a CSR that segger_polygon_props and segger_polygon_join_* take as it is
+ *     cell_ids       [K] int32       the cell of ring q
+ *     n_transcripts  [K] int64       its counted rows (duplicates included)
+ *     counters       [SEGGER_BOUNDARY_COUNTERS] uint64:  0 counted rows, 1 present cells (at least one counted row), 2 K,
+ *                    3 V, 4 rows with a cell id >= n_cells, 5 rows with a non-finite coordinate, 6 cells the chunked route
+ *                    refused, 7 the largest such cell id + 1
+ *   The arrays are sized by the caller for the worst case: ring_offsets min(n_rows, n_cells) + 1, cell_ids and n_transcripts
+ *   min(n_rows, n_cells), xy_out xy_capacity vertices; n_rows << smoothing vertices always suffice, and nothing is written
+ *   at or beyond xy_capacity (the caller compares counters[3] with it).  A present cell whose hull has fewer than 3
+ *   vertices -- fewer than 3 distinct points, or only collinear ones -- has no polygon: the reference's
+ *   np.unique(points) < 3 -> None and its collinear case, where shapely's hull is no Polygon.  present - K cells dropped.
+ *
+ * Stages, on one stream without a host synchronisation (every size downstream of the keys is a device counter):
+ *   keys     key = cell << 32 | row for a counted row, n_cells << 32 otherwise; one keys-only radix sort, stable by
+ *            construction (the row is part of the key): a cell's rows are contiguous, in ascending row order;
+ *   segments the first sorted position of every present cell (a stream compaction) and its length;
+ *   hull     one wave per cell, the cells binned by route on the device: n <= 64 points in registers; 64 < n <=
+ *            SEGGER_MORPH_MAX_VERTS staged in LDS; above that the chunked route: hull what is staged, move the hull to the
+ *            front of LDS, stage the next SEGGER_MORPH_MAX_VERTS - h points, hull again, until the cell is consumed.  If a
+ *            running hull has more than SEGGER_BOUNDARY_CHUNK_MAX_HULL vertices while points remain, the cell is refused
+ *            (counters[6], [7]; no polygon): every round then stages at least half a buffer of new points.
+ *            The march is segger_polygon_props': from the lowest (x, then y) point, counter-clockwise; the next vertex is
+ *            the most clockwise point as seen from the current one, ties go to the larger distance, then to the lower
+ *            index; a point equal to the current one never competes.  A point on a hull edge or equal to another point
+ *            is never a hull vertex.  The products run on the coordinates as given minus the current vertex, fp64, FMA
+ *            contraction off: exact when the coordinates are integers below 2^25 in magnitude (or share such a grid).
+ *            The hull's vertices are copies of input coordinates, bit for bit;
+ *   scan     K, V and the offsets: an exclusive scan of h << smoothing over the cells with h >= 3;
+ *   emit     the rings.  With smoothing = s > 0, s Chaikin iterations as the reference writes them: out[2k] = 0.75 p[k] +
+ *            0.25 p[k + 1], out[2k + 1] = 0.25 p[k] + 0.75 p[k + 1], indices cyclic, two products and one sum per
+ *            coordinate, unfused, iterated: every output vertex is computed from the s + 1 hull vertices it depends on,
+ *            level by level, with the operations numpy performs -- the same bits.  A ring of h vertices becomes h 2^s.
+ *   No floating-point atomics.  The same rows in any order give the same bytes whenever the orientation products above are
+ *   exact; with coordinates for which they round, points within rounding of a hull edge may be decided differently.
+ *
+ * Workspace: segger_cell_boundaries_workspace_bytes(n_rows, n_cells), 256-byte aligned: with N = max(n_rows, 1),
+ *   C = max(min(n_rows, n_cells), 1) and up() rounding up to 256:  256 + 2 up(4 C) + up(4 (N / 4097 + 1)) + up(8 N) +
+ *   up(16 N) + 4 up(4 C) + the storage of the sort and of the compaction.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative n_rows, workspace_bytes or xy_capacity,
+ *   2^31 - 1 rows or more, n_cells outside 1 .. 2^31 - 1, smoothing outside 0 .. SEGGER_BOUNDARY_MAX_SMOOTHING, and for
+ *   n_rows > 0 a NULL pointer (keep may be NULL; xy_out may be NULL when xy_capacity = 0), a misaligned pointer (xy and
+ *   xy_out: 16 bytes), a workspace below the size above.  n_rows = 0 returns SEGGER_OK after checking counters and
+ *   ring_offsets for NULL and launches nothing: the caller's zeroed counters and ring_offsets[0] = 0 stand.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_BOUNDARY_MAX_SMOOTHING 6
+#define SEGGER_BOUNDARY_CHUNK_MAX_HULL 2048   /* half of SEGGER_MORPH_MAX_VERTS */
+#define SEGGER_BOUNDARY_COUNTERS 8
+int64_t segger_cell_boundaries_workspace_bytes(int64_t n_rows, int64_t n_cells);
+int segger_cell_boundaries(const double* xy /* [N, 2] */, const int32_t* cell, const uint8_t* keep /* or NULL */,
+                           int64_t n_rows, int64_t n_cells, int32_t smoothing, int64_t* ring_offsets, double* xy_out,
+                           int64_t xy_capacity, int32_t* cell_ids, int64_t* n_transcripts, uint64_t* counters,
+                           void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -24,6 +24,7 @@ CONTAM_MAX_TYPES, CONTAM_MAX_K, CONTAM_MAX_REF_GENES, CONTAM_LDS_BYTES = 256, 64
 MORPH_MAX_VERTS, MORPH_COLS, MORPH_ERR_OFFSETS, MORPH_ERR_CAP = 4096, 12, 1, 2                       # SEGGER_MORPH_*
 PJOIN_CONTAINS, PJOIN_INTERSECTS = 0, 1                                                                # SEGGER_PJOIN_*
 PJOIN_ERR_OFFSETS, PJOIN_ERR_CAP, PJOIN_ERR_BUFFER, PJOIN_ERR_FILL = 1, 2, 4, 8
+BOUNDARY_MAX_SMOOTHING, BOUNDARY_CHUNK_MAX_HULL, BOUNDARY_COUNTERS = 6, 2048, 8                       # SEGGER_BOUNDARY_*
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -367,6 +368,9 @@ EXPORTS = {
                                             C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]),
     "segger_polygon_join_fill": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_double, C.c_double,
                                            C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, C.c_int64, vp]),
+    "segger_cell_boundaries_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "segger_cell_boundaries": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp,
+                                         C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,488 @@
+// segger_cell_boundaries: one boundary polygon per segmented cell, the convex hull of the cell's transcripts, optionally
+// rounded by Chaikin corner cutting -- the reference's generate_boundaries with method="convex_hull"
+// (src/segger/export/boundary.py:157-217; the default method, "delaunay", is not built).  include/segger_amd.h has the
+// contract.  The output is a ring CSR that segger_polygon_props and segger_polygon_join_* take as it is.
+//
+// Kernels and library calls on one stream, no host synchronisation (every size after the keys is a device counter):
+//   bnd_keys_kernel    one thread per row: key = cell << 32 | row for a counted row, the sentinel n_cells << 32 otherwise;
+//   (rocprim keys sort: stable by construction, the row is part of the key; rocprim select: the first sorted position of
+//   every present cell)
+//   bnd_bin_kernel     one thread per present cell: its length, its route (rings.h: append_by_route for the two ring
+//                      routes, one integer atomic per cell for the rare chunked one);
+//   bnd_short_kernel   n <= 64: one wave per cell, point `lane` in registers, no LDS;
+//   bnd_long_kernel    64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per cell, the points in LDS (64 KB);
+//   bnd_chunk_kernel   above that: the same body, round after round: hull what is staged, reload the hull to the front of
+//                      LDS, stage the next points behind it;
+//   bnd_scan_kernel    one workgroup: the cells with h >= 3, their output positions and ring offsets, K and V;
+//   bnd_emit_kernel<S> one wave per kept cell: the ring, after S Chaikin iterations.
+// The march (march_start, march_step) is rings.h's, the one morphology.hip runs over a ring's vertices.  A hull kernel
+// writes hull vertex k of a cell to slot k of the cell's own segment of a scratch array (h <= n: there is room); that is
+// also where the chunked route reads its running hull back from.  The points are gathered through the sorted keys as
+// they are staged, once each; no sorted copy of the coordinates exists.
+//
+// Arithmetic: float64, FMA contraction off (rings.h).  The march subtracts the current vertex from the coordinates as
+// given -- no translation, so a hull vertex is an input coordinate bit for bit (-0.0 read as +0.0) -- and its cross
+// products are exact for integer coordinates below 2^25.  No floating-point atomics; a list's order depends on the order
+// of the atomics, a cell's ring does not.
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no scratch in any kernel of the unit, the library's
+// included (the sort is instantiated with NoScratchSortConfig); bnd_long_kernel and bnd_chunk_kernel hold 65536 B of LDS,
+// two single-wave workgroups per CU.
+#include <math.h>
+
+#include "common.h"
+#include "post_common.h"
+#include "rings.h"
+#include "sort_config.h"
+
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
+#pragma clang fp contract(off)
+
+namespace segger {
+namespace {
+
+constexpr int kBndThreads = 256;
+constexpr int kBndWaves = kBndThreads / kWave;
+constexpr int kBndScanThreads = 1024;
+constexpr int kBndCap = SEGGER_MORPH_MAX_VERTS;                      // points in LDS
+constexpr int kWordChunk = 3;                                        // the third list's length, after rings.h's words
+
+static_assert(SEGGER_BOUNDARY_CHUNK_MAX_HULL < kBndCap, "a round of the chunked route must stage at least one new point");
+
+// counters block of segger_cell_boundaries
+enum { kCounted = 0, kPresent = 1, kKept = 2, kVerts = 3, kBadCell = 4, kNonFinite = 5, kRefused = 6, kRefusedCell = 7 };
+static_assert(kRefusedCell + 1 == SEGGER_BOUNDARY_COUNTERS, "the header documents the block");
+
+// ---------------------------------------------------------------- keys ---
+__global__ __launch_bounds__(kBndThreads) void bnd_keys_kernel(const double* __restrict__ xy, const int32_t* __restrict__ cell,
+                                                               const uint8_t* __restrict__ keep, int64_t n, int64_t n_cells,
+                                                               unsigned long long* __restrict__ keys,
+                                                               unsigned long long* __restrict__ counters) {
+  const int64_t stride = (int64_t)gridDim.x * kBndThreads;
+  const unsigned long long sentinel = (unsigned long long)n_cells << 32;
+  int n_counted = 0, n_bad = 0, n_nonfinite = 0;                     // at most 2^31 / (256 * grid) + 1 rows per thread
+  for (int64_t i = (int64_t)blockIdx.x * kBndThreads + threadIdx.x; i < n; i += stride) {
+    const int32_t c = cell[i];
+    unsigned long long key = sentinel;
+    if (c >= 0 && (!keep || keep[i])) {
+      if ((int64_t)c >= n_cells) ++n_bad;
+      else {
+        const double2 p = reinterpret_cast<const double2*>(xy)[i];
+        if (p.x - p.x == 0.0 && p.y - p.y == 0.0) {                  // finite
+          key = ((unsigned long long)(uint32_t)c << 32) | (unsigned long long)i;
+          ++n_counted;
+        } else ++n_nonfinite;
+      }
+    }
+    keys[i] = key;
+  }
+  n_counted = wave_sum_i32(n_counted);
+  n_bad = wave_sum_i32(n_bad);
+  n_nonfinite = wave_sum_i32(n_nonfinite);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    if (n_counted) atomicAdd(counters + kCounted, (unsigned long long)n_counted);
+    if (n_bad) atomicAdd(counters + kBadCell, (unsigned long long)n_bad);
+    if (n_nonfinite) atomicAdd(counters + kNonFinite, (unsigned long long)n_nonfinite);
+  }
+}
+
+// position p of the sorted order starts a cell: a real key whose cell differs from its predecessor's
+struct BndCellHead {
+  const unsigned long long* keys;
+  unsigned long long sentinel;
+  __host__ __device__ bool operator()(const int32_t& p) const {
+    const unsigned long long k = keys[p];
+    return k < sentinel && (p == 0 || (keys[p - 1] >> 32) != (k >> 32));
+  }
+};
+
+// ---------------------------------------------------------------- segments and routes ---
+struct BndSegs {
+  const unsigned long long* keys;                                    // sorted
+  const int32_t* head;                                               // [present] first sorted position of a present cell
+  int32_t* len;                                                      // [present] its counted rows
+  int32_t* hull_n;                                                   // [present] its hull's vertices; 0: refused
+  double2* hull;                                                     // [n_rows] hull vertex k of segment j at head[j] + k
+};
+
+__global__ __launch_bounds__(kBndThreads) void bnd_bin_kernel(BndSegs s, const unsigned long long* __restrict__ counters,
+                                                              int32_t* __restrict__ words, int32_t* __restrict__ list_short,
+                                                              int32_t* __restrict__ list_long, int32_t* __restrict__ list_chunk) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t present = (int64_t)counters[kPresent];
+  const int32_t n_counted = (int32_t)counters[kCounted];
+  const int64_t stride = (int64_t)gridDim.x * kBndThreads;
+  // whole waves iterate together: append_by_route needs every lane of a wave in the loop
+  for (int64_t base = (int64_t)blockIdx.x * kBndThreads + (threadIdx.x & ~(kWave - 1)); base < present; base += stride) {
+    const int64_t j = base + lane;
+    int route = -1;
+    if (j < present) {
+      const int32_t n = (j + 1 < present ? s.head[j + 1] : n_counted) - s.head[j];
+      s.len[j] = n;
+      route = n > kBndCap ? 2 : ring_route(n);
+      if (route == 2) list_chunk[atomicAdd(&words[kWordChunk], 1)] = (int32_t)j;
+    }
+    append_by_route(route, j, words, list_short, list_long);
+  }
+}
+
+// ---------------------------------------------------------------- the hull of one cell, one wave ---
+// sorted position s of the keys -> the point of its row, -0.0 as +0.0 (equal points then have equal bits, and which of
+// them the march meets first cannot show in the output)
+__device__ __forceinline__ P2 point_at(const double* __restrict__ xy, const unsigned long long* __restrict__ keys, int64_t s) {
+  const double2 p = reinterpret_cast<const double2*>(xy)[keys[s] & 0xffffffffull];
+  return P2{p.x + 0.0, p.y + 0.0};
+}
+
+// The march over the m points of a store: hull vertex k goes to out[k]; returns h <= m.  Lane 0 writes: the vertex is the
+// same in every lane.
+template <class Ring>
+__device__ __forceinline__ int march_to(const Ring& ring, int m, double2* out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int start = march_start(ring, m);
+  int h = 0;
+  int cur = start;
+  for (int step = 0; step < m; ++step) {
+    const P2 p = ring.uni(cur);
+    if (lane == 0) out[h] = double2{p.x, p.y};
+    ++h;
+    const Cand best = march_step(ring, m, p);
+    if (best.i < 0 || best.i == start) break;
+    cur = best.i;
+  }
+  return h;
+}
+
+__global__ __launch_bounds__(kBndThreads) void bnd_short_kernel(const double* __restrict__ xy, BndSegs s,
+                                                                const int32_t* __restrict__ words, const int32_t* __restrict__ list) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int count = words[kWordShort];
+  const int n_waves = (int)gridDim.x * kBndWaves;
+  for (int w = (int)blockIdx.x * kBndWaves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {               // wave-uniform
+    const int j = list[w];
+    const int64_t b = s.head[j];
+    const int n = __builtin_amdgcn_readfirstlane(s.len[j]);          // 1 .. 64
+    const P2 mine = point_at(xy, s.keys, b + (lane < n ? lane : 0)); // the lanes beyond n: a copy that never competes
+    const RegRing ring{mine.x, mine.y};
+    const int h = march_to(ring, n, s.hull + b);
+    if (lane == 0) s.hull_n[j] = h;
+  }
+}
+
+// One cell in LDS, n > 64 points.  n <= kBndCap is one round.  Beyond that, round after round: the hull of what is staged
+// goes to the cell's slots of s.hull, comes back to the front of pts, and the next kBndCap - h points are staged behind it.
+// The running hull never loses a vertex of the final one, so the last round's hull is the cell's.  A workgroup is one wave.
+__device__ __forceinline__ void lds_cell(const double* __restrict__ xy, const BndSegs& s, int j, double2* __restrict__ pts,
+                                         unsigned long long* __restrict__ counters) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t b = s.head[j];
+  const int n = __builtin_amdgcn_readfirstlane(s.len[j]);
+  double2* out = s.hull + b;
+  const LdsRing ring{pts};
+  int h = 0, consumed = 0;
+  while (true) {
+    const int take = min(kBndCap - h, n - consumed);
+    __syncthreads();                                                 // the previous round's (or cell's) readers are done
+    for (int k = lane; k < h; k += kWave) pts[k] = out[k];           // written by this wave before the barrier
+    for (int k = lane; k < take; k += kWave) {
+      const P2 p = point_at(xy, s.keys, b + consumed + k);
+      pts[h + k] = double2{p.x, p.y};
+    }
+    __syncthreads();
+    h = march_to(ring, h + take, out);
+    consumed += take;
+    if (consumed >= n) break;
+    if (h > SEGGER_BOUNDARY_CHUNK_MAX_HULL) {                        // no room to make progress: refuse the cell
+      if (lane == 0) {
+        atomicAdd(counters + kRefused, 1ull);
+        atomicMax(counters + kRefusedCell, (s.keys[b] >> 32) + 1ull);
+      }
+      h = 0;
+      break;
+    }
+  }
+  if (lane == 0) s.hull_n[j] = h;
+}
+
+__global__ __launch_bounds__(kWave) void bnd_long_kernel(const double* __restrict__ xy, BndSegs s, const int32_t* __restrict__ words,
+                                                         const int32_t* __restrict__ list, unsigned long long* __restrict__ counters) {
+  __shared__ double2 pts[kBndCap];
+  const int count = words[kWordLong];
+  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) lds_cell(xy, s, list[w], pts, counters);
+}
+
+__global__ __launch_bounds__(kWave) void bnd_chunk_kernel(const double* __restrict__ xy, BndSegs s, const int32_t* __restrict__ words,
+                                                          const int32_t* __restrict__ list, unsigned long long* __restrict__ counters) {
+  __shared__ double2 pts[kBndCap];
+  const int count = words[kWordChunk];
+  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) lds_cell(xy, s, list[w], pts, counters);
+}
+
+// ---------------------------------------------------------------- keep and scan ---
+// One workgroup over the present cells in ascending cell id: a cell with h >= 3 is kept; its position among the kept and
+// the exclusive sum of h << smoothing before it are its row of the outputs and its ring offset.
+__global__ __launch_bounds__(kBndScanThreads) void bnd_scan_kernel(BndSegs s, int smoothing, int32_t* __restrict__ kept_seg,
+                                                                   int64_t* __restrict__ ring_offsets, int32_t* __restrict__ cell_ids,
+                                                                   int64_t* __restrict__ n_transcripts,
+                                                                   unsigned long long* __restrict__ counters) {
+  __shared__ int64_t wave_verts[kBndScanThreads / kWave];
+  __shared__ int wave_kept[kBndScanThreads / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int64_t present = (int64_t)counters[kPresent];
+  int64_t carry_v = 0;                                               // vertices and kept cells before this chunk
+  int carry_k = 0;
+  for (int64_t base = 0; base < present; base += kBndScanThreads) {
+    const int64_t j = base + threadIdx.x;
+    const int h = j < present ? s.hull_n[j] : 0;
+    const bool kept = h >= 3;
+    const int64_t mine = kept ? (int64_t)h << smoothing : 0;
+    int64_t v = mine;
+    int k = kept ? 1 : 0;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {                            // inclusive scans of the wave
+      const int src = lane >= d ? lane - d : lane;
+      const int64_t ov = (int64_t)shfl64((uint64_t)v, src);
+      const int ok = __shfl(k, src, kWave);
+      if (lane >= d) { v += ov; k += ok; }
+    }
+    if (lane == kWave - 1) { wave_verts[wave] = v; wave_kept[wave] = k; }
+    __syncthreads();
+    int64_t before_v = carry_v, all_v = carry_v;
+    int before_k = carry_k, all_k = carry_k;
+    for (int w = 0; w < kBndScanThreads / kWave; ++w) {
+      const int64_t tv = wave_verts[w];
+      const int tk = wave_kept[w];
+      if (w < wave) { before_v += tv; before_k += tk; }
+      all_v += tv;
+      all_k += tk;
+    }
+    if (kept) {
+      const int q = before_k + k - 1;
+      kept_seg[q] = (int32_t)j;
+      ring_offsets[q] = before_v + v - mine;
+      cell_ids[q] = (int32_t)(s.keys[s.head[j]] >> 32);
+      n_transcripts[q] = (int64_t)s.len[j];
+    }
+    carry_v = all_v;
+    carry_k = all_k;
+    __syncthreads();                                                 // the totals are rewritten by the next chunk
+  }
+  if (threadIdx.x == 0) {
+    ring_offsets[carry_k] = carry_v;
+    counters[kKept] = (unsigned long long)carry_k;
+    counters[kVerts] = (unsigned long long)carry_v;
+  }
+}
+
+// ---------------------------------------------------------------- emit ---
+// Vertex j of the ring after S Chaikin iterations of the h-vertex hull.  A vertex of level l (the ring after l
+// iterations, 2^l h vertices) with index q comes from the vertices q >> 1 and (q >> 1) + 1 of level l - 1, so vertex j of
+// level S depends on S + 1 consecutive (cyclic) hull vertices from j >> S on.  w holds, level after level, the S - l + 1
+// consecutive vertices of level l from index j >> (S - l) on; which two entries of the previous level make entry t
+// depends on the parity of that index alone: the array indices are compile-time constants and w stays in registers.
+// f(int_c<0>{}) .. f(int_c<N - 1>{}): a loop whose counter is a constant expression in its body
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (N > 0) {
+    static_for<N - 1>(f);
+    f(int_c<N - 1>{});
+  }
+}
+
+// N + 1 consecutive vertices of a level in w -> the N of the next level that start at an index of parity b, in w
+template <int N>
+__device__ __forceinline__ void chaikin_level(P2* w, bool b) {
+  P2 nw[N];
+  static_for<N>([&](auto t_) __attribute__((always_inline)) {
+    constexpr int t = decltype(t_)::value;
+    // (values first, then the choice: a choice between two elements would be a choice between two addresses)
+    const P2 p0 = w[t >> 1], q0 = w[(t >> 1) + 1], p1 = w[(t + 1) >> 1], q1 = w[((t + 1) >> 1) + 1];
+    const double px = b ? p1.x : p0.x, py = b ? p1.y : p0.y, qx = b ? q1.x : q0.x, qy = b ? q1.y : q0.y;
+    const bool odd = b != ((t & 1) != 0);
+    const double wp = odd ? 0.25 : 0.75, wq = odd ? 0.75 : 0.25;
+    nw[t] = P2{wp * px + wq * qx, wp * py + wq * qy};
+  });
+  static_for<N>([&](auto t_) __attribute__((always_inline)) { w[decltype(t_)::value] = nw[decltype(t_)::value]; });
+}
+
+template <int S>
+__device__ __forceinline__ P2 chaikin_vertex(const double2* __restrict__ hull, int h, int j) {
+  P2 w[S + 1];
+  const int first = j >> S;
+  static_for<S + 1>([&](auto t_) __attribute__((always_inline)) {
+    constexpr int t = decltype(t_)::value;
+    const double2 p = hull[(first + t) % h];
+    w[t] = P2{p.x, p.y};
+  });
+  static_for<S>([&](auto l_) __attribute__((always_inline)) {
+    constexpr int l = decltype(l_)::value + 1;
+    // entries 0 .. S - l of level l from entries 0 .. S - l + 1 of level l - 1; the parity of this level's first index
+    chaikin_level<S - l + 1>(w, ((j >> (S - l)) & 1) != 0);
+  });
+  return w[0];
+}
+
+template <int S>
+__global__ __launch_bounds__(kBndThreads) void bnd_emit_kernel(BndSegs s, const int32_t* __restrict__ kept_seg,
+                                                               const int64_t* __restrict__ ring_offsets,
+                                                               const unsigned long long* __restrict__ counters,
+                                                               double2* __restrict__ xy_out, int64_t capacity) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t K = (int64_t)counters[kKept];
+  const int64_t n_waves = (int64_t)gridDim.x * kBndWaves;
+  for (int64_t q = (int64_t)blockIdx.x * kBndWaves + (threadIdx.x >> 6); q < K; q += n_waves) {                 // wave-uniform
+    const int j = kept_seg[q];
+    const int h = s.hull_n[j];
+    const double2* hull = s.hull + s.head[j];
+    const int64_t at0 = ring_offsets[q];
+    const int total = h << S;
+    for (int v = lane; v < total; v += kWave) {
+      const P2 p = chaikin_vertex<S>(hull, h, v);
+      if (at0 + v < capacity) xy_out[at0 + v] = double2{p.x, p.y};
+    }
+  }
+}
+
+// ---------------------------------------------------------------- host ---
+int bnd_check_sizes(const char* who, int64_t n_rows, int64_t n_cells) {
+  SEGGER_REQUIRE(n_rows >= 0, "%s: negative n_rows", who);
+  SEGGER_REQUIRE(n_rows < 0x7fffffffLL, "%s: 2^31 - 1 rows or more", who);
+  SEGGER_REQUIRE(n_cells >= 1 && n_cells <= 0x7fffffffLL, "%s: n_cells = %lld outside 1 .. 2^31 - 1", who, (long long)n_cells);
+  return SEGGER_OK;
+}
+
+struct BndLayout {
+  RingLists rings;
+  size_t list_chunk, keys, hull, head, len, hull_n, kept_seg, temp, total;
+  size_t temp_bytes;
+  int key_bits;
+  int64_t cells_cap;
+};
+
+// with n_rows and n_cells below 2^31 every term is below 2^36 bytes: nothing here can overflow
+BndLayout bnd_layout(int64_t n_rows, int64_t n_cells) {
+  BndLayout l;
+  l.key_bits = 32 + bit_length((unsigned long long)n_cells);         // the sentinel n_cells << 32 is the largest key
+  const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
+  l.cells_cap = n_rows < n_cells ? (n_rows > 0 ? n_rows : 1) : n_cells;
+  const size_t c4 = (size_t)l.cells_cap * 4;
+  Carver c;
+  l.rings = take_ring_lists(c, l.cells_cap);
+  l.list_chunk = c.take((n / (kBndCap + 1) + 1) * 4);
+  l.keys = c.take(n * 8);                                            // sorted keys
+  l.hull = c.take(n * 16);                                           // the hulls; before that, the unsorted keys
+  l.head = c.take(c4);
+  l.len = c.take(c4);
+  l.hull_n = c.take(c4);
+  l.kept_seg = c.take(c4);
+  size_t a = 0, b = 0;
+  unsigned long long* k64 = nullptr;
+  int32_t* i32 = nullptr;
+  size_t* cnt = nullptr;
+  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, a, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
+  (void)rocprim::select(nullptr, b, rocprim::counting_iterator<int32_t>(0), i32, cnt, n, BndCellHead{nullptr, 0}, (hipStream_t)0);
+  l.temp_bytes = a > b ? a : b;
+  l.temp = c.take(l.temp_bytes > 0 ? l.temp_bytes : 1);
+  l.total = c.total();
+  return l;
+}
+
+template <int S>
+void launch_emit(unsigned grid, hipStream_t stream, const BndSegs& s, const int32_t* kept_seg, const int64_t* ring_offsets,
+                 const unsigned long long* counters, double2* xy_out, int64_t capacity) {
+  hipLaunchKernelGGL((bnd_emit_kernel<S>), dim3(grid), dim3(kBndThreads), 0, stream, s, kept_seg, ring_offsets, counters, xy_out,
+                     capacity);
+}
+
+}  // namespace
+}  // namespace segger
+
+using namespace segger;
+
+extern "C" int64_t segger_cell_boundaries_workspace_bytes(int64_t n_rows, int64_t n_cells) {
+  const int rc = bnd_check_sizes("segger_cell_boundaries_workspace_bytes", n_rows, n_cells);
+  if (rc != SEGGER_OK) return rc;
+  return (int64_t)bnd_layout(n_rows, n_cells).total;
+}
+
+extern "C" int segger_cell_boundaries(const double* xy, const int32_t* cell, const uint8_t* keep, int64_t n_rows, int64_t n_cells,
+                                      int32_t smoothing, int64_t* ring_offsets, double* xy_out, int64_t xy_capacity,
+                                      int32_t* cell_ids, int64_t* n_transcripts, uint64_t* counters, void* workspace,
+                                      int64_t workspace_bytes, segger_stream_t stream_) {
+  const char* who = "segger_cell_boundaries";
+  hipStream_t stream = (hipStream_t)stream_;
+  const int rc = bnd_check_sizes(who, n_rows, n_cells);
+  if (rc != SEGGER_OK) return rc;
+  SEGGER_REQUIRE(smoothing >= 0 && smoothing <= SEGGER_BOUNDARY_MAX_SMOOTHING, "%s: smoothing = %d outside 0 .. %d", who,
+                 (int)smoothing, SEGGER_BOUNDARY_MAX_SMOOTHING);
+  SEGGER_REQUIRE(workspace_bytes >= 0 && xy_capacity >= 0, "%s: negative workspace_bytes or xy_capacity", who);
+  if (n_rows == 0) {                               // nothing launched: the caller's zeroed counters and ring_offsets[0] stand
+    SEGGER_REQUIRE(counters && ring_offsets, "%s: NULL pointer", who);
+    return SEGGER_OK;
+  }
+  SEGGER_REQUIRE(xy && cell && ring_offsets && cell_ids && n_transcripts && counters && workspace, "%s: NULL pointer", who);
+  SEGGER_REQUIRE(xy_out || xy_capacity == 0, "%s: NULL xy_out with xy_capacity > 0", who);
+  SEGGER_REQUIRE(is_aligned(xy, 16) && is_aligned(xy_out, 16), "%s: xy and xy_out must be 16-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(ring_offsets, 8) && is_aligned(n_transcripts, 8) && is_aligned(counters, 8),
+                 "%s: ring_offsets, n_transcripts and counters must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(cell, 4) && is_aligned(cell_ids, 4), "%s: cell and cell_ids must be 4-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  const BndLayout l = bnd_layout(n_rows, n_cells);
+  SEGGER_REQUIRE((size_t)workspace_bytes >= l.total, "%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, l.total);
+
+  int32_t* words = at<int32_t>(workspace, l.rings.words);
+  int32_t* list_short = at<int32_t>(workspace, l.rings.list_short);
+  int32_t* list_long = at<int32_t>(workspace, l.rings.list_long);
+  int32_t* list_chunk = at<int32_t>(workspace, l.list_chunk);
+  unsigned long long* keys_in = at<unsigned long long>(workspace, l.hull);       // dead once sorted: the hulls go there
+  unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
+  int32_t* head = at<int32_t>(workspace, l.head);
+  int32_t* kept_seg = at<int32_t>(workspace, l.kept_seg);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
+  const BndSegs s{keys, head, at<int32_t>(workspace, l.len), at<int32_t>(workspace, l.hull_n), at<double2>(workspace, l.hull)};
+  const int cus = cu_count_or_default();
+  const int64_t cap = l.cells_cap;
+
+  SEGGER_HIP(hipMemsetAsync(words, 0, kRingWordsBytes, stream));
+  SEGGER_HIP(hipMemsetAsync(cnt, 0, SEGGER_BOUNDARY_COUNTERS * sizeof(unsigned long long), stream));
+  hipLaunchKernelGGL(bnd_keys_kernel, dim3(grid_stride_blocks(n_rows, kBndThreads, (int64_t)cus * 32)), dim3(kBndThreads), 0, stream,
+                     xy, cell, keep, n_rows, n_cells, keys_in, cnt);
+  SEGGER_LAUNCH_CHECK("bnd_keys_kernel");
+  size_t temp_bytes = l.temp_bytes;
+  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, l.temp), temp_bytes, keys_in, keys, (size_t)n_rows, 0,
+                                                           (unsigned)l.key_bits, stream));
+  temp_bytes = l.temp_bytes;
+  SEGGER_HIP(rocprim::select(at<char>(workspace, l.temp), temp_bytes, rocprim::counting_iterator<int32_t>(0), head,
+                             reinterpret_cast<size_t*>(cnt + kPresent), (size_t)n_rows,
+                             BndCellHead{keys, (unsigned long long)n_cells << 32}, stream));
+  hipLaunchKernelGGL(bnd_bin_kernel, dim3(grid_stride_blocks(cap, kBndThreads, (int64_t)cus * 8)), dim3(kBndThreads), 0, stream, s,
+                     (const unsigned long long*)cnt, words, list_short, list_long, list_chunk);
+  SEGGER_LAUNCH_CHECK("bnd_bin_kernel");
+  hipLaunchKernelGGL(bnd_short_kernel, dim3(grid_stride_blocks(cap, kBndWaves, (int64_t)cus * 8)), dim3(kBndThreads), 0, stream, xy, s,
+                     (const int32_t*)words, (const int32_t*)list_short);
+  SEGGER_LAUNCH_CHECK("bnd_short_kernel");
+  hipLaunchKernelGGL(bnd_long_kernel, dim3(grid_stride_blocks(ceil_div(n_rows, kWave + 1), 1, (int64_t)cus * 2)), dim3(kWave), 0,
+                     stream, xy, s, (const int32_t*)words, (const int32_t*)list_long, cnt);
+  SEGGER_LAUNCH_CHECK("bnd_long_kernel");
+  hipLaunchKernelGGL(bnd_chunk_kernel, dim3(grid_stride_blocks(n_rows / (kBndCap + 1), 1, (int64_t)cus * 2)), dim3(kWave), 0, stream,
+                     xy, s, (const int32_t*)words, (const int32_t*)list_chunk, cnt);
+  SEGGER_LAUNCH_CHECK("bnd_chunk_kernel");
+  hipLaunchKernelGGL(bnd_scan_kernel, dim3(1), dim3(kBndScanThreads), 0, stream, s, (int)smoothing, kept_seg, ring_offsets, cell_ids,
+                     n_transcripts, cnt);
+  SEGGER_LAUNCH_CHECK("bnd_scan_kernel");
+  const unsigned emit_grid = grid_stride_blocks(cap, kBndWaves, (int64_t)cus * 8);
+  double2* out = reinterpret_cast<double2*>(xy_out);
+  switch (smoothing) {
+    case 0: launch_emit<0>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+    case 1: launch_emit<1>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+    case 2: launch_emit<2>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+    case 3: launch_emit<3>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+    case 4: launch_emit<4>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+    case 5: launch_emit<5>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+    default: launch_emit<6>(emit_grid, stream, s, kept_seg, ring_offsets, cnt, out, xy_capacity); break;
+  }
+  SEGGER_LAUNCH_CHECK("bnd_emit_kernel");
+  return SEGGER_OK;
+}

@@ -15,7 +15,7 @@
 // Per polygon, in float64 on coordinates translated to the ring's first vertex, with FMA contraction off (a cross
 // product of exactly representable coordinates is then exact, and cross(a, b) = -cross(b, a) to the bit):
 //   1. shoelace area, centroid sums, vertex sums, bounds (bounds on the untranslated coordinates: exact);
-//   2. convex hull by gift wrapping from the lexicographically lowest vertex: each step is one wave-wide arg-max of
+//   2. convex hull by gift wrapping (rings.h: march_step) from the lexicographically lowest vertex: each step is one wave-wide arg-max of
 //      "most clockwise as seen from the current vertex", ties broken by the larger distance, then by the lower index; a
 //      vertex that coincides with the current one never competes.  Collinear and duplicate vertices therefore never
 //      enter the hull and the march returns to its start after h <= n steps (n steps is also a hard cap);
@@ -74,33 +74,6 @@ struct LdsHull {
   __device__ __forceinline__ P2 at(int k) const { return own(k); }
   __device__ __forceinline__ P2 uni(int k) const { return own(k); }
 };
-
-// ---------------------------------------------------------------- gift wrapping ---
-struct Cand { int i; double dx, dy; };                               // a vertex and its offset from the current hull vertex
-
-// is b ahead of a in the march?  (i < 0: no candidate; neither offset is zero)
-__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
-  if (b.i < 0) return false;
-  if (a.i < 0) return true;
-  const double cr = a.dx * b.dy - a.dy * b.dx;                       // < 0: b is to the right of current -> a
-  if (cr != 0.0) return cr < 0.0;
-  const double da = a.dx * a.dx + a.dy * a.dy, db = b.dx * b.dx + b.dy * b.dy;
-  if (da != db) return db > da;
-  return b.i < a.i;
-}
-
-__device__ __forceinline__ Cand wave_best(Cand c) {
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) {
-    Cand o;
-    o.i = __shfl_xor(c.i, m, kWave);
-    o.dx = shfl_xor_f64(c.dx, m);
-    o.dy = shfl_xor_f64(c.dy, m);
-    if (cand_better(c, o)) c = o;
-  }
-  c.i = __builtin_amdgcn_readfirstlane(c.i);                         // one answer per wave whatever the inputs hold
-  return c;
-}
 
 // ---------------------------------------------------------------- circles ---
 struct Circle { double cx, cy, r2; };
@@ -199,16 +172,7 @@ __device__ __forceinline__ void polygon_body(const Ring& ring, Hull& hull, int n
     const P2 p = ring.uni(cur);
     hull.push(h, cur, p);
     ++h;
-    Cand best{-1, 0.0, 0.0};
-    for (int base = 0; base < n; base += kWave) {
-      const int i = base + lane;
-      if (i < n) {
-        const P2 q = ring.own(i);
-        const Cand c{i, q.x - p.x, q.y - p.y};
-        if ((c.dx != 0.0 || c.dy != 0.0) && cand_better(best, c)) best = c;
-      }
-    }
-    best = wave_best(best);
+    const Cand best = march_step(ring, n, p);                        // rings.h: the tie rules
     if (best.i < 0 || best.i == start) break;
     cur = best.i;
   }

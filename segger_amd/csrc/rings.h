@@ -5,6 +5,8 @@
 // its first vertex.  A binning kernel classifies every polygon and appends it to the list of its route; the polygon kernels
 // read the list lengths from the workspace words and load what the binning kernel counted.  One definition each: the units
 // agree on "entries", "open vertices" and "route" because they run the same code, and a fix is made here and nowhere else.
+// The gift-wrapping march of morphology.hip is here too, because boundaries.hip runs it over a cell's transcripts (that unit
+// reads no ring CSR -- it writes one -- and uses the stores, append_by_route and the march).
 //
 // Floating point: this header sets `#pragma clang fp contract(off)` itself, to the end of the including unit.  The loaders
 // only subtract, but wave_sum_f64's additions are inlined next to the callers' products, which must not fuse with them.
@@ -144,6 +146,77 @@ __device__ __forceinline__ LongRing stage_long_ring(const int64_t* __restrict__ 
   }
   __syncthreads();
   return r;
+}
+
+// ---------------------------------------------------------------- gift wrapping: the march, one wave ---
+// The convex hull of the n points of a store (own / uni as above), counter-clockwise from the lowest (x, then y, then
+// index) point: from the current hull vertex the next one is the most clockwise point as seen from it, ties (collinear
+// with it) go to the larger distance, then to the lower index, and a point that coincides with the current vertex never
+// competes.  Collinear and duplicate points therefore never enter the hull, and the march is back at its start after
+// h <= n steps.  morphology.hip marches over a ring's vertices, boundaries.hip over a cell's transcripts.
+struct Cand { int i; double dx, dy; };                               // a vertex and its offset from the current hull vertex
+
+// is b ahead of a in the march?  (i < 0: no candidate; neither offset is zero)
+__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
+  if (b.i < 0) return false;
+  if (a.i < 0) return true;
+  const double cr = a.dx * b.dy - a.dy * b.dx;                       // < 0: b is to the right of current -> a
+  if (cr != 0.0) return cr < 0.0;
+  const double da = a.dx * a.dx + a.dy * a.dy, db = b.dx * b.dx + b.dy * b.dy;
+  if (da != db) return db > da;
+  return b.i < a.i;
+}
+
+__device__ __forceinline__ Cand wave_best(Cand c) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {
+    Cand o;
+    o.i = __shfl_xor(c.i, m, kWave);
+    o.dx = shfl_xor_f64(c.dx, m);
+    o.dy = shfl_xor_f64(c.dy, m);
+    if (cand_better(c, o)) c = o;
+  }
+  c.i = __builtin_amdgcn_readfirstlane(c.i);                         // one answer per wave whatever the inputs hold
+  return c;
+}
+
+// the point that follows hull vertex p (the same in every lane) among the n of the store; i < 0: every point equals p
+template <class Ring>
+__device__ __forceinline__ Cand march_step(const Ring& ring, int n, P2 p) {
+  const int lane = threadIdx.x & (kWave - 1);
+  Cand best{-1, 0.0, 0.0};
+  for (int base = 0; base < n; base += kWave) {
+    const int i = base + lane;
+    if (i < n) {
+      const P2 q = ring.own(i);
+      const Cand c{i, q.x - p.x, q.y - p.y};
+      if ((c.dx != 0.0 || c.dy != 0.0) && cand_better(best, c)) best = c;
+    }
+  }
+  return wave_best(best);
+}
+
+// where the march starts: the index of the lowest (x, then y, then index) of the n >= 1 points, the same in every lane
+template <class Ring>
+__device__ __forceinline__ int march_start(const Ring& ring, int n) {
+  const int lane = threadIdx.x & (kWave - 1);
+  int s_i = -1;
+  double s_x = 0.0, s_y = 0.0;
+  for (int base = 0; base < n; base += kWave) {
+    const int i = base + lane;
+    if (i < n) {
+      const P2 p = ring.own(i);
+      if (s_i < 0 || p.x < s_x || (p.x == s_x && p.y < s_y)) { s_i = i; s_x = p.x; s_y = p.y; }
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {
+    const int oi = __shfl_xor(s_i, m, kWave);
+    const double ox = shfl_xor_f64(s_x, m), oy = shfl_xor_f64(s_y, m);
+    const bool take = oi >= 0 && (s_i < 0 || ox < s_x || (ox == s_x && (oy < s_y || (oy == s_y && oi < s_i))));
+    if (take) { s_i = oi; s_x = ox; s_y = oy; }
+  }
+  return __builtin_amdgcn_readfirstlane(s_i);
 }
 
 // ---------------------------------------------------------------- host: workspace and arguments ---

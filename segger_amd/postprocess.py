@@ -336,6 +336,12 @@ class SegmentationAccumulator:
         """``expression_matrix(self.segmentation(max_iter, thresholds), xy)``: the count matrix of what has been fed so far."""
         return expression_matrix(self.segmentation(max_iter, thresholds), xy)
 
+    def boundaries(self, xy: Tensor, max_iter: int = 250, thresholds: str = "torch", **kw) -> Dict[str, Tensor]:
+        """``segmentation_boundaries(self.segmentation(max_iter, thresholds), xy, **kw)``: one boundary polygon per cell of
+        what has been fed so far, from the transcripts :meth:`expression` counts (:mod:`segger_amd.boundaries`)."""
+        from .boundaries import segmentation_boundaries
+        return segmentation_boundaries(self.segmentation(max_iter, thresholds), xy, **kw)
+
 
 EXPRESSION_COUNTERS = ("n_kept", "nnz", "n_cells_present", "n_genes_present", "n_bad")
 
