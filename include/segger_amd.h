@@ -1504,8 +1504,9 @@ int segger_polygon_join_fill(const double* points, int64_t n_points, const int64
 /* ------------------------------------------------------------------------
  * Cell boundary polygons: one ring per segmented cell, the convex hull of the cell's transcripts -- the reference's
  * generate_boundaries / cell_boundary with method="convex_hull" (src/segger/export/boundary.py:157-217), optionally rounded
- * by Chaikin corner cutting (boundary.py:42-54).  The reference's DEFAULT method, "delaunay" (boundary.py:57-154, a
- * sequential pruning of a Delaunay triangulation), is NOT built.  The kernels behind segger_amd.boundaries.
+ * by Chaikin corner cutting (boundary.py:42-54).  The reference's DEFAULT method, "delaunay" (boundary.py:57-154, the
+ * outline of a pruned Delaunay triangulation), is segger_cell_outlines below, an entry point of its own; this one does not
+ * route to it.  The kernels behind segger_amd.boundaries.cell_boundaries.
  * csrc/boundaries.hip.  Purely additive: two new symbols, SEGGER_ABI_VERSION stays 32.
  *
  * Input:  xy [n_rows, 2] fp64 (16-byte aligned), cell [n_rows] int32, keep [n_rows] bytes or NULL (= all ones), and the
@@ -1568,6 +1569,61 @@ int segger_cell_boundaries(const double* xy /* [N, 2] */, const int32_t* cell, c
                            int64_t n_rows, int64_t n_cells, int32_t smoothing, int64_t* ring_offsets, double* xy_out,
                            int64_t xy_capacity, int32_t* cell_ids, int64_t* n_transcripts, uint64_t* counters,
                            void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Concave cell outlines: one ring per segmented cell from the pruned Delaunay triangulation of the cell's transcripts --
+ * the reference's generate_boundaries / cell_boundary with its DEFAULT method="delaunay" (_CellOutline,
+ * src/segger/export/boundary.py:57-154), optionally rounded by Chaikin corner cutting.  The kernels behind
+ * segger_amd.boundaries.cell_outlines, csrc/outlines.hip.  Purely additive: two new symbols, SEGGER_ABI_VERSION stays 32.
+ * segger_cell_boundaries is unchanged; it does not route to this entry point.
+ *
+ * Input, output, the counted rows, the order of the cells, the sizes of the arrays and the workspace rule are those of
+ * segger_cell_boundaries above, with `connectivity` (the reference's knob, default 2.0) in front of `smoothing`.  A ring is
+ * open, counter-clockwise, starts at its lexicographically lowest vertex and lists EVERY vertex of the outline, collinear
+ * ones included (shapely's polygonize does not simplify); a vertex is an input coordinate bit for bit (-0.0 as +0.0).
+ *     counters [SEGGER_OUTLINE_COUNTERS] uint64: 0 .. 5 as above; 6 cells with more than SEGGER_OUTLINE_MAX_POINTS distinct
+ *              points, 7 the largest such cell id + 1; 8 cells whose triangulation contradicted itself, 9 the largest such
+ *              cell id + 1.  A cell counted in 6 or 8 gets no polygon.
+ *
+ * Stages per cell, one single-wave workgroup per cell with its whole state in LDS (68 bytes per point of capacity: 136 KB
+ * for SEGGER_OUTLINE_MAX_POINTS = 2048, 17 KB on the route of the cells with at most 256 rows):
+ *   points   sorted by (x, y), exact duplicates dropped, multiplicity > 1 remembered.  Fewer than 3 distinct points, or
+ *            all collinear: no polygon (the reference's np.unique(points) < 3 -> None, and qhull's error -> None);
+ *   Delaunay grown edge by edge from point 0 and its nearest neighbour: the apex of a directed edge a -> b is the point
+ *            left of ab that no other such point's in-circle test beats.  orient2d and incircle run on coordinate
+ *            differences in fp64, FMA contraction off: exact when the coordinates share a grid and span fewer than 2^11
+ *            steps of it in the cell.  Co-circular points tie; the tie is broken towards the fan from the lowest vertex of
+ *            the co-circular polygon, which need not be qhull's choice;
+ *   d_max    the largest nearest-neighbour distance (_nn_max): per vertex the shortest incident Delaunay edge, 0 for a
+ *            point with multiplicity > 1; lengths are sqrt(dx dx + dy dy);
+ *   peel 1   remove a triangle with a rim edge longer than 2 connectivity d_max, to the fixed point;
+ *   peel 2   remove a triangle with a rim edge e for which (length > 1.5 connectivity d_max and angle > 90) or
+ *            angle > 180 - 11.25 / connectivity, angle = degrees(acos(clamp(u.v / (|u| |v| + 1e-12), -1, 1))) at the
+ *            vertex opposite e.  Both predicates are static, so the fixed points do not depend on the order of removal;
+ *   largest  the edge-connected components of the surviving triangles; the one of largest area is kept; equal areas: the
+ *            one whose lowest vertex is lower, then the one found first (the reference's choice is GEOS's order and is
+ *            not reproduced).  Nothing survives: no polygon;
+ *   ring     the component's rim walked with the interior on the left; then `smoothing` Chaikin iterations as above.
+ *            shapely's buffer(0) after the smoothing, which can alter a smoothed concave ring that touches itself, is
+ *            not reproduced.
+ * A cell with more than SEGGER_OUTLINE_MAX_POINTS distinct points is refused (counters[6], [7]); larger cells would need
+ * a global-memory route, which is not built.  Every loop is bounded before it is entered: at most 2 n - 5 triangles,
+ * 3 per triangle directed edges, rounds at most the triangle count, a ring walk of at most one step per directed edge;
+ * a table that overflows or a walk past its bound -- possible only when rounded predicates contradict each other --
+ * refuses the cell through counters[8], [9].
+ *
+ * Workspace: segger_cell_outlines_workspace_bytes(n_rows, n_cells), 256-byte aligned: with N, C and up() as above
+ *   256 + 2 up(4 C) + up(8 N) + up(16 N) + 4 up(4 C) + the storage of the sort and of the compaction.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: everything segger_cell_boundaries rejects, and
+ *   a connectivity that is not a finite number > 0.  n_rows = 0 returns SEGGER_OK as above.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_OUTLINE_MAX_POINTS 2048   /* 68 B of LDS per point: 139264 of the 163840 B of a CU */
+#define SEGGER_OUTLINE_COUNTERS 10
+int64_t segger_cell_outlines_workspace_bytes(int64_t n_rows, int64_t n_cells);
+int segger_cell_outlines(const double* xy /* [N, 2] */, const int32_t* cell, const uint8_t* keep /* or NULL */,
+                         int64_t n_rows, int64_t n_cells, double connectivity, int32_t smoothing, int64_t* ring_offsets,
+                         double* xy_out, int64_t xy_capacity, int32_t* cell_ids, int64_t* n_transcripts,
+                         uint64_t* counters, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -21,5 +21,6 @@ from .geometry import points_in_polygons  # noqa: F401
 from .neighbors import prediction_graph_shape  # noqa: F401
 from . import boundaries  # noqa: F401
 from .boundaries import cell_boundaries, segmentation_boundaries  # noqa: F401
+from .boundaries import cell_outlines, segmentation_outlines  # noqa: F401
 
 __version__ = "0.1.0"

@@ -8,10 +8,12 @@ What is built is the reference's ``method="convex_hull"``, with its rule for deg
 points, or only collinear ones: no polygon, the cell is dropped), the optional Chaikin smoothing (``boundary.py:42-54``) and
 ``n_transcripts`` per cell.
 
-NOT BUILT: ``method="delaunay"``, the reference's DEFAULT (``boundary.py:57-154``).  It prunes a Delaunay triangulation
-edge by edge, in an order that decides the result; it is not reproduced, and asking for it raises ``NotImplementedError``.
-The outline a default ``segger export`` writes is therefore NOT what this module returns: it returns the convex outline
-that ``segger export --method convex_hull`` writes.
+The reference's DEFAULT, ``method="delaunay"`` (``boundary.py:57-154``: the outline of a pruned Delaunay triangulation), is
+built as entry points of its own, :func:`cell_outlines` and :func:`segmentation_outlines` (``segger_cell_outlines``,
+csrc/outlines.hip; one single-wave workgroup owns one cell).  NOT BUILT: the ``method="delaunay"`` SPELLING on
+:func:`cell_boundaries`, which still raises ``NotImplementedError`` -- that function returns the convex outline that
+``segger export --method convex_hull`` writes; cells above ``SEGGER_OUTLINE_MAX_POINTS`` distinct points; GEOS's order
+among components of equal area; ``buffer(0)`` repairs of a smoothed concave ring.
 
 The rings come back as the ring CSR of :mod:`segger_amd.rings`, open (no closing duplicate), counter-clockwise from the
 lexicographically lowest vertex: :func:`segger_amd.morphology.polygon_props` and
@@ -34,10 +36,11 @@ from torch import Tensor
 
 from . import _lib as L
 
-__all__ = ["cell_boundaries", "segmentation_boundaries"]
+__all__ = ["cell_boundaries", "segmentation_boundaries", "cell_outlines", "segmentation_outlines"]
 
 METHODS = ("convex_hull", "delaunay")
 COUNTERS = ("n_counted", "n_present", "n_kept", "n_vertices", "n_bad_cell", "n_non_finite", "n_refused", "refused_cell")
+OUTLINE_COUNTER_NAMES = COUNTERS + ("n_failed", "failed_cell")
 MAX_ROWS = (1 << 31) - 2
 
 
@@ -47,6 +50,14 @@ def _check_options(who: str, smoothing, method) -> int:
     if method == "delaunay":
         raise NotImplementedError(f"{who}: method='delaunay', the reference's default (src/segger/export/boundary.py:57-154, a "
                                   f"sequential pruning of a Delaunay triangulation), is not built; use method='convex_hull'")
+    return _check_smoothing(who, smoothing)
+
+
+def _oracle_hint(who: str) -> str:
+    return f"tests/{'outline' if who.endswith('outlines') else 'boundaries'}_cases.py holds the CPU oracle"
+
+
+def _check_smoothing(who: str, smoothing) -> int:
     if isinstance(smoothing, bool) or not isinstance(smoothing, int) or not 0 <= smoothing <= L.BOUNDARY_MAX_SMOOTHING:
         raise ValueError(f"{who}: smoothing must be an int in 0 .. {L.BOUNDARY_MAX_SMOOTHING} (Chaikin iterations; each doubles "
                          f"the vertices), got {smoothing!r}")
@@ -82,6 +93,25 @@ def cell_boundaries(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, 
     named)."""
     who = "cell_boundaries"
     smoothing = _check_options(who, smoothing, method)
+    dev, pts, ids, mask, n, n_cells = _rows(who, xy, cell, n_cells, keep)
+    capacity, ring_offsets, out, cell_ids, n_tx, counters = _outputs(dev, n, n_cells, smoothing, L.BOUNDARY_COUNTERS)
+    if n:
+        ws, ws_bytes = L.workspace("segger_cell_boundaries_workspace_bytes", dev, n, n_cells)
+        L.call("segger_cell_boundaries", dev, pts.data_ptr(), ids.data_ptr(), L.ptr(mask), n, n_cells, smoothing,
+               ring_offsets.data_ptr(), out.data_ptr(), capacity, cell_ids.data_ptr(), n_tx.data_ptr(), counters.data_ptr(),
+               ws.data_ptr(), ws_bytes)
+        del ws
+    c = dict(zip(COUNTERS, counters.tolist()))               # the one wait for the device
+    _raise_for_rows(who, c, n_cells)
+    if c["n_refused"]:
+        raise L.SeggerAmdError(f"{who}: {c['n_refused']} cells of more than {L.MORPH_MAX_VERTS} transcripts kept a running hull "
+                               f"above {L.BOUNDARY_CHUNK_MAX_HULL} vertices (SEGGER_BOUNDARY_CHUNK_MAX_HULL) while points "
+                               f"remained, cell {c['refused_cell'] - 1} among them; such a cell gets no polygon")
+    return _result(c, capacity, ring_offsets, out, cell_ids, n_tx)
+
+
+def _rows(who: str, xy, cell, n_cells, keep):
+    """the checks and conversions of the rows both entry points take -> (device, xy float64, ids int32, mask, n, n_cells)"""
     if not isinstance(xy, Tensor) or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_floating_point():
         raise ValueError(f"{who}: xy is a floating-point [n_rows, 2] tensor")
     if not isinstance(cell, Tensor) or cell.dim() != 1 or cell.is_floating_point() or cell.dtype == torch.bool:
@@ -93,7 +123,7 @@ def cell_boundaries(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, 
         raise ValueError(f"{who}: xy, cell and keep are on different devices")
     if n_cells is not None and not 1 <= int(n_cells) < (1 << 31):
         raise ValueError(f"{who}: n_cells must be in 1 .. 2^31 - 1, got {n_cells}")
-    L.need_device(who, xy, cell, keep, hint="tests/boundaries_cases.py holds the CPU oracle")
+    L.need_device(who, xy, cell, keep, hint=_oracle_hint(who))
     dev = xy.device
     pts = xy.detach().to(torch.float64).contiguous()
     ids = cell.detach()
@@ -104,27 +134,25 @@ def cell_boundaries(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, 
     if n_cells is None:
         n_cells = max(int(ids.max()) + 1, 1) if n else 1
     n_cells = min(int(n_cells), (1 << 31) - 1)
+    return dev, pts, ids, mask, n, n_cells
+
+
+def _outputs(dev, n: int, n_cells: int, smoothing: int, n_counters: int):
+    """the worst-case output arrays of a call: (capacity, ring_offsets, xy, cell_ids, n_transcripts, counters)"""
     cap = max(min(n, n_cells), 1)
     capacity = n << smoothing
-    ring_offsets = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
-    out = torch.empty(capacity, 2, dtype=torch.float64, device=dev)
-    cell_ids = torch.empty(cap, dtype=torch.int32, device=dev)
-    n_tx = torch.empty(cap, dtype=torch.int64, device=dev)
-    counters = torch.zeros(L.BOUNDARY_COUNTERS, dtype=torch.int64, device=dev)
-    if n:
-        ws, ws_bytes = L.workspace("segger_cell_boundaries_workspace_bytes", dev, n, n_cells)
-        L.call("segger_cell_boundaries", dev, pts.data_ptr(), ids.data_ptr(), L.ptr(mask), n, n_cells, smoothing,
-               ring_offsets.data_ptr(), out.data_ptr(), capacity, cell_ids.data_ptr(), n_tx.data_ptr(), counters.data_ptr(),
-               ws.data_ptr(), ws_bytes)
-        del ws
-    c = dict(zip(COUNTERS, counters.tolist()))               # the one wait for the device
+    return (capacity, torch.zeros(cap + 1, dtype=torch.int64, device=dev), torch.empty(capacity, 2, dtype=torch.float64, device=dev),
+            torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int64, device=dev),
+            torch.zeros(n_counters, dtype=torch.int64, device=dev))
+
+
+def _raise_for_rows(who: str, c: dict, n_cells: int) -> None:
     if c["n_bad_cell"] or c["n_non_finite"]:
         raise L.SeggerAmdError(f"{who}: {c['n_bad_cell']} kept rows have a cell id outside [0, {n_cells}) and "
                                f"{c['n_non_finite']} a NaN or infinite coordinate; they took part in nothing")
-    if c["n_refused"]:
-        raise L.SeggerAmdError(f"{who}: {c['n_refused']} cells of more than {L.MORPH_MAX_VERTS} transcripts kept a running hull "
-                               f"above {L.BOUNDARY_CHUNK_MAX_HULL} vertices (SEGGER_BOUNDARY_CHUNK_MAX_HULL) while points "
-                               f"remained, cell {c['refused_cell'] - 1} among them; such a cell gets no polygon")
+
+
+def _result(c: dict, capacity: int, ring_offsets, out, cell_ids, n_tx) -> Dict[str, Tensor]:
     K, V = c["n_kept"], c["n_vertices"]
     assert V <= capacity, (V, capacity)                      # h <= n for every cell
     verts = out[:V]
@@ -153,9 +181,12 @@ def segmentation_boundaries(result: Dict[str, Tensor], xy: Tensor, n_cells: Opti
     and offers ``--include-all-transcripts`` and ``--min-similarity`` instead of the per-gene threshold.  None of the
     three is applied here: filter the returned ``n_transcripts`` for the first, pass your own mask to
     :func:`cell_boundaries` for the others."""
-    who = "segmentation_boundaries"
+    return _segmented("segmentation_boundaries", cell_boundaries, result, xy, n_cells, kw)
+
+
+def _segmented(who: str, fn, result, xy, n_cells, kw) -> Dict[str, Tensor]:
     cols = [result[k] for k in ("row_index", "cell_encoding", "similarity", "similarity_threshold")]
-    L.need_device(who, *cols, hint="tests/boundaries_cases.py holds the CPU oracle")
+    L.need_device(who, *cols, hint=_oracle_hint(who))
     n = int(cols[0].numel())
     if any(int(t.numel()) != n for t in cols):
         raise ValueError(f"{who}: columns of different lengths")
@@ -164,4 +195,63 @@ def segmentation_boundaries(result: Dict[str, Tensor], xy: Tensor, n_cells: Opti
     dev = cols[0].device
     keep = cols[2].to(torch.float32).double() >= cols[3].double()          # false when either side is NaN
     pts = xy.detach().to(device=dev)[cols[0].to(dev)]                      # the gather by row_index is plumbing
-    return cell_boundaries(pts, cols[1], n_cells, keep=keep, **kw)
+    return fn(pts, cols[1], n_cells, keep=keep, **kw)
+
+
+def cell_outlines(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, keep: Optional[Tensor] = None,
+                  connectivity: float = 2.0, smoothing: int = 0) -> Dict[str, Tensor]:
+    """The concave outline of every cell: the reference's DEFAULT ``method="delaunay"`` (``_CellOutline``,
+    ``boundary.py:57-154``) -- triangulate the cell's distinct transcripts, peel off the rim every triangle with a rim edge
+    longer than ``2 * connectivity * d_max``, then every one with a rim edge that is long and faces an obtuse angle or
+    faces an angle above ``180 - 11.25 / connectivity`` degrees, and return the outline of the largest piece that remains,
+    after ``smoothing`` Chaikin iterations.  ``d_max`` is the cell's largest nearest-neighbour distance.
+
+    The arguments, the counted rows and the returned dict (``ring_offsets``, ``xy``, ``cell_ids``, ``n_transcripts``,
+    ``n_dropped``) are :func:`cell_boundaries`'s; ``connectivity`` is a finite number > 0.  A ring is open,
+    counter-clockwise from its lowest (x, then y) vertex, and lists every vertex of the outline, collinear ones included;
+    a vertex is an input coordinate bit for bit.  ``n_dropped`` counts the present cells without a polygon: fewer than 3
+    distinct points, all collinear, or every triangle peeled.  One wait for the device.
+
+    What the ring is, and why it does not depend on the order in which the reference's ``_prune`` visits its edges:
+    DESIGN 3.5j.  What is NOT reproduced: the choice among components of EQUAL area (GEOS's order there; here the one
+    with the lower lowest vertex); qhull's choice among co-circular points (here the fan from their lowest vertex);
+    ``.buffer(0)`` after the smoothing, which can alter a smoothed concave ring that touches itself; and the orientation
+    and start vertex shapely hands to ``_chaikin`` -- the smoothed vertices have the same bits either way, since a vertex
+    is ``0.75 p + 0.25 q`` of an edge ``p q`` whichever way the ring runs, only their order differs.
+
+    UNVERIFIED, as in this module's header: not verified against shapely, so ``polygonize`` (one polygon per
+    edge-connected piece, dangling edges ignored) rests on knowledge of the library.  The pruning itself is pinned to a
+    run of the reference's ``_CellOutline.refine`` (tests/golden/outlines_small.npz).
+
+    Raises ``ValueError`` for bad shapes, dtypes or options and ``SeggerAmdError`` for a kept row with a cell id
+    ``>= n_cells`` or a non-finite coordinate, for a cell with more than ``SEGGER_OUTLINE_MAX_POINTS`` distinct points
+    (the cell is named; a route through global memory for such cells is not built), and for a cell whose triangulation
+    contradicted itself (rounded predicates on coordinates that share no grid can do that; the cell is named)."""
+    who = "cell_outlines"
+    smoothing = _check_smoothing(who, smoothing)
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, float)) or not 0 < connectivity < float("inf"):
+        raise ValueError(f"{who}: connectivity must be a finite number > 0, got {connectivity!r}")
+    dev, pts, ids, mask, n, n_cells = _rows(who, xy, cell, n_cells, keep)
+    capacity, ring_offsets, out, cell_ids, n_tx, counters = _outputs(dev, n, n_cells, smoothing, L.OUTLINE_COUNTERS)
+    if n:
+        ws, ws_bytes = L.workspace("segger_cell_outlines_workspace_bytes", dev, n, n_cells)
+        L.call("segger_cell_outlines", dev, pts.data_ptr(), ids.data_ptr(), L.ptr(mask), n, n_cells, float(connectivity), smoothing,
+               ring_offsets.data_ptr(), out.data_ptr(), capacity, cell_ids.data_ptr(), n_tx.data_ptr(), counters.data_ptr(),
+               ws.data_ptr(), ws_bytes)
+        del ws
+    c = dict(zip(OUTLINE_COUNTER_NAMES, counters.tolist()))       # the one wait for the device
+    _raise_for_rows(who, c, n_cells)
+    if c["n_refused"]:
+        raise L.SeggerAmdError(f"{who}: {c['n_refused']} cells have more than {L.OUTLINE_MAX_POINTS} distinct points "
+                               f"(SEGGER_OUTLINE_MAX_POINTS, the LDS budget of one cell), cell {c['refused_cell'] - 1} among "
+                               f"them; such a cell gets no polygon")
+    if c["n_failed"]:
+        raise L.SeggerAmdError(f"{who}: the triangulation of {c['n_failed']} cells contradicted itself (rounded predicates), "
+                               f"cell {c['failed_cell'] - 1} among them; such a cell gets no polygon")
+    return _result(c, capacity, ring_offsets, out, cell_ids, n_tx)
+
+
+def segmentation_outlines(result: Dict[str, Tensor], xy: Tensor, n_cells: Optional[int] = None, **kw) -> Dict[str, Tensor]:
+    """:func:`cell_outlines` of the segmented transcripts of ``result``, chosen by the rule of
+    :func:`segmentation_boundaries`; ``kw`` is ``connectivity`` and ``smoothing``."""
+    return _segmented("segmentation_outlines", cell_outlines, result, xy, n_cells, kw)

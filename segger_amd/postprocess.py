@@ -342,6 +342,12 @@ class SegmentationAccumulator:
         from .boundaries import segmentation_boundaries
         return segmentation_boundaries(self.segmentation(max_iter, thresholds), xy, **kw)
 
+    def outlines(self, xy: Tensor, max_iter: int = 250, thresholds: str = "torch", **kw) -> Dict[str, Tensor]:
+        """``segmentation_outlines(self.segmentation(max_iter, thresholds), xy, **kw)``: the concave outline per cell, the
+        reference's default ``method="delaunay"`` (:func:`segger_amd.boundaries.cell_outlines`)."""
+        from .boundaries import segmentation_outlines
+        return segmentation_outlines(self.segmentation(max_iter, thresholds), xy, **kw)
+
 
 EXPRESSION_COUNTERS = ("n_kept", "nnz", "n_cells_present", "n_genes_present", "n_bad")
 
