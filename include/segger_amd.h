@@ -225,7 +225,8 @@ typedef struct segger_gatv2_bwd_args {
   int64_t ld_gxr;
   float* grad_att;        /* [H*C] */
   float* grad_bias;       /* [H*C] or NULL */
-  void* workspace;        /* segger_gatv2_bwd_workspace_bytes() */
+  void* workspace;        /* segger_gatv2_bwd_workspace_bytes_two_pass(); with src_unique set
+                             segger_gatv2_bwd_workspace_bytes() suffices */
   size_t workspace_bytes;
   const uint8_t* keep_bits_dst; /* optional dropout bit planes (see forward) in by_dst / by_src slot order */
   const uint8_t* keep_bits_src;
@@ -241,15 +242,27 @@ typedef struct segger_gatv2_bwd_args {
   int64_t ld_zero;
   int32_t grad_xl_zeroed; /* one-pass form (src_unique): grad_xl already holds zeros (see zero_rows_out): skip the fill */
   int32_t passes;         /* segger_gatv2_bwd only -- 0: the whole backward (default); 1: the destination-side pass alone
-                             (grad_pre, dsum, grad_xr, grad_att, grad_bias; grad_xl too in the one-pass form); 2: the
-                             source-side pass alone (grad_xl from the grad_pre / dsum an earlier passes = 1 call left in
-                             the same buffers).  1 then 2 == 0; exists so that a profiler / bench.py can time the two
-                             kernels of the backward separately (roofline.dominant).  3: the destination KERNEL alone --
-                             as 1 without the two small launches that sum its per-workgroup grad_att / grad_bias partials
-                             (those two outputs are then not written): timing only. */
+                             (grad_pre, dsum, grad_xr, grad_bias; grad_xl and grad_att too in the one-pass form); 2: the
+                             source-side KERNEL alone (grad_xl from the grad_pre / dsum an earlier passes = 1 call left in
+                             the same buffers; grad_att / grad_bias are not written).  Exists so that a profiler / bench.py
+                             can time the two kernels of the backward separately (roofline.dominant): 1 then 2 gives the
+                             row gradients and grad_bias of 0.  grad_att of the two-pass form is a sum over both passes'
+                             rows (per destination x_r * (c1 Sde + c2 Sg), per source x_l * (c1 Sde + c2 Sg), with Sde /
+                             Sg the row's sums of de and de * sgn(t)): only passes = 0 sums both halves; passes = 1 leaves
+                             the destination half alone in grad_att.  3: the destination KERNEL alone -- as 1 without
+                             the two small launches that sum its per-workgroup grad_att / grad_bias partials (those two
+                             outputs are then not written): timing only. */
 } segger_gatv2_bwd_args;
 
+/* Workspace of the one-pass form (src_unique) -- equal to the two-pass size for n_src = 0. */
 size_t segger_gatv2_bwd_workspace_bytes(int64_t n_dst, int32_t heads, int32_t channels);
+/* Workspace of the two-pass form: the destination pass's per-workgroup partials of grad_att / grad_bias, the source
+ * pass's per-workgroup partials of grad_att (one [H*C] row per workgroup of by-source rows: grows with n_src; n_edges
+ * decides between 4 and 4 * (64 / group size) source rows per workgroup as the launcher does) and the partials of their
+ * deterministic sum.  Purely additive: one new symbol, no existing signature or struct changes, so SEGGER_ABI_VERSION
+ * stays 32; a two-pass call handed only segger_gatv2_bwd_workspace_bytes() returns SEGGER_EWORKSPACE. */
+size_t segger_gatv2_bwd_workspace_bytes_two_pass(int64_t n_dst, int64_t n_src, int64_t n_edges, int32_t heads,
+                                                 int32_t channels);
 int segger_gatv2_bwd(const segger_gatv2_bwd_args* args, segger_stream_t stream);
 /* The backward of both edge types of one HeteroConv layer (ist_encoder.py:109-134 under autograd): `a` a two-pass edge
  * type (tx-neighbors-tx), `b` a one-pass one (src_unique: tx-belongs-bd) whose grad_xl is the matrix `a` zero-fills

@@ -94,7 +94,8 @@ int wgrad_f32_launch(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x,
                      float* partial, int64_t* n_slabs, hipStream_t stream);
 
 // ------------------------------------------------- deferred partial sums ---
-// out0[e] (e < split) / out1[e - split] (e >= split; out1 may be NULL) = sum_s partial[s * width + e], slabs in order.
+// out0[e] (e < split) / out1[e - split] (e >= split; out1 may be NULL) = sum_s partial[s * width + e], slabs in order,
+// plus, for e < width2 (<= width), sum_s partial2[s * width2 + e] over a second run of n_slabs2 slabs.
 // Between segger_reductions_defer_begin() and segger_reductions_flush() (csrc/reduce.hip) the kernels that leave
 // per-workgroup partial sums (weight gradients, grad_att / grad_bias slabs) queue their final sum here instead of
 // launching it; defer_reduce() returns false when nothing is being deferred (or the sum is too long for one pass,
@@ -103,6 +104,7 @@ int wgrad_f32_launch(const void* dy, int64_t ld_dy, const void* x, int64_t ld_x,
 struct ReduceSeg {
   const float* partial; int64_t n_slabs; int64_t width; int64_t split; float* out0; float* out1;
   float* scratch;      // >= kReduceGroups * width floats behind the partials (sums longer than one pass go through it)
+  const float* partial2 = nullptr; int32_t n_slabs2 = 0; int32_t width2 = 0;
 };
 constexpr int kReduceGroups = 32;
 bool defer_reduce(const ReduceSeg& seg, hipStream_t stream);

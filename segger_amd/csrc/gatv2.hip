@@ -7,9 +7,12 @@ namespace segger {
 
 // grad_att / grad_bias = column sums of the slab [nblocks][width], in two deterministic stages:
 // stage 1: kSlabSplits row ranges x 64-column chunks -> part[kSlabSplits][width]; stage 2: sum the splits.
+// The two-pass backward leaves a second slab [nblocks2][width2] (the source pass's share of grad_att, width2 <= width):
+// its columns are summed into the same partials, split into row ranges of its own.
 constexpr int kSlabSplits = 128;
 
 __global__ __launch_bounds__(256) void slab_reduce_stage1(const float* __restrict__ slab, int64_t nblocks, int width,
+                                                         const float* __restrict__ slab2, int64_t nblocks2, int width2,
                                                          float* __restrict__ part) {
   __shared__ float sm[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -20,6 +23,20 @@ __global__ __launch_bounds__(256) void slab_reduce_stage1(const float* __restric
   float s = 0.f;
   if (colx < width)
     for (int64_t r = r0 + wave; r < r1; r += 4) s += slab[r * width + colx];
+  if (colx < width2) {
+    const int64_t per2 = (nblocks2 + kSlabSplits - 1) / kSlabSplits;
+    const int64_t q0 = (int64_t)blockIdx.y * per2;
+    const int64_t q1 = q0 + per2 < nblocks2 ? q0 + per2 : nblocks2;
+    // (one slab per 16 source rows: eight times the rows of the first slab, so eight loads in flight per lane)
+    float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int64_t r = q0 + wave;
+    for (; r + 28 < q1; r += 32) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t[k] += slab2[(r + 4 * k) * width2 + colx];
+    }
+    for (; r < q1; r += 4) t[0] += slab2[r * width2 + colx];
+    s += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+  }
   sm[wave][lane] = s;
   __syncthreads();
   if (wave == 0 && colx < width) part[(int64_t)blockIdx.y * width + colx] = sm[0][lane] + sm[1][lane] + sm[2][lane] + sm[3][lane];
@@ -183,12 +200,41 @@ extern "C" int segger_gatv2_fwd_pair(const segger_gatv2_fwd_args* a, const segge
   return SEGGER_EINVAL;
 }
 
+namespace {
+// workspace of one backward, in floats: [dst_cap][2 HC] destination-pass slab | [src_cap][HC] source-pass slab |
+// [kSlabSplits][2 HC] partials of the slab sum
+struct BwdWorkspace { int64_t dst_cap, src_cap; size_t floats; };
+
+BwdWorkspace bwd_workspace(int64_t n_dst, int64_t n_src, int64_t n_edges, int heads, int channels) {
+  BwdWorkspace w{0, 0, 0};
+  const int64_t hc = (int64_t)heads * channels;
+  if (n_dst > 0) {
+    // upper bound over both modes: wave-per-row has the most blocks (4 rows per block-iteration)
+    const int64_t per = 4 * (int64_t)bwd_row_iters(n_dst);
+    w.dst_cap = (n_dst + per - 1) / per + kNumXcd;
+  }
+  if (n_src > 0 && gatv2_has_specialised(heads, channels)) {
+    // the source pass walks 4 rows per block in wave-per-row mode, 4 * (64 / group size) otherwise (Geo::NG)
+    const int lpr = heads * channels / 8;
+    int gs = 1;
+    while (gs < lpr) gs *= 2;
+    const bool wpr = (double)n_edges / (double)n_src >= kWavePerRowDegree;
+    const int64_t per = wpr ? 4 : 4 * (64 / gs);
+    w.src_cap = (n_src + per - 1) / per + kNumXcd;
+  }
+  w.floats = (size_t)(w.dst_cap + kSlabSplits) * 2 * hc + (size_t)w.src_cap * hc;
+  return w;
+}
+}  // namespace
+
+extern "C" size_t segger_gatv2_bwd_workspace_bytes_two_pass(int64_t n_dst, int64_t n_src, int64_t n_edges, int32_t heads,
+                                                           int32_t channels) {
+  if ((n_dst <= 0 && n_src <= 0) || heads <= 0 || channels <= 0) return 16;
+  return bwd_workspace(n_dst, n_src, n_edges, heads, channels).floats * sizeof(float);
+}
+
 extern "C" size_t segger_gatv2_bwd_workspace_bytes(int64_t n_dst, int32_t heads, int32_t channels) {
-  if (n_dst <= 0 || heads <= 0 || channels <= 0) return 16;
-  // upper bound over both modes: wave-per-row has the most blocks (4 rows per block-iteration)
-  const int64_t per = 4 * (int64_t)bwd_row_iters(n_dst);
-  const int64_t blocks = (n_dst + per - 1) / per + kNumXcd;
-  return (size_t)(blocks + kSlabSplits) * 2 * heads * channels * sizeof(float);
+  return segger_gatv2_bwd_workspace_bytes_two_pass(n_dst, 0, 0, heads, channels);
 }
 
 // ---- backward in phases (shared by segger_gatv2_bwd and segger_gatv2_bwd_pair) ------------------------------
@@ -197,6 +243,8 @@ struct BwdState {
   GatParams p;
   bool direct = false, specialised = false;
   int64_t n_dst = 0, n_src = 0, n_edges = 0;
+  int64_t dst_blocks = 0, src_blocks = 0;     // rows the passes launched so far left in slab / slab_src
+  float* part = nullptr;                      // partials of the slab sum, behind both slabs
 };
 
 // argument checks + the parameters both passes share
@@ -233,7 +281,8 @@ int bwd_prepare(const segger_gatv2_bwd_args* a, BwdState& s) {
   SEGGER_REQUIRE(!(a->dropout_p > 0.f) || n_edges == 0 ||
                      ((a->by_dst.eid || a->keep_bits_dst) && (direct || a->by_src.eid || a->keep_bits_src)),
                  "segger_gatv2_bwd: eid arrays (or keep_bits) are required for dropout");
-  const size_t need = segger_gatv2_bwd_workspace_bytes(n_dst, a->heads, a->channels);
+  const BwdWorkspace w = bwd_workspace(n_dst, direct ? 0 : n_src, direct ? 0 : n_edges, a->heads, a->channels);
+  const size_t need = (n_dst > 0 || w.src_cap > 0) ? w.floats * sizeof(float) : 16;
   if (a->workspace == nullptr || a->workspace_bytes < need) {
     set_error("segger_gatv2_bwd: workspace %zu < %zu bytes", a->workspace_bytes, need);
     return SEGGER_EWORKSPACE;
@@ -251,6 +300,8 @@ int bwd_prepare(const segger_gatv2_bwd_args* a, BwdState& s) {
   p.gout = a->grad_out; p.ld_go = a->ld_go; p.gpre = a->grad_pre; p.ld_gp = a->ld_gp; p.dsum = a->dsum;
   p.gxl = a->grad_xl; p.ld_gxl = a->ld_gxl; p.gxr = a->grad_xr; p.ld_gxr = a->ld_gxr;
   p.slab = static_cast<float*>(a->workspace);
+  p.slab_src = p.slab + w.dst_cap * 2 * hc;
+  s.part = p.slab_src + w.src_cap * hc;
   p.slope = a->negative_slope; p.apply_gelu = a->apply_gelu;
   set_dropout(p, a->dropout_p, a->seed, a->seed_dev);
   return SEGGER_OK;
@@ -288,17 +339,20 @@ int bwd_zero_fill(const segger_gatv2_bwd_args* a, const BwdState& s, hipStream_t
   return SEGGER_OK;
 }
 
-// grad_att / grad_bias from the per-block slabs a destination pass (s.p still holds its block count) left behind
+// grad_att / grad_bias from the per-block slabs the passes left behind: s.dst_blocks rows of the destination pass and,
+// after a source pass, s.src_blocks rows of grad_att alone
 int bwd_reduce_slab(const segger_gatv2_bwd_args* a, const BwdState& s, hipStream_t stream) {
   if (!s.specialised) return SEGGER_OK;                   // the generic kernels write grad_att / grad_bias themselves
   const GatParams& p = s.p;
   const int hc = a->heads * a->channels, width = 2 * hc;
-  float* part = p.slab + p.nblocks * width;              // behind the per-block slabs
-  if (defer_reduce(ReduceSeg{p.slab, p.nblocks, width, hc, a->grad_att, a->grad_bias, part}, stream)) return SEGGER_OK;
+  const int width2 = s.src_blocks > 0 ? hc : 0;
+  if (defer_reduce(ReduceSeg{p.slab, s.dst_blocks, width, hc, a->grad_att, a->grad_bias, s.part, p.slab_src,
+                             (int32_t)s.src_blocks, width2}, stream))
+    return SEGGER_OK;
   hipLaunchKernelGGL(slab_reduce_stage1, dim3((width + 63) / 64, kSlabSplits), dim3(256), 0, stream,
-                     p.slab, p.nblocks, width, part);
+                     p.slab, s.dst_blocks, width, p.slab_src, s.src_blocks, width2, s.part);
   hipLaunchKernelGGL(slab_reduce_stage2, dim3((width + 255) / 256), dim3(256), 0, stream,
-                     part, width, hc, a->grad_att, a->grad_bias);
+                     s.part, width, hc, a->grad_att, a->grad_bias);
   SEGGER_LAUNCH_CHECK("slab_reduce kernels");
   return SEGGER_OK;
 }
@@ -333,7 +387,9 @@ extern "C" int segger_gatv2_bwd(const segger_gatv2_bwd_args* a, segger_stream_t 
     if (s.n_dst > 0) {
       GenericOut gen; gen.grad_att = a->grad_att; gen.grad_bias = a->grad_bias;
       CHECK_RC(launch(Pass::BwdDst, s.p, a->dtype, a->heads, a->channels, use_wave_per_row(a->by_dst), stream, gen));
-      if (a->passes != 3) CHECK_RC(bwd_reduce_slab(a, s, stream));
+      s.dst_blocks = s.p.nblocks;
+      // the one-pass form and passes = 1 end here: the sums of the destination pass alone
+      if (s.direct || a->passes == 1) CHECK_RC(bwd_reduce_slab(a, s, stream));
     } else {
       CHECK_RC(bwd_no_destinations(a, stream));
     }
@@ -341,7 +397,12 @@ extern "C" int segger_gatv2_bwd(const segger_gatv2_bwd_args* a, segger_stream_t 
   // ---- source side -----------------------------------------------------------
   if (s.direct || a->passes == 1 || a->passes == 3) return SEGGER_OK;
   bwd_src_params(a, s);
-  if (s.n_src > 0) CHECK_RC(launch(Pass::BwdSrc, s.p, a->dtype, a->heads, a->channels, use_wave_per_row(a->by_src), stream));
+  if (s.n_src > 0) {
+    CHECK_RC(launch(Pass::BwdSrc, s.p, a->dtype, a->heads, a->channels, use_wave_per_row(a->by_src), stream));
+    s.src_blocks = s.p.nblocks;
+  }
+  // grad_att needs both passes' slabs: summed once, behind the source pass (passes = 2 is the source kernel alone)
+  if (a->passes == 0 && s.n_dst > 0) CHECK_RC(bwd_reduce_slab(a, s, stream));
   return SEGGER_OK;
 }
 
@@ -368,7 +429,7 @@ extern "C" int segger_gatv2_bwd_pair(const segger_gatv2_bwd_args* a, const segge
   bwd_dst_params(a, sa);
   sa.p.zero_rows = b->grad_xl; sa.p.ld_zero = b->ld_gxl;
   CHECK_RC(launch(Pass::BwdDst, sa.p, a->dtype, a->heads, a->channels, false, stream));
-  CHECK_RC(bwd_reduce_slab(a, sa, stream));
+  sa.dst_blocks = sa.p.nblocks;
   bwd_src_params(a, sa);
   sa.p.zero_rows = nullptr; sa.p.ld_zero = 0;
   bwd_dst_params(b, sb);
@@ -378,6 +439,8 @@ extern "C" int segger_gatv2_bwd_pair(const segger_gatv2_bwd_args* a, const segge
     case SEGGER_F16:  CHECK_RC(gatv2_launch_bwd_src_dst_pair_f16(sa.p, sb.p, a->heads, a->channels, stream)); break;
     default: set_error("gatv2: unknown dtype %d", a->dtype); return SEGGER_EINVAL;
   }
+  sa.src_blocks = sa.p.nblocks; sb.dst_blocks = sb.p.nblocks;
+  CHECK_RC(bwd_reduce_slab(a, sa, stream));
   return bwd_reduce_slab(b, sb, stream);
 }
 

@@ -86,6 +86,7 @@ struct GatParams {
   void* gxl; int64_t ld_gxl;
   void* gxr; int64_t ld_gxr;
   float* slab;                   // [nblocks][2][HC] partial grad_att | grad_bias
+  float* slab_src;               // src pass: [nblocks][HC] partial grad_att (the by-source half of the endpoint split)
   // scalars
   float slope;
   float drop_scale;              // 1/(1-p)
@@ -653,10 +654,16 @@ __global__ __launch_bounds__(256, SEGGER_FWD_WAVES) void gatv2_fwd_pair_kernel(G
 //   de_ij  = a_ij * (keep/(1-p) * <g_j, x_l[i]>_h - D[j,h])
 //   grad_xr[j] = att * (c1 * sum_i de_ij + c2 * sum_i de_ij * sgn(t_ij))
 //   grad_att   = c1 * sum_ij de_ij * t_ij + c2 * sum_ij de_ij * |t_ij| ;  grad_bias = sum_j g[j]
+// With t_ij = x_l[i] + x_r[j] both grad_att sums split exactly by endpoint:
+//   grad_att   = sum_j x_r[j] * (c1 * Sde_j + c2 * Sg_j)  +  sum_i x_l[i] * (c1 * Sde_i + c2 * Sg_i)
+// with Sde = sum de and Sg = sum de * sgn(t) over the in-edges of destination j / the out-edges of source i: the per-row
+// sums both passes keep anyway (for grad_xr / grad_xl).  The two-pass form therefore adds to grad_att once per ROW, the
+// first sum here and the second in the source pass (slab_src), instead of two packed FMAs per channel pair and EDGE.
 // ============================================================================
 // DIRECT: every source node has at most one out-edge (segger's tx-belongs-bd: a transcript lies in at most one
 // boundary), so grad_xl[i] has a single term and this pass stores it itself -- no by-source view, no source pass.
-// The caller zero-fills grad_xl first (sources without an out-edge).
+// The caller zero-fills grad_xl first (sources without an out-edge).  Without a source pass there are no by-source
+// sums, so the direct form keeps grad_att as per-edge sums (Pt, Qt).
 // (the direct form keeps 8 more values per lane live: it is built for 2 waves per SIMD instead of spilling)
 template <typename T, int H, int LPH, bool WPR, bool DIRECT, int UFORCE = 0>
 __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t bid) {
@@ -682,10 +689,14 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
   char* __restrict__ gxl_base = static_cast<char*>(p.gxl) + (size_t)ch0 * sizeof(T);
   const uint32_t ld_gxl = (uint32_t)(p.ld_gxl * sizeof(T));
 
-  f32x2 a1[4], na1[4], a2[4], Pt[4], Qt[4], dbias[4];
+  // Pt / Qt: the direct form's per-edge sums; datt2: the two-pass form's per-row sum (the other set is never touched)
+  f32x2 a1[4], na1[4], a2[4], Pt[4], Qt[4], datt2[4], dbias[4];
   load_att(p.att, ch0, p.slope, kLog2e, a1, a2);
+  const float c1 = 0.5f * (1.f + p.slope), c2 = 0.5f * (1.f - p.slope);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { na1[i] = -a1[i]; Pt[i] = splat(0.f); Qt[i] = splat(0.f); dbias[i] = splat(0.f); }
+  for (int i = 0; i < 4; ++i) {
+    na1[i] = -a1[i]; Pt[i] = splat(0.f); Qt[i] = splat(0.f); datt2[i] = splat(0.f); dbias[i] = splat(0.f);
+  }
 
 #pragma unroll 1
   for (int it = 0; it < p.rows_per_wave_iter; ++it) {
@@ -775,11 +786,13 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const f32x2 sg = f32x2{sign_mul(nde, nt[i].x), sign_mul(nde, nt[i].y)};    // de * sgn(t)
-          Pt[i] = pk_fma(nde2, nt[i], Pt[i]);                                        // de * t
-          Qt[i] = pk_fma(-sg, nt[i], Qt[i]);                                         // de * |t|
           Sg[i] = Sg[i] + sg;
-          if constexpr (DIRECT)      // the source pass's formula with this edge as the only term
+          if constexpr (DIRECT) {
+            Pt[i] = pk_fma(nde2, nt[i], Pt[i]);                                      // de * t
+            Qt[i] = pk_fma(-sg, nt[i], Qt[i]);                                       // de * |t|
+            // the source pass's formula with this edge as the only term
             gx[i] = pk_fma(splat(a_eff), g[i], (a1[i] * de + a2[i] * sg) * kLn2);
+          }
         }
         if constexpr (DIRECT) {
           if (valid[u] && L.lane_on)
@@ -811,15 +824,22 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
 #pragma unroll
       for (int i = 0; i < 4; ++i) dxr[i] = (a1[i] * Sde + a2[i] * Sg[i]) * kLn2;
       store_pairs(static_cast<T*>(p.gxr) + row * p.ld_gxr + ch0, dxr);
+      if constexpr (!DIRECT) {       // this row's share of grad_att: x_r * (c1 * Sde + c2 * Sg), with nxr = -x_r
+#pragma unroll
+        for (int i = 0; i < 4; ++i) datt2[i] = datt2[i] - nxr[i] * (splat(c1 * Sde) + Sg[i] * c2);
+      }
     }
   }
 
-  // grad_att = c1 * Pt + c2 * Qt ; block partials of grad_att / grad_bias -> slab[blk]
-  const float c1 = 0.5f * (1.f + p.slope), c2 = 0.5f * (1.f - p.slope);
+  // direct: grad_att = c1 * Pt + c2 * Qt ; block partials of grad_att / grad_bias -> slab[blk]
   float datt[8], db[8];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    datt[2 * i] = c1 * Pt[i].x + c2 * Qt[i].x; datt[2 * i + 1] = c1 * Pt[i].y + c2 * Qt[i].y;
+    if constexpr (DIRECT) {
+      datt[2 * i] = c1 * Pt[i].x + c2 * Qt[i].x; datt[2 * i + 1] = c1 * Pt[i].y + c2 * Qt[i].y;
+    } else {
+      datt[2 * i] = datt2[i].x; datt[2 * i + 1] = datt2[i].y;
+    }
     db[2 * i] = dbias[i].x; db[2 * i + 1] = dbias[i].y;
   }
 #pragma unroll
@@ -853,7 +873,7 @@ __global__ __launch_bounds__(256, DIRECT ? 2 : SEGGER_BWD_DST_WAVES) void gatv2_
 template <typename T, int H, int LPH, bool WPR>
 __device__ __forceinline__ void gatv2_bwd_src_body(SEGGER_BODY_PARAM p, int64_t bid) {
   using G = Geo<H, LPH>;
-  constexpr int GS = G::GS, NG = G::NG, U = SEGGER_SRC_UNROLL < GS ? SEGGER_SRC_UNROLL : GS;
+  constexpr int GS = G::GS, NG = G::NG, U = SEGGER_SRC_UNROLL < GS ? SEGGER_SRC_UNROLL : GS, HC = G::HC;
   const int64_t blk = xcd_remap(bid, p.nblocks_padded, p.nblocks);
   if (blk < 0) return;
   const LaneGeo L = lane_geo<G>();
@@ -877,12 +897,35 @@ __device__ __forceinline__ void gatv2_bwd_src_body(SEGGER_BODY_PARAM p, int64_t 
   float Sde = 0.f;
   int64_t beg = 0, end = 0;
   if (row_ok) { beg = p.indptr[row]; end = p.indptr[row + 1]; }
+  // The by-source half of grad_att (see the destination pass): every wave hands in x_l * (c1 * Sde + c2 * Sg) summed over
+  // its rows, the block stores the sum of its four waves as slab_src[blk][HC].  EVERY block stores one, whatever its
+  // waves did (edgeless rows, rows past n_rows: zeros) -- the slab sum reads them all.  Each wave passes exactly one
+  // barrier on either way out.
+  __shared__ float red_src[4][HC];
+  auto block_partial = [&](const f32x2 (&w)[4]) {
+    float d[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { d[2 * i] = w[i].x; d[2 * i + 1] = w[i].y; }
+#pragma unroll
+    for (int off = GS; off < 64; off <<= 1) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) d[k] += __shfl_xor(d[k], off, 64);
+    }
+    if (L.grp == 0 && L.lane_on) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) red_src[L.wave][L.ch0 + k] = d[k];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < HC; i += 256)
+      p.slab_src[blk * HC + i] = red_src[0][i] + red_src[1][i] + red_src[2][i] + red_src[3][i];
+  };
   // tx-belongs-bd by source: most transcripts have no out-edge; such waves only write zeros
   if (__all(beg == end)) {
     if (row_ok && L.lane_on && (!WPR || L.grp == 0)) {
       store_pairs(static_cast<T*>(p.gxl) + row * p.ld_gxl + ch0, acc);
       if (p.zero_rows) store_pairs(static_cast<T*>(p.zero_rows) + row * p.ld_zero + ch0, acc);     // (acc is zero here)
     }
+    block_partial(acc);                                                                            // (and here)
     return;
   }
   load_att(p.att, ch0, p.slope, kLog2e, a1, a2);
@@ -944,6 +987,14 @@ __device__ __forceinline__ void gatv2_bwd_src_body(SEGGER_BODY_PARAM p, int64_t 
   else
     walk_row<GS, WPR, kMetaNone, U>(p.col, nullptr, beg, end, L.lane, L.grp, L.gl, body);
 
+  {   // this wave's rows' share of grad_att: x_l * (c1 * Sde + c2 * Sg), with nv = -x_l.  Invalid slots and rows past
+      // n_rows carry de = 0; in wave-per-row mode the groups hold partial sums of ONE row and the same x_l: summed below
+    const float c1 = 0.5f * (1.f + p.slope), c2 = 0.5f * (1.f - p.slope);
+    f32x2 w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = -(nv[i] * (splat(c1 * Sde) + Sg[i] * c2));
+    block_partial(w);
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] = acc[i] + (a1[i] * Sde + a2[i] * Sg[i]) * kLn2;
   if constexpr (WPR) {

@@ -16,7 +16,8 @@
 namespace segger {
 namespace {
 
-constexpr int kMaxSegs = 56;                    // 56 x 56 B + 8 by value in the kernel arguments (< 4 KiB)
+constexpr int kMaxSegs = 56;                    // 56 x 72 B + 8 by value in the kernel arguments (< 4 KiB)
+static_assert(sizeof(ReduceSeg) * kMaxSegs + 8 <= 4096, "the table travels as a kernel argument");
 constexpr int64_t kOnePassSlabs = 128;          // longer sums first fold into kReduceGroups interleaved groups
 
 struct ReduceBatch { int n; ReduceSeg seg[kMaxSegs]; };
@@ -39,6 +40,14 @@ __global__ __launch_bounds__(256) void reduce_many_kernel(ReduceBatch b) {
     s2 += p[(s + 2) * g.width]; s3 += p[(s + 3) * g.width];
   }
   for (; s < g.n_slabs; ++s) s0 += p[s * g.width];
+  if (e < g.width2) {
+    const float* __restrict__ q = g.partial2 + e;
+    for (s = 0; s + 3 < g.n_slabs2; s += 4) {
+      s0 += q[s * g.width2];       s1 += q[(s + 1) * g.width2];
+      s2 += q[(s + 2) * g.width2]; s3 += q[(s + 3) * g.width2];
+    }
+    for (; s < g.n_slabs2; ++s) s0 += q[s * g.width2];
+  }
   const float t = (s0 + s1) + (s2 + s3);
   if (e < g.split) g.out0[e] = t;
   else if (g.out1) g.out1[e - g.split] = t;
@@ -58,6 +67,14 @@ __global__ __launch_bounds__(256) void reduce_many_fold_kernel(ReduceBatch b) {
     s2 += p[(s + 2 * kReduceGroups) * g.width]; s3 += p[(s + 3 * kReduceGroups) * g.width];
   }
   for (; s < g.n_slabs; s += kReduceGroups) s0 += p[s * g.width];
+  if (e < g.width2) {
+    const float* __restrict__ q = g.partial2 + e;
+    for (s = grp; s + 3 * kReduceGroups < g.n_slabs2; s += 4 * kReduceGroups) {
+      s0 += q[s * g.width2];                       s1 += q[(s + kReduceGroups) * g.width2];
+      s2 += q[(s + 2 * kReduceGroups) * g.width2]; s3 += q[(s + 3 * kReduceGroups) * g.width2];
+    }
+    for (; s < g.n_slabs2; s += kReduceGroups) s0 += q[s * g.width2];
+  }
   g.scratch[(int64_t)grp * g.width + e] = (s0 + s1) + (s2 + s3);
 }
 
@@ -65,7 +82,7 @@ __global__ __launch_bounds__(256) void reduce_many_fold_kernel(ReduceBatch b) {
 
 bool defer_reduce(const ReduceSeg& seg, hipStream_t stream) {
   std::lock_guard<std::mutex> lock(g_mu);
-  if (!g_active || g_batch.n >= kMaxSegs || (seg.n_slabs > kOnePassSlabs && seg.scratch == nullptr)) return false;
+  if (!g_active || g_batch.n >= kMaxSegs || ((seg.n_slabs > kOnePassSlabs || seg.n_slabs2 > kOnePassSlabs) && seg.scratch == nullptr)) return false;
   // the table belongs to ONE device and ONE stream (the bracket's): a backward of another model on another GPU or
   // stream of this process must not leave its sum to a flush that runs elsewhere -- it launches its own
   int dev = -1;
@@ -111,10 +128,10 @@ extern "C" int segger_reductions_flush(segger_stream_t stream) {
   int64_t long_width = 0;
   for (int i = 0; i < g_batch.n; ++i) {
     ReduceSeg& g = g_batch.seg[i];
-    if (g.n_slabs <= kOnePassSlabs) continue;
+    if (g.n_slabs <= kOnePassSlabs && g.n_slabs2 <= kOnePassSlabs) continue;
     longs.seg[longs.n++] = g;
     long_width = g.width > long_width ? g.width : long_width;
-    g.partial = g.scratch; g.n_slabs = kReduceGroups;
+    g.partial = g.scratch; g.n_slabs = kReduceGroups; g.n_slabs2 = 0; g.width2 = 0;
   }
   if (longs.n > 0) {
     hipLaunchKernelGGL(reduce_many_fold_kernel, dim3((unsigned)((long_width + 255) / 256), (unsigned)longs.n, kReduceGroups),

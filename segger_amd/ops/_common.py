@@ -57,8 +57,9 @@ def _has_specialised(heads: int, channels: int) -> bool:
 
 
 @functools.lru_cache(maxsize=4096)
-def _gat_bwd_ws_bytes(n_dst: int, heads: int, channels: int) -> int:
-    return int(_lib.load().segger_gatv2_bwd_workspace_bytes(n_dst, heads, channels))
+def _gat_bwd_ws_bytes(n_dst: int, n_src: int, n_edges: int, heads: int, channels: int) -> int:
+    """``n_src`` / ``n_edges``: of the by-source view the source pass walks; 0 for the one-pass form."""
+    return int(_lib.load().segger_gatv2_bwd_workspace_bytes_two_pass(n_dst, n_src, n_edges, heads, channels))
 
 
 @functools.lru_cache(maxsize=4096)

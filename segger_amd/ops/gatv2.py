@@ -162,7 +162,8 @@ def _gat_bwd_args(g: EdgeGraph, xl: Tensor, xr: Tensor, att: Tensor, bias: Optio
     a.grad_xr, a.ld_gxr = _rows(grad_xr, hc, "grad_xr")
     gparams = torch.empty((2, hc), dtype=torch.float32, device=dev)
     a.grad_att, a.grad_bias = gparams[0].data_ptr(), gparams[1].data_ptr()
-    ws_bytes = _gat_bwd_ws_bytes(n_dst, heads, channels)
+    two_pass = not a.src_unique
+    ws_bytes = _gat_bwd_ws_bytes(n_dst, g.n_src if two_pass else 0, g.n_edges if two_pass else 0, heads, channels)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
     _defer_keep(ws, gparams)
