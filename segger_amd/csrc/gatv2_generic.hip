@@ -236,13 +236,11 @@ __global__ __launch_bounds__(256) void gen_bwd_src_kernel(GenParams q) {
 }
 
 template <typename T>
-int launch_generic(int pass, const GenParams& q, hipStream_t stream) {
-  const int64_t nb = (q.g.n_rows + 3) / 4;
-  if (nb == 0) return SEGGER_OK;
-  if (nb > 0x7fffffffLL) { set_error("gatv2 (generic): too many rows"); return SEGGER_EUNSUPPORTED; }
-  dim3 grid((unsigned)nb), block(256);
-  if (pass == 0) hipLaunchKernelGGL((gen_fwd_kernel<T>), grid, block, 0, stream, q);
-  else if (pass == 1) hipLaunchKernelGGL((gen_bwd_dst_kernel<T>), grid, block, 0, stream, q);
+int launch_generic(Pass pass, const GenParams& q, hipStream_t stream) {
+  if (q.g.nblocks == 0) return SEGGER_OK;
+  dim3 grid((unsigned)q.g.nblocks), block(256);
+  if (pass == Pass::Fwd) hipLaunchKernelGGL((gen_fwd_kernel<T>), grid, block, 0, stream, q);
+  else if (pass == Pass::BwdDst) hipLaunchKernelGGL((gen_bwd_dst_kernel<T>), grid, block, 0, stream, q);
   else hipLaunchKernelGGL((gen_bwd_src_kernel<T>), grid, block, 0, stream, q);
   SEGGER_LAUNCH_CHECK("gatv2 generic kernel");
   return SEGGER_OK;
@@ -257,15 +255,15 @@ bool gatv2_has_specialised(int heads, int channels) {
   return false;
 }
 
-// pass: 0 fwd, 1 bwd-dst (grad_att / grad_bias zero-filled here, then atomically accumulated), 2 bwd-src
-int gatv2_launch_generic(int pass, GatParams& p, int dtype, int heads, int channels, float* grad_att, float* grad_bias,
+// p.nblocks: blocks of four rows (gatv2_grid, one row per wave)
+int gatv2_launch_generic(Pass pass, const GatParams& p, int dtype, int heads, int channels, float* grad_att, float* grad_bias,
                          hipStream_t stream) {
   if (channels > 64 * kMaxCPL) {
     set_error("gatv2: channels=%d exceeds the generic kernel's limit of %d", channels, 64 * kMaxCPL);
     return SEGGER_EUNSUPPORTED;
   }
   GenParams q{p, heads, channels, grad_att, grad_bias};
-  if (pass == 1) {
+  if (pass == Pass::BwdDst) {
     SEGGER_HIP(hipMemsetAsync(grad_att, 0, (size_t)heads * channels * sizeof(float), stream));
     if (grad_bias) SEGGER_HIP(hipMemsetAsync(grad_bias, 0, (size_t)heads * channels * sizeof(float), stream));
   }

@@ -22,9 +22,16 @@
 #define INST_KERNEL gatv2_bwd_src_kernel
 #define INST_PN bwd_src
 #endif
-#define INST_CAT2(a, b, c) gatv2_launch_##a##_##b
-#define INST_CAT(a, b) INST_CAT2(a, b, )
+#define INST_CAT2(a, b) gatv2_launch_##a##_##b
+#define INST_CAT(a, b) INST_CAT2(a, b)
 #define INST_NAME INST_CAT(INST_PN, INST_TN)
+#if SEGGER_INST_PASS == 0
+#define INST_PAIR_KERNEL gatv2_fwd_pair_kernel
+#define INST_PAIR_NAME INST_CAT(fwd_pair, INST_TN)
+#elif SEGGER_INST_PASS == 2
+#define INST_PAIR_KERNEL gatv2_bwd_src_dst_pair_kernel
+#define INST_PAIR_NAME INST_CAT(bwd_src_dst_pair, INST_TN)
+#endif
 
 namespace segger {
 namespace {
@@ -50,8 +57,9 @@ namespace {
   do {                                                                                                             \
     static void* scratch = nullptr; static int64_t scratch_rows = 0;                                               \
     if (scratch_rows < p.n_rows) { (void)hipMalloc(&scratch, (size_t)p.n_rows * 3 * H * LPH * 8 * 4); scratch_rows = p.n_rows; } \
-    p.gxl = scratch; p.ld_gxl = 3 * H * LPH * 8;                                                                   \
-    hipLaunchKernelGGL((INST_KERNEL<INST_T, H, LPH, WPR>), dim3((unsigned)(EXP_GRID)), dim3(256), 0, stream, p);  \
+    GatParams q = p;                                                                                               \
+    q.gxl = scratch; q.ld_gxl = 3 * H * LPH * 8;                                                                   \
+    hipLaunchKernelGGL((INST_KERNEL<INST_T, H, LPH, WPR>), dim3((unsigned)(EXP_GRID)), dim3(256), 0, stream, q);  \
   } while (0)
 #elif SEGGER_INST_PASS == 0 && SEGGER_INST_DTYPE != 0
 // 16-bit forward: the LDS-gather kernel where the view carries block tables (flagship geometry, no attention output)
@@ -71,92 +79,49 @@ namespace {
 #endif
 
 template <int H, int LPH, bool WPR>
-int launch_one(GatParams& p, hipStream_t stream) {
-  using G = Geo<H, LPH>;
-  const int64_t rows_per_wave = WPR ? 1 : G::NG;
-  const int iters = (SEGGER_INST_PASS == 1) ? p.rows_per_wave_iter : 1;
-  const int64_t rows_per_block = 4 * rows_per_wave * iters;
-  p.nblocks = (p.n_rows + rows_per_block - 1) / rows_per_block;
-  p.nblocks_padded = pad_to_xcd(p.nblocks);
+int launch_one(const GatParams& p, hipStream_t stream) {
   if (p.nblocks == 0) return SEGGER_OK;
-  if (p.nblocks_padded > 0x7fffffffLL) {
-    set_error("gatv2: %lld rows need more than 2^31 blocks", (long long)p.n_rows);
-    return SEGGER_EUNSUPPORTED;
-  }
   INST_LAUNCH(H, LPH, WPR);
   SEGGER_LAUNCH_CHECK("gatv2 kernel launch");
   return SEGGER_OK;
 }
 
-#if SEGGER_INST_PASS == 0
+#ifdef INST_PAIR_KERNEL
+// b's blocks come first: b.nblocks_padded is a multiple of the XCD count, so both block maps stay XCD-contiguous
 template <int H, int LPH>
-int launch_pair(GatParams& a, GatParams& b, hipStream_t stream) {
-  using G = Geo<H, LPH>;
-  a.nblocks = (a.n_rows + 4 * G::NG - 1) / (4 * G::NG);           // group-per-row
-  b.nblocks = (b.n_rows + 3) / 4;                                   // wave-per-row
-  a.nblocks_padded = pad_to_xcd(a.nblocks);
-  b.nblocks_padded = pad_to_xcd(b.nblocks);
+int launch_pair(const GatParams& a, const GatParams& b, hipStream_t stream) {
   const int64_t grid = a.nblocks_padded + b.nblocks_padded;
   if (grid == 0) return SEGGER_OK;
-  if (grid > 0x7fffffffLL) { set_error("gatv2: too many blocks"); return SEGGER_EUNSUPPORTED; }
-  hipLaunchKernelGGL((gatv2_fwd_pair_kernel<INST_T, H, LPH>), dim3((unsigned)grid), dim3(256), 0, stream, a, b);
+  hipLaunchKernelGGL((INST_PAIR_KERNEL<INST_T, H, LPH>), dim3((unsigned)grid), dim3(256), 0, stream, a, b);
   SEGGER_LAUNCH_CHECK("gatv2 pair launch");
   return SEGGER_OK;
 }
 #endif
 
+int no_instance(int heads, int channels) {
+  set_error("gatv2: heads=%d channels=%d has no specialised kernel (supported: channels in {32,64}, heads in {1,2,3,4})",
+            heads, channels);
+  return SEGGER_EUNSUPPORTED;
+}
+
 }  // namespace
 
-#if SEGGER_INST_PASS == 2
-namespace {
-template <int H, int LPH>
-int launch_src_dst_pair(GatParams& a, GatParams& b, hipStream_t stream) {
-  using G = Geo<H, LPH>;
-  a.nblocks = (a.n_rows + 4 * G::NG - 1) / (4 * G::NG);           // source pass, group-per-row, one row batch per wave
-  const int64_t per_b = 4 * (int64_t)b.rows_per_wave_iter;        // one-pass destination pass, wave-per-row
-  b.nblocks = (b.n_rows + per_b - 1) / per_b;
-  a.nblocks_padded = pad_to_xcd(a.nblocks);
-  b.nblocks_padded = pad_to_xcd(b.nblocks);
-  const int64_t grid = a.nblocks_padded + b.nblocks_padded;
-  if (grid == 0) return SEGGER_OK;
-  if (grid > 0x7fffffffLL) { set_error("gatv2: too many blocks"); return SEGGER_EUNSUPPORTED; }
-  hipLaunchKernelGGL((gatv2_bwd_src_dst_pair_kernel<INST_T, H, LPH>), dim3((unsigned)grid), dim3(256), 0, stream, a, b);
-  SEGGER_LAUNCH_CHECK("gatv2 backward pair launch");
-  return SEGGER_OK;
-}
-}  // namespace
-#define INST_BPAIR_CAT2(a) gatv2_launch_bwd_src_dst_pair_##a
-#define INST_BPAIR_CAT(a) INST_BPAIR_CAT2(a)
-int INST_BPAIR_CAT(INST_TN)(GatParams& a, GatParams& b, int heads, int channels, hipStream_t stream) {
-#define X(H, LPH) if (heads == H && channels == LPH * 8) return launch_src_dst_pair<H, LPH>(a, b, stream);
+#ifdef INST_PAIR_KERNEL
+int INST_PAIR_NAME(const GatParams& a, const GatParams* b, int heads, int channels, bool, hipStream_t stream) {
+#define X(H, LPH) if (heads == H && channels == LPH * 8) return launch_pair<H, LPH>(a, *b, stream);
   SEGGER_GEOMETRIES(X)
 #undef X
-  set_error("gatv2: heads=%d channels=%d has no specialised kernel", heads, channels);
-  return SEGGER_EUNSUPPORTED;
+  return no_instance(heads, channels);
 }
 #endif
 
-#if SEGGER_INST_PASS == 0
-#define INST_PAIR_CAT2(a) gatv2_launch_fwd_pair_##a
-#define INST_PAIR_CAT(a) INST_PAIR_CAT2(a)
-int INST_PAIR_CAT(INST_TN)(GatParams& a, GatParams& b, int heads, int channels, hipStream_t stream) {
-#define X(H, LPH) if (heads == H && channels == LPH * 8) return launch_pair<H, LPH>(a, b, stream);
-  SEGGER_GEOMETRIES(X)
-#undef X
-  set_error("gatv2: heads=%d channels=%d has no specialised kernel", heads, channels);
-  return SEGGER_EUNSUPPORTED;
-}
-#endif
-
-int INST_NAME(GatParams& p, int heads, int channels, bool wpr, hipStream_t stream) {
+int INST_NAME(const GatParams& p, const GatParams*, int heads, int channels, bool wpr, hipStream_t stream) {
 #define X(H, LPH)                                      \
   if (heads == H && channels == LPH * 8)               \
     return wpr ? launch_one<H, LPH, true>(p, stream) : launch_one<H, LPH, false>(p, stream);
   SEGGER_GEOMETRIES(X)
 #undef X
-  set_error("gatv2: heads=%d channels=%d has no specialised kernel (supported: channels in {32,64}, heads in {1,2,3,4})",
-            heads, channels);
-  return SEGGER_EUNSUPPORTED;
+  return no_instance(heads, channels);
 }
 
 }  // namespace segger

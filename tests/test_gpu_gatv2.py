@@ -607,3 +607,68 @@ def test_lds_gather_forward_is_bit_identical(cuda, dtype):
     gw = build_edge_graph(wide, 4000, 16)
     gw.by_dst.block_tables()
     assert gw.by_dst.tables is None
+
+
+def _exact_workspace_cases(route):
+    """(n_src, n_dst, edge_index, unique sources) of one route of the (2, 64) backward"""
+    g = torch.Generator().manual_seed(11)
+    if route == "group_per_row":                       # average degree below 32 in both views
+        for n_dst in (1, 15, 16, 17, 33):
+            for n_src in (1, 15, 16, 17, 33):
+                e = min(31 * min(n_dst, n_src), 2 * max(n_dst, n_src))
+                yield n_src, n_dst, random_graph(n_src, n_dst, e, seed=n_dst * 64 + n_src, isolated=False), False
+    elif route == "wave_per_row":                      # average source degree exactly 32: four source rows per block
+        for n_src in (3, 4, 5):
+            src = torch.arange(n_src).repeat(32)
+            yield n_src, 7, torch.stack([src, torch.randint(0, 7, (32 * n_src,), generator=g)]), False
+    elif route == "one_pass":                          # unique sources: the destination pass alone, no source slab
+        for n_dst, e in ((1, 5), (17, 40), (33, 2000)):
+            src = torch.randperm(e + 3, generator=g)[:e]
+            yield e + 3, n_dst, torch.stack([src, torch.randint(0, n_dst, (e,), generator=g)]), True
+    else:                                              # 65536 destinations: the first size at which a wave walks two row batches
+        yield 65536, 65536, random_graph(65536, 65536, 131072, seed=5), False
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("route", ["group_per_row", "wave_per_row", "one_pass", "two_row_batches"])
+def test_backward_workspace_is_exactly_as_large_as_stated(cuda, dtype, route):
+    """segger_gatv2_bwd through the raw ABI with the workspace at exactly segger_gatv2_bwd_workspace_bytes[_two_pass] bytes,
+    between two guard regions of a sentinel byte: the guards stay intact (the kernels write one slab row per block and the
+    reduction reads them back, so the stated size has to cover every block of both passes), and grad_att / grad_bias equal,
+    bit for bit, those of the same call with eight times the workspace (the order of the sums does not depend on capacity)."""
+    import ctypes
+    from segger_amd import _lib, ops
+    from segger_amd.graph import build_edge_graph
+    from segger_amd.ops.gatv2 import _gat_bwd_args
+    H, C, GUARD, MARK = 2, 64, 1 << 16, 0xA5
+    hc, lib = H * C, _lib.load()
+    gen = torch.Generator().manual_seed(3)
+    for n_src, n_dst, ei, unique in _exact_workspace_cases(route):
+        who = (route, n_src, n_dst)
+        graph = build_edge_graph(ei.to(cuda), n_src, n_dst, need_by_src="lazy" if unique else True)
+        xl, xr, gy = (torch.randn(n, hc, generator=gen).to(dtype).to(cuda) for n in (n_src, n_dst, n_dst))
+        att, bias = (torch.randn(hc, generator=gen).to(cuda) * 0.3 for _ in range(2))
+        out, lse = torch.empty(n_dst, hc, dtype=dtype, device=cuda), torch.empty(n_dst, H, device=cuda)
+        pre = torch.empty_like(out)
+        ops.gatv2_fwd_launch(graph.by_dst, xl, xr, att, bias, H, C, out, pre=pre, lse=lse, apply_gelu=True)
+        results = []
+        for factor in (1, 8):
+            gxl, gxr = torch.empty_like(xl), torch.empty_like(xr)
+            a, gparams, keep, _ = _gat_bwd_args(graph, xl, xr, att, bias, H, C, gy, pre, lse, gxl, gxr, apply_gelu=True)
+            assert bool(a.src_unique) == unique, who
+            if unique:
+                stated = lib.segger_gatv2_bwd_workspace_bytes(n_dst, H, C)
+            else:
+                stated = lib.segger_gatv2_bwd_workspace_bytes_two_pass(n_dst, n_src, int(ei.shape[1]), H, C)
+            size = stated * factor
+            buf = torch.full((GUARD + size + GUARD,), MARK, dtype=torch.uint8, device=cuda)
+            a.workspace, a.workspace_bytes = buf.data_ptr() + GUARD, size
+            with _lib.on_device(cuda):
+                rc = lib.segger_gatv2_bwd(ctypes.byref(a), _lib.stream_ptr(cuda))
+            _lib.check(rc, "segger_gatv2_bwd")
+            torch.cuda.synchronize()
+            assert bool((buf[:GUARD] == MARK).all()) and bool((buf[GUARD + size:] == MARK).all()), (who, factor)
+            results.append((gparams.clone(), gxl, gxr))
+        for exact, roomy in zip(*results):
+            assert torch.equal(exact, roomy), who
+        assert bool(torch.isfinite(results[0][0]).all()), who
