@@ -998,7 +998,8 @@ int segger_colsum(const void* x, int64_t ld, int64_t n, int32_t cols, int32_t dt
  *   grid: origin (x0,y0), square cells of side `cell`, nx x ny cells (points outside are
  *   clamped into the border cells, so any grid is valid; the host picks ~2 points per cell);
  *   nbr [m,k] int32: neighbour ids sorted by distance, padded with n (scipy's convention);
- *   dist [m,k] fp32 or NULL: distances, +inf for padding;  1 <= k <= 64; max_dist may be +inf.
+ *   dist [m,k] fp32 or NULL: distances, +inf for padding;  1 <= k <= 64; max_dist may be +inf and is a
+ *   strict bound, as scipy's is: a point at exactly max_dist (squared fp32 distances compared) is padding.
  * ---------------------------------------------------------------------- */
 size_t segger_knn_workspace_bytes(int64_t n_points, int32_t nx, int32_t ny);
 int segger_knn_grid(const float* points, int64_t n_points, const float* queries, int64_t n_queries, int32_t k,

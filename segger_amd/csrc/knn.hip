@@ -5,9 +5,25 @@
 //   1. bin every point into a cell of side `cell` (ids clamped to the nx x ny grid), radix-sort point
 //      ids by cell (rocPRIM), build cell_start[] and a cell-ordered copy of the coordinates;
 //   2. one thread per query walks square rings of cells around its own cell, keeping the k best
-//      candidates in a sorted register array.  After ring r every point within r*cell of the query has
-//      been seen (floor(a + r) - floor(a) = r), so the walk stops when the k-th distance <= r*cell,
-//      when r*cell >= max_dist, or when the ring has left the grid on all sides.
+//      candidates in a sorted register array.  With exact cell coordinates every point within r*cell of
+//      the query has been seen after ring r (floor(a + r) - floor(a) = r), so the walk could stop when
+//      the k-th distance <= r*cell, when r*cell >= max_dist, or when the ring has left the grid on all
+//      sides.  The cell coordinates are float32, so the walk stops at reach(r) = (r - slack)*cell:
+//
+//      A point's coordinate is t = fl(fl(p - x0) * fl(1/cell)): three roundings, so t = u (1 + e) with
+//      u = (p - x0)/cell and |e| <= 3 eps + O(eps^2), eps = 2^-24.  t is monotone in p, the cell is
+//      floor(t) clamped to [0, n - 1], and clamping moves cells no farther apart.  Take p <= q with
+//      u_q - u_p < r - slack.  If both t lie in [0, n], |u| <= n (1 + 4 eps) for both and
+//      t_q - t_p < r - slack + 6 eps n (1 + 4 eps), so the cells differ by at most r once
+//      slack >= 6 eps n (1 + 4 eps).  If t_q > n >= t_p (q clamps to n - 1), u_q > n (1 - eps) and the
+//      same sum bounds n - t_p; t_p < 0 <= t_q is the mirror image with |u_q| < r <= n, and if both lie
+//      outside on opposite sides r > n - 1 already.  The distances add their own roundings: cd = dx*dx +
+//      dy*dy is within 4 eps of the true square, reach*reach within 5 eps of its own, 4.5 eps of r
+//      together on the distance.  slack = 2^-20 max(nx, ny) = 16 eps max(nx, ny) covers both
+//      (6 + 4.5 < 16, r <= max(nx, ny)); it is 0.03 cells on the largest grid knn_grid makes (30001).
+//      A grid so large that slack >= r has reach 0 for that ring: the walk goes on, which is exact.
+// max_dist is a strict bound, as scipy's distance_upper_bound is: a candidate is kept when its squared
+// float32 distance is < max_dist^2, and a point at exactly max_dist is not a neighbour.
 // Output rows are sorted by distance; missing neighbours (fewer than k within max_dist) are padded with
 // index n_points and distance +inf, exactly like scipy.
 #include "common.h"
@@ -70,7 +86,7 @@ __global__ __launch_bounds__(128) void knn_query_kernel(const float* __restrict_
       const float2 p = sorted_pts[s];
       const float dx = p.x - qx, dy = p.y - qy;
       float cd = dx * dx + dy * dy;
-      if (cd <= max_d2 && cd < kth) {
+      if (cd < max_d2 && cd < kth) {
         int ci = perm[s];
 #pragma unroll
         for (int i = 0; i < K; ++i) {               // sorted insertion: bubble the displaced entry down
@@ -84,6 +100,7 @@ __global__ __launch_bounds__(128) void knn_query_kernel(const float* __restrict_
   };
 
   const int rmax = max(max(cx, g.nx - 1 - cx), max(cy, g.ny - 1 - cy));
+  const float slack = ldexpf((float)max(g.nx, g.ny), -20);   // float32 cell coordinates: see the header
   for (int r = 0; r <= rmax; ++r) {
     if (r == 0) {
       visit(cx, cy);
@@ -98,7 +115,7 @@ __global__ __launch_bounds__(128) void knn_query_kernel(const float* __restrict_
         if (x_hi < g.nx) visit(x_hi, y);
       }
     }
-    const float reach = (float)r * g.cell;           // every point within `reach` of the query has been seen
+    const float reach = fmaxf((float)r - slack, 0.f) * g.cell;   // every point within `reach` of the query has been seen
     const float reach2 = reach * reach;
     if (reach2 >= max_d2 || kth <= reach2) break;
   }

@@ -21,9 +21,24 @@ from torch import Tensor
 from . import _lib
 
 
+def grid_rule(x0: float, y0: float, x1: float, y1: float, n: int, max_dist: float = math.inf,
+              points_per_cell: float = 2.0) -> Tuple[float, int, int]:
+    """The grid :func:`knn_grid` bins ``n`` points of the bounding box ``[x0, x1] x [y0, y1]`` into (host arithmetic
+    only) -> ``(cell, nx, ny)``: about ``points_per_cell`` points per cell, a cell no wider than ``max_dist``, at most
+    ``4n + O(sqrt n)`` cells and at most 30001 cells along an axis."""
+    w, h = max(x1 - x0, 1e-6), max(y1 - y0, 1e-6)
+    cell = math.sqrt(w * h * points_per_cell / n)
+    if math.isfinite(max_dist):
+        cell = min(cell, max_dist)
+    cell = max(cell, math.sqrt(w * h / (4.0 * n)), max(w, h) / 30000.0)              # <= 4n cells, < 2^31 cells
+    return cell, int(w / cell) + 1, int(h / cell) + 1
+
+
 def knn_grid(points: Tensor, k: int, max_dist: float = math.inf, query: Optional[Tensor] = None,
              return_dist: bool = False, points_per_cell: float = 2.0) -> Tuple[Tensor, Optional[Tensor]]:
-    """Neighbour table ``[m, k]`` (int32; ids into ``points`` sorted by distance; ``len(points)`` = padding)."""
+    """Neighbour table ``[m, k]`` (int32; ids into ``points`` sorted by distance; ``len(points)`` = padding).
+    ``max_dist`` is a strict bound, as scipy's ``distance_upper_bound`` is: a point at exactly ``max_dist`` (in float32)
+    is not a neighbour."""
     _lib.require_cuda(points)
     dev = points.device
     pts = points.to(torch.float32).contiguous()
@@ -41,12 +56,7 @@ def knn_grid(points: Tensor, k: int, max_dist: float = math.inf, query: Optional
     both = pts if query is None else torch.cat([pts, q])
     lo, hi = both.min(0).values, both.max(0).values
     x0, y0, x1, y1 = (float(v) for v in torch.stack([lo, hi]).flatten().tolist())    # one host sync per graph
-    w, h = max(x1 - x0, 1e-6), max(y1 - y0, 1e-6)
-    cell = math.sqrt(w * h * points_per_cell / n)
-    if math.isfinite(max_dist):
-        cell = min(cell, max_dist)
-    cell = max(cell, math.sqrt(w * h / (4.0 * n)), max(w, h) / 30000.0)              # <= 4n cells, < 2^31 cells
-    nx, ny = int(w / cell) + 1, int(h / cell) + 1
+    cell, nx, ny = grid_rule(x0, y0, x1, y1, n, max_dist, points_per_cell)
     ws, ws_bytes = _lib.workspace("segger_knn_workspace_bytes", dev, n, nx, ny)
     _lib.call("segger_knn_grid", dev, pts.data_ptr(), n, None if query is None else q.data_ptr(), m, k, float(max_dist),
               x0, y0, cell, nx, ny, nbr.data_ptr(), _lib.ptr(dist), ws.data_ptr(), ws_bytes)

@@ -70,3 +70,58 @@ def test_knn_million_points_property(cuda):
     d = (pts[None, :, :] - pts[idx][:, None, :]).pow(2).sum(-1).sqrt()       # [64, 1M] brute force, exact differences
     ref = d.topk(15, largest=False).values
     assert torch.allclose(ref, dist[idx], atol=1e-3)
+
+
+# ---------------------------------------------------------------------------------------------- tests/knn_cases.py
+# Named inputs built against the kernel (exact ties at max_dist, points that float32 binning moves one ring out, every
+# capacity, degenerate sets, caller-chosen grids), each certified on the CPU (tests/test_knn_cases.py) and compared in
+# full, ties included, by the one checker knn_cases.check.
+import knn_cases as kc
+
+
+def run_case(case, cuda):
+    """The case through ``knn_grid``, or through the C entry point with the case's own grid exactly as ``knn_grid`` calls
+    it -> (nbr, dist or None) as numpy."""
+    from segger_amd import _lib
+    from segger_amd.neighbors import knn_grid
+    pts = torch.from_numpy(case["points"]).to(cuda)
+    qs = None if case["queries"] is None else torch.from_numpy(case["queries"]).to(cuda)
+    want_dist = case.get("dist", True)
+    if case["grid"] == "python":
+        nbr, dist = knn_grid(pts, case["k"], case["max_dist"], query=qs, return_dist=want_dist)
+    else:
+        x0, y0, cell, nx, ny = case["grid"]
+        n, m, k = len(pts), len(pts if qs is None else qs), case["k"]
+        nbr = torch.full((m, k), -7, dtype=torch.int32, device=cuda)
+        dist = torch.full((m, k), -7.0, dtype=torch.float32, device=cuda) if want_dist else None
+        ws, ws_bytes = _lib.workspace("segger_knn_workspace_bytes", cuda, n, nx, ny)
+        _lib.call("segger_knn_grid", cuda, pts.data_ptr(), n, _lib.ptr(qs), m, k, float(case["max_dist"]), x0, y0, cell, nx, ny,
+                  nbr.data_ptr(), _lib.ptr(dist), ws.data_ptr(), ws_bytes)
+    return nbr.cpu().numpy(), None if dist is None else dist.cpu().numpy()
+
+
+@pytest.mark.parametrize("name", kc.NAMES)
+def test_knn_case(cuda, name):
+    case = kc.all_cases()[name]
+    ref_d, _ = kc.reference_of(name)
+    nbr, dist = run_case(case, cuda)
+    kc.check(case, nbr, dist, ref_d)
+    if case.get("exact"):                                           # exact arithmetic: the answer is the reference's, bit for bit
+        assert np.array_equal(dist, ref_d.astype(np.float32))
+
+
+@pytest.mark.parametrize("max_dist,k", kc.LATTICE)
+def test_lattice_edge_counts(cuda, max_dist, k):
+    """The graphs built on the table have the edges of the strict bound: a neighbour at exactly max_dist is none."""
+    from segger_amd.neighbors import prediction_graph_uniform, transcripts_graph
+    name = f"lattice_strict_d{int(max_dist)}_k{k}"
+    pts = kc.all_cases()[name]["points"]
+    ref_d, ref_i = kc.reference_of(name)
+    tx = torch.from_numpy(pts).to(cuda)
+    ei = transcripts_graph(tx, k, max_dist)
+    assert ei.shape == (2, int(np.isfinite(ref_d).sum()))
+    assert torch.equal(ei[0].cpu(), torch.from_numpy(np.repeat(np.arange(144), np.isfinite(ref_d).sum(1))))
+    rows = np.arange(0, 144, 5)                                     # boundary centroids on lattice points: the same ties
+    ep = prediction_graph_uniform(tx, tx[torch.from_numpy(rows).to(cuda)], k, max_dist)
+    assert ep.shape == (2, int(np.isfinite(ref_d[rows]).sum()))
+    assert torch.equal(ep[0].cpu(), torch.from_numpy(np.repeat(np.arange(len(rows)), np.isfinite(ref_d[rows]).sum(1))))
