@@ -1620,8 +1620,8 @@ int segger_cell_boundaries(const double* xy /* [N, 2] */, const int32_t* cell, c
  *   ring     the component's rim walked with the interior on the left; then `smoothing` Chaikin iterations as above.
  *            shapely's buffer(0) after the smoothing, which can alter a smoothed concave ring that touches itself, is
  *            not reproduced.
- * A cell with more than SEGGER_OUTLINE_MAX_POINTS distinct points is refused (counters[6], [7]); larger cells would need
- * a global-memory route, which is not built.  Every loop is bounded before it is entered: at most 2 n - 5 triangles,
+ * A cell with more than SEGGER_OUTLINE_MAX_POINTS distinct points is refused (counters[6], [7]) by this entry point; the
+ * route through global memory for such cells is segger_cell_outlines_large below.  Every loop is bounded before it is entered: at most 2 n - 5 triangles,
  * 3 per triangle directed edges, rounds at most the triangle count, a ring walk of at most one step per directed edge;
  * a table that overflows or a walk past its bound -- possible only when rounded predicates contradict each other --
  * refuses the cell through counters[8], [9].
@@ -1638,6 +1638,57 @@ int segger_cell_outlines(const double* xy /* [N, 2] */, const int32_t* cell, con
                          int64_t n_rows, int64_t n_cells, double connectivity, int32_t smoothing, int64_t* ring_offsets,
                          double* xy_out, int64_t xy_capacity, int32_t* cell_ids, int64_t* n_transcripts,
                          uint64_t* counters, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Concave cell outlines with a route through global memory for large cells: segger_cell_outlines plus two arguments, the
+ * kernels behind segger_amd.boundaries.cell_outlines(large_cells="global"), csrc/outlines_large.hip.  Purely additive: two
+ * new symbols, SEGGER_ABI_VERSION stays 32; segger_cell_outlines keeps its signature, its behaviour and its messages.
+ *
+ *     lds_max_points  0 .. SEGGER_OUTLINE_MAX_POINTS: a cell with more distinct points than this leaves the LDS routes for
+ *                     the large route; 0 sends every cell there.  SEGGER_OUTLINE_MAX_POINTS is the value to pass; lower
+ *                     ones exist to test and to time the large route on small cells.
+ *     large_rows      0 .. n_rows: the caller's bound on the summed COUNTED ROWS (duplicates included) of the cells that
+ *                     take the large route -- every cell with more than lds_max_points counted rows is a safe choice.  It
+ *                     sizes the workspace.  A cell takes a slice of as many rows as it has with one atomic add when it is
+ *                     routed; when the slices handed out would exceed large_rows, or the cell has more than 2^28 rows
+ *                     (directed-edge ids and hash slots are 32-bit), the cell is refused through counters[6], [7] exactly
+ *                     as segger_cell_outlines refuses it: no polygon, nothing read or written outside a slice, the other
+ *                     cells unaffected.  Which cells are refused when large_rows is too small depends on the order in
+ *                     which they arrive, and a refusal cascades: the row counter only grows (rows given back under a
+ *                     slice handed out meanwhile would be handed out twice), so once one cell did not fit, every
+ *                     large cell that arrives after it in the call is refused as well, even one that would have
+ *                     fitted.  With a sufficient bound none is.
+ *     counters [SEGGER_OUTLINE_LARGE_COUNTERS] uint64: 0 .. 9 as for segger_cell_outlines (6, 7 now count what is still
+ *                     refused); 10 cells the large route handled, 11 their distinct points, 12 the rows of the slices
+ *                     handed out.
+ *
+ * A ring has the same bytes whichever route produced it: the large route runs the six stages above with the same orient2d,
+ * incircle and tie rule, the same seed, and adds a component's area in the same order.  It differs in how: one 256-thread
+ * workgroup per cell with the cell's state in its slice and 32-bit vertex, edge and triangle ids; the rows sorted in the
+ * slice by a bitonic network; the directed-edge hash open addressing over 8 slots per distinct point; and the apex search
+ * pruned -- the points are sorted by x and a better apex lies inside or on the circle through the edge and the best apex
+ * so far, so the search runs outward from the edge and stops at the circle's x-extent, computed with its rounding error
+ * added, so that a point on the circle is still seen.  The work per triangle is a chain of dependent reads of global
+ * memory: such a cell takes far longer than its share of an LDS cell's time (README has the figures), and the large
+ * kernel starts when the LDS kernels are done.
+ *
+ * Workspace: segger_cell_outlines_large_workspace_bytes(n_rows, n_cells, large_rows): with R = max(large_rows, 1)
+ *   segger_cell_outlines_workspace_bytes(n_rows, n_cells) + up(4 C) + up(8 C)                      the large list, its slices
+ *   + up(16 R) + up(R) + 2 up(24 R) + up(6 R) + up(8 R) + up(64 R) + up(32 R)                      175 bytes per row:
+ *   points, multiplicity flags, triangle vertices and twins (3 uint32 x 2 triangles each), predicate bits, labels, hash keys
+ *   and hash ids.  Monotone in large_rows.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: everything segger_cell_outlines rejects,
+ *   lds_max_points outside its range, large_rows negative or above n_rows.  n_rows = 0 returns SEGGER_OK as above.
+ * NOT BUILT: overlapping the large cells with the small ones (one stream, the kernels run one after another); a sort of
+ *   the rows that is not a bitonic network (O(n log^2 n) passes over the slice).
+ * ---------------------------------------------------------------------- */
+#define SEGGER_OUTLINE_LARGE_COUNTERS 13
+int64_t segger_cell_outlines_large_workspace_bytes(int64_t n_rows, int64_t n_cells, int64_t large_rows);
+int segger_cell_outlines_large(const double* xy /* [N, 2] */, const int32_t* cell, const uint8_t* keep /* or NULL */,
+                               int64_t n_rows, int64_t n_cells, double connectivity, int32_t smoothing,
+                               int64_t* ring_offsets, double* xy_out, int64_t xy_capacity, int32_t* cell_ids,
+                               int64_t* n_transcripts, uint64_t* counters, void* workspace, int64_t workspace_bytes,
+                               int32_t lds_max_points, int64_t large_rows, segger_stream_t stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

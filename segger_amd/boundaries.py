@@ -12,7 +12,8 @@ The reference's DEFAULT, ``method="delaunay"`` (``boundary.py:57-154``: the outl
 built as entry points of its own, :func:`cell_outlines` and :func:`segmentation_outlines` (``segger_cell_outlines``,
 csrc/outlines.hip; one single-wave workgroup owns one cell).  NOT BUILT: the ``method="delaunay"`` SPELLING on
 :func:`cell_boundaries`, which still raises ``NotImplementedError`` -- that function returns the convex outline that
-``segger export --method convex_hull`` writes; cells above ``SEGGER_OUTLINE_MAX_POINTS`` distinct points; GEOS's order
+``segger export --method convex_hull`` writes; cells above ``SEGGER_OUTLINE_MAX_POINTS`` distinct points unless
+``large_cells="global"`` is passed (a route through global memory, csrc/outlines_large.hip); GEOS's order
 among components of equal area; ``buffer(0)`` repairs of a smoothed concave ring.
 
 The rings come back as the ring CSR of :mod:`segger_amd.rings`, open (no closing duplicate), counter-clockwise from the
@@ -41,6 +42,8 @@ __all__ = ["cell_boundaries", "segmentation_boundaries", "cell_outlines", "segme
 METHODS = ("convex_hull", "delaunay")
 COUNTERS = ("n_counted", "n_present", "n_kept", "n_vertices", "n_bad_cell", "n_non_finite", "n_refused", "refused_cell")
 OUTLINE_COUNTER_NAMES = COUNTERS + ("n_failed", "failed_cell")
+LARGE_OUTLINE_COUNTER_NAMES = OUTLINE_COUNTER_NAMES + ("n_large_cells", "n_large_points", "n_large_rows")
+LARGE_CELLS = ("refuse", "global")
 MAX_ROWS = (1 << 31) - 2
 
 
@@ -199,7 +202,8 @@ def _segmented(who: str, fn, result, xy, n_cells, kw) -> Dict[str, Tensor]:
 
 
 def cell_outlines(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, keep: Optional[Tensor] = None,
-                  connectivity: float = 2.0, smoothing: int = 0) -> Dict[str, Tensor]:
+                  connectivity: float = 2.0, smoothing: int = 0, large_cells: str = "refuse",
+                  _lds_max_points: Optional[int] = None) -> Dict[str, Tensor]:
     """The concave outline of every cell: the reference's DEFAULT ``method="delaunay"`` (``_CellOutline``,
     ``boundary.py:57-154``) -- triangulate the cell's distinct transcripts, peel off the rim every triangle with a rim edge
     longer than ``2 * connectivity * d_max``, then every one with a rim edge that is long and faces an obtuse angle or
@@ -223,24 +227,57 @@ def cell_outlines(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, ke
     edge-connected piece, dangling edges ignored) rests on knowledge of the library.  The pruning itself is pinned to a
     run of the reference's ``_CellOutline.refine`` (tests/golden/outlines_small.npz).
 
+    ``large_cells`` says what happens to a cell with more than ``SEGGER_OUTLINE_MAX_POINTS`` = 2048 distinct points, the
+    LDS budget of one cell.  ``"refuse"`` (the default): the call raises and names the cell.  ``"global"``: such a cell
+    takes the route through global memory (``segger_cell_outlines_large``, csrc/outlines_large.hip: one workgroup per
+    cell, its state in a slice of the workspace, 175 bytes per row of the cell) and gets the ring it would get from the
+    LDS route, bit for bit; the call then costs one more wait for the device (a ``bincount`` sizes the slices by the rows
+    of the cells with more than 2048 kept rows), and such a cell takes far longer than a small one -- README has the
+    figures.  Still refused under ``"global"``: a single cell of more than 2^28 rows.  ``_lds_max_points`` (tests and
+    timing only) lowers the threshold; 0 sends every cell through global memory.
+
     Raises ``ValueError`` for bad shapes, dtypes or options and ``SeggerAmdError`` for a kept row with a cell id
-    ``>= n_cells`` or a non-finite coordinate, for a cell with more than ``SEGGER_OUTLINE_MAX_POINTS`` distinct points
-    (the cell is named; a route through global memory for such cells is not built), and for a cell whose triangulation
-    contradicted itself (rounded predicates on coordinates that share no grid can do that; the cell is named)."""
+    ``>= n_cells`` or a non-finite coordinate, for a cell that was refused as above (the cell is named), and for a cell
+    whose triangulation contradicted itself (rounded predicates on coordinates that share no grid can do that; the cell
+    is named)."""
     who = "cell_outlines"
     smoothing = _check_smoothing(who, smoothing)
     if isinstance(connectivity, bool) or not isinstance(connectivity, (int, float)) or not 0 < connectivity < float("inf"):
         raise ValueError(f"{who}: connectivity must be a finite number > 0, got {connectivity!r}")
+    if large_cells not in LARGE_CELLS:
+        raise ValueError(f"{who}: large_cells {large_cells!r} is neither 'refuse' nor 'global'")
+    if _lds_max_points is None:
+        _lds_max_points = L.OUTLINE_MAX_POINTS
+    if (isinstance(_lds_max_points, bool) or not isinstance(_lds_max_points, int) or not 0 <= _lds_max_points <= L.OUTLINE_MAX_POINTS
+            or (large_cells == "refuse" and _lds_max_points != L.OUTLINE_MAX_POINTS)):
+        raise ValueError(f"{who}: _lds_max_points must be an int in 0 .. {L.OUTLINE_MAX_POINTS}, and {L.OUTLINE_MAX_POINTS} unless "
+                         f"large_cells='global', got {_lds_max_points!r}")
     dev, pts, ids, mask, n, n_cells = _rows(who, xy, cell, n_cells, keep)
-    capacity, ring_offsets, out, cell_ids, n_tx, counters = _outputs(dev, n, n_cells, smoothing, L.OUTLINE_COUNTERS)
-    if n:
+    to_global = large_cells == "global"
+    names = LARGE_OUTLINE_COUNTER_NAMES if to_global else OUTLINE_COUNTER_NAMES
+    capacity, ring_offsets, out, cell_ids, n_tx, counters = _outputs(dev, n, n_cells, smoothing, len(names))
+    if n and to_global:
+        # the rows of the cells that can leave the LDS routes: plumbing, and one more wait for the device
+        ok = (ids >= 0) & (ids < n_cells) if mask is None else (ids >= 0) & (ids < n_cells) & (mask != 0)
+        per_cell = torch.bincount(ids[ok].long(), minlength=1)
+        large_rows = int(per_cell[per_cell > _lds_max_points].sum())
+        ws, ws_bytes = L.workspace("segger_cell_outlines_large_workspace_bytes", dev, n, n_cells, large_rows)
+        L.call("segger_cell_outlines_large", dev, pts.data_ptr(), ids.data_ptr(), L.ptr(mask), n, n_cells, float(connectivity),
+               smoothing, ring_offsets.data_ptr(), out.data_ptr(), capacity, cell_ids.data_ptr(), n_tx.data_ptr(),
+               counters.data_ptr(), ws.data_ptr(), ws_bytes, _lds_max_points, large_rows)
+        del ws
+    elif n:
         ws, ws_bytes = L.workspace("segger_cell_outlines_workspace_bytes", dev, n, n_cells)
         L.call("segger_cell_outlines", dev, pts.data_ptr(), ids.data_ptr(), L.ptr(mask), n, n_cells, float(connectivity), smoothing,
                ring_offsets.data_ptr(), out.data_ptr(), capacity, cell_ids.data_ptr(), n_tx.data_ptr(), counters.data_ptr(),
                ws.data_ptr(), ws_bytes)
         del ws
-    c = dict(zip(OUTLINE_COUNTER_NAMES, counters.tolist()))       # the one wait for the device
+    c = dict(zip(names, counters.tolist()))                       # the one wait for the device
     _raise_for_rows(who, c, n_cells)
+    if c["n_refused"] and to_global:
+        raise L.SeggerAmdError(f"{who}: {c['n_refused']} cells were refused by the global-memory route (a cell of more than 2^28 "
+                               f"rows, or slices beyond the {large_rows} rows sized for), cell {c['refused_cell'] - 1} among them; "
+                               f"such a cell gets no polygon")
     if c["n_refused"]:
         raise L.SeggerAmdError(f"{who}: {c['n_refused']} cells have more than {L.OUTLINE_MAX_POINTS} distinct points "
                                f"(SEGGER_OUTLINE_MAX_POINTS, the LDS budget of one cell), cell {c['refused_cell'] - 1} among "
@@ -253,5 +290,5 @@ def cell_outlines(xy: Tensor, cell: Tensor, n_cells: Optional[int] = None, *, ke
 
 def segmentation_outlines(result: Dict[str, Tensor], xy: Tensor, n_cells: Optional[int] = None, **kw) -> Dict[str, Tensor]:
     """:func:`cell_outlines` of the segmented transcripts of ``result``, chosen by the rule of
-    :func:`segmentation_boundaries`; ``kw`` is ``connectivity`` and ``smoothing``."""
+    :func:`segmentation_boundaries`; ``kw`` is ``connectivity``, ``smoothing`` and ``large_cells``."""
     return _segmented("segmentation_outlines", cell_outlines, result, xy, n_cells, kw)

@@ -344,7 +344,8 @@ class SegmentationAccumulator:
 
     def outlines(self, xy: Tensor, max_iter: int = 250, thresholds: str = "torch", **kw) -> Dict[str, Tensor]:
         """``segmentation_outlines(self.segmentation(max_iter, thresholds), xy, **kw)``: the concave outline per cell, the
-        reference's default ``method="delaunay"`` (:func:`segger_amd.boundaries.cell_outlines`)."""
+        reference's default ``method="delaunay"`` (:func:`segger_amd.boundaries.cell_outlines`; ``kw`` is its ``connectivity``,
+        ``smoothing`` and ``large_cells``)."""
         from .boundaries import segmentation_outlines
         return segmentation_outlines(self.segmentation(max_iter, thresholds), xy, **kw)
 
