@@ -1690,6 +1690,69 @@ int segger_cell_outlines_large(const double* xy /* [N, 2] */, const int32_t* cel
                                int64_t* n_transcripts, uint64_t* counters, void* workspace, int64_t workspace_bytes,
                                int32_t lds_max_points, int64_t large_rows, segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Boundary polygons from a label image: per label the border with the most vertices, as a ring CSR -- the reference's
+ * masks_to_contours (src/segger/io/utils.py:8-41: per label a regionprops crop, cv2.findContours(RETR_LIST,
+ * CHAIN_APPROX_SIMPLE), the contour with the most vertices, dropped with <= 2) as its CosMx intake drives it
+ * (src/segger/io/cosmx.py:79-107).  The kernels behind segger_amd.contours.label_contours, csrc/contours.hip.  Purely
+ * additive: two new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ *     labels        [height, width] int32, row = y, column = x, 0 = background, every value in 0 .. max_label.
+ *     compartment   NULL, or [height, width] uint8: a pixel counts as its label only if bit `code` of the 256-bit set
+ *                   valid0 .. valid3 (bit c of word c / 64) is set -- np.where(np.isin(compartment, codes), labels, 0)
+ *                   fused into the read; no masked image is written.
+ *     max_label     0 .. SEGGER_CONTOUR_MAX_LABEL: sizes five int32 tables.  Ids may be sparse.
+ *     scale, trans  a vertex (x, y) is written as (x * scale_x + trans_x, y * scale_y + trans_y), one multiplication and
+ *                   one addition in fp64, not fused; the integer coordinates are exact before it.
+ *     ring_offsets  [C + 1] int64, label_ids [C] int32, n_pixels [C] int64 with C = max(min(max_label, height * width), 1):
+ *                   the kept labels ascending, the masked pixel count of each.  Entries past the kept count are untouched.
+ *     xy_out        [xy_capacity, 2] fp64.  A vertex at or past xy_capacity is not written; counters[8] says so and
+ *                   counters[2] is the capacity that suffices.  ring_offsets is complete either way.
+ *     counters      [SEGGER_CONTOUR_COUNTERS] uint64: 0 labels present, 1 labels kept, 2 vertices, 3 labels dropped for
+ *                   <= 2 points, 4 borders traced, 5 the longest ring, 6 labels whose winner shared its count with another
+ *                   border (ties broken), 7 pixels with a label outside 0 .. max_label (they count as background), 8 the
+ *                   overflow word: 1 when vertices > xy_capacity, 9 labels that took the global route.
+ *
+ * The result, exactly.  The foreground of label L is {labels == L} after the mask.  Its borders are those of Suzuki and
+ * Abe's border following with 8-connected foreground: every outer and every hole border of every 8-connected component, each
+ * a closed chain of border pixels.  The reference hands cv2 the transposed crop, so the raster scan is x-major (cv rows are
+ * x, cv columns are y) and that order is used wherever an order matters.  CHAIN_APPROX_SIMPLE: a chain point is kept iff
+ * the step into it differs from the step out of it, cyclically -- the tip of a one-pixel spur is kept, the pixels of the
+ * spur appear twice in the chain, an isolated pixel is one point.  Per label the border with the most kept points wins,
+ * hole borders included; among equal counts the one whose canonical start is smallest in the scan order (UNPINNED: the
+ * reference takes the last in cv2's list order, which is not known here).  A label whose winner has <= 2 points is
+ * dropped.  A ring starts at the border's first pixel in the x-major scan -- of the visits to that pixel the one whose
+ * previous pixel comes first clockwise from "y - 1" -- and runs in the direction border following gives; it is open (no
+ * closing duplicate) and may be longer than SEGGER_MORPH_MAX_VERTS: the CSR has no cap, the downstream units refuse such
+ * a ring themselves.  UNPINNED: cv2 was never run; for an outer border this start is believed to be cv2's.
+ * The same bytes from run to run, for any launch geometry and on either route: nothing floating-point happens before the
+ * final conversion, and the atomics are integer min, max and add.
+ *
+ *     lds_max_bits  0 .. SEGGER_CONTOUR_LDS_BITS: a label whose crop, rows padded to 32 columns, has at most this many bits
+ *                   is traced over a bit mask in LDS; a larger one over the image in global memory (slow: every probe is
+ *                   a read of the image).  SEGGER_CONTOUR_LDS_BITS is the value to pass; 0 sends every label there.
+ *
+ * Workspace: segger_label_contours_workspace_bytes(height, width, max_label), 256-byte aligned: with up(x) = x rounded up
+ *   to 256 and C as above:  5 up(4 (max_label + 1)) + 6 up(4 C) + the storage of the compaction.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative height or width, height * width >= 2^31,
+ *   max_label outside 0 .. SEGGER_CONTOUR_MAX_LABEL, lds_max_bits outside its range, a scale or translation that is not
+ *   finite, negative workspace_bytes or xy_capacity, NULL or misaligned pointers, a workspace that is too small.
+ *   height * width = 0 or max_label = 0 returns SEGGER_OK and launches nothing: the caller's zeroed counters and
+ *   ring_offsets[0] stand.
+ * NOT BUILT: the reference's simplify(tolerance) (GEOS's topology-preserving simplifier), TIFF reading,
+ *   fix_invalid_geometry, the id strings, FOV stitching.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_CONTOUR_MAX_LABEL (1 << 24)  /* five int32 tables of max_label + 1 entries: 320 MB at the cap */
+#define SEGGER_CONTOUR_LDS_BITS 32768       /* 4 KB of LDS per single-wave workgroup: 32 of them fit a CU */
+#define SEGGER_CONTOUR_COUNTERS 10
+int64_t segger_label_contours_workspace_bytes(int64_t height, int64_t width, int64_t max_label);
+int segger_label_contours(const int32_t* labels /* [H, W] */, const uint8_t* compartment /* [H, W] or NULL */,
+                          uint64_t valid0, uint64_t valid1, uint64_t valid2, uint64_t valid3, int64_t height,
+                          int64_t width, int64_t max_label, double scale_x, double scale_y, double trans_x,
+                          double trans_y, int64_t* ring_offsets, double* xy_out, int64_t xy_capacity, int32_t* label_ids,
+                          int64_t* n_pixels, uint64_t* counters, void* workspace, int64_t workspace_bytes,
+                          int32_t lds_max_bits, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -22,5 +22,7 @@ from .neighbors import prediction_graph_shape  # noqa: F401
 from . import boundaries  # noqa: F401
 from .boundaries import cell_boundaries, segmentation_boundaries  # noqa: F401
 from .boundaries import cell_outlines, segmentation_outlines  # noqa: F401
+from . import contours  # noqa: F401
+from .contours import label_contours  # noqa: F401
 
 __version__ = "0.1.0"

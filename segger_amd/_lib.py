@@ -27,6 +27,7 @@ PJOIN_ERR_OFFSETS, PJOIN_ERR_CAP, PJOIN_ERR_BUFFER, PJOIN_ERR_FILL = 1, 2, 4, 8
 BOUNDARY_MAX_SMOOTHING, BOUNDARY_CHUNK_MAX_HULL, BOUNDARY_COUNTERS = 6, 2048, 8                       # SEGGER_BOUNDARY_*
 OUTLINE_MAX_POINTS, OUTLINE_COUNTERS = 2048, 10                                                        # SEGGER_OUTLINE_*
 OUTLINE_LARGE_COUNTERS = 13
+CONTOUR_MAX_LABEL, CONTOUR_LDS_BITS, CONTOUR_COUNTERS = 1 << 24, 32768, 10                             # SEGGER_CONTOUR_*
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -380,6 +381,10 @@ EXPORTS = {
     "segger_cell_outlines_large_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "segger_cell_outlines_large": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int32, vp, vp, C.c_int64, vp, vp, vp,
                                              vp, C.c_int64, C.c_int32, C.c_int64, vp]),
+    "segger_label_contours_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "segger_label_contours": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64,
+                                        C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, C.c_int64, vp, vp, vp, vp,
+                                        C.c_int64, C.c_int32, vp]),
 }
 
 _lib: Optional[C.CDLL] = None
