@@ -1739,8 +1739,8 @@ int segger_cell_outlines_large(const double* xy /* [N, 2] */, const int32_t* cel
  *   finite, negative workspace_bytes or xy_capacity, NULL or misaligned pointers, a workspace that is too small.
  *   height * width = 0 or max_label = 0 returns SEGGER_OK and launches nothing: the caller's zeroed counters and
  *   ring_offsets[0] stand.
- * NOT BUILT: the reference's simplify(tolerance) (GEOS's topology-preserving simplifier), TIFF reading,
- *   fix_invalid_geometry, the id strings, FOV stitching.
+ * The reference's simplify(tolerance) and is_valid that follow are segger_simplify_rings_* and segger_rings_simple below.
+ * NOT BUILT: TIFF reading, the repairs of fix_invalid_geometry, the id strings, FOV stitching.
  * ---------------------------------------------------------------------- */
 #define SEGGER_CONTOUR_MAX_LABEL (1 << 24)  /* five int32 tables of max_label + 1 entries: 320 MB at the cap */
 #define SEGGER_CONTOUR_LDS_BITS 32768       /* 4 KB of LDS per single-wave workgroup: 32 of them fit a CU */
@@ -1752,6 +1752,97 @@ int segger_label_contours(const int32_t* labels /* [H, W] */, const uint8_t* com
                           double trans_y, int64_t* ring_offsets, double* xy_out, int64_t xy_capacity, int32_t* label_ids,
                           int64_t* n_pixels, uint64_t* counters, void* workspace, int64_t workspace_bytes,
                           int32_t lds_max_bits, segger_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Ring simplification and validity on a ring CSR: what the reference's CosMx intake does right after masks_to_contours,
+ * `geometry.simplify(tolerance)` (src/segger/io/cosmx.py:94-96, GEOS's topology-preserving simplifier, per polygon), and
+ * the `is_valid` that fix_invalid_geometry asks first (io/utils.py:127-136; io/preprocessor.py:472).  The kernels behind
+ * segger_amd.simplify.simplify_rings / rings_simple, csrc/simplify.hip.  Purely additive: four new symbols,
+ * SEGGER_ABI_VERSION stays 32.
+ *
+ * The arithmetic.  A ring is xy[off[p] .. off[p + 1]) as segger_polygon_props takes it: either orientation, a closing
+ * duplicate of its first vertex dropped bit for bit, n open vertices v_0 .. v_(n-1), index n meaning v_0.  Everything is
+ * fp64 on the ring translated to its first vertex (v_k = xy_k - xy_0, one subtraction) before any product, no FMA
+ * contraction.  Coordinates are finite.
+ *   dist2(v; a, b), the squared distance from v to the closed segment (a, b), is segger_polygon_join_*'s, in its order:
+ *     e = b - a, w = v - a, cr = e.x w.y - e.y w.x, dot = w.x e.x + w.y e.y, len2 = e.x e.x + e.y e.y;
+ *     dist2 = w.x w.x + w.y w.y if dot <= 0 or len2 == 0;  |v - b|^2 (the same form) if dot >= len2;  cr cr / len2 otherwise.
+ *   orient(a, b, c) is the sign of (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x) as computed.
+ *   touch(s, t) of two closed segments s = (a, b), t = (c, d): true when they share a point, unless what they share is a
+ *     single point that is an endpoint of both.  A collinear overlap longer than a point is a touch, an endpoint in the
+ *     other segment's interior is a touch, a zero-length segment is a point.  As computed, without a division:
+ *       o1 = orient(a, b, c), o2 = orient(a, b, d), o3 = orient(c, d, a), o4 = orient(c, d, b);
+ *       in(o, p; q, r) = o == 0, p within the coordinate intervals of q and r, p != q and p != r;
+ *       touch = (o1 o2 < 0 and o3 o4 < 0) or in(o1, c; a, b) or in(o2, d; a, b) or in(o3, a; c, d) or in(o4, b; c, d)
+ *               or (a != b and {a, b} == {c, d}).
+ *     With coordinates whose translated differences are integers below 2^26 every orient is exact and touch is the
+ *     geometric statement.
+ *
+ * segger_simplify_rings_*: Douglas-Peucker over the closed sequence v_0 .. v_(n-1), v_0 of a ring of n >= 3 -- n input
+ * edges e_k = (v_k, v_(k+1)), root section (0, n) -- depth first, left before right.  A section (i, j) with j == i + 1
+ * emits its input edge.  Otherwise m is the interior index with the largest dist2(v_k; v_i, v_j), the lowest index among
+ * equals, and the section is FLATTENED (the chord (v_i, v_j) is emitted, the interior dropped) iff
+ *   (a) dist2(v_m; v_i, v_j) <= tol * tol, and
+ *   (b) with preserve_topology: the chord touches no input edge outside the section (e_k, k < i or k >= j) and no chord
+ *       emitted so far -- which, the walk being left first, are exactly the consecutive pairs of the kept vertices with
+ *       index <= i;
+ * otherwise it is split at m.  Vertex 0 is always kept; the kept vertices are the section ends.  The chord back over an
+ * emitted chord is a touch and is refused, so after a split of the root at least three vertices stay and no minimum-size
+ * rule is needed; without preserve_topology (b) is dropped and this is the classical algorithm.  In either mode a ring that
+ * comes out with fewer than 3 vertices -- with the guard only when the root itself is flattened, every vertex within tol of
+ * v_0 and nothing yet to touch -- is returned as it went in and counted.  A ring of fewer than 3 open vertices passes
+ * through.  Output rings are open: the n open vertices of a ring passed through or restored, the kept ones otherwise, as
+ * the INPUT's bytes (untranslated), with the index into xy of each.
+ *
+ * UNPINNED.  GEOS could not be run where this was written and the reference was never run.  GEOS's
+ * TopologyPreservingSimplifier has this structure (farthest point; a candidate segment refused when it has an interior
+ * intersection with input or output segments; depth-first recursion); three of its details are NOT reproduced and may
+ * differ between GEOS versions: its minimum-size rule at shallow depth, its optional removal of the ring's endpoint, and
+ * its "jump" check.  Its output may therefore differ from this one in single vertices.  Downstream code accepts any start.
+ *
+ *   _mark     tolerance: fp64 on the device, finite and >= 0; tolerance_stride 0 = one value for all, 1 = one per polygon.
+ *             small_max_verts 0 .. SEGGER_SIMPLIFY_SMALL_VERTS: a ring of at most this many vertices runs in the small
+ *             LDS tier (4864 B per single-wave workgroup), a longer one in the large (77824 B, two per CU); the same code,
+ *             the same bytes; SEGGER_SIMPLIFY_SMALL_VERTS is the value to pass, 0 sends every ring to the large tier.
+ *             Writes out_offsets [n_polygons + 1] (the output CSR) and counters [SEGGER_SIMPLIFY_COUNTERS] int64:
+ *             0 vertices in (open), 1 vertices out, 2 sections visited (single edges included), 3 chords refused by the
+ *             guard, 4 rings passed through, 5 rings restored after collapse, 6 the longest output ring, 7 the error word:
+ *             SEGGER_MORPH_ERR_OFFSETS / _CAP as segger_polygon_props sets them, SEGGER_SIMPLIFY_ERR_TOL for a tolerance
+ *             that is negative or not finite; such a ring gets no output vertices.  The keep mask stays in the workspace.
+ *   _emit     after _mark, same workspace: xy_out [capacity, 2] fp64 and vertex_index [capacity] int64, capacity >=
+ *             counters[1]; nothing is written at or past capacity.
+ * segger_rings_simple: ok [n_polygons] uint8 and reason [n_polygons, 3] int32 = (code, i, j).  A ring is simple iff at
+ * least 3 vertices are left when consecutive duplicates are dropped (cyclically; otherwise SEGGER_RING_TOO_FEW, -1, -1)
+ * and no two of its edges e_i, e_j, i < j, touch (otherwise SEGGER_RING_TOUCH and the lowest such pair in (i, j) order,
+ * indices into the open ring as given, duplicates not dropped).  Adjacent edges share their common endpoint, which touch
+ * allows; a fold-back is a touch.  This is what is_valid asks of a single-shell polygon.  The error word is the first
+ * int32 of the workspace.
+ *
+ * Workspace, 256-byte aligned, with up(x) = x rounded up to 256: segger_simplify_rings_workspace_bytes(P, V) =
+ *   256 + 2 up(4 P) + up(16 P) + up(V); segger_rings_simple needs (P, 0).
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative sizes, 2^31 - 1 polygons or more, a
+ *   stride or small_max_verts outside its range, NULL or misaligned pointers, a workspace that is too small.
+ *   n_polygons = 0 returns SEGGER_OK and launches nothing.  No scratch, no atomics on floats: the same bytes from run to
+ *   run and for any order of the polygons in the CSR.
+ * NOT BUILT: resort_coordinates, the buffer(0) repair, holes and multi-part polygons, rings above SEGGER_MORPH_MAX_VERTS.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_SIMPLIFY_SMALL_VERTS 256
+#define SEGGER_SIMPLIFY_COUNTERS 8
+#define SEGGER_SIMPLIFY_ERR_TOL 4
+#define SEGGER_RING_OK 0
+#define SEGGER_RING_TOO_FEW 1
+#define SEGGER_RING_TOUCH 2
+int64_t segger_simplify_rings_workspace_bytes(int64_t n_polygons, int64_t n_vertices);
+int segger_simplify_rings_mark(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                               const double* tolerance, int64_t tolerance_stride, int32_t preserve_topology,
+                               int32_t small_max_verts, int64_t* out_offsets, int64_t* counters, void* workspace,
+                               int64_t workspace_bytes, segger_stream_t stream);
+int segger_simplify_rings_emit(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                               const int64_t* out_offsets, double* xy_out, int64_t* vertex_index, int64_t capacity,
+                               void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+int segger_rings_simple(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices, uint8_t* ok,
+                        int32_t* reason, int32_t small_max_verts, void* workspace, int64_t workspace_bytes,
+                        segger_stream_t stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

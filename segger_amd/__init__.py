@@ -24,5 +24,7 @@ from .boundaries import cell_boundaries, segmentation_boundaries  # noqa: F401
 from .boundaries import cell_outlines, segmentation_outlines  # noqa: F401
 from . import contours  # noqa: F401
 from .contours import label_contours  # noqa: F401
+from . import simplify  # noqa: F401
+from .simplify import contour_tolerance, rings_simple, simplify_rings  # noqa: F401
 
 __version__ = "0.1.0"

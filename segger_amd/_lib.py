@@ -28,6 +28,8 @@ BOUNDARY_MAX_SMOOTHING, BOUNDARY_CHUNK_MAX_HULL, BOUNDARY_COUNTERS = 6, 2048, 8 
 OUTLINE_MAX_POINTS, OUTLINE_COUNTERS = 2048, 10                                                        # SEGGER_OUTLINE_*
 OUTLINE_LARGE_COUNTERS = 13
 CONTOUR_MAX_LABEL, CONTOUR_LDS_BITS, CONTOUR_COUNTERS = 1 << 24, 32768, 10                             # SEGGER_CONTOUR_*
+SIMPLIFY_SMALL_VERTS, SIMPLIFY_COUNTERS, SIMPLIFY_ERR_TOL = 256, 8, 4                                  # SEGGER_SIMPLIFY_*
+RING_OK, RING_TOO_FEW, RING_TOUCH = 0, 1, 2                                                            # SEGGER_RING_*
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -385,6 +387,11 @@ EXPORTS = {
     "segger_label_contours": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, C.c_int64, vp, vp, vp, vp,
                                         C.c_int64, C.c_int32, vp]),
+    "segger_simplify_rings_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "segger_simplify_rings_mark": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64,
+                                             vp]),
+    "segger_simplify_rings_emit": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, vp]),
+    "segger_rings_simple": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int32, vp, C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -10,7 +10,8 @@ written from that definition plus independent properties (raster round trip, Pic
 ``skimage`` could be run, so cv2's start vertex, orientation and order among borders of equal length are supposed, not
 checked; downstream code accepts any start and either orientation.
 
-NOT BUILT: the reference's ``simplify(tolerance)`` (GEOS's topology-preserving simplifier), TIFF reading,
+The step the reference takes next, ``simplify(tolerance)`` followed by ``is_valid``, is :mod:`segger_amd.simplify`
+(``simplify_rings``, ``contour_tolerance``, ``rings_simple``).  NOT BUILT: TIFF reading, the repairs of
 ``fix_invalid_geometry``, the id strings, FOV stitching."""
 from __future__ import annotations
 
