@@ -1844,6 +1844,87 @@ int segger_rings_simple(const int64_t* ring_offsets, const double* xy, int64_t n
                         int32_t* reason, int32_t small_max_verts, void* workspace, int64_t workspace_bytes,
                         segger_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Polygon overlap join of two ring CSRs A and B: every pair (a, b) whose closed polygons share a point, and the area of
+ * their intersection -- the reference's polygons_in_polygons (src/segger/geometry/query.py:244-285, a CPU gpd.sjoin with
+ * predicate='intersects', called from data/tiling.py:134) and what a comparison of a segmentation with a vendor's needs
+ * (IoU per cell).  The kernels behind segger_amd.overlap.polygon_overlaps / polygons_in_polygons, csrc/polygon_overlap.hip.
+ * Purely additive: three new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * Polygons are single exterior rings, xy[off[p] .. off[p + 1]) as segger_polygon_props takes them: either orientation, a
+ * closing duplicate of the first vertex dropped bit for bit, a ring above SEGGER_MORPH_MAX_VERTS refused through the
+ * set's error word (A's is int32 word 0 of the workspace, B's is word 8; SEGGER_MORPH_ERR_OFFSETS / _CAP).  A ring with
+ * fewer than 3 open vertices pairs with nothing.  Coordinates are finite.
+ *
+ * The area, measure-theoretically, so that shared edges, collinear overlaps, nesting and self-overlap are no special
+ * cases.  For ring A with s_A the sign of its shoelace sum and an edge e = (p -> q) with p.x != q.x let
+ * sigma_e = s_A sign(p.x - q.x).  With a baseline y0 not above any vertex of the pair,
+ *     1_A(x, y) = sum over e of sigma_e [x in the half-open x-range of e] [y0 <= y < y_e(x)]      almost everywhere
+ * (vertical edges contribute nothing), hence
+ *     area(A and B) = sum over e in A, f in B of sigma_e sigma_f I(e, f),
+ *     I(e, f) = the integral of min(y_e(x), y_f(x)) - y0 over the overlap [xl, xr] of the two x-ranges:
+ * one trapezoid, or two split at the single crossing of the two lines.  (For a ring that winds twice round a region 1_A is
+ * 2 there: the sum is then the integral of 1_A 1_B, which is what "area" means for such a ring here.)
+ * As computed: fp64, no FMA contraction, BOTH rings translated to the first vertex of ring A before any product, y0 the
+ * lowest translated y of the pair;  y_e(x) = p.y (q.y) when x == p.x (q.x), else p.y + (x - p.x) * ((q.y - p.y) / (q.x - p.x));
+ * el, er, fl, fr the two lines at xl and xr, w = xr - xl, ml = min(el, fl) - y0, mr = min(er, fr) - y0;  when el - fl and
+ * er - fr have strictly opposite signs t = (el - fl) / ((el - fl) - (er - fr)), mc = (el + t (er - el)) - y0 and
+ * I = 0.5 w (t (ml + mc) + (1 - t) (mc + mr)), otherwise I = 0.5 w (ml + mr).  Edge pair (k of A, l of B) has index
+ * t = k n_b + l and belongs to lane t mod 64; a lane adds its terms in increasing t from +0.0 (a pair whose closed x-ranges
+ * are apart is skipped: its term is zero); the 64 sums are combined by the xor butterfly at distances 1, 2, .. 32.  The
+ * result is 0 when the predicate below is false, and otherwise clamped into [0, min(area_a[a], area_b[b])].  The bits are
+ * the same from run to run, for any order of the polygons in either set, for any grid and on every tier.
+ *   Error: a term carries at most 16 u W H absolute error (u = 2^-53; W, H the pair's joint extent) and the summation of T
+ *   non-zero terms at most (T - 1) u S, S the sum of their magnitudes: |area - exact| <= 2^-52 (T S + 16 T W H).
+ *
+ * The predicate: intersects(A, B) iff some edge of A and some edge of B share a point (closed segments: with o1 .. o4 the
+ * four orient() of segger_rings_simple's touch, (o1 o2 < 0 and o3 o4 < 0) or an o_i == 0 whose point lies within the
+ * coordinate intervals of the other segment -- touch WITHOUT its shared-endpoint exemption), or vertex 0 of A is inside B
+ * by segger_polygon_join_*'s half-open parity rule, or vertex 0 of B is inside A.  Exact for coordinates whose translated
+ * differences are integers below 2^26.  This is GEOS's 'intersects' for valid rings; what GEOS answers for invalid rings
+ * is UNPINNED (it was never run).
+ *
+ * Candidates: every (a, b), both of 3 or more vertices, whose closed bounding boxes overlap -- found over a uniform grid
+ * of nx x ny cells of side `cell` from (x0, y0) (coordinates outside are clamped into the border cells), B binned, A
+ * walking: a pair is emitted only in the cell (max(cx0_a, cx0_b), max(cy0_a, cy0_b)), the cell of the lower-left corner
+ * of the two boxes' intersection, so once.  A polygon whose box covers more than SEGGER_OVERLAP_WIDE_CELLS cells is "wide"
+ * and is tested against every polygon of the other set instead.  The grid decides the speed and nothing else: the SET of
+ * candidates is the same for any grid; their order in `candidates` is unspecified.
+ *
+ *   _candidates  bins both sets, builds the grid, counts: writes *n_candidates (int64, device) and keeps its tables in the
+ *                workspace for _pairs.  Zeroes the workspace's words.
+ *   _pairs       after _candidates, same arguments and workspace, capacity >= *n_candidates: writes candidates [capacity]
+ *                int64 = a << 32 | b, intersects [capacity] uint8 and area [capacity] fp64 (nothing at or past capacity, nothing
+ *                past *n_candidates).  area_a [Pa], area_b [Pb]: the polygons' areas for the clamp (segger_polygon_props'), or
+ *                both NULL for no upper clamp.  Tiers by n = max(n_a, n_b): n <= reg_max_verts (0 .. 64) both rings in
+ *                registers, no LDS; n <= small_max_verts (0 .. SEGGER_OVERLAP_SMALL_VERTS) both in the LDS of a
+ *                single-wave workgroup, 8192 B; otherwise 131072 B, one workgroup per CU.  64 and
+ *                SEGGER_OVERLAP_SMALL_VERTS are the values to pass; 0, 0 sends every pair to the large tier (tests and
+ *                timing).  int32 word 16 of the workspace counts the pairs that took an LDS tier.
+ * Workspace, 256-byte aligned, with up(x) = x rounded up to 256 and C = nx ny: segger_polygon_overlap_workspace_bytes(Pa, Pb,
+ *   nx, ny) = 256 + 2 up(4 Pa) + 2 up(4 Pb) + up(32 Pa) + up(32 Pb) + up(16 Pa) + up(16 Pb) + up(4 Pa) + up(4 Pb) +
+ *   up(4 (C + 1)) + up(4 C) + up(4 SEGGER_OVERLAP_WIDE_CELLS Pb) + up(8 (Pa + Pb + 1)).  Monotone in every argument.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative sizes, 2^31 / SEGGER_OVERLAP_WIDE_CELLS
+ *   polygons or more in a set, a bad grid, a tier bound outside its range, NULL or misaligned pointers, a workspace that is
+ *   too small.  An empty set on either side returns SEGGER_OK and launches nothing.  No scratch, no atomics on floats.
+ * NOT BUILT: predicate 'contains' (deciding it exactly needs the sub-segments of an edge between boundary touches), the
+ *   intersection polygon itself, holes, multi-part polygons.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_OVERLAP_SMALL_VERTS 256
+#define SEGGER_OVERLAP_WIDE_CELLS 64
+int64_t segger_polygon_overlap_workspace_bytes(int64_t n_polygons_a, int64_t n_polygons_b, int32_t nx, int32_t ny);
+int segger_polygon_overlap_candidates(const int64_t* ring_offsets_a, const double* xy_a, int64_t n_polygons_a,
+                                      int64_t n_vertices_a, const int64_t* ring_offsets_b, const double* xy_b,
+                                      int64_t n_polygons_b, int64_t n_vertices_b, double x0, double y0, double cell, int32_t nx,
+                                      int32_t ny, int64_t* n_candidates, void* workspace, int64_t workspace_bytes,
+                                      segger_stream_t stream);
+int segger_polygon_overlap_pairs(const int64_t* ring_offsets_a, const double* xy_a, int64_t n_polygons_a, int64_t n_vertices_a,
+                                 const int64_t* ring_offsets_b, const double* xy_b, int64_t n_polygons_b, int64_t n_vertices_b,
+                                 double x0, double y0, double cell, int32_t nx, int32_t ny, const double* area_a,
+                                 const double* area_b, const int64_t* n_candidates, int64_t* candidates, uint8_t* intersects,
+                                 double* area, int64_t capacity, int32_t reg_max_verts, int32_t small_max_verts, void* workspace,
+                                 int64_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -26,5 +26,7 @@ from . import contours  # noqa: F401
 from .contours import label_contours  # noqa: F401
 from . import simplify  # noqa: F401
 from .simplify import contour_tolerance, rings_simple, simplify_rings  # noqa: F401
+from . import overlap  # noqa: F401
+from .overlap import match_polygons, polygon_overlaps, polygons_in_polygons  # noqa: F401
 
 __version__ = "0.1.0"

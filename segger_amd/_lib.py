@@ -30,6 +30,7 @@ OUTLINE_LARGE_COUNTERS = 13
 CONTOUR_MAX_LABEL, CONTOUR_LDS_BITS, CONTOUR_COUNTERS = 1 << 24, 32768, 10                             # SEGGER_CONTOUR_*
 SIMPLIFY_SMALL_VERTS, SIMPLIFY_COUNTERS, SIMPLIFY_ERR_TOL = 256, 8, 4                                  # SEGGER_SIMPLIFY_*
 RING_OK, RING_TOO_FEW, RING_TOUCH = 0, 1, 2                                                            # SEGGER_RING_*
+OVERLAP_SMALL_VERTS, OVERLAP_WIDE_CELLS = 256, 64                                                      # SEGGER_OVERLAP_*
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -392,6 +393,12 @@ EXPORTS = {
                                              vp]),
     "segger_simplify_rings_emit": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, vp]),
     "segger_rings_simple": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int32, vp, C.c_int64, vp]),
+    "segger_polygon_overlap_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "segger_polygon_overlap_candidates": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                                    C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]),
+    "segger_polygon_overlap_pairs": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                               C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32,
+                                               vp, C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None
