@@ -1,15 +1,23 @@
-// The front end and the back end that the two units writing one ring per cell share (boundaries.hip: the convex hull;
-// outlines.hip: the pruned Delaunay outline; included after rings.h and sort_config.h).  Front: the key of a row, the
-// position where a cell starts in the sorted keys, the segments.  Back: the scan that keeps the cells with a ring and
-// places them, and the emit kernel with its Chaikin stage.  In between each unit runs its own kernels, which write ring
-// vertex k of segment j to hull[head[j] + k] and the ring's length to hull_n[j].  The kernels are defined here, in an
-// unnamed namespace: every including unit gets its own copies under the same names, and a fix is made once.
+// The front end and the back end that the units writing one ring per cell share (boundaries.hip: the convex hull;
+// outlines.hip and outlines_large.hip: the pruned Delaunay outline; included after rings.h and sort_config.h).  Front: the
+// key of a row, the position where a cell starts in the sorted keys, the segments.  Back: the scan that keeps the cells with
+// a ring and places them (post_common.h's GroupScan over vertices and kept cells at once), and the emit kernel with its
+// Chaikin stage.  In between each unit runs its own kernels, which write ring vertex k of segment j to hull[head[j] + k] and
+// the ring's length to hull_n[j].  The host half is here as well, once: the head of the workspace layout
+// (take_cell_rings), the refusals of a call (bnd_check_sizes, check_cell_rings_call), the views into a workspace
+// (cell_rings_views) and the launches of the front and of the back (launch_cell_rings_front / _back); a unit keeps its own
+// regions, its own refusals and the launches of its own kernels.  Everything is defined in an unnamed namespace: every
+// including unit gets its own copies under the same names, and a fix is made once.
 #pragma once
 #include <math.h>
 
 #include "common.h"
 #include "post_common.h"
 #include "rings.h"
+#include "sort_config.h"
+
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 #pragma clang fp contract(off)
 
@@ -89,52 +97,26 @@ __global__ __launch_bounds__(kBndScanThreads) void bnd_scan_kernel(BndSegs s, in
                                                                    int64_t* __restrict__ ring_offsets, int32_t* __restrict__ cell_ids,
                                                                    int64_t* __restrict__ n_transcripts,
                                                                    unsigned long long* __restrict__ counters) {
-  __shared__ int64_t wave_verts[kBndScanThreads / kWave];
-  __shared__ int wave_kept[kBndScanThreads / kWave];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  __shared__ ScanPair totals[kBndScanThreads / kWave];
   const int64_t present = (int64_t)counters[kPresent];
-  int64_t carry_v = 0;                                               // vertices and kept cells before this chunk
-  int carry_k = 0;
+  GroupScan<kBndScanThreads, ScanPair> scan{totals, ScanPair{0, 0}}; // vertices and kept cells before
   for (int64_t base = 0; base < present; base += kBndScanThreads) {
     const int64_t j = base + threadIdx.x;
     const int h = j < present ? s.hull_n[j] : 0;
     const bool kept = h >= 3;
-    const int64_t mine = kept ? (int64_t)h << smoothing : 0;
-    int64_t v = mine;
-    int k = kept ? 1 : 0;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {                            // inclusive scans of the wave
-      const int src = lane >= d ? lane - d : lane;
-      const int64_t ov = (int64_t)shfl64((uint64_t)v, src);
-      const int ok = __shfl(k, src, kWave);
-      if (lane >= d) { v += ov; k += ok; }
-    }
-    if (lane == kWave - 1) { wave_verts[wave] = v; wave_kept[wave] = k; }
-    __syncthreads();
-    int64_t before_v = carry_v, all_v = carry_v;
-    int before_k = carry_k, all_k = carry_k;
-    for (int w = 0; w < kBndScanThreads / kWave; ++w) {
-      const int64_t tv = wave_verts[w];
-      const int tk = wave_kept[w];
-      if (w < wave) { before_v += tv; before_k += tk; }
-      all_v += tv;
-      all_k += tk;
-    }
+    const ScanPair before = scan.step(ScanPair{kept ? (int64_t)h << smoothing : 0, kept ? 1 : 0});
     if (kept) {
-      const int q = before_k + k - 1;
+      const int q = before.k;
       kept_seg[q] = (int32_t)j;
-      ring_offsets[q] = before_v + v - mine;
+      ring_offsets[q] = before.v;
       cell_ids[q] = (int32_t)(s.keys[s.head[j]] >> 32);
       n_transcripts[q] = (int64_t)s.len[j];
     }
-    carry_v = all_v;
-    carry_k = all_k;
-    __syncthreads();                                                 // the totals are rewritten by the next chunk
   }
   if (threadIdx.x == 0) {
-    ring_offsets[carry_k] = carry_v;
-    counters[kKept] = (unsigned long long)carry_k;
-    counters[kVerts] = (unsigned long long)carry_v;
+    ring_offsets[scan.carry.k] = scan.carry.v;
+    counters[kKept] = (unsigned long long)scan.carry.k;
+    counters[kVerts] = (unsigned long long)scan.carry.v;
   }
 }
 
@@ -234,6 +216,124 @@ void launch_emit_for(int smoothing, unsigned grid, hipStream_t stream, const Bnd
     case 5: launch_emit<5>(grid, stream, s, kept_seg, ring_offsets, counters, xy_out, capacity); break;
     default: launch_emit<6>(grid, stream, s, kept_seg, ring_offsets, counters, xy_out, capacity); break;
   }
+}
+
+// The regions every workspace of these units starts with, and what sizes them.  keys: the sorted keys; hull: the rings,
+// and before that the unsorted keys (dead once sorted); head, len, hull_n, kept_seg: one int32 per possible cell; temp: the
+// larger of the sort's and the select's.  A unit takes its own regions after these.  With n_rows and n_cells below 2^31
+// every term is below 2^36 bytes: nothing here can overflow.
+struct CellRingsLayout {
+  RingLists rings;
+  size_t keys, hull, head, len, hull_n, kept_seg, temp;
+  size_t temp_bytes;
+  int key_bits;
+  int64_t cells_cap;
+};
+
+CellRingsLayout take_cell_rings(Carver& c, int64_t n_rows, int64_t n_cells) {
+  CellRingsLayout l;
+  l.key_bits = 32 + bit_length((unsigned long long)n_cells);         // the sentinel n_cells << 32 is the largest key
+  const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
+  l.cells_cap = n_rows < n_cells ? (n_rows > 0 ? n_rows : 1) : n_cells;
+  const size_t c4 = (size_t)l.cells_cap * 4;
+  l.rings = take_ring_lists(c, l.cells_cap);
+  l.keys = c.take(n * 8);
+  l.hull = c.take(n * 16);
+  l.head = c.take(c4);
+  l.len = c.take(c4);
+  l.hull_n = c.take(c4);
+  l.kept_seg = c.take(c4);
+  size_t a = 0, b = 0;
+  unsigned long long* k64 = nullptr;
+  int32_t* i32 = nullptr;
+  size_t* cnt = nullptr;
+  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, a, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
+  (void)rocprim::select(nullptr, b, rocprim::counting_iterator<int32_t>(0), i32, cnt, n, BndCellHead{nullptr, 0}, (hipStream_t)0);
+  l.temp_bytes = a > b ? a : b;
+  l.temp = c.take(l.temp_bytes > 0 ? l.temp_bytes : 1);
+  return l;
+}
+
+// the arguments the three entry points share
+struct CellRingsCall {
+  const double* xy; const int32_t* cell; const uint8_t* keep; int64_t n_rows, n_cells; int32_t smoothing;
+  int64_t* ring_offsets; double* xy_out; int64_t xy_capacity; int32_t* cell_ids; int64_t* n_transcripts; uint64_t* counters;
+  void* workspace; int64_t workspace_bytes;
+};
+
+// What all three refuse about a call whose sizes passed (bnd_check_sizes comes first: `need` is a layout's total, and a
+// layout is defined for sizes that passed), in one order and one wording.  `unit` holds the unit's own refusals of scalar
+// arguments, where they stand: after smoothing.  *empty: n_rows == 0, nothing is launched and the caller's zeroed counters
+// and ring_offsets[0] stand.
+template <class F>
+int check_cell_rings_call(const char* who, const CellRingsCall& a, size_t need, F&& unit, bool* empty) {
+  *empty = false;
+  SEGGER_REQUIRE(a.smoothing >= 0 && a.smoothing <= SEGGER_BOUNDARY_MAX_SMOOTHING, "%s: smoothing = %d outside 0 .. %d", who,
+                 (int)a.smoothing, SEGGER_BOUNDARY_MAX_SMOOTHING);
+  const int rc = unit();
+  if (rc != SEGGER_OK) return rc;
+  SEGGER_REQUIRE(a.workspace_bytes >= 0 && a.xy_capacity >= 0, "%s: negative workspace_bytes or xy_capacity", who);
+  if (a.n_rows == 0) {
+    SEGGER_REQUIRE(a.counters && a.ring_offsets, "%s: NULL pointer", who);
+    *empty = true;
+    return SEGGER_OK;
+  }
+  SEGGER_REQUIRE(a.xy && a.cell && a.ring_offsets && a.cell_ids && a.n_transcripts && a.counters && a.workspace, "%s: NULL pointer", who);
+  SEGGER_REQUIRE(a.xy_out || a.xy_capacity == 0, "%s: NULL xy_out with xy_capacity > 0", who);
+  SEGGER_REQUIRE(is_aligned(a.xy, 16) && is_aligned(a.xy_out, 16), "%s: xy and xy_out must be 16-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(a.ring_offsets, 8) && is_aligned(a.n_transcripts, 8) && is_aligned(a.counters, 8),
+                 "%s: ring_offsets, n_transcripts and counters must be 8-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(a.cell, 4) && is_aligned(a.cell_ids, 4), "%s: cell and cell_ids must be 4-byte aligned", who);
+  SEGGER_REQUIRE(is_aligned(a.workspace, 256), "%s: workspace must be 256-byte aligned", who);
+  SEGGER_REQUIRE((size_t)a.workspace_bytes >= need, "%s: workspace %lld < %zu bytes", who, (long long)a.workspace_bytes, need);
+  return SEGGER_OK;
+}
+
+// the shared regions of a workspace as pointers
+struct CellRingsViews {
+  int32_t *words, *list_short, *list_long, *head, *kept_seg;
+  unsigned long long *keys_in, *keys;                                // unsorted, in the hull's region (dead once sorted); sorted
+  char* temp;
+  unsigned long long* cnt;                                           // the caller's counters
+  BndSegs s;
+};
+CellRingsViews cell_rings_views(const CellRingsCall& a, const CellRingsLayout& l) {
+  void* ws = a.workspace;
+  return CellRingsViews{at<int32_t>(ws, l.rings.words), at<int32_t>(ws, l.rings.list_short), at<int32_t>(ws, l.rings.list_long),
+                        at<int32_t>(ws, l.head), at<int32_t>(ws, l.kept_seg), at<unsigned long long>(ws, l.hull),
+                        at<unsigned long long>(ws, l.keys), at<char>(ws, l.temp), reinterpret_cast<unsigned long long*>(a.counters),
+                        BndSegs{at<unsigned long long>(ws, l.keys), at<int32_t>(ws, l.head), at<int32_t>(ws, l.len),
+                                at<int32_t>(ws, l.hull_n), at<double2>(ws, l.hull)}};
+}
+
+// Front: the words and the unit's n_counters counters zeroed, the keys, the keys-only sort, the first sorted position of
+// every present cell into head with their number in counters[kPresent].
+int launch_cell_rings_front(const CellRingsCall& a, const CellRingsLayout& l, const CellRingsViews& v, int n_counters, int cus,
+                            hipStream_t stream) {
+  SEGGER_HIP(hipMemsetAsync(v.words, 0, kRingWordsBytes, stream));
+  SEGGER_HIP(hipMemsetAsync(v.cnt, 0, n_counters * sizeof(unsigned long long), stream));
+  hipLaunchKernelGGL(bnd_keys_kernel, dim3(grid_stride_blocks(a.n_rows, kBndThreads, (int64_t)cus * 32)), dim3(kBndThreads), 0, stream,
+                     a.xy, a.cell, a.keep, a.n_rows, a.n_cells, v.keys_in, v.cnt);
+  SEGGER_LAUNCH_CHECK("bnd_keys_kernel");
+  size_t temp_bytes = l.temp_bytes;
+  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(v.temp, temp_bytes, v.keys_in, v.keys, (size_t)a.n_rows, 0,
+                                                           (unsigned)l.key_bits, stream));
+  temp_bytes = l.temp_bytes;
+  SEGGER_HIP(rocprim::select(v.temp, temp_bytes, rocprim::counting_iterator<int32_t>(0), v.head,
+                             reinterpret_cast<size_t*>(v.cnt + kPresent), (size_t)a.n_rows,
+                             BndCellHead{v.keys, (unsigned long long)a.n_cells << 32}, stream));
+  return SEGGER_OK;
+}
+
+// Back: the kept cells placed, then their rings emitted after `smoothing` Chaikin iterations.
+int launch_cell_rings_back(const CellRingsCall& a, const CellRingsLayout& l, const CellRingsViews& v, int cus, hipStream_t stream) {
+  hipLaunchKernelGGL(bnd_scan_kernel, dim3(1), dim3(kBndScanThreads), 0, stream, v.s, (int)a.smoothing, v.kept_seg, a.ring_offsets,
+                     a.cell_ids, a.n_transcripts, v.cnt);
+  SEGGER_LAUNCH_CHECK("bnd_scan_kernel");
+  launch_emit_for((int)a.smoothing, grid_stride_blocks(l.cells_cap, kBndWaves, (int64_t)cus * 8), stream, v.s, v.kept_seg,
+                  a.ring_offsets, v.cnt, reinterpret_cast<double2*>(a.xy_out), a.xy_capacity);
+  SEGGER_LAUNCH_CHECK("bnd_emit_kernel");
+  return SEGGER_OK;
 }
 
 }  // namespace

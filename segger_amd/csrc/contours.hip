@@ -28,7 +28,8 @@
 //                    it counts the kept points (CHAIN_APPROX_SIMPLE: the step in differs from the step out) and finds
 //                    the canonical start, the smallest (scan index, clockwise code of the previous pixel).  The winner:
 //                    most kept points, then the smaller canonical start.
-//   ct_offsets_kernel  one workgroup: the labels with more than 2 points, compacted; ring_offsets; the counters.
+//   ct_offsets_kernel  one workgroup: the labels with more than 2 points, compacted; ring_offsets; the counters (the scan
+//                      of vertices and kept labels is post_common.h's GroupScan; the longest ring is a maximum beside it).
 //   ct_emit_kernel   one thread per kept label follows the winner from its canonical start over the image and writes xy.
 // Nothing depends on the order in which threads arrive: atomics are integer min, max and add.
 // Every loop is bounded before it is entered: a border has at most 8 states per pixel of the crop.
@@ -312,49 +313,35 @@ __global__ __launch_bounds__(kCtOffThreads) void ct_offsets_kernel(CtTables t, C
                                                                    int64_t* __restrict__ ring_offsets, int32_t* __restrict__ label_ids,
                                                                    int64_t* __restrict__ n_pixels, int64_t xy_capacity,
                                                                    unsigned long long* __restrict__ counters) {
-  __shared__ long long sv[kCtOffWaves];
-  __shared__ int sk[kCtOffWaves], sl[kCtOffWaves];
+  __shared__ ScanPair totals[kCtOffWaves];
+  __shared__ int sl[kCtOffWaves];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
   const int present = (int)counters[kCtPresent];
-  long long v_base = 0;
-  int k_base = 0, longest = 0;
+  GroupScan<kCtOffThreads, ScanPair> scan{totals, ScanPair{0, 0}};   // vertices and kept labels before
+  int longest = 0;                                                   // of this thread's labels; combined after the loop
   for (int base = 0; base < present; base += kCtOffThreads) {
     const int j = base + tid;
     const int cnt = j < present ? w.cnt[j] : 0;
     const int keep = cnt > 2;
-    long long v = keep ? cnt : 0;
-    int k = keep;
-#pragma unroll
-    for (int q = 1; q < kWave; q <<= 1) {                            // inclusive scans inside the wave
-      const long long ov = (long long)shfl64((unsigned long long)v, lane >= q ? lane - q : lane);
-      const int ok = __shfl(k, lane >= q ? lane - q : lane, kWave);
-      if (lane >= q) { v += ov; k += ok; }
-    }
-    int lw = keep ? cnt : 0;
-#pragma unroll
-    for (int q = 1; q < kWave; q <<= 1) lw = max(lw, __shfl_xor(lw, q, kWave));
-    if (lane == kWave - 1) { sv[wave] = v; sk[wave] = k; sl[wave] = lw; }
-    __syncthreads();
-    long long v_before = v_base, v_all = 0;
-    int k_before = k_base, k_all = 0;
-#pragma unroll
-    for (int q = 0; q < kCtOffWaves; ++q) {
-      if (q < wave) { v_before += sv[q]; k_before += sk[q]; }
-      v_all += sv[q]; k_all += sk[q];
-      longest = max(longest, sl[q]);
-    }
+    longest = max(longest, keep ? cnt : 0);
+    const ScanPair before = scan.step(ScanPair{keep ? cnt : 0, keep});
     if (keep) {
-      const int at = k_before + k - 1;
+      const int at = before.k;
       const int label = w.present[j];
       kept[at] = j;
-      ring_offsets[at] = v_before + v - cnt;
+      ring_offsets[at] = before.v;
       label_ids[at] = label;
       n_pixels[at] = t.count[label];
     }
-    v_base += v_all; k_base += k_all;
-    __syncthreads();
   }
+#pragma unroll
+  for (int q = 1; q < kWave; q <<= 1) longest = max(longest, __shfl_xor(longest, q, kWave));
+  if (lane == 0) sl[wave] = longest;
+  __syncthreads();
   if (tid == 0) {
+    for (int q = 0; q < kCtOffWaves; ++q) longest = max(longest, sl[q]);
+    const long long v_base = scan.carry.v;
+    const int k_base = scan.carry.k;
     ring_offsets[k_base] = v_base;
     counters[kCtKept] = (unsigned long long)k_base;
     counters[kCtVertices] = (unsigned long long)v_base;

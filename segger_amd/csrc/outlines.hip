@@ -4,7 +4,8 @@
 // include/segger_amd.h has the contract, DESIGN 3.5j the argument why the peel's order does not decide the result.
 //
 // The front end (keys, keys-only sort, compaction to present cells) and the back end (scan, emit with the Chaikin stage)
-// are boundaries.hip's, shared through cell_rings.h.  In between:
+// are boundaries.hip's, shared through cell_rings.h: their kernels, and the host code that lays out the workspace, refuses
+// a call and launches them.  In between:
 //   out_bin_kernel       one thread per present cell: its length and its route (rings.h: append_by_route);
 //   out_cell_kernel<N>   one single-wave WORKGROUP per cell, the whole per-cell state in LDS, N = 256 for a cell of at
 //                        most 256 rows (17 KB: nine cells per CU) and N = SEGGER_OUTLINE_MAX_POINTS otherwise.
@@ -46,9 +47,6 @@
 #include "sort_config.h"
 #include "cell_rings.h"
 #include "outline_cell.h"
-
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #pragma clang fp contract(off)
 
@@ -99,37 +97,13 @@ __global__ __launch_bounds__(kWave) void out_cell_kernel(const double* __restric
 }
 
 // ---------------------------------------------------------------- host ---
-struct OutLayout {
-  RingLists rings;
-  size_t keys, hull, head, len, hull_n, kept_seg, temp, total;
-  size_t temp_bytes;
-  int key_bits;
-  int64_t cells_cap;
-};
+// cell_rings.h's head and nothing else
+struct OutLayout { CellRingsLayout head; size_t total; };
 
-// with n_rows and n_cells below 2^31 every term is below 2^36 bytes: nothing here can overflow
 OutLayout out_layout(int64_t n_rows, int64_t n_cells) {
   OutLayout l;
-  l.key_bits = 32 + bit_length((unsigned long long)n_cells);         // the sentinel n_cells << 32 is the largest key
-  const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-  l.cells_cap = n_rows < n_cells ? (n_rows > 0 ? n_rows : 1) : n_cells;
-  const size_t c4 = (size_t)l.cells_cap * 4;
   Carver c;
-  l.rings = take_ring_lists(c, l.cells_cap);
-  l.keys = c.take(n * 8);                                            // sorted keys
-  l.hull = c.take(n * 16);                                           // the rings; before that, the unsorted keys
-  l.head = c.take(c4);
-  l.len = c.take(c4);
-  l.hull_n = c.take(c4);
-  l.kept_seg = c.take(c4);
-  size_t a = 0, b = 0;
-  unsigned long long* k64 = nullptr;
-  int32_t* i32 = nullptr;
-  size_t* cnt = nullptr;
-  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, a, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
-  (void)rocprim::select(nullptr, b, rocprim::counting_iterator<int32_t>(0), i32, cnt, n, BndCellHead{nullptr, 0}, (hipStream_t)0);
-  l.temp_bytes = a > b ? a : b;
-  l.temp = c.take(l.temp_bytes > 0 ? l.temp_bytes : 1);
+  l.head = take_cell_rings(c, n_rows, n_cells);
   l.total = c.total();
   return l;
 }
@@ -151,66 +125,35 @@ extern "C" int segger_cell_outlines(const double* xy, const int32_t* cell, const
                                     void* workspace, int64_t workspace_bytes, segger_stream_t stream_) {
   const char* who = "segger_cell_outlines";
   hipStream_t stream = (hipStream_t)stream_;
-  const int rc = bnd_check_sizes(who, n_rows, n_cells);
+  const CellRingsCall a{xy, cell, keep, n_rows, n_cells, smoothing, ring_offsets, xy_out, xy_capacity, cell_ids, n_transcripts,
+                        counters, workspace, workspace_bytes};
+  int rc = bnd_check_sizes(who, n_rows, n_cells);
   if (rc != SEGGER_OK) return rc;
-  SEGGER_REQUIRE(smoothing >= 0 && smoothing <= SEGGER_BOUNDARY_MAX_SMOOTHING, "%s: smoothing = %d outside 0 .. %d", who,
-                 (int)smoothing, SEGGER_BOUNDARY_MAX_SMOOTHING);
-  SEGGER_REQUIRE(connectivity > 0.0 && connectivity - connectivity == 0.0, "%s: connectivity = %g is not a finite number > 0", who,
-                 connectivity);
-  SEGGER_REQUIRE(workspace_bytes >= 0 && xy_capacity >= 0, "%s: negative workspace_bytes or xy_capacity", who);
-  if (n_rows == 0) {                               // nothing launched: the caller's zeroed counters and ring_offsets[0] stand
-    SEGGER_REQUIRE(counters && ring_offsets, "%s: NULL pointer", who);
-    return SEGGER_OK;
-  }
-  SEGGER_REQUIRE(xy && cell && ring_offsets && cell_ids && n_transcripts && counters && workspace, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(xy_out || xy_capacity == 0, "%s: NULL xy_out with xy_capacity > 0", who);
-  SEGGER_REQUIRE(is_aligned(xy, 16) && is_aligned(xy_out, 16), "%s: xy and xy_out must be 16-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(ring_offsets, 8) && is_aligned(n_transcripts, 8) && is_aligned(counters, 8),
-                 "%s: ring_offsets, n_transcripts and counters must be 8-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(cell, 4) && is_aligned(cell_ids, 4), "%s: cell and cell_ids must be 4-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
   const OutLayout l = out_layout(n_rows, n_cells);
-  SEGGER_REQUIRE((size_t)workspace_bytes >= l.total, "%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, l.total);
+  bool empty = false;
+  rc = check_cell_rings_call(who, a, l.total, [&] {
+    SEGGER_REQUIRE(connectivity > 0.0 && connectivity - connectivity == 0.0, "%s: connectivity = %g is not a finite number > 0", who,
+                   connectivity);
+    return SEGGER_OK;
+  }, &empty);
+  if (rc != SEGGER_OK || empty) return rc;
 
-  int32_t* words = at<int32_t>(workspace, l.rings.words);
-  int32_t* list_short = at<int32_t>(workspace, l.rings.list_short);
-  int32_t* list_long = at<int32_t>(workspace, l.rings.list_long);
-  unsigned long long* keys_in = at<unsigned long long>(workspace, l.hull);       // dead once sorted: the rings go there
-  unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
-  int32_t* head = at<int32_t>(workspace, l.head);
-  int32_t* kept_seg = at<int32_t>(workspace, l.kept_seg);
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
-  const BndSegs s{keys, head, at<int32_t>(workspace, l.len), at<int32_t>(workspace, l.hull_n), at<double2>(workspace, l.hull)};
+  const CellRingsViews v = cell_rings_views(a, l.head);
+  const BndSegs& s = v.s;
   const OutParams prm{connectivity};
   const int cus = cu_count_or_default();
-  const int64_t cap = l.cells_cap;
+  const int64_t cap = l.head.cells_cap;
 
-  SEGGER_HIP(hipMemsetAsync(words, 0, kRingWordsBytes, stream));
-  SEGGER_HIP(hipMemsetAsync(cnt, 0, SEGGER_OUTLINE_COUNTERS * sizeof(unsigned long long), stream));
-  hipLaunchKernelGGL(bnd_keys_kernel, dim3(grid_stride_blocks(n_rows, kBndThreads, (int64_t)cus * 32)), dim3(kBndThreads), 0, stream,
-                     xy, cell, keep, n_rows, n_cells, keys_in, cnt);
-  SEGGER_LAUNCH_CHECK("bnd_keys_kernel");
-  size_t temp_bytes = l.temp_bytes;
-  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, l.temp), temp_bytes, keys_in, keys, (size_t)n_rows, 0,
-                                                           (unsigned)l.key_bits, stream));
-  temp_bytes = l.temp_bytes;
-  SEGGER_HIP(rocprim::select(at<char>(workspace, l.temp), temp_bytes, rocprim::counting_iterator<int32_t>(0), head,
-                             reinterpret_cast<size_t*>(cnt + kPresent), (size_t)n_rows,
-                             BndCellHead{keys, (unsigned long long)n_cells << 32}, stream));
+  rc = launch_cell_rings_front(a, l.head, v, SEGGER_OUTLINE_COUNTERS, cus, stream);
+  if (rc != SEGGER_OK) return rc;
   hipLaunchKernelGGL(out_bin_kernel, dim3(grid_stride_blocks(cap, kBndThreads, (int64_t)cus * 8)), dim3(kBndThreads), 0, stream, s,
-                     (const unsigned long long*)cnt, words, list_short, list_long);
+                     (const unsigned long long*)v.cnt, v.words, v.list_short, v.list_long);
   SEGGER_LAUNCH_CHECK("out_bin_kernel");
   hipLaunchKernelGGL((out_cell_kernel<kOutSmall>), dim3(grid_stride_blocks(cap, 1, (int64_t)cus * 9)), dim3(kWave), 0, stream, xy, s,
-                     (const int32_t*)words, (int)kWordShort, (const int32_t*)list_short, prm, cnt);
+                     (const int32_t*)v.words, (int)kWordShort, (const int32_t*)v.list_short, prm, v.cnt);
   SEGGER_LAUNCH_CHECK("out_cell_kernel<256>");
   hipLaunchKernelGGL((out_cell_kernel<kOutMax>), dim3(grid_stride_blocks(n_rows / (kOutSmall + 1), 1, (int64_t)cus)), dim3(kWave), 0,
-                     stream, xy, s, (const int32_t*)words, (int)kWordLong, (const int32_t*)list_long, prm, cnt);
+                     stream, xy, s, (const int32_t*)v.words, (int)kWordLong, (const int32_t*)v.list_long, prm, v.cnt);
   SEGGER_LAUNCH_CHECK("out_cell_kernel<max>");
-  hipLaunchKernelGGL(bnd_scan_kernel, dim3(1), dim3(kBndScanThreads), 0, stream, s, (int)smoothing, kept_seg, ring_offsets, cell_ids,
-                     n_transcripts, cnt);
-  SEGGER_LAUNCH_CHECK("bnd_scan_kernel");
-  launch_emit_for((int)smoothing, grid_stride_blocks(cap, kBndWaves, (int64_t)cus * 8), stream, s, kept_seg, ring_offsets, cnt,
-                  reinterpret_cast<double2*>(xy_out), xy_capacity);
-  SEGGER_LAUNCH_CHECK("bnd_emit_kernel");
-  return SEGGER_OK;
+  return launch_cell_rings_back(a, l.head, v, cus, stream);
 }

@@ -1,7 +1,8 @@
 // segger_cell_outlines_large: segger_cell_outlines with a third route, through global memory, for the cells whose distinct
 // points exceed the LDS budget (or a caller's lower `lds_max_points`).  include/segger_amd.h has the contract.
 //
-// The front end, the back end and the two LDS routes are those of outlines.hip (cell_rings.h, outline_cell.h).  New here:
+// The front end, the back end and the host code that drives them are cell_rings.h's, the two LDS routes outline_cell.h's,
+// all shared with outlines.hip.  New here:
 //   outl_bin_kernel      as out_bin_kernel; with lds_max_points = 0 every present cell goes to the large list at once;
 //   outl_lds_kernel<N>   outline_cell<N> with the limit min(N, lds_max_points): a cell that exceeds it in stage 1 takes a
 //                        slice of the large-cell workspace with one atomic bump of its rows and is appended to the large
@@ -40,9 +41,6 @@
 #include "sort_config.h"
 #include "cell_rings.h"
 #include "outline_cell.h"
-
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #pragma clang fp contract(off)
 
@@ -582,38 +580,18 @@ __global__ __launch_bounds__(kLgThreads) void outl_large_kernel(const double* __
 }
 
 // ---------------------------------------------------------------- host ---
+// cell_rings.h's head, then the large list and the arrays over large_rows.  With n_rows below 2^31 every term is below 2^38
+// bytes: nothing here can overflow.
 struct LargeLayout {
-  RingLists rings;
-  size_t keys, hull, head, len, hull_n, kept_seg, temp, list_large, at_large, pts, flg, tv, nb, ef, label, hkey, hid, total;
-  size_t temp_bytes;
-  int key_bits;
-  int64_t cells_cap;
+  CellRingsLayout head;
+  size_t list_large, at_large, pts, flg, tv, nb, ef, label, hkey, hid, total;
 };
 
-// The head is segger_cell_outlines' layout, term for term; then the large list and the arrays over large_rows.  With n_rows
-// below 2^31 every term is below 2^38 bytes: nothing here can overflow.
 LargeLayout large_layout(int64_t n_rows, int64_t n_cells, int64_t large_rows) {
   LargeLayout l;
-  l.key_bits = 32 + bit_length((unsigned long long)n_cells);         // the sentinel n_cells << 32 is the largest key
-  const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-  l.cells_cap = n_rows < n_cells ? (n_rows > 0 ? n_rows : 1) : n_cells;
-  const size_t c4 = (size_t)l.cells_cap * 4;
   Carver c;
-  l.rings = take_ring_lists(c, l.cells_cap);
-  l.keys = c.take(n * 8);                                            // sorted keys
-  l.hull = c.take(n * 16);                                           // the rings; before that, the unsorted keys
-  l.head = c.take(c4);
-  l.len = c.take(c4);
-  l.hull_n = c.take(c4);
-  l.kept_seg = c.take(c4);
-  size_t a = 0, b = 0;
-  unsigned long long* k64 = nullptr;
-  int32_t* i32 = nullptr;
-  size_t* cnt = nullptr;
-  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, a, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
-  (void)rocprim::select(nullptr, b, rocprim::counting_iterator<int32_t>(0), i32, cnt, n, BndCellHead{nullptr, 0}, (hipStream_t)0);
-  l.temp_bytes = a > b ? a : b;
-  l.temp = c.take(l.temp_bytes > 0 ? l.temp_bytes : 1);
+  l.head = take_cell_rings(c, n_rows, n_cells);
+  const size_t c4 = (size_t)l.head.cells_cap * 4;
   const size_t r = (size_t)(large_rows > 0 ? large_rows : 1);
   l.list_large = c.take(c4);
   l.at_large = c.take(2 * c4);
@@ -654,80 +632,49 @@ extern "C" int segger_cell_outlines_large(const double* xy, const int32_t* cell,
                                           segger_stream_t stream_) {
   const char* who = "segger_cell_outlines_large";
   hipStream_t stream = (hipStream_t)stream_;
-  const int rc = large_check_sizes(who, n_rows, n_cells, large_rows);
+  const CellRingsCall a{xy, cell, keep, n_rows, n_cells, smoothing, ring_offsets, xy_out, xy_capacity, cell_ids, n_transcripts,
+                        counters, workspace, workspace_bytes};
+  int rc = large_check_sizes(who, n_rows, n_cells, large_rows);
   if (rc != SEGGER_OK) return rc;
-  SEGGER_REQUIRE(smoothing >= 0 && smoothing <= SEGGER_BOUNDARY_MAX_SMOOTHING, "%s: smoothing = %d outside 0 .. %d", who,
-                 (int)smoothing, SEGGER_BOUNDARY_MAX_SMOOTHING);
-  SEGGER_REQUIRE(connectivity > 0.0 && connectivity - connectivity == 0.0, "%s: connectivity = %g is not a finite number > 0", who,
-                 connectivity);
-  SEGGER_REQUIRE(lds_max_points >= 0 && lds_max_points <= SEGGER_OUTLINE_MAX_POINTS, "%s: lds_max_points = %d outside 0 .. %d", who,
-                 (int)lds_max_points, SEGGER_OUTLINE_MAX_POINTS);
-  SEGGER_REQUIRE(workspace_bytes >= 0 && xy_capacity >= 0, "%s: negative workspace_bytes or xy_capacity", who);
-  if (n_rows == 0) {                               // nothing launched: the caller's zeroed counters and ring_offsets[0] stand
-    SEGGER_REQUIRE(counters && ring_offsets, "%s: NULL pointer", who);
-    return SEGGER_OK;
-  }
-  SEGGER_REQUIRE(xy && cell && ring_offsets && cell_ids && n_transcripts && counters && workspace, "%s: NULL pointer", who);
-  SEGGER_REQUIRE(xy_out || xy_capacity == 0, "%s: NULL xy_out with xy_capacity > 0", who);
-  SEGGER_REQUIRE(is_aligned(xy, 16) && is_aligned(xy_out, 16), "%s: xy and xy_out must be 16-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(ring_offsets, 8) && is_aligned(n_transcripts, 8) && is_aligned(counters, 8),
-                 "%s: ring_offsets, n_transcripts and counters must be 8-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(cell, 4) && is_aligned(cell_ids, 4), "%s: cell and cell_ids must be 4-byte aligned", who);
-  SEGGER_REQUIRE(is_aligned(workspace, 256), "%s: workspace must be 256-byte aligned", who);
   const LargeLayout l = large_layout(n_rows, n_cells, large_rows);
-  SEGGER_REQUIRE((size_t)workspace_bytes >= l.total, "%s: workspace %lld < %zu bytes", who, (long long)workspace_bytes, l.total);
+  bool empty = false;
+  rc = check_cell_rings_call(who, a, l.total, [&] {
+    SEGGER_REQUIRE(connectivity > 0.0 && connectivity - connectivity == 0.0, "%s: connectivity = %g is not a finite number > 0", who,
+                   connectivity);
+    SEGGER_REQUIRE(lds_max_points >= 0 && lds_max_points <= SEGGER_OUTLINE_MAX_POINTS, "%s: lds_max_points = %d outside 0 .. %d", who,
+                   (int)lds_max_points, SEGGER_OUTLINE_MAX_POINTS);
+    return SEGGER_OK;
+  }, &empty);
+  if (rc != SEGGER_OK || empty) return rc;
 
-  int32_t* words = at<int32_t>(workspace, l.rings.words);
-  int32_t* list_short = at<int32_t>(workspace, l.rings.list_short);
-  int32_t* list_long = at<int32_t>(workspace, l.rings.list_long);
-  unsigned long long* keys_in = at<unsigned long long>(workspace, l.hull);       // dead once sorted: the rings go there
-  unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
-  int32_t* head = at<int32_t>(workspace, l.head);
-  int32_t* kept_seg = at<int32_t>(workspace, l.kept_seg);
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
-  const BndSegs s{keys, head, at<int32_t>(workspace, l.len), at<int32_t>(workspace, l.hull_n), at<double2>(workspace, l.hull)};
-  const LargeLists ll{words, at<int32_t>(workspace, l.list_large), at<int64_t>(workspace, l.at_large)};
+  const CellRingsViews v = cell_rings_views(a, l.head);
+  const BndSegs& s = v.s;
+  const LargeLists ll{v.words, at<int32_t>(workspace, l.list_large), at<int64_t>(workspace, l.at_large)};
   const LargeArrays A{at<double2>(workspace, l.pts),   at<uint8_t>(workspace, l.flg),   at<uint32_t>(workspace, l.tv),
                       at<uint32_t>(workspace, l.nb),   at<uint8_t>(workspace, l.ef),    at<uint32_t>(workspace, l.label),
                       at<unsigned long long>(workspace, l.hkey), at<uint32_t>(workspace, l.hid)};
   const OutParams prm{connectivity};
   const int cus = cu_count_or_default();
-  const int64_t cap = l.cells_cap;
+  const int64_t cap = l.head.cells_cap;
   const int lds_max = (int)lds_max_points;
 
-  SEGGER_HIP(hipMemsetAsync(words, 0, kRingWordsBytes, stream));
-  SEGGER_HIP(hipMemsetAsync(cnt, 0, SEGGER_OUTLINE_LARGE_COUNTERS * sizeof(unsigned long long), stream));
-  hipLaunchKernelGGL(bnd_keys_kernel, dim3(grid_stride_blocks(n_rows, kBndThreads, (int64_t)cus * 32)), dim3(kBndThreads), 0, stream,
-                     xy, cell, keep, n_rows, n_cells, keys_in, cnt);
-  SEGGER_LAUNCH_CHECK("bnd_keys_kernel");
-  size_t temp_bytes = l.temp_bytes;
-  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, l.temp), temp_bytes, keys_in, keys, (size_t)n_rows, 0,
-                                                           (unsigned)l.key_bits, stream));
-  temp_bytes = l.temp_bytes;
-  SEGGER_HIP(rocprim::select(at<char>(workspace, l.temp), temp_bytes, rocprim::counting_iterator<int32_t>(0), head,
-                             reinterpret_cast<size_t*>(cnt + kPresent), (size_t)n_rows,
-                             BndCellHead{keys, (unsigned long long)n_cells << 32}, stream));
-  hipLaunchKernelGGL(outl_bin_kernel, dim3(grid_stride_blocks(cap, kBndThreads, (int64_t)cus * 8)), dim3(kBndThreads), 0, stream, s, cnt,
-                     list_short, list_long, ll, lds_max, large_rows);
+  rc = launch_cell_rings_front(a, l.head, v, SEGGER_OUTLINE_LARGE_COUNTERS, cus, stream);
+  if (rc != SEGGER_OK) return rc;
+  hipLaunchKernelGGL(outl_bin_kernel, dim3(grid_stride_blocks(cap, kBndThreads, (int64_t)cus * 8)), dim3(kBndThreads), 0, stream, s, v.cnt,
+                     v.list_short, v.list_long, ll, lds_max, large_rows);
   SEGGER_LAUNCH_CHECK("outl_bin_kernel");
   if (lds_max > 0) {
     hipLaunchKernelGGL((outl_lds_kernel<kOutSmall>), dim3(grid_stride_blocks(cap, 1, (int64_t)cus * 9)), dim3(kWave), 0, stream, xy, s,
-                       (int)kWordShort, (const int32_t*)list_short, prm, lds_max < kOutSmall ? lds_max : kOutSmall, ll, large_rows, cnt);
+                       (int)kWordShort, (const int32_t*)v.list_short, prm, lds_max < kOutSmall ? lds_max : kOutSmall, ll, large_rows, v.cnt);
     SEGGER_LAUNCH_CHECK("outl_lds_kernel<256>");
     hipLaunchKernelGGL((outl_lds_kernel<kOutMax>), dim3(grid_stride_blocks(n_rows / (kOutSmall + 1), 1, (int64_t)cus)), dim3(kWave), 0,
-                       stream, xy, s, (int)kWordLong, (const int32_t*)list_long, prm, lds_max, ll, large_rows, cnt);
+                       stream, xy, s, (int)kWordLong, (const int32_t*)v.list_long, prm, lds_max, ll, large_rows, v.cnt);
     SEGGER_LAUNCH_CHECK("outl_lds_kernel<max>");
   }
   if (large_rows > 0) {                            // a cell of the large route has more than lds_max rows
     hipLaunchKernelGGL(outl_large_kernel, dim3(grid_stride_blocks(large_rows / (lds_max + 1), 1, (int64_t)cus * 4)), dim3(kLgThreads), 0,
-                       stream, xy, s, ll, A, prm, cnt);
+                       stream, xy, s, ll, A, prm, v.cnt);
     SEGGER_LAUNCH_CHECK("outl_large_kernel");
   }
-  hipLaunchKernelGGL(bnd_scan_kernel, dim3(1), dim3(kBndScanThreads), 0, stream, s, (int)smoothing, kept_seg, ring_offsets, cell_ids,
-                     n_transcripts, cnt);
-  SEGGER_LAUNCH_CHECK("bnd_scan_kernel");
-  launch_emit_for((int)smoothing, grid_stride_blocks(cap, kBndWaves, (int64_t)cus * 8), stream, s, kept_seg, ring_offsets, cnt,
-                  reinterpret_cast<double2*>(xy_out), xy_capacity);
-  SEGGER_LAUNCH_CHECK("bnd_emit_kernel");
-  return SEGGER_OK;
+  return launch_cell_rings_back(a, l.head, v, cus, stream);
 }

@@ -3,7 +3,8 @@
 // over polygons.buffer(d) (src/segger/data/utils/neighbors.py:223-238).  include/segger_amd.h has the contract and the
 // predicate; this is the exact offset of the ring (Minkowski sum with a disc), not GEOS's polyline approximation of it.
 //
-// Six kernels and one radix sort on one stream, no host synchronisation:
+// Six kernels and one radix sort on one stream, no host synchronisation (the grid and its cell_of are rings.h's; the
+// scan kernel and the slot of a match, hit_slot, are post_common.h's):
 //   pjoin_keys_kernel   one thread per point: key = cell << 32 | point id (cells clamped to the nx x ny grid);
 //   (rocprim keys sort: stable by construction, the id is part of the key)
 //   pjoin_cells_kernel  one thread per sorted position: cell_start[] and the cell-ordered float64 copy of the points (the
@@ -13,13 +14,13 @@
 //   pjoin_short_kernel  n <= 64: one wave per polygon, the ring in registers, edges broadcast by readlane, no LDS;
 //   pjoin_long_kernel   64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the ring in LDS (64 KB),
 //                       every lane reading the same edge (an LDS broadcast);
-//   pjoin_scan_kernel   one workgroup: counts -> pair_offsets, in place.
+//   counts_to_offsets_kernel<int64>  one workgroup: counts -> pair_offsets, in place.
 // The two polygon kernels are templates on "count" / "fill" over ONE traversal (polygon_body): the wave walks the rows of
 // grid cells that overlap the ring's bounds grown by d and a rounding margin, each row one contiguous span of the
 // cell-ordered points, 64 points at a time, one point per lane, and loops over the edges accumulating the crossing parity
-// and the smallest squared distance.  A match's slot is the polygon's offset + the matches before it in the traversal (a
-// running count + ballot + prefix popcount): no atomic decides a slot, so the list of a polygon is in (cell row, cell,
-// point id) order whatever the scheduling, and the same call gives the same bytes.
+// and the smallest squared distance.  A match's slot is the polygon's offset + the matches before it in the traversal
+// (hit_slot): no atomic decides a slot, so the list of a polygon is in (cell row, cell, point id) order whatever the
+// scheduling, and the same call gives the same bytes.
 //
 // Arithmetic: float64, the point and the vertices translated to the ring's first vertex, FMA contraction off, so with
 // coordinates that are exactly representable after the translation the cross product, and with it the parity and "on the
@@ -42,18 +43,9 @@ namespace {
 
 constexpr int kPjThreads = 256;
 constexpr int kPjWaves = kPjThreads / kWave;
-constexpr int kScanThreads = 1024;
-
-struct PjGrid { double x0, y0, inv_cell; int nx, ny; };
-
-// the cell of a coordinate, clamped into 0 .. n - 1 (NaN -> 0): monotone in v, which is what the walk relies on
-__device__ __forceinline__ int cell_of(double v, double origin, double inv_cell, int n) {
-  const double c = floor((v - origin) * inv_cell);
-  return (int)fmin(fmax(c, 0.0), (double)(n - 1));
-}
 
 // ---------------------------------------------------------------- the points ---
-__global__ __launch_bounds__(kPjThreads) void pjoin_keys_kernel(const double* __restrict__ pts, int64_t n, PjGrid g,
+__global__ __launch_bounds__(kPjThreads) void pjoin_keys_kernel(const double* __restrict__ pts, int64_t n, UniformGrid g,
                                                                 unsigned long long* __restrict__ keys) {
   const int64_t stride = (int64_t)gridDim.x * kPjThreads;
   for (int64_t i = (int64_t)blockIdx.x * kPjThreads + threadIdx.x; i < n; i += stride) {
@@ -107,7 +99,7 @@ struct JoinArgs {
   const double* xy;
   const double* buffer;                                              // [P] or NULL = 0
   int predicate;
-  PjGrid g;
+  UniformGrid g;
   const int32_t* cell_start;
   const double2* pts;                                                // cell-ordered
   const unsigned long long* keys;                                    // cell-ordered; the low word is the point id
@@ -174,12 +166,7 @@ __device__ __forceinline__ void polygon_body(const Ring& ring, int n, P2 org, do
       }
       const bool hit = valid && (a.predicate == SEGGER_PJOIN_CONTAINS ? (best < dd || (inside && best > 0.0))
                                                                       : (best <= dd || inside));
-      const unsigned long long mask = __ballot(hit);
-      if (kFill && hit) {
-        const int64_t slot = begin + found + (int64_t)__popcll(mask & ((1ull << lane) - 1));
-        if (slot >= 0 && slot < end) a.out[slot] = (int64_t)(a.keys[s] & 0xffffffffull);
-      }
-      found += (int64_t)__popcll(mask);
+      hit_slot<kFill>(hit, begin, end, found, [&](int64_t slot) { a.out[slot] = (int64_t)(a.keys[s] & 0xffffffffull); });
     }
   }
   if (lane == 0) {
@@ -210,33 +197,6 @@ __global__ __launch_bounds__(kWave) void pjoin_long_kernel(JoinArgs a, const int
     LdsRing ring{pts};
     polygon_body<kFill>(ring, r.n, r.first, wave_min_f64(r.xmin), wave_min_f64(r.ymin), wave_max_f64(r.xmax), wave_max_f64(r.ymax),
                         p, a);
-  }
-}
-
-// pair_offsets[1 .. P] holds the counts; afterwards pair_offsets[p] = the counts of the polygons before p
-__global__ __launch_bounds__(kScanThreads) void pjoin_scan_kernel(int64_t* __restrict__ pair_offsets, int64_t P) {
-  __shared__ int64_t wave_total[kScanThreads / kWave];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < P; base += kScanThreads) {
-    const int64_t i = base + threadIdx.x;
-    int64_t v = i < P ? pair_offsets[i + 1] : 0;
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {                            // inclusive scan of the wave
-      const int64_t o = (int64_t)shfl64((uint64_t)v, lane >= s ? lane - s : lane);
-      if (lane >= s) v += o;
-    }
-    if (lane == kWave - 1) wave_total[wave] = v;
-    __syncthreads();
-    int64_t before = carry, all = carry;
-    for (int w = 0; w < kScanThreads / kWave; ++w) {
-      const int64_t t = wave_total[w];
-      if (w < wave) before += t;
-      all += t;
-    }
-    if (i < P) pair_offsets[i + 1] = before + v;
-    carry = all;
-    __syncthreads();                                                 // wave_total is rewritten by the next chunk
   }
 }
 
@@ -302,7 +262,7 @@ JoinArgs join_args(const PjCall& c, const PjLayout& l, int64_t* pair_offsets, in
   a.xy = c.xy;
   a.buffer = c.buffer;
   a.predicate = c.predicate;
-  a.g = PjGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny};
+  a.g = UniformGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny};
   a.cell_start = at<int32_t>(c.workspace, l.cell_start);
   a.pts = at<double2>(c.workspace, l.pts);
   a.keys = at<unsigned long long>(c.workspace, l.keys);
@@ -370,8 +330,9 @@ extern "C" int segger_polygon_join_count(const double* points, int64_t n_points,
   SEGGER_LAUNCH_CHECK("pjoin_bin_kernel");
   const int rc2 = launch_polygons<false>(c, l, a, stream);
   if (rc2 != SEGGER_OK) return rc2;
-  hipLaunchKernelGGL(pjoin_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, pair_offsets, n_polygons);
-  SEGGER_LAUNCH_CHECK("pjoin_scan_kernel");
+  hipLaunchKernelGGL((counts_to_offsets_kernel<int64_t>), dim3(1), dim3(kScanThreads), 0, stream, pair_offsets, n_polygons,
+                     (int64_t*)nullptr);
+  SEGGER_LAUNCH_CHECK("counts_to_offsets_kernel");
   return SEGGER_OK;
 }
 

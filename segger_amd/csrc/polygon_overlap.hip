@@ -4,11 +4,13 @@
 // the sizing of a segmentation-against-vendor comparison (IoU per cell).  include/segger_amd.h has the contract: the
 // measure-theoretic area formula, the predicate, the arithmetic.
 //
-// Kernels, one stream, no host synchronisation inside an entry point:
+// Kernels, one stream, no host synchronisation inside an entry point (the grid, cell_of and segments_meet are rings.h's; the
+// scan kernel and the slot of a candidate, hit_slot, are post_common.h's):
 //   ov_bin_kernel    one thread per polygon of a set: checks its ring (rings.h), its bounding box, the range of grid cells
 //                    the box covers, and appends it to the list of its route -- "gridded" (at most SEGGER_OVERLAP_WIDE_CELLS
 //                    cells) or "wide"; a gridded polygon of set B adds one to the count of every cell it covers;
-//   ov_scan_kernel   one workgroup: counts -> starts, in place (the cells of the grid; the items of the candidate pass);
+//   counts_to_offsets_kernel<int32 | int64>  one workgroup: counts -> starts, in place (the cells of the grid; the items of
+//                    the candidate pass);
 //   ov_grid_kernel   one thread per gridded polygon of B: its id into every cell it covers (an integer cursor per cell: the
 //                    order within a cell is the scheduling's, and nothing that is returned depends on it);
 //   ov_cand_kernel   count / fill over ONE traversal, one wave per item.  Item a < Pa is polygon a of A: gridded, it walks
@@ -41,19 +43,10 @@ namespace {
 
 constexpr int kOvThreads = 256;
 constexpr int kOvWaves = kOvThreads / kWave;
-constexpr int kOvScanThreads = 1024;
 constexpr int kOvSmallCap = SEGGER_OVERLAP_SMALL_VERTS;
 constexpr int kOvLargeCap = SEGGER_MORPH_MAX_VERTS;
 // int32 words of the workspace's first region: set A's flag and list lengths at 0 .. 2 (rings.h), set B's at 8 .. 10
 constexpr int kWordsB = 8, kWordLdsPairs = 16;
-
-struct OvGrid { double x0, y0, inv_cell; int nx, ny; };
-
-// the cell of a coordinate, clamped into 0 .. n - 1 (NaN -> 0): monotone in v, which is what the pair rule relies on
-__device__ __forceinline__ int cell_of(double v, double origin, double inv_cell, int n) {
-  const double c = floor((v - origin) * inv_cell);
-  return (int)fmin(fmax(c, 0.0), (double)(n - 1));
-}
 
 __device__ __forceinline__ bool is_wide(int4 c) { return (int64_t)(c.z - c.x + 1) * (c.w - c.y + 1) > SEGGER_OVERLAP_WIDE_CELLS; }
 // closed boxes
@@ -66,7 +59,7 @@ struct OvSet {
   int32_t *words, *list_grid, *list_wide;
 };
 
-__global__ __launch_bounds__(kOvThreads) void ov_bin_kernel(OvSet s, OvGrid g, int32_t* __restrict__ cell_count) {
+__global__ __launch_bounds__(kOvThreads) void ov_bin_kernel(OvSet s, UniformGrid g, int32_t* __restrict__ cell_count) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t stride = (int64_t)gridDim.x * kOvThreads;
   // whole waves iterate together: append_by_route needs every lane of a wave in the loop
@@ -101,40 +94,8 @@ __global__ __launch_bounds__(kOvThreads) void ov_bin_kernel(OvSet s, OvGrid g, i
   }
 }
 
-// v[1 .. n] holds counts; afterwards v[i] = the counts before i, v[n] the total (v[0] = 0 is written); *total, if given, too
-template <class T>
-__global__ __launch_bounds__(kOvScanThreads) void ov_scan_kernel(T* __restrict__ v, int64_t n, int64_t* __restrict__ total) {
-  __shared__ int64_t wave_total[kOvScanThreads / kWave];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < n; base += kOvScanThreads) {
-    const int64_t i = base + threadIdx.x;
-    int64_t x = i < n ? (int64_t)v[i + 1] : 0;
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {                            // inclusive scan of the wave
-      const int64_t o = (int64_t)shfl64((uint64_t)x, lane >= s ? lane - s : lane);
-      if (lane >= s) x += o;
-    }
-    if (lane == kWave - 1) wave_total[wave] = x;
-    __syncthreads();
-    int64_t before = carry, all = carry;
-    for (int w = 0; w < kOvScanThreads / kWave; ++w) {
-      const int64_t t = wave_total[w];
-      if (w < wave) before += t;
-      all += t;
-    }
-    if (i < n) v[i + 1] = (T)(before + x);
-    carry = all;
-    __syncthreads();                                                 // wave_total is rewritten by the next chunk
-  }
-  if (threadIdx.x == 0) {
-    v[0] = 0;
-    if (total) *total = carry;
-  }
-}
-
 __global__ __launch_bounds__(kOvThreads) void ov_grid_kernel(const int4* __restrict__ cells, const int32_t* __restrict__ words,
-                                                             const int32_t* __restrict__ list_grid, OvGrid g,
+                                                             const int32_t* __restrict__ list_grid, UniformGrid g,
                                                              const int32_t* __restrict__ cell_start, int32_t* __restrict__ cursor,
                                                              int32_t* __restrict__ entries, int64_t capacity) {
   const int count = words[kWordShort];
@@ -154,7 +115,7 @@ __global__ __launch_bounds__(kOvThreads) void ov_grid_kernel(const int4* __restr
 // ---------------------------------------------------------------- candidates ---
 struct OvCand {
   const double4 *box_a, *box_b; const int4 *cells_a, *cells_b; const int32_t *nv_a, *nv_b;
-  int64_t Pa, Pb; OvGrid g;
+  int64_t Pa, Pb; UniformGrid g;
   const int32_t *cell_start, *entries;
   int64_t* item_off;                                                 // [Pa + Pb + 1]: count writes [i + 1], fill reads
   int64_t* cand; int64_t capacity;                                   // fill: a << 32 | b
@@ -181,12 +142,7 @@ __device__ __forceinline__ int64_t span_test(const OvCand& c, int64_t me, double
         }
       }
     }
-    const unsigned long long m = __ballot(hit);
-    if (kFill && hit) {
-      const int64_t slot = begin + found + (int64_t)__popcll(m & ((1ull << lane) - 1));
-      if (slot >= 0 && slot < end) c.cand[slot] = kMode == 2 ? ((other << 32) | me) : ((me << 32) | other);
-    }
-    found += (int64_t)__popcll(m);
+    hit_slot<kFill>(hit, begin, end, found, [&](int64_t slot) { c.cand[slot] = kMode == 2 ? ((other << 32) | me) : ((me << 32) | other); });
   }
   return found;
 }
@@ -224,19 +180,7 @@ __global__ __launch_bounds__(kOvThreads) void ov_cand_kernel(OvCand c) {
 }
 
 // ---------------------------------------------------------------- the pair ---
-__device__ __forceinline__ int orient(P2 a, P2 b, P2 c) {
-  const double d = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x);
-  return (int)(d > 0.0) - (int)(d < 0.0);
-}
-__device__ __forceinline__ bool in_box(P2 p, P2 a, P2 b) {
-  return fmin(a.x, b.x) <= p.x && p.x <= fmax(a.x, b.x) && fmin(a.y, b.y) <= p.y && p.y <= fmax(a.y, b.y);
-}
-// the closed segments (a, b) and (c, d) share a point: simplify.hip's touch without its shared-endpoint exemption
-__device__ __forceinline__ bool segments_meet(P2 a, P2 b, P2 c, P2 d) {
-  const int o1 = orient(a, b, c), o2 = orient(a, b, d), o3 = orient(c, d, a), o4 = orient(c, d, b);
-  if (o1 * o2 < 0 && o3 * o4 < 0) return true;
-  return (o1 == 0 && in_box(c, a, b)) || (o2 == 0 && in_box(d, a, b)) || (o3 == 0 && in_box(a, c, d)) || (o4 == 0 && in_box(b, c, d));
-}
+// (segments_meet is rings.h's, defined next to simplify.hip's touch)
 // y of the line through p and q (p.x != q.x) at x; an endpoint's own y at an endpoint's x, so shared vertices agree bit for bit
 __device__ __forceinline__ double y_at(P2 p, P2 q, double x) {
   if (x == p.x) return p.y;
@@ -462,7 +406,7 @@ OvSet ov_set(const OvCall& c, const OvLayout& l, bool b) {
 OvCand ov_cand(const OvCall& c, const OvLayout& l, int64_t* cand, int64_t capacity) {
   void* ws = c.workspace;
   return OvCand{at<double4>(ws, l.box_a), at<double4>(ws, l.box_b), at<int4>(ws, l.cells_a), at<int4>(ws, l.cells_b),
-                at<int32_t>(ws, l.nv_a), at<int32_t>(ws, l.nv_b), c.Pa, c.Pb, OvGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny},
+                at<int32_t>(ws, l.nv_a), at<int32_t>(ws, l.nv_b), c.Pa, c.Pb, UniformGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny},
                 at<int32_t>(ws, l.cell_start), at<int32_t>(ws, l.entries), at<int64_t>(ws, l.item_off), cand, capacity};
 }
 
@@ -507,8 +451,8 @@ extern "C" int segger_polygon_overlap_candidates(const int64_t* ring_offsets_a, 
   hipLaunchKernelGGL(ov_bin_kernel, dim3(grid_stride_blocks(c.Pb, kOvThreads, (int64_t)cus * 8)), dim3(kOvThreads), 0, stream, sb, k.g,
                      cell_start);
   SEGGER_LAUNCH_CHECK("ov_bin_kernel<b>");
-  hipLaunchKernelGGL((ov_scan_kernel<int32_t>), dim3(1), dim3(kOvScanThreads), 0, stream, cell_start, n_cells, (int64_t*)nullptr);
-  SEGGER_LAUNCH_CHECK("ov_scan_kernel<cells>");
+  hipLaunchKernelGGL((counts_to_offsets_kernel<int32_t>), dim3(1), dim3(kScanThreads), 0, stream, cell_start, n_cells, (int64_t*)nullptr);
+  SEGGER_LAUNCH_CHECK("counts_to_offsets_kernel<cells>");
   hipLaunchKernelGGL(ov_grid_kernel, dim3(grid_stride_blocks(c.Pb, kOvThreads, (int64_t)cus * 8)), dim3(kOvThreads), 0, stream,
                      (const int4*)sb.cells, (const int32_t*)sb.words, (const int32_t*)sb.list_grid, k.g, (const int32_t*)cell_start, cursor,
                      at<int32_t>(workspace, l.entries), c.Pb * SEGGER_OVERLAP_WIDE_CELLS);
@@ -516,8 +460,8 @@ extern "C" int segger_polygon_overlap_candidates(const int64_t* ring_offsets_a, 
   hipLaunchKernelGGL((ov_cand_kernel<false>), dim3(grid_stride_blocks(c.Pa + c.Pb, kOvWaves, (int64_t)cus * 16)), dim3(kOvThreads), 0,
                      stream, k);
   SEGGER_LAUNCH_CHECK("ov_cand_kernel<count>");
-  hipLaunchKernelGGL((ov_scan_kernel<int64_t>), dim3(1), dim3(kOvScanThreads), 0, stream, k.item_off, c.Pa + c.Pb, n_candidates);
-  SEGGER_LAUNCH_CHECK("ov_scan_kernel<items>");
+  hipLaunchKernelGGL((counts_to_offsets_kernel<int64_t>), dim3(1), dim3(kScanThreads), 0, stream, k.item_off, c.Pa + c.Pb, n_candidates);
+  SEGGER_LAUNCH_CHECK("counts_to_offsets_kernel<items>");
   return SEGGER_OK;
 }
 

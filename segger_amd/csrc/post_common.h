@@ -1,7 +1,8 @@
 // Host-side scaffolding shared by the translation units (included after common.h): the predicates that decide whether a
 // pointer may be dereferenced, the rule that places the scratch arrays inside a caller's workspace, the step from a dtype
-// code to an element type, and the whole-wave integer helpers of the post-processing kernels.  One definition each: a
-// fix to the carving rule or to an alignment check is made here and nowhere else.
+// code to an element type, and the integer helpers of the post-processing kernels: the whole-wave sums, the one-workgroup
+// scan (GroupScan, and the counts-to-offsets kernel made of it alone) and the slot of a hit in a count / fill traversal.
+// One definition each: a fix to the carving rule, to an alignment check or to the scan is made here and nowhere else.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -92,6 +93,83 @@ __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
 #pragma unroll
   for (int m = 1; m < kWave; m <<= 1) v += (int64_t)shfl_xor64((uint64_t)v, m);
   return v;
+}
+
+// ---------------------------------------------------------------- device: the one-workgroup scan ---
+// What a scan adds up: an int64, or an int64 and an int scanned together in one pass (vertices and kept rings).
+struct ScanPair { int64_t v; int k; };
+__device__ __forceinline__ ScanPair operator+(ScanPair a, ScanPair b) { return ScanPair{a.v + b.v, a.k + b.k}; }
+__device__ __forceinline__ ScanPair operator-(ScanPair a, ScanPair b) { return ScanPair{a.v - b.v, a.k - b.k}; }
+__device__ __forceinline__ int64_t scan_shfl(int64_t a, int src) { return (int64_t)shfl64((uint64_t)a, src); }
+__device__ __forceinline__ ScanPair scan_shfl(ScanPair a, int src) { return ScanPair{scan_shfl(a.v, src), __shfl(a.k, src, kWave)}; }
+
+constexpr int kScanThreads = 1024;                                   // the workgroup of the scan kernels
+
+// A scan over more items than the workgroup has threads, kThreads items a chunk: an inclusive shuffle scan per wave, the
+// waves' totals in LDS (`totals`, kThreads / kWave entries), a linear sum over the waves, and the carry of the chunks
+// before.  step(mine), called by every thread of the workgroup with its item's value (zero past the end), returns the
+// carry plus the values of the chunk's earlier threads -- the exclusive sum at the item -- and moves the carry on.  Two
+// barriers a step, whatever T; after the last step `carry` is the total, in every thread.  Integer sums: no order shows.
+template <int kThreads, class T>
+struct GroupScan {
+  T* totals;
+  T carry;
+  __device__ __forceinline__ T step(T mine) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    T v = mine;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {                            // inclusive scan of the wave
+      const T o = scan_shfl(v, lane >= d ? lane - d : lane);
+      if (lane >= d) v = v + o;
+    }
+    if (lane == kWave - 1) totals[wave] = v;
+    __syncthreads();
+    T before = carry, all = carry;
+    for (int w = 0; w < kThreads / kWave; ++w) {
+      const T t = totals[w];
+      if (w < wave) before = before + t;
+      all = all + t;
+    }
+    carry = all;
+    __syncthreads();                                                 // the totals are rewritten by the next step
+    return before + v - mine;
+  }
+};
+
+namespace {
+// v[1 .. n] holds counts; afterwards v[i] = the counts before i, v[n] the total (v[0] = 0 is written); *total, if given, too.
+// One workgroup.  Every including unit that launches it gets its own copy, as with cell_rings.h's kernels.
+template <class T>
+__global__ __launch_bounds__(kScanThreads) void counts_to_offsets_kernel(T* __restrict__ v, int64_t n, int64_t* __restrict__ total) {
+  __shared__ int64_t totals[kScanThreads / kWave];
+  GroupScan<kScanThreads, int64_t> scan{totals, 0};
+  for (int64_t base = 0; base < n; base += kScanThreads) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t mine = i < n ? (int64_t)v[i + 1] : 0;
+    const int64_t before = scan.step(mine);
+    if (i < n) v[i + 1] = (T)(before + mine);
+  }
+  if (threadIdx.x == 0) {
+    v[0] = 0;
+    if (total) *total = scan.carry;
+  }
+}
+}  // namespace
+
+// ---------------------------------------------------------------- device: the slot of a hit, count / fill ---
+// A traversal that a count pass and a fill pass walk alike, one wave, 64 candidates a step.  Every lane calls this once a
+// step: `found` is the hits of the steps before and moves on by this step's; the slot of a lane with a hit is begin + found
+// + the hit lanes below it, and write(slot) runs if that is in [0, end) (kWrite = false: the count pass, never).  No atomic
+// decides a slot, so the order of a list is the traversal's whatever the scheduling, and the same call gives the same bytes.
+template <bool kWrite = true, class F>
+__device__ __forceinline__ void hit_slot(bool hit, int64_t begin, int64_t end, int64_t& found, F&& write) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const unsigned long long m = __ballot(hit);
+  if (kWrite && hit) {
+    const int64_t slot = begin + found + (int64_t)__popcll(m & ((1ull << lane) - 1));
+    if (slot >= 0 && slot < end) write(slot);
+  }
+  found += (int64_t)__popcll(m);
 }
 
 // float bits whose unsigned order is the float order: -0.0 sorts just below +0.0 as a value of its own and NaNs are the

@@ -6,7 +6,9 @@
 // read the list lengths from the workspace words and load what the binning kernel counted.  One definition each: the units
 // agree on "entries", "open vertices" and "route" because they run the same code, and a fix is made here and nowhere else.
 // The gift-wrapping march of morphology.hip is here too, because boundaries.hip runs it over a cell's transcripts (that unit
-// reads no ring CSR -- it writes one -- and uses the stores, append_by_route and the march).
+// reads no ring CSR -- it writes one -- and uses the stores, append_by_route and the march).  So is the plane geometry that
+// two units share: the uniform double grid with its monotone cell_of (polygon_join.hip, polygon_overlap.hip) and the segment
+// predicates orient, same, in_box, segments_meet and touch (polygon_overlap.hip, simplify.hip).
 //
 // Floating point: this header sets `#pragma clang fp contract(off)` itself, to the end of the including unit.  The loaders
 // only subtract, but wave_sum_f64's additions are inlined next to the callers' products, which must not fuse with them.
@@ -57,6 +59,49 @@ __device__ __forceinline__ double wave_max_f64(double v) {
 #pragma unroll
   for (int m = 1; m < kWave; m <<= 1) v = fmax(v, shfl_xor_f64(v, m));
   return v;
+}
+
+// ---------------------------------------------------------------- the uniform grid of the joins ---
+// nx x ny square cells from (x0, y0), inv_cell = 1 / side.  (knn.hip's float grid is another struct under another contract.)
+struct UniformGrid { double x0, y0, inv_cell; int nx, ny; };
+
+// The cell of a coordinate, clamped into 0 .. n - 1 (NaN -> 0).  MONOTONE in v: that is what polygon_join.hip's walk (a
+// point inside the grown bounds is in a walked cell) and polygon_overlap.hip's pair rule (the cell of the lower-left corner
+// of two boxes' intersection is the maximum of their first cells) rely on, whatever the grid.
+__device__ __forceinline__ int cell_of(double v, double origin, double inv_cell, int n) {
+  const double c = floor((v - origin) * inv_cell);
+  return (int)fmin(fmax(c, 0.0), (double)(n - 1));
+}
+
+// ---------------------------------------------------------------- segment predicates ---
+// One expression each, contraction off: exact when the coordinate differences and their products are representable.
+__device__ __forceinline__ int orient(P2 a, P2 b, P2 c) {
+  const double d = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x);
+  return (int)(d > 0.0) - (int)(d < 0.0);
+}
+__device__ __forceinline__ bool same(P2 a, P2 b) { return a.x == b.x && a.y == b.y; }
+// p is collinear with (a, b) already: is it on the closed segment?
+__device__ __forceinline__ bool in_box(P2 p, P2 a, P2 b) {
+  return fmin(a.x, b.x) <= p.x && p.x <= fmax(a.x, b.x) && fmin(a.y, b.y) <= p.y && p.y <= fmax(a.y, b.y);
+}
+// p lies on (a, b) and is neither a nor b
+__device__ __forceinline__ bool inside_of(int o, P2 p, P2 a, P2 b) { return o == 0 && in_box(p, a, b) && !same(p, a) && !same(p, b); }
+
+// Two predicates over the closed segments (a, b) and (c, d); both hold at a proper crossing.  They differ at endpoints:
+// segments_meet holds whenever the segments share any point, an endpoint included (the overlap join's "intersects");
+// touch exempts a shared endpoint -- consecutive edges of a ring meet at one and are not a defect -- and holds only when
+// an endpoint of one lies strictly inside the other, or when both are the same segment, longer than a point (the
+// simplifier's guard and the ring validity of include/segger_amd.h).
+__device__ __forceinline__ bool segments_meet(P2 a, P2 b, P2 c, P2 d) {
+  const int o1 = orient(a, b, c), o2 = orient(a, b, d), o3 = orient(c, d, a), o4 = orient(c, d, b);
+  if (o1 * o2 < 0 && o3 * o4 < 0) return true;
+  return (o1 == 0 && in_box(c, a, b)) || (o2 == 0 && in_box(d, a, b)) || (o3 == 0 && in_box(a, c, d)) || (o4 == 0 && in_box(b, c, d));
+}
+__device__ __forceinline__ bool touch(P2 a, P2 b, P2 c, P2 d) {
+  const int o1 = orient(a, b, c), o2 = orient(a, b, d), o3 = orient(c, d, a), o4 = orient(c, d, b);
+  if (o1 * o2 < 0 && o3 * o4 < 0) return true;                       // a proper crossing
+  if (inside_of(o1, c, a, b) || inside_of(o2, d, a, b) || inside_of(o3, a, c, d) || inside_of(o4, b, c, d)) return true;
+  return !same(a, b) && ((same(a, c) && same(b, d)) || (same(a, d) && same(b, c)));      // the same segment, longer than a point
 }
 
 // ---------------------------------------------------------------- the two ring stores ---

@@ -1,8 +1,9 @@
 // segger_simplify_rings_mark / _emit and segger_rings_simple: the two steps the reference's CosMx intake takes right after
 // masks_to_contours -- `geometry.simplify(tolerance)` (GEOS's topology-preserving simplifier, src/segger/io/cosmx.py:94-96)
 // and the `is_valid` that fix_invalid_geometry asks first (io/utils.py:127-136) -- over the project's ring CSR.
-// include/segger_amd.h has the contract: guarded Douglas-Peucker over the closed vertex sequence, `touch` of two segments,
-// what a simple ring is.  UNPINNED against GEOS (never run): see the header.
+// include/segger_amd.h has the contract: guarded Douglas-Peucker over the closed vertex sequence, `touch` of two segments
+// (rings.h defines it, next to the overlap join's segments_meet), what a simple ring is.  UNPINNED against GEOS (never
+// run): see the header.
 //
 // Kernels, one stream, no host synchronisation inside an entry point:
 //   sr_bin_kernel     one thread per polygon: checks its ring (rings.h) and its tolerance, passes a ring of fewer than 3
@@ -12,9 +13,10 @@
 //                     farthest vertex (lowest index among equals); the guard is a strided loop over the input edges outside
 //                     the section and the chords emitted so far, with a ballot for "any touch".  Writes the keep mask (one
 //                     byte per input vertex) and the ring's four statistics into the workspace;
-//   sr_scan_kernel    one workgroup: the kept counts -> out_offsets, the statistics -> the counters (integer sums: the same
-//                     bytes whatever the order);
-//   sr_emit_kernel    one wave per ring: the kept vertices' INPUT bytes and their indices, slot = offset + ballot prefix;
+//   sr_scan_kernel    one workgroup: the kept counts -> out_offsets (post_common.h's GroupScan), the statistics -> the
+//                     counters (integer sums: the same bytes whatever the order);
+//   sr_emit_kernel    one wave per ring: the kept vertices' INPUT bytes and their indices, each at its hit_slot
+//                     (post_common.h);
 //   sr_valid_kernel   one single-wave workgroup per ring: for edge i (uniform) the lanes stride over the edges j > i; the
 //                     first lane of the first ballot that is not empty is the lowest j, so the reported pair is the lowest
 //                     in (i, j) order whatever the scheduling -- no atomic decides it.
@@ -52,25 +54,7 @@ constexpr int kLargeCap = SEGGER_MORPH_MAX_VERTS;
 constexpr int kKindPass = 1, kKindRestored = 2;                      // bits 24 .. of a ring's fourth statistic
 
 // ---------------------------------------------------------------- the predicates of the contract ---
-__device__ __forceinline__ int orient(P2 a, P2 b, P2 c) {
-  const double d = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x);
-  return (int)(d > 0.0) - (int)(d < 0.0);
-}
-__device__ __forceinline__ bool same(P2 a, P2 b) { return a.x == b.x && a.y == b.y; }
-// p is collinear with (a, b) already: is it on the closed segment?
-__device__ __forceinline__ bool in_box(P2 p, P2 a, P2 b) {
-  return fmin(a.x, b.x) <= p.x && p.x <= fmax(a.x, b.x) && fmin(a.y, b.y) <= p.y && p.y <= fmax(a.y, b.y);
-}
-// p lies on (a, b) and is neither a nor b
-__device__ __forceinline__ bool inside_of(int o, P2 p, P2 a, P2 b) { return o == 0 && in_box(p, a, b) && !same(p, a) && !same(p, b); }
-
-__device__ __forceinline__ bool touch(P2 a, P2 b, P2 c, P2 d) {
-  const int o1 = orient(a, b, c), o2 = orient(a, b, d), o3 = orient(c, d, a), o4 = orient(c, d, b);
-  if (o1 * o2 < 0 && o3 * o4 < 0) return true;                       // a proper crossing
-  if (inside_of(o1, c, a, b) || inside_of(o2, d, a, b) || inside_of(o3, a, c, d) || inside_of(o4, b, c, d)) return true;
-  return !same(a, b) && ((same(a, c) && same(b, d)) || (same(a, d) && same(b, c)));      // the same segment, longer than a point
-}
-
+// (touch and same are rings.h's)
 __device__ __forceinline__ double dist2(P2 v, P2 a, P2 b) {
   const double ex = b.x - a.x, ey = b.y - a.y;
   const double wx = v.x - a.x, wy = v.y - a.y;
@@ -234,7 +218,7 @@ __global__ __launch_bounds__(kSrScanThreads) void sr_scan_kernel(const int4* __r
   __shared__ int64_t wave_total[kSrScanThreads / kWave];
   __shared__ int64_t sums[SEGGER_SIMPLIFY_COUNTERS][kSrScanThreads / kWave];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  int64_t carry = 0;
+  GroupScan<kSrScanThreads, int64_t> scan{wave_total, 0};
   int64_t acc[SEGGER_SIMPLIFY_COUNTERS] = {};
   for (int64_t base = 0; base < P; base += kSrScanThreads) {
     const int64_t i = base + threadIdx.x;
@@ -242,23 +226,8 @@ __global__ __launch_bounds__(kSrScanThreads) void sr_scan_kernel(const int4* __r
     acc[0] += s.y; acc[1] += s.x; acc[2] += s.z; acc[3] += s.w & 0xffffff;
     acc[4] += (s.w >> 24) == kKindPass; acc[5] += (s.w >> 24) == kKindRestored;
     acc[6] = acc[6] > s.x ? acc[6] : (int64_t)s.x;
-    int64_t v = s.x;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {                            // inclusive scan of the wave
-      const int64_t o = (int64_t)shfl64((uint64_t)v, lane >= d ? lane - d : lane);
-      if (lane >= d) v += o;
-    }
-    if (lane == kWave - 1) wave_total[wave] = v;
-    __syncthreads();
-    int64_t before = carry, all = carry;
-    for (int w = 0; w < kSrScanThreads / kWave; ++w) {
-      const int64_t t = wave_total[w];
-      if (w < wave) before += t;
-      all += t;
-    }
-    if (i < P) out_offsets[i + 1] = before + v;
-    carry = all;
-    __syncthreads();                                                 // wave_total is rewritten by the next chunk
+    const int64_t before = scan.step((int64_t)s.x);
+    if (i < P) out_offsets[i + 1] = before + s.x;
   }
   if (threadIdx.x == 0) out_offsets[0] = 0;
 #pragma unroll
@@ -296,14 +265,10 @@ __global__ __launch_bounds__(kSrThreads) void sr_emit_kernel(const int64_t* __re
     int64_t found = 0;
     for (int64_t base = b; base < e; base += kWave) {
       const int64_t k = base + lane;
-      const bool kept = k < e && mask[k] != 0;
-      const unsigned long long m = __ballot(kept);
-      const int64_t slot = begin + found + (int64_t)__popcll(m & ((1ull << lane) - 1));
-      if (kept && slot >= 0 && slot < end) {
+      hit_slot(k < e && mask[k] != 0, begin, end, found, [&](int64_t slot) {
         reinterpret_cast<double2*>(xy_out)[slot] = reinterpret_cast<const double2*>(xy)[k];
         vertex_index[slot] = k;
-      }
-      found += (int64_t)__popcll(m);
+      });
     }
   }
 }

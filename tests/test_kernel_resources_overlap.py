@@ -12,7 +12,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-KERNELS = ("ov_bin_kernel", "ov_scan_kernel", "ov_grid_kernel", "ov_cand_kernel", "ov_pair_reg_kernel", "ov_pair_lds_kernel")
+# the scan is post_common.h's counts_to_offsets_kernel (once ov_scan_kernel), still one instance per type: 9 rows as before
+KERNELS = ("ov_bin_kernel", "counts_to_offsets_kernel", "ov_grid_kernel", "ov_cand_kernel", "ov_pair_reg_kernel", "ov_pair_lds_kernel")
 LDS_PER_CU = 160 * 1024
 
 
@@ -40,4 +41,4 @@ def test_overlap_kernels_use_no_scratch_and_the_stated_lds(rows):
     assert lds[("ov_pair_lds_kernel", False)] == 2 * 4096 * 16 == 131072
     assert LDS_PER_CU // lds[("ov_pair_lds_kernel", False)] == 1 and LDS_PER_CU // lds[("ov_pair_lds_kernel", True)] >= 16
     assert lds[("ov_bin_kernel", False)] == 0 and lds[("ov_grid_kernel", False)] == 0 and lds[("ov_cand_kernel", False)] == 0
-    assert lds[("ov_scan_kernel", False)] <= 2048
+    assert lds[("counts_to_offsets_kernel", False)] <= 2048
