@@ -9,7 +9,9 @@
 //   out_bin_kernel       one thread per present cell: its length and its route (rings.h: append_by_route);
 //   out_cell_kernel<N>   one single-wave WORKGROUP per cell, the whole per-cell state in LDS, N = 256 for a cell of at
 //                        most 256 rows (17 KB: nine cells per CU) and N = SEGGER_OUTLINE_MAX_POINTS otherwise.
-// The per-cell code itself, outline_cell<N> with its predicates, is in outline_cell.h: outlines_large.hip runs it too.
+// Both kernels and the per-cell code are outline_cell.h's, shared with outlines_large.hip: stages 2 to 6 are written once
+// over a route (outline_stages<R>), and LdsRoute<N> is the route described here.  This unit's own part is what a cell with
+// more distinct points than N gets: the refusal.
 // Why a single-wave workgroup and not a wave of a larger one: the state of a large cell is 136 KB, so only one fits a CU
 // whatever the workgroup's shape, and the triangulation is a chain of dependent steps (a triangle is found, then its
 // edges are looked up) in which more waves would wait on one another at a barrier per step; with one wave a barrier
@@ -53,48 +55,12 @@
 namespace segger {
 namespace {
 
-// ---------------------------------------------------------------- routes ---
-__global__ __launch_bounds__(kBndThreads) void out_bin_kernel(BndSegs s, const unsigned long long* __restrict__ counters,
-                                                              int32_t* __restrict__ words, int32_t* __restrict__ list_short,
-                                                              int32_t* __restrict__ list_long) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t present = (int64_t)counters[kPresent];
-  const int32_t n_counted = (int32_t)counters[kCounted];
-  const int64_t stride = (int64_t)gridDim.x * kBndThreads;
-  // whole waves iterate together: append_by_route needs every lane of a wave in the loop
-  for (int64_t base = (int64_t)blockIdx.x * kBndThreads + (threadIdx.x & ~(kWave - 1)); base < present; base += stride) {
-    const int64_t j = base + lane;
-    int route = -1;
-    if (j < present) {
-      const int32_t n = (j + 1 < present ? s.head[j + 1] : n_counted) - s.head[j];
-      s.len[j] = n;
-      route = n > kOutSmall;
-    }
-    append_by_route(route, j, words, list_short, list_long);
-  }
-}
-
-template <int N>
-__global__ __launch_bounds__(kWave) void out_cell_kernel(const double* __restrict__ xy, BndSegs s, const int32_t* __restrict__ words,
-                                                         int word, const int32_t* __restrict__ list, OutParams prm,
-                                                         unsigned long long* __restrict__ counters) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[OutLds<N>::kBytes];
-  const int count = words[word];
-  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
-    const int j = list[w];
-    __syncthreads();                                                 // the previous cell's readers are done
-    int h = outline_cell<N>(xy, s, j, lds, prm, N);
-    if (h < 0) {
-      if (threadIdx.x == 0) {
-        const unsigned long long id = (s.keys[s.head[j]] >> 32) + 1ull;
-        atomicAdd(counters + (h == kTooMany ? kRefused : kFailed), 1ull);
-        atomicMax(counters + (h == kTooMany ? kRefusedCell : kFailedCell), id);
-      }
-      h = 0;
-    }
-    if (threadIdx.x == 0) s.hull_n[j] = h;
-  }
-}
+// a cell above the capacity of its LDS route is refused through the counters
+struct RefuseTooMany {
+  __device__ __forceinline__ bool every_cell() const { return false; }
+  __device__ __forceinline__ int limit(int n) const { return n; }
+  __device__ __forceinline__ void operator()(const BndSegs& s, int j, int n, unsigned long long* counters) const { refuse_cell(s, j, counters); }
+};
 
 // ---------------------------------------------------------------- host ---
 // cell_rings.h's head and nothing else
@@ -131,11 +97,7 @@ extern "C" int segger_cell_outlines(const double* xy, const int32_t* cell, const
   if (rc != SEGGER_OK) return rc;
   const OutLayout l = out_layout(n_rows, n_cells);
   bool empty = false;
-  rc = check_cell_rings_call(who, a, l.total, [&] {
-    SEGGER_REQUIRE(connectivity > 0.0 && connectivity - connectivity == 0.0, "%s: connectivity = %g is not a finite number > 0", who,
-                   connectivity);
-    return SEGGER_OK;
-  }, &empty);
+  rc = check_cell_rings_call(who, a, l.total, [&] { return check_connectivity(who, connectivity); }, &empty);
   if (rc != SEGGER_OK || empty) return rc;
 
   const CellRingsViews v = cell_rings_views(a, l.head);
@@ -146,14 +108,15 @@ extern "C" int segger_cell_outlines(const double* xy, const int32_t* cell, const
 
   rc = launch_cell_rings_front(a, l.head, v, SEGGER_OUTLINE_COUNTERS, cus, stream);
   if (rc != SEGGER_OK) return rc;
-  hipLaunchKernelGGL(out_bin_kernel, dim3(grid_stride_blocks(cap, kBndThreads, (int64_t)cus * 8)), dim3(kBndThreads), 0, stream, s,
-                     (const unsigned long long*)v.cnt, v.words, v.list_short, v.list_long);
+  const RefuseTooMany refuse;
+  hipLaunchKernelGGL(out_bin_kernel<RefuseTooMany>, dim3(grid_stride_blocks(cap, kBndThreads, (int64_t)cus * 8)), dim3(kBndThreads), 0,
+                     stream, s, v.cnt, v.words, v.list_short, v.list_long, refuse);
   SEGGER_LAUNCH_CHECK("out_bin_kernel");
-  hipLaunchKernelGGL((out_cell_kernel<kOutSmall>), dim3(grid_stride_blocks(cap, 1, (int64_t)cus * 9)), dim3(kWave), 0, stream, xy, s,
-                     (const int32_t*)v.words, (int)kWordShort, (const int32_t*)v.list_short, prm, v.cnt);
+  hipLaunchKernelGGL((out_cell_kernel<kOutSmall, RefuseTooMany>), dim3(grid_stride_blocks(cap, 1, (int64_t)cus * 9)), dim3(kWave), 0,
+                     stream, xy, s, (const int32_t*)v.words, (int)kWordShort, (const int32_t*)v.list_short, prm, refuse, v.cnt);
   SEGGER_LAUNCH_CHECK("out_cell_kernel<256>");
-  hipLaunchKernelGGL((out_cell_kernel<kOutMax>), dim3(grid_stride_blocks(n_rows / (kOutSmall + 1), 1, (int64_t)cus)), dim3(kWave), 0,
-                     stream, xy, s, (const int32_t*)v.words, (int)kWordLong, (const int32_t*)v.list_long, prm, v.cnt);
+  hipLaunchKernelGGL((out_cell_kernel<kOutMax, RefuseTooMany>), dim3(grid_stride_blocks(n_rows / (kOutSmall + 1), 1, (int64_t)cus)),
+                     dim3(kWave), 0, stream, xy, s, (const int32_t*)v.words, (int)kWordLong, (const int32_t*)v.list_long, prm, refuse, v.cnt);
   SEGGER_LAUNCH_CHECK("out_cell_kernel<max>");
   return launch_cell_rings_back(a, l.head, v, cus, stream);
 }

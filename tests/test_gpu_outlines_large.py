@@ -59,6 +59,68 @@ def test_every_shared_case_on_the_global_route(cuda, connectivity, smoothing):
     same_bytes(got, scene_run(cuda, connectivity=connectivity, smoothing=smoothing), (connectivity, smoothing))
 
 
+# ---------------------------------------------------------------- the component rule, across routes ---
+def tie_cell(n, seed, delta):
+    """a cloud and its mirror image, 1200 grid steps up and `delta` to the right: congruent, so every area ties exactly"""
+    a = oc.cloud(n, seed, 300)
+    return np.concatenate([a, a * [-1.0, 1.0] + [delta / oc.GRID, 1200.0 / oc.GRID]])
+
+
+def three_clouds(ns, seed):
+    """three clouds side by side, the small one first: the triangulation starts there, at point 0"""
+    out, x = [], 0.0
+    for i, (n, half) in enumerate(zip(ns, (150, 300, 200))):
+        out.append(oc.cloud(n, seed + i, half, ((x + half) / oc.GRID, 0.0)))
+        x += 2 * half + 350
+    return np.concatenate(out)
+
+
+# name -> (points, connectivity, the two best areas tie).  Triangle numbers (the triangulation's growth replayed on the host,
+# not part of the test): tie_128 240 triangles, the winner's root 73 against 32; tie_340 662 triangles, roots 86 against 6;
+# later_240 462 triangles, the largest component's root 66, the first component's 0; later_330 643 triangles, 86 after 0.
+# So in every case the kept component is not the first found, and on the global route another wave holds it.
+COMPONENT_CASES = {
+    "tie_128": (lambda: tie_cell(64, 7, 28), 0.5, True),
+    "tie_340": (lambda: tie_cell(170, 0, -8), 0.5, True),
+    "later_240": (lambda: three_clouds((50, 110, 80), 2), 1.0, False),
+    "later_330": (lambda: three_clouds((70, 150, 110), 1), 1.0, False),
+}
+
+
+def ring_by_the_component_rule(points, connectivity):
+    """-> (the oracle's ring under the device's rule: the larger area, then the lower lowest vertex; the components as
+    (twice the area, lowest vertex), best first)"""
+    st = oc.State(points)
+    alive, _ = oc.prune_sequential(st, connectivity)
+    comps = sorted(((area2, int(st.simplices[ts].min()), ts) for area2, ts in oc.components(st, alive)), key=lambda c: c[:2])
+    comps.sort(key=lambda c: -c[0])                                          # stable: equal areas stay by lowest vertex
+    return st.points[oc.ring_of(st, comps[0][2])], [c[:2] for c in comps]
+
+
+@pytest.mark.parametrize("name", COMPONENT_CASES)
+def test_the_component_rule_gives_the_same_ring_on_every_route(cuda, name):
+    make, connectivity, tie = COMPONENT_CASES[name]
+    pts = make()
+    rows, small = len(pts), name in ("tie_128", "later_240")
+    assert (rows <= 256) == small and len(np.unique(pts, axis=0)) == rows
+    ring, comps = ring_by_the_component_rule(pts, connectivity)
+    if tie:                                                                  # every condition of exactness but the last one
+        with pytest.raises(AssertionError, match="components of equal area"):
+            oc.check_case(pts, connectivity)
+        assert comps[0][0] == comps[1][0] > comps[2][0] and comps[0][1] < comps[1][1]
+    else:
+        assert oc.check_case(pts, connectivity)["components"] >= 3 and np.array_equal(ring, oc.outline(pts, connectivity))
+        assert comps[0][1] > 0 and min(c[1] for c in comps) == 0             # point 0, where the growth starts, is elsewhere
+    assert small or len(oc.State(pts).simplices) > 256
+    want = (np.array([0, len(ring)]), ring, np.array([0], dtype=np.int32), np.array([rows]), 0)
+    xy, ids = np.random.default_rng(5).permutation(pts), np.zeros(rows, dtype=np.int32)
+    lds = run(cuda, xy, ids, 1, connectivity=connectivity)
+    glob = run(cuda, xy, ids, 1, connectivity=connectivity, large_cells="global", _lds_max_points=0)
+    assert_same(lds, want, (name, "default"))
+    assert_same(glob, want, (name, "global"))
+    same_bytes(lds, glob, name)
+
+
 @pytest.fixture(scope="module")
 def limit_cells():
     """the two cells at the limit, one of 2049 points above it, a small cell; id 3 is absent"""
