@@ -29,7 +29,19 @@ struct ArgmaxParams {
   float* max_sim; int64_t* max_eid; int64_t* seg_idx; float* sim;
 };
 
-template <typename T, int LPC>
+// eight consecutive channels of a row: one 16-byte load, or element by element where the base or the leading dimension
+// is not 16-byte aligned -- the same eight values and the same arithmetic after them, so a view's alignment never
+// changes a score
+template <typename T, bool VEC> __device__ __forceinline__ void load8(const T* p, float (&f)[8]) {
+  if constexpr (VEC) {
+    Vec8<T>::load(p, f);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = load1(p + k);
+  }
+}
+
+template <typename T, int LPC, bool VEC>
 __global__ __launch_bounds__(256) void edge_cos_argmax_kernel(ArgmaxParams p) {
   constexpr int RPW = 64 / LPC;                       // rows per wave
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -39,7 +51,7 @@ __global__ __launch_bounds__(256) void edge_cos_argmax_kernel(ArgmaxParams p) {
   const T* zs = static_cast<const T*>(p.zs) + row * p.ld_zs + gl * 8;
   const T* zd = static_cast<const T*>(p.zd) + gl * 8;
   float a[8];
-  Vec8<T>::load(zs, a);
+  load8<T, VEC>(zs, a);
   float na = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) na = fmaf(a[k], a[k], na);
@@ -50,7 +62,7 @@ __global__ __launch_bounds__(256) void edge_cos_argmax_kernel(ArgmaxParams p) {
   for (int64_t e = beg; e < end; ++e) {
     const int64_t j = p.col[e];
     float b[8];
-    Vec8<T>::load(zd + j * p.ld_zd, b);
+    load8<T, VEC>(zd + j * p.ld_zd, b);
     float dot = 0.f, nb = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { dot = fmaf(a[k], b[k], dot); nb = fmaf(b[k], b[k], nb); }
@@ -71,7 +83,7 @@ __global__ __launch_bounds__(256) void edge_cos_argmax_kernel(ArgmaxParams p) {
   }
 }
 
-// any channel count: one wave per row, lanes stride the channels
+// any other channel count: one wave per row, lanes stride the channels
 template <typename T>
 __global__ __launch_bounds__(256) void edge_cos_argmax_generic_kernel(ArgmaxParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -112,19 +124,20 @@ __global__ __launch_bounds__(256) void edge_cos_argmax_generic_kernel(ArgmaxPara
 template <typename T>
 int launch_argmax(const ArgmaxParams& p, hipStream_t stream) {
   const int C = p.channels;
+  const bool vec_ok = is_aligned(p.zs, 16) && is_aligned(p.zd, 16) &&
+                      (p.ld_zs * sizeof(T)) % 16 == 0 && (p.ld_zd * sizeof(T)) % 16 == 0;
   auto go = [&](auto lpc_c) {
     constexpr int LPC = decltype(lpc_c)::value;
     const int64_t rows_per_block = 4 * (64 / LPC);
     const int64_t nb = (p.n_rows + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL((edge_cos_argmax_kernel<T, LPC>), dim3((unsigned)nb), dim3(256), 0, stream, p);
+    if (vec_ok) hipLaunchKernelGGL((edge_cos_argmax_kernel<T, LPC, true>), dim3((unsigned)nb), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((edge_cos_argmax_kernel<T, LPC, false>), dim3((unsigned)nb), dim3(256), 0, stream, p);
   };
-  const bool vec_ok = (C % 8 == 0) && is_aligned(p.zs, 16) && is_aligned(p.zd, 16) &&
-                      (p.ld_zs * sizeof(T)) % 16 == 0 && (p.ld_zd * sizeof(T)) % 16 == 0;
-  if (vec_ok && C == 8) go(int_c<1>{});
-  else if (vec_ok && C == 16) go(int_c<2>{});
-  else if (vec_ok && C == 32) go(int_c<4>{});
-  else if (vec_ok && C == 64) go(int_c<8>{});
-  else if (vec_ok && C == 128) go(int_c<16>{});
+  if (C == 8) go(int_c<1>{});
+  else if (C == 16) go(int_c<2>{});
+  else if (C == 32) go(int_c<4>{});
+  else if (C == 64) go(int_c<8>{});
+  else if (C == 128) go(int_c<16>{});
   else {
     const int64_t nb = (p.n_rows + 3) / 4;
     hipLaunchKernelGGL((edge_cos_argmax_generic_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, p);

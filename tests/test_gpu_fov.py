@@ -9,6 +9,8 @@ import math
 import pytest
 import torch
 
+import index_parity as ip
+
 pytestmark = pytest.mark.gpu
 
 
@@ -89,6 +91,15 @@ def test_streamed_batches_match_oracle_and_auroc(oracle, fov, dtype, atol):
             seg_ref, _ = oracle.predict_assign(z_ref["tx"], z_ref["bd"], eic, bc["bd"]["index"])
             # (near-ties within the fp32 error may legitimately flip)
             assert (seg.cpu() == seg_ref).double().mean().item() > 0.999
+        # ... proved row by row, in every storage type, with the tolerance the scores were just held to
+        n_tx, where = bc["tx"].num_nodes, f"test_streamed_batches[{dtype}] batch {ids[0]}.."
+        ip.explain_mismatches(seg.cpu(), eic[0], eic[1], ref, n_tx, dst_index=bc["bd"]["index"], tol=atol, label=where + " vs oracle")
+        # and the head alone is exact given its inputs: float64 scores of the DEVICE embeddings upcast, the head's own
+        # tolerance (tests/test_gpu_heads.py::test_edge_cos_argmax) -- the encoder's error has no part in this one
+        own = oracle.edge_scores(z["tx"].double().cpu(), z["bd"].double().cpu(), eic)
+        assert (sim.double().cpu() - own).abs().max().item() <= ip.HEAD_TOL[dtype]
+        ip.explain_mismatches(seg.cpu(), eic[0], eic[1], own, n_tx, dst_index=bc["bd"]["index"], tol=ip.HEAD_TOL[dtype],
+                              label=where + " head on its own inputs")
         sims.append(sim.cpu()); refs.append(ref); labs.append((bc["bd"]["index"][eic[1]].long() == bc["tx"]["cell"][eic[0]]))
     sim, ref, lab = torch.cat(sims), torch.cat(refs), torch.cat(labs)
     a_dev = auroc(sim.cuda(), lab.cuda())

@@ -2,8 +2,9 @@
 of the kernels in the same direction cannot pass unnoticed:
 
 * ``encoder_small.npz``  -- inputs, weights under the reference's state-dict names and STORED float64 answers
-  (embeddings, layer-0 attention, predict 4-tuple, segmentation loss, parameter gradients); the oracle is not
-  run here at all.  Tolerances as in test_gpu_model.py: fp32 5e-5 on unit-norm embeddings, bf16 3e-2.
+  (embeddings, layer-0 attention, predict 4-tuple, segmentation loss, parameter gradients); the oracle's encoder is
+  not run here at all (only its cosine, on the STORED embeddings, to prove every assignment mismatch a tie:
+  tests/index_parity.py).  Tolerances as in test_gpu_model.py: fp32 5e-5 on unit-norm embeddings, bf16 3e-2.
 * ``triplet_selector.npz`` -- genuine outputs of the reference's own ``models/triplet_loss.py`` (made by
   tests/golden/make_golden.py): the device selector must reproduce positives / negatives bit-exactly from the same
   four uniform draws, ``loss_tx`` (through ``segger_triplet_*``) and ``loss_bd`` within 1e-6
@@ -15,6 +16,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+import index_parity as ip
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -68,6 +71,12 @@ def test_encoder_golden_embeddings_attention_and_predict(cuda, dtype):
     agree = (pred[1].numpy() == z["out::pred_seg"]).mean()
     # an assignment can only differ where the two best candidates are within rounding of each other
     assert agree > (0.995 if dtype == torch.float32 else 0.95), agree
+    # ... proved row by row against the float64 scores of the STORED golden embeddings, with the scores' own tolerance
+    import segger_oracle
+    ei = b[segger_oracle.TX_NB_BD].edge_index
+    scores = segger_oracle.edge_scores(torch.from_numpy(z["out::z_tx"]), torch.from_numpy(z["out::z_bd"]), ei)
+    ip.explain_mismatches(pred[1], *ip.restrict_rows(b["tx"]["predict_mask"], ei[0], ei[1], scores), dst_index=b["bd"]["index"],
+                          tol=tol, label=f"test_encoder_golden_embeddings_attention_and_predict[{dtype}]")
     if dtype == torch.float32:
         diff = pred[1].numpy() != z["out::pred_seg"]
         assert np.abs(pred[2].double().numpy() - z["out::pred_sim"])[diff].max(initial=0.0) < 5e-5

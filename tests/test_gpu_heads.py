@@ -2,6 +2,8 @@
 import pytest
 import torch
 
+import index_parity as ip
+
 pytestmark = pytest.mark.gpu
 
 
@@ -50,6 +52,65 @@ def test_edge_cos_argmax(oracle, cuda, dtype, C):
         assert (max_eid[:5].cpu() == ei.shape[1]).all() and (seg[:5].cpu() == -1).all() and (max_sim[:5].cpu() == 0).all()
         agree = (seg.cpu() == seg_ref).float().mean()
         assert agree > 0.995, f"assignment agreement {agree}"
+        # ... and that is proved row by row.  The oracle scored these very inputs upcast, so this is also the statement
+        # that the head is exact given its inputs: the oracle's assignment, bar ties within the head's own tolerance
+        ip.explain_mismatches(seg.cpu(), src, dst, sim_ref, n_tx, dst_index=bd_index, min_similarity=min_sim, tol=tol,
+                              max_eid=max_eid.cpu(), max_sim=max_sim.cpu(), label=f"test_edge_cos_argmax[{C}-{dtype}] min_sim={min_sim}")
+
+
+def _head_view(z, kind, cuda):
+    """``z`` on the device as the route wants it: dense, or a column slice of a tensor 16 columns wider (full of junk) that
+    starts 8 elements in ("ld": 16-byte aligned base and leading dimension) or 1 element in ("unaligned")."""
+    if kind == "contiguous":
+        return z.to(cuda)
+    n, c = z.shape
+    off = 8 if kind == "ld" else 1
+    wide = torch.full((n, c + 16), 3.0, dtype=z.dtype, device=cuda)
+    wide[:, off:off + c] = z.to(cuda)
+    view = wide[:, off:off + c]
+    assert wide.stride(0) % 8 == 0 and (view.data_ptr() % 16 == 0) == (kind == "ld") and not (n > 1 and view.is_contiguous())
+    return view
+
+
+def _run_head(cuda, case, kind, min_sim):
+    from segger_amd import ops
+    from segger_amd.graph import csr_from_coo
+    by_src = csr_from_coo(case["src"].to(cuda), case["dst"].to(cuda), case["n_rows"], case["n_cols"])
+    out = ops.edge_cos_argmax(by_src, _head_view(case["z_src"], kind, cuda), _head_view(case["z_dst"], kind, cuda),
+                              dst_index=case["dst_index"].to(cuda), min_similarity=min_sim, return_sim=True)
+    return tuple(t.cpu() for t in out)
+
+
+@pytest.mark.parametrize("dtype", ip.DTYPES, ids=lambda d: str(d).split(".")[1])
+@pytest.mark.parametrize("route", ip.routes(), ids=ip.route_id)
+def test_edge_cos_argmax_every_route(cuda, dtype, route):
+    """Every launch route of the head (tests/index_parity.py ``routes``) on inputs whose winners are built and whose float64
+    top-two gaps are certified >= 1e-3 on the CPU (tests/test_index_parity.py): scores within the head's tolerance of the
+    oracle on the upcast inputs; ``max_eid``, ``seg`` and every -1 EXACTLY the oracle's -- no share, no proof.  Then the
+    planted rows at the same width and view: duplicated edges and all-zero rows (lowest edge id), an all-negative row
+    (negative maximum, assigned), one-hot rows whose scores are exactly 1, 0, -1 against thresholds on and one float32
+    past them.  "unaligned": also bit for bit what the dense copy gives."""
+    kind, channels, n_rows = route
+    tol = ip.HEAD_TOL[dtype]
+    for case in (ip.designed_case(channels, n_rows, dtype), ip.planted_case(channels, dtype)):
+        planted = "exact_rows" in case
+        empty = torch.bincount(case["src"], minlength=case["n_rows"]) == 0
+        for min_sim in case["thresholds"]:
+            score, max_ref, eid_ref, seg_ref = ip.reference(case, min_sim)
+            max_sim, max_eid, seg, sim = _run_head(cuda, case, kind, min_sim)
+            print(route, "planted" if planted else "designed", min_sim, "max score error", float((sim.double() - score).abs().max()),
+                  "index differences", int((max_eid != eid_ref).sum()), int((seg != seg_ref).sum()))
+            assert torch.allclose(sim.double(), score, atol=tol, rtol=0) and torch.allclose(max_sim.double(), max_ref, atol=tol, rtol=0)
+            assert torch.equal(max_eid, eid_ref) and torch.equal(seg, seg_ref)
+            assert bool((max_sim[empty] == 0).all()) and bool((max_eid[empty] == case["src"].numel()).all())
+            if planted:
+                exact = torch.isin(case["src"], torch.tensor(case["exact_rows"]))
+                assert torch.equal(sim.double()[exact], score[exact]) and bool(torch.isfinite(sim).all())
+                assert max_sim[ip.ROW_NEG] < 0 and max_sim[ip.ROW_NEG] == sim[max_eid[ip.ROW_NEG]]
+                assert max_sim[[ip.ROW_HOT_1, ip.ROW_HOT_0, ip.ROW_HOT_M1]].tolist() == [1.0, 0.0, -1.0]
+            if kind == "unaligned":
+                dense = _run_head(cuda, case, "contiguous", min_sim)
+                assert all(torch.equal(a, b) for a, b in zip((max_sim, max_eid, seg, sim), dense))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])

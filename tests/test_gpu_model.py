@@ -7,6 +7,8 @@ for a single kernel; four stacked bf16 layers round four times)."""
 import pytest
 import torch
 
+import index_parity as ip
+
 pytestmark = pytest.mark.gpu
 
 
@@ -94,6 +96,10 @@ def test_predict_step_matches_oracle(oracle, cuda):
     b["tx"]["predict_mask"] = torch.rand(spec.n_tx, generator=g) < 0.7
     b["tx"]["index"] = torch.randperm(10 * spec.n_tx, generator=g)[: spec.n_tx]
     b["bd"]["index"] = (torch.randperm(spec.n_bd, generator=g) + 7).to(torch.int32)
+    # the float64 score of every candidate edge, for the rows predict_step returns: what each index mismatch is proved against
+    ei = b[oracle.TX_NB_BD].edge_index
+    z_ref = oracle.ist_encoder_forward(sd, b.x_dict, b.edge_index_dict, b.pos_dict, b.batch_dict, n_heads=2)
+    candidates = ip.restrict_rows(b["tx"]["predict_mask"], ei[0], ei[1], oracle.edge_scores(z_ref["tx"], z_ref["bd"], ei))
     for min_sim in (None, 0.3):
         out = m.predict_step(b.to(cuda), 0, min_similarity=min_sim)
         ref = oracle.predict_step(sd, b, n_heads=2, min_similarity=min_sim)
@@ -102,6 +108,9 @@ def test_predict_step_matches_oracle(oracle, cuda):
         assert torch.allclose(out[2].double(), ref[2], atol=5e-5)
         # assignments can only differ where the two best candidates are within rounding of each other
         assert (out[1] == ref[1]).float().mean() > 0.998
+        # ... proved row by row, with the tolerance the scores were just held to
+        ip.explain_mismatches(out[1], *candidates, dst_index=b["bd"]["index"], min_similarity=min_sim, tol=5e-5,
+                              label=f"test_predict_step_matches_oracle min_sim={min_sim}")
         assert out[1].dtype == torch.int64 and out[2].dtype == torch.float32
 
 
