@@ -1740,7 +1740,8 @@ int segger_cell_outlines_large(const double* xy /* [N, 2] */, const int32_t* cel
  *   height * width = 0 or max_label = 0 returns SEGGER_OK and launches nothing: the caller's zeroed counters and
  *   ring_offsets[0] stand.
  * The reference's simplify(tolerance) and is_valid that follow are segger_simplify_rings_* and segger_rings_simple below.
- * NOT BUILT: TIFF reading, the repairs of fix_invalid_geometry, the id strings, FOV stitching.
+ * The first repair of fix_invalid_geometry, resort_coordinates, is segger_rings_resort.
+ * NOT BUILT: TIFF reading, the buffer(0) repair of fix_invalid_geometry, the id strings, FOV stitching.
  * ---------------------------------------------------------------------- */
 #define SEGGER_CONTOUR_MAX_LABEL (1 << 24)  /* five int32 tables of max_label + 1 entries: 320 MB at the cap */
 #define SEGGER_CONTOUR_LDS_BITS 32768       /* 4 KB of LDS per single-wave workgroup: 32 of them fit a CU */
@@ -1824,7 +1825,8 @@ int segger_label_contours(const int32_t* labels /* [H, W] */, const uint8_t* com
  *   stride or small_max_verts outside its range, NULL or misaligned pointers, a workspace that is too small.
  *   n_polygons = 0 returns SEGGER_OK and launches nothing.  No scratch, no atomics on floats: the same bytes from run to
  *   run and for any order of the polygons in the CSR.
- * NOT BUILT: resort_coordinates, the buffer(0) repair, holes and multi-part polygons, rings above SEGGER_MORPH_MAX_VERTS.
+ * The repair that fix_invalid_geometry tries on the rings that are not simple, resort_coordinates, is segger_rings_resort
+ * below.  NOT BUILT: the buffer(0) repair, holes and multi-part polygons, rings above SEGGER_MORPH_MAX_VERTS.
  * ---------------------------------------------------------------------- */
 #define SEGGER_SIMPLIFY_SMALL_VERTS 256
 #define SEGGER_SIMPLIFY_COUNTERS 8
@@ -1843,6 +1845,62 @@ int segger_simplify_rings_emit(const int64_t* ring_offsets, const double* xy, in
 int segger_rings_simple(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices, uint8_t* ok,
                         int32_t* reason, int32_t small_max_verts, void* workspace, int64_t workspace_bytes,
                         segger_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Ring repair on a ring CSR: the first repair of the reference's fix_invalid_geometry (src/segger/io/utils.py:127-159,
+ * called for every boundary intake at io/preprocessor.py:311, :316 and :472), resort_coordinates (io/utils.py:83-102) --
+ * the vertices of the closed coordinate sequence re-sorted by np.arctan2 around their mean -- for the rings a mask
+ * selects.  The kernel behind segger_amd.repair.resort_rings / repair_rings, csrc/repair.hip.  Purely additive: one new
+ * symbol, SEGGER_ABI_VERSION stays 32.
+ *
+ * A ring is xy[off[p] .. off[p + 1]) as segger_rings_simple takes it, n open vertices v_0 .. v_(n-1).  A ring keeps its
+ * vertex count, so ring_offsets is the output's too.  A ring that is not selected, or has fewer than 3 open vertices, and
+ * every row of xy outside the rings is copied through bit for bit with vertex_index the row itself.  For a selected ring:
+ *   centre   c = (sum_{k<n} v_k + v_0) / (n + 1) per coordinate in fp64 -- the reference sorts the CLOSED sequence, so
+ *            vertex 0 counts twice.  The order of the sum: 64 partial sums s_l = ((0 + v_l) + v_(l+64)) + v_(l+128) + ...
+ *            (ascending k, starting from +0; s_l = 0 where l >= n), then six rounds m = 1, 2, 4, 8, 16, 32 of
+ *            s_l <- s_l + s_(l xor m) for every l at once; then (s_0 + v_0) / (n + 1), one addition and one division.
+ *            The centre is never returned: only the order depends on it.
+ *   d_k      = (fl(x_k - c_x), fl(y_k - c_y)), the rounded differences the reference hands to arctan2.
+ *   order    ascending EXACT angle of d_k in (-pi, pi] with arctan2's conventions: d = (0, 0) has angle 0; d_y = 0 (either
+ *            zero), d_x < 0 has angle +pi and comes last.  Vertices at one exact angle go by ascending squared length of
+ *            d, compared exactly (at one angle that is the order of |d_x|, or of |d_y| where d_x = 0), then by ascending
+ *            input index.  The result is counter-clockwise around c and starts at the first vertex past the negative-x ray.
+ *            The reference's closing duplicate is not emitted: it would sit next to its twin and add nothing.
+ *   exact    the comparator is the half-plane class of d (d_y < 0; angle 0; d_y > 0; angle pi) and, within a class, the
+ *            sign of d_a x d_b = a_x b_y - a_y b_x obtained without rounding: each product as its rounded value plus the
+ *            FMA's error term, the four terms summed into a non-overlapping expansion whose highest non-zero component
+ *            carries the sign.  Neither a float64 atan2 key nor a float64 cross product: both mis-order vertices whose
+ *            angles differ by less than their rounding (tests/repair_cases.py holds such pairs).  Exact while every
+ *            non-zero |d_x|, |d_y| lies in 2^-480 .. 2^480 (no product overflows, every error term is representable);
+ *            coordinates are finite.  With coordinates that are not numbers the output is still a permutation of the ring.
+ *   closed   a ring GIVEN with a closing duplicate (n + 1 entries) keeps its n + 1 entries: c and the d_k are as above, the
+ *            duplicate has d_0 and index n and is therefore emitted after vertex 0 and after every vertex with the same d.
+ * Writes xy_out [n_vertices, 2] fp64 (the INPUT's bytes; xy_out must not be xy) and vertex_index [n_vertices] int64, the
+ * row of xy each output row came from: xy_out = xy[vertex_index], a permutation within every ring.
+ *   select   uint8 [n_polygons], non-zero = re-sort this ring; NULL = all.  Every ring's offsets are checked, selected or not.
+ *   small_max_verts  as segger_rings_simple: a ring of at most this many vertices runs in the small LDS tier (4608 B per
+ *            single-wave workgroup: the differences 16 B and an index 2 B a vertex), a longer one in the large (73728 B,
+ *            two per CU); the same code, the same bytes; SEGGER_SIMPLIFY_SMALL_VERTS is the value to pass.
+ * One single-wave workgroup per selected ring sorts the vertex indices in LDS with a bitonic network over the padded size.
+ * The error word is the first int32 of the workspace: SEGGER_MORPH_ERR_OFFSETS / _CAP as segger_polygon_props sets them
+ * (a ring above SEGGER_MORPH_MAX_VERTS is refused); such a ring is copied through.
+ *
+ * Workspace, 256-byte aligned: 256 + 2 up(4 P) bytes; segger_simplify_rings_workspace_bytes(P, 0) is enough and is what
+ *   the Python side passes.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative sizes, 2^31 - 1 polygons or more, a
+ *   small_max_verts outside its range, NULL or misaligned pointers, xy_out == xy, a workspace that is too small.
+ *   n_polygons = 0 returns SEGGER_OK and launches nothing (xy_out and vertex_index are not written).  No scratch, no
+ *   atomics on floats: the same bytes from run to run, for any order of the polygons in the CSR and on either tier.
+ * UNPINNED against numpy where float64 arctan2 values tie or invert by rounding: np.argsort is not stable there and the
+ *   reference's order among such vertices is whatever its sort does; the exact order above is this project's contract.
+ * NOT BUILT: the buffer(0) fallback that fix_invalid_geometry takes when the re-sorted ring is still invalid, with its
+ *   largest-component rule (GEOS's answer on a self-crossing ring depends on winding, and GEOS could not be run); holes
+ *   and multi-part polygons; rings above SEGGER_MORPH_MAX_VERTS.
+ * ---------------------------------------------------------------------- */
+int segger_rings_resort(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                        const uint8_t* select /* [n_polygons] or NULL = all */, double* xy_out, int64_t* vertex_index,
+                        int32_t small_max_verts, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Polygon overlap join of two ring CSRs A and B: every pair (a, b) whose closed polygons share a point, and the area of

@@ -26,6 +26,8 @@ from . import contours  # noqa: F401
 from .contours import label_contours  # noqa: F401
 from . import simplify  # noqa: F401
 from .simplify import contour_tolerance, rings_simple, simplify_rings  # noqa: F401
+from . import repair  # noqa: F401
+from .repair import repair_rings, resort_rings  # noqa: F401
 from . import overlap  # noqa: F401
 from .overlap import match_polygons, polygon_overlaps, polygons_in_polygons  # noqa: F401
 

@@ -393,6 +393,7 @@ EXPORTS = {
                                              vp]),
     "segger_simplify_rings_emit": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, vp]),
     "segger_rings_simple": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int32, vp, C.c_int64, vp]),
+    "segger_rings_resort": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int32, vp, C.c_int64, vp]),
     "segger_polygon_overlap_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "segger_polygon_overlap_candidates": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                     C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]),

@@ -11,8 +11,9 @@ written from that definition plus independent properties (raster round trip, Pic
 checked; downstream code accepts any start and either orientation.
 
 The step the reference takes next, ``simplify(tolerance)`` followed by ``is_valid``, is :mod:`segger_amd.simplify`
-(``simplify_rings``, ``contour_tolerance``, ``rings_simple``).  NOT BUILT: TIFF reading, the repairs of
-``fix_invalid_geometry``, the id strings, FOV stitching."""
+(``simplify_rings``, ``contour_tolerance``, ``rings_simple``); the re-sort of ``fix_invalid_geometry`` is
+:mod:`segger_amd.repair`.  NOT BUILT: TIFF reading, the ``buffer(0)`` repair of ``fix_invalid_geometry``, the id strings,
+FOV stitching."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, Optional, Sequence

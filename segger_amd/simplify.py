@@ -21,8 +21,11 @@ input or output segments; depth-first recursion), but three of its details are n
 versions: its minimum-size rule at shallow depth, its optional removal of the ring's endpoint, and its "jump" check.
 Downstream code accepts any start vertex.
 
-NOT BUILT: ``resort_coordinates``, the ``buffer(0)`` repair, holes and multi-part polygons, rings above
-``SEGGER_MORPH_MAX_VERTS`` (refused, naming the polygon, as the other ring consumers do)."""
+What ``fix_invalid_geometry`` does next with the rings that are not simple, ``resort_coordinates``, is
+:func:`segger_amd.repair.resort_rings`; :func:`segger_amd.repair.repair_rings` is the whole check / re-sort / check.
+
+NOT BUILT: the ``buffer(0)`` repair, holes and multi-part polygons, rings above ``SEGGER_MORPH_MAX_VERTS`` (refused,
+naming the polygon, as the other ring consumers do)."""
 from __future__ import annotations
 
 import math
