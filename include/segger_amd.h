@@ -1983,6 +1983,60 @@ int segger_polygon_overlap_pairs(const int64_t* ring_offsets_a, const double* xy
                                  double* area, int64_t capacity, int32_t reg_max_verts, int32_t small_max_verts, void* workspace,
                                  int64_t workspace_bytes, segger_stream_t stream);
 
+/* ----------------------------------------------------------------------
+ * Fragment cells (csrc/fragments.hip; segger_amd.fragments): connected components of the unassigned
+ * transcripts over the transcript-graph edges whose embeddings agree.  Upstream segger calls this "fragment mode"
+ * (use_cc); the reference snapshot this project follows does not contain it, so the contract below is this project's own
+ * and is UNPINNED by any reference run.
+ *
+ * State: parent [n_transcripts] int32, initialised by the caller to the identity (parent[i] = i), and counters
+ * [SEGGER_FRAGMENTS_COUNTERS] int64, zeroed by the caller: 0 edges seen, 1 live edges, 2 kept edges, 3 edges with an id
+ * out of range (all four summed over the updates), 4 candidates (unassigned transcripts), 5 components (singletons
+ * included), 6 fragments, 7 candidates whose parent chain held a value these kernels cannot have written (4 .. 7 are set by
+ * _finalize).
+ *
+ *   _update    one launch, enqueue only.  Edge e = (src[e], dst[e]), local ids of one batch of n_nodes rows; tx_index
+ *              [n_nodes] int64 maps a local id to its transcript (NULL: the identity); mask [n_nodes] uint8 (NULL: all
+ *              true); unassigned [n_transcripts] uint8.  An edge with a local id outside [0, n_nodes), or -- its source's
+ *              mask being true -- a transcript id outside [0, n_transcripts), is counted (counter 3) and takes part in
+ *              nothing: no such id is ever an address.  An edge is LIVE when mask[src] is true, both transcripts are
+ *              unassigned and differ, and edge_keep[e] (uint8, NULL: all true) is non-zero.  A live edge is KEPT when
+ *                z != NULL:           sim >= min_similarity with sim = dot / (max(sqrt(aa), 1e-8f) * max(sqrt(bb), 1e-8f)),
+ *                                     dot, aa, bb the three sums over the `channels` stored values of rows src and dst of z
+ *                                     ([n_nodes, channels] in `dtype`, row stride ld_z elements) accumulated in fp32 (fused
+ *                                     multiply-adds, lane partial sums combined by a tree); sqrt, the multiply and the divide
+ *                                     are correctly rounded fp32 -- so |sim - exact cosine of the stored values| <=
+ *                                     (2 channels + 6) 2^-24, and a cosine of small-integer rows is exact;
+ *                similarity != NULL:  similarity[e] >= min_similarity (fp32, exact; no row is read);
+ *                neither:             always.
+ *              NaN is never >= anything: not kept.  The endpoints of a kept edge are united in `parent`: the larger root is
+ *              hooked under the smaller by an agent-scope compare-and-swap, so parent[i] <= i throughout and the root of a
+ *              component is its smallest transcript.  Rows that are whole 16-byte pieces (base, ld_z and channels) are read
+ *              16 bytes a lane; any other shape an element a lane.
+ *   _finalize  flattens parent (parent[i] = root of i for every candidate; further updates may follow), counts the members
+ *              of every root, and writes fragment [n_transcripts] int64 = first_id + rank for the members of a component of
+ *              min_size members or more, -1 for everything else, where rank numbers those components by their smallest
+ *              transcript, ascending; root [capacity] and size [capacity] int32 per fragment in rank order (nothing at or
+ *              past capacity; n_transcripts / min_size always suffices).  Workspace, 256-byte aligned, with up(x) = x
+ *              rounded up to 256: up(4 n_transcripts) + up(8 (ceil(n_transcripts / SEGGER_FRAGMENTS_CHUNK) + 1)) bytes.
+ * Every output is a function of the SET of kept edges: not of the order of edges, batches or atomics.  No scratch, integer
+ * atomics only.  Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative sizes, n_transcripts
+ * outside [1, 2^31), 2^31 nodes or more, channels outside 1 .. SEGGER_FRAGMENTS_MAX_CHANNELS, an unknown dtype, both z and
+ * similarity, a NaN min_similarity, min_size < 1, a negative first_id or capacity, NULL or misaligned pointers, a workspace
+ * that is too small.  n_edges = 0 returns SEGGER_OK and launches nothing.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_FRAGMENTS_COUNTERS 8
+#define SEGGER_FRAGMENTS_CHUNK 2048
+#define SEGGER_FRAGMENTS_MAX_CHANNELS 1024
+int segger_fragments_update(const void* z, int64_t ld_z, int32_t channels, int32_t dtype, const float* similarity,
+                            const uint8_t* edge_keep, const int64_t* src, const int64_t* dst, int64_t n_edges,
+                            const int64_t* tx_index, const uint8_t* mask, int64_t n_nodes, const uint8_t* unassigned,
+                            int64_t n_transcripts, float min_similarity, int32_t* parent, int64_t* counters,
+                            segger_stream_t stream);
+int segger_fragments_finalize(int32_t* parent, const uint8_t* unassigned, int64_t n_transcripts, int64_t min_size,
+                              int64_t first_id, int64_t* fragment, int32_t* root, int32_t* size, int64_t capacity,
+                              int64_t* counters, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

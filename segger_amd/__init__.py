@@ -30,5 +30,7 @@ from . import repair  # noqa: F401
 from .repair import repair_rings, resort_rings  # noqa: F401
 from . import overlap  # noqa: F401
 from .overlap import match_polygons, polygon_overlaps, polygons_in_polygons  # noqa: F401
+from . import fragments  # noqa: F401
+from .fragments import FragmentAccumulator, fragment_cells, connected_components, unassigned_mask, merge_fragments  # noqa: F401
 
 __version__ = "0.1.0"

@@ -31,6 +31,7 @@ CONTOUR_MAX_LABEL, CONTOUR_LDS_BITS, CONTOUR_COUNTERS = 1 << 24, 32768, 10      
 SIMPLIFY_SMALL_VERTS, SIMPLIFY_COUNTERS, SIMPLIFY_ERR_TOL = 256, 8, 4                                  # SEGGER_SIMPLIFY_*
 RING_OK, RING_TOO_FEW, RING_TOUCH = 0, 1, 2                                                            # SEGGER_RING_*
 OVERLAP_SMALL_VERTS, OVERLAP_WIDE_CELLS = 256, 64                                                      # SEGGER_OVERLAP_*
+FRAGMENTS_COUNTERS, FRAGMENTS_CHUNK, FRAGMENTS_MAX_CHANNELS = 8, 2048, 1024                            # SEGGER_FRAGMENTS_*
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -400,6 +401,9 @@ EXPORTS = {
     "segger_polygon_overlap_pairs": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32,
                                                vp, C.c_int64, vp]),
+    "segger_fragments_update": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp,
+                                          C.c_int64, C.c_float, vp, vp, vp]),
+    "segger_fragments_finalize": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None
