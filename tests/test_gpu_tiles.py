@@ -1,4 +1,4 @@
-"""N2 on the device: the tile batcher (segger_amd/tiles.py) run on ``cuda`` tensors against naive restatements
+"""N2 on the device: the tile batcher (segger_amd/tiles/) run on ``cuda`` tensors against naive restatements
 computed on the HOST copy of the same graph -- partition vs brute force (reference data/partition/dataset.py:340-579
 as used by data/tile_dataset.py:13-153), ``PredictTiles`` vs a bounding-box filter and ``PredictTileIndex`` vs
 ``PredictTiles`` (data/tile_dataset.py:156-264), the bin-packed sampler over a device partition vs the one over the
@@ -132,31 +132,37 @@ def test_sampler_over_device_partition_equals_host(graphs):
         assert list(sd) == list(sh) and list(sd) == list(sh)               # (second pass: the re-packed epoch)
 
 
+def check_csr_views_equal_host_stable_sort(part, ids):
+    """The sorted views ``graph.edge_graph`` hands out for ``part.batch(ids)`` against a stable argsort of the batch's own
+    COO list on the host, all three edge types."""
+    from segger_amd.graph import batch_cache, edge_graph
+    b = part.batch(ids)
+    for et in ETS:
+        ei = b[et].edge_index
+        ns, nd = b[et[0]].num_nodes, b[et[2]].num_nodes
+        g = edge_graph(batch_cache(b), et, ei, ns, nd)
+        eic = ei.cpu().long()
+        for view, rows, cols, n_rows in ((g.by_dst, eic[1], eic[0], nd), (g.by_src, eic[0], eic[1], ns)):
+            indptr, col, eid = naive_csr(rows, cols, n_rows)
+            assert torch.equal(view.indptr.cpu(), indptr), (ids, et)
+            assert torch.equal(view.col.cpu(), col) and torch.equal(view.eid.cpu(), eid), (ids, et)
+        # a consumer that needs the by-source view the factory skipped ("lazy" + unique sources) can still get it
+        lazy = edge_graph(batch_cache(b), et, ei, ns, nd, need_by_src="lazy")
+        by_src = lazy.require_by_src()
+        indptr, col, eid = naive_csr(eic[0], eic[1], ns)
+        assert torch.equal(by_src.indptr.cpu(), indptr) and torch.equal(by_src.col.cpu(), col)
+
+
 def test_slide_csr_slices_equal_host_stable_sort(graphs):
     """``TilePartition.build_csr`` (one HIP radix sort per edge store per slide, sliced per batch) against a stable
     argsort of the batch's own COO list on the host: single tiles, multi-tile batches, all three edge types."""
-    from segger_amd.graph import batch_cache, edge_graph
     host, dev = graphs
     part = T.partition_by_tiling(dev, T.SquareTiling(all_pos(dev), 25.0), margin=2.0)
     part.build_csr()
     part.csr_max_tiles = 64
     n_t = len(part)
     for ids in ([0], [n_t - 1], [3, 1, 7], list(range(n_t))):
-        b = part.batch(ids)
-        for et in ETS:
-            ei = b[et].edge_index
-            ns, nd = b[et[0]].num_nodes, b[et[2]].num_nodes
-            g = edge_graph(batch_cache(b), et, ei, ns, nd)
-            eic = ei.cpu().long()
-            for view, rows, cols, n_rows in ((g.by_dst, eic[1], eic[0], nd), (g.by_src, eic[0], eic[1], ns)):
-                indptr, col, eid = naive_csr(rows, cols, n_rows)
-                assert torch.equal(view.indptr.cpu(), indptr), (ids, et)
-                assert torch.equal(view.col.cpu(), col) and torch.equal(view.eid.cpu(), eid), (ids, et)
-            # a consumer that needs the by-source view the factory skipped ("lazy" + unique sources) can still get it
-            lazy = edge_graph(batch_cache(b), et, ei, ns, nd, need_by_src="lazy")
-            by_src = lazy.require_by_src()
-            indptr, col, eid = naive_csr(eic[0], eic[1], ns)
-            assert torch.equal(by_src.indptr.cpu(), indptr) and torch.equal(by_src.col.cpu(), col)
+        check_csr_views_equal_host_stable_sort(part, ids)
 
 
 def test_slide_csr_sorted_in_tile_ranges_equals_one_sort(graphs):
@@ -355,3 +361,90 @@ def test_rank_local_fov_generation_equals_shards_of_the_whole_fov(cuda):
         seen |= set(tiles)
         del loc, ref
     assert seen == {t for ids in batches for t in ids}
+
+
+# ------------------------------------------------------------------------- a partition with holes
+@pytest.fixture(scope="module")
+def holed(cuda):
+    """tests/tile_cases.py on the device: tile 4 empty, tile 1 without boundaries, tile 7 without a tx-belongs-bd edge."""
+    from tile_cases import MARGIN, SIDE, holed_graph
+    host = holed_graph()
+    dev = host.to(cuda)
+    h_tiling = T.SquareTiling(all_pos(host), SIDE)
+    labels = {nt: h_tiling.label(host[nt].pos) for nt in ("tx", "bd")}
+    mk = lambda: T.partition_by_tiling(dev, T.SquareTiling(all_pos(dev), SIDE), margin=MARGIN)
+    part = mk()
+    part.build_csr()
+    part.csr_max_tiles = 64
+    return host, h_tiling, labels, part, mk
+
+
+def holed_cases():
+    from tile_cases import EMPTY_TILE, NO_BD_TILE
+    return [[t] for t in range(9)] + [[EMPTY_TILE, 2], [NO_BD_TILE, EMPTY_TILE], [7, 1], list(range(9))]
+
+
+def test_holed_partition_on_device_batches_and_csr_views(holed):
+    """Batches of a partition with empty tiles, tiles without one node type and tiles without one edge type: the batch
+    equals the brute-force collation on the host, and its sorted views (sliced from the slide-level sort) equal a host
+    stable sort of its own edge lists."""
+    from tile_cases import assert_batch_equals_naive
+    host, h_tiling, labels, part, _ = holed
+    assert part.node_sizes["tx"][4] == 0 and part.node_sizes["bd"][1] == 0 and part.edge_sizes[TX_BD][7] == 0
+    for ids in [[]] + holed_cases() + [list(range(8, -1, -1))]:
+        assert_batch_equals_naive(part.batch(ids), host, h_tiling, labels, ids)
+    for ids in holed_cases():
+        check_csr_views_equal_host_stable_sort(part, ids)
+
+
+def test_holed_partition_chunked_sort_equals_one_sort(holed):
+    """The slide-level sort in at least three ranges of whole tiles, one of them ending right behind the empty tile:
+    bit for bit the stores of the single sort."""
+    host, h_tiling, labels, one, mk = holed
+    many = mk()
+    many.csr_sort_max_edges = int(many.edge_sizes[TX_TX].max()) + 1
+    chunks = many._sort_chunks(TX_TX)
+    assert len(chunks) >= 3 and any(t1 == 5 for _, t1 in chunks), chunks     # ... [t0, 5) | [5, ...): tile 4 is empty
+    many.build_csr()
+    for et in ETS:
+        for side in ("by_dst", "by_src"):
+            for k in ("ptr", "col", "eid"):
+                assert torch.equal(one._csr[et][side][k], many._csr[et][side][k]), (et, side, k)
+    assert many.checksum() == one.checksum()
+
+
+def inside(view, store):
+    """``view`` lies inside the storage of ``store`` (first to last element, by address)."""
+    if view.untyped_storage().data_ptr() != store.untyped_storage().data_ptr():
+        return False
+    if view.numel() == 0:
+        return True
+    lo = store.data_ptr()
+    hi = lo + store.numel() * store.element_size()
+    last = view.data_ptr() + sum((n - 1) * st for n, st in zip(view.shape, view.stride())) * view.element_size()
+    return lo <= view.data_ptr() and last + view.element_size() <= hi
+
+
+def test_single_tile_batches_are_views_and_allocate_nothing(holed):
+    """One tile: ``edge_index``, every node attribute and the sorted views' ``indptr`` / ``col`` / ``eid`` are views of the
+    slide-level stores, ``batch`` a view of the persistent zero vector, and assembling the batch allocates no device
+    memory."""
+    from segger_amd.graph import batch_cache, edge_graph
+    host, h_tiling, labels, part, _ = holed
+    for t in range(9):
+        part.batch([t])                                                     # warm: the zero vectors
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        b = part.batch([t])
+        assert torch.cuda.memory_allocated() == before, t
+        for nt in ("tx", "bd"):
+            for a, v in part.data[nt].items():
+                assert inside(b[nt][a], v), (t, nt, a)
+            assert inside(b[nt]["batch"], part._zero_vec[nt]) and b[nt]["batch"].numel() == int(part.node_sizes[nt][t])
+        for et in ETS:
+            assert inside(b[et].edge_index, part.data[et].edge_index), (t, et)
+            g = edge_graph(batch_cache(b), et, b[et].edge_index, b[et[0]].num_nodes, b[et[2]].num_nodes)
+            for side in ("by_dst", "by_src"):
+                v, st = getattr(g, side), part._csr[et][side]
+                assert inside(v.indptr, st["ptr"]) and inside(v.col, st["col"]) and inside(v.eid, st["eid"]), (t, et, side)
+                assert v.indptr.numel() == v.n_rows + 1

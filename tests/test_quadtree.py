@@ -1,4 +1,4 @@
-"""Adaptive quadtree tiling (segger_amd/tiles.py, torch path on the CPU): ``QuadTreeTiling`` against a brute-force
+"""Adaptive quadtree tiling (segger_amd/tiles/tiling.py, torch path on the CPU): ``QuadTreeTiling`` against a brute-force
 recursive quadtree and its own stated properties on the point sets (A)-(G), then through ``partition_by_tiling``,
 ``TileBatchSampler`` and ``PredictQuadTreeIndex`` on a density-skewed graph.  The tree is exact integer arithmetic:
 every comparison is equality."""

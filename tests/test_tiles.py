@@ -301,3 +301,165 @@ def test_fov_graph_subset_is_the_induced_subgraph():
         loc = sub[et].edge_index
         assert loc.shape == e_glob.shape
         assert torch.equal(ids_s[loc[0]], e_glob[0]) and torch.equal(ids_d[loc[1]], e_glob[1])
+
+
+# ---------------------------------------------------------------------------------------- segments
+def test_segments_group_slice_and_lay_out():
+    """``Segments`` on its own: segments 1 and 3 of four are empty."""
+    seg = T.Segments.from_labels(torch.tensor([2, 0, 2, 2, 0]), 4)
+    assert seg.perm.tolist() == [1, 4, 0, 2, 3]                            # the stable order
+    assert seg.sizes.tolist() == [2, 0, 3, 0] and seg.indptr.tolist() == [0, 2, 2, 5, 5] == seg.ptr
+    assert [seg.size(t) for t in range(4)] == [2, 0, 3, 0] and seg.span(2) == (2, 5) and seg.span(3) == (5, 5)
+    v = torch.arange(15.0).reshape(5, 3)[seg.perm]
+    e = torch.arange(10).reshape(2, 5)[:, seg.perm]
+    for t in (1, 3):                                                        # empty views with the right trailing shape
+        assert seg.view(v, t).shape == (0, 3) and seg.view(v, t).dtype == v.dtype
+        assert seg.view(e, t, dim=1).shape == (2, 0) and seg.view(e, t, dim=1).dtype == e.dtype
+    assert seg.view(v, 2)[:, 0].tolist() == [0.0, 6.0, 9.0] and seg.view(e, 0, dim=1).tolist() == [[1, 4], [6, 9]]
+    assert seg.take(v, []).shape == (0, 3) and seg.take(e, [], dim=1).shape == (2, 0)
+    assert seg.take(v, [3]).shape == (0, 3)
+    assert seg.take(v, [2, 0])[:, 0].tolist() == [0.0, 6.0, 9.0, 3.0, 12.0]
+    assert seg.take(e, [2, 0], dim=1).tolist() == [[0, 2, 3, 1, 4], [5, 7, 8, 6, 9]]
+    for t in (0, 2):                                                        # one id: the view itself, no copy
+        assert seg.take(v, [t]).data_ptr() == seg.view(v, t).data_ptr() == v.data_ptr() + seg.ptr[t] * 3 * v.element_size()
+        assert seg.take(e, [t], dim=1).data_ptr() == e.data_ptr() + seg.ptr[t] * e.element_size()
+    assert seg.layout([]) == ([], [], 0) and seg.layout([2]) == ([3], [0], 3)
+    assert seg.layout([2, 1, 0, 3]) == ([3, 0, 2, 0], [0, 3, 3, 5], 5)
+    ends = seg.with_ends()                                                  # a store with one more entry behind every segment
+    assert type(ends) is T.Segments
+    assert [ends.span(t) for t in range(4)] == [(seg.ptr[t] + t, seg.ptr[t + 1] + t + 1) for t in range(4)]
+    assert ends.view(torch.arange(9), 2).tolist() == [4, 5, 6, 7] and ends.view(torch.arange(9), 3).tolist() == [8]
+    given = T.Segments(torch.tensor([3, 0, 2]))                             # from sizes: no permutation
+    assert given.perm is None and given.ptr == [0, 3, 3, 5]
+    for bad in ([0, -1], [0, 4]):
+        with pytest.raises(ValueError, match=r"tile labels must lie in \[0, 4\)"):
+            T.Segments.from_labels(torch.tensor(bad), 4)
+    with pytest.raises(ValueError, match=r"node type 'tx': tile labels must lie in \[0, 4\)"):
+        T.Segments.from_labels(torch.tensor([4]), 4, "node type 'tx'")
+
+
+# ------------------------------------------------------------------------- a partition with holes
+@pytest.fixture(scope="module")
+def holed():
+    from tile_cases import MARGIN, SIDE, holed_graph
+    g = holed_graph()
+    tiling = T.SquareTiling(torch.cat([g["tx"].pos, g["bd"].pos]), SIDE)
+    labels = {nt: tiling.label(g[nt].pos) for nt in ("tx", "bd")}
+    return g, tiling, labels, T.partition_by_tiling(g, tiling, margin=MARGIN)
+
+
+def test_holed_partition_has_the_holes(holed):
+    from tile_cases import EMPTY_TILE, NO_BD_TILE, NO_BELONGS_TILE
+    g, tiling, labels, part = holed
+    assert len(tiling) == 9 and 250 <= g["tx"].num_nodes <= 400 and 20 <= g["bd"].num_nodes <= 40
+    assert part.node_sizes["tx"][EMPTY_TILE] == 0 and part.node_sizes["bd"][EMPTY_TILE] == 0
+    assert all(int(v[EMPTY_TILE]) == 0 for v in part.edge_sizes.values())
+    assert part.node_sizes["tx"][NO_BD_TILE] > 0 and part.node_sizes["bd"][NO_BD_TILE] == 0
+    assert part.node_sizes["bd"][NO_BELONGS_TILE] > 0 and part.edge_sizes[TX_BD][NO_BELONGS_TILE] == 0
+    assert part.edge_sizes[TX_TX][NO_BELONGS_TILE] > 0 and part.edge_sizes[TX_NB_BD][NO_BELONGS_TILE] > 0
+    for et in (TX_TX, TX_BD, TX_NB_BD):                                     # some edges cross tiles and were dropped
+        assert 0 < int(part.edge_sizes[et].sum()) < g[et].edge_index.shape[1]
+
+
+def test_holed_partition_batches_equal_brute_force_collate(holed):
+    from tile_cases import EMPTY_TILE, NO_BD_TILE, assert_batch_equals_naive
+    g, tiling, labels, part = holed
+    cases = [[]] + [[t] for t in range(9)] + [[EMPTY_TILE, 2], [NO_BD_TILE, EMPTY_TILE], [7, 1], list(range(8, -1, -1))]
+    for ids in cases:
+        assert_batch_equals_naive(part.batch(ids), g, tiling, labels, ids)
+    assert_batch_equals_naive(part.batch([-1]), g, tiling, labels, [8])
+    assert_batch_equals_naive(part.batch([-9, -5]), g, tiling, labels, [0, 4])
+    for t in range(9):                                                      # one tile: views of the slide stores
+        b = part.batch([t])
+        for nt in ("tx", "bd"):
+            for a in ("x", "pos", "index", "cluster", "mask"):
+                assert b[nt][a].untyped_storage().data_ptr() == part.data[nt][a].untyped_storage().data_ptr()
+        for et in (TX_TX, TX_BD, TX_NB_BD):
+            assert b[et].edge_index.untyped_storage().data_ptr() == part.data[et].edge_index.untyped_storage().data_ptr()
+
+
+def _same_batch(x, y):
+    assert x.num_graphs == y.num_graphs
+    for nt in ("tx", "bd"):
+        assert set(x[nt].keys()) == set(y[nt].keys())
+        for k, v in y[nt].items():
+            assert x[nt][k].dtype == v.dtype and torch.equal(x[nt][k], v), (nt, k)
+    for et in (TX_TX, TX_BD, TX_NB_BD):
+        assert torch.equal(x[et].edge_index, y[et].edge_index), et
+
+
+def _storages(part):
+    ts = [v for st in list(part.data._nodes.values()) + list(part.data._edges.values()) for v in st.values()]
+    for d in (part.node_perm, part.node_indptr, part.node_sizes, part.edge_indptr, part.edge_sizes):
+        ts += list(d.values())
+    return {t.untyped_storage().data_ptr() for t in ts if isinstance(t, torch.Tensor) and t.numel()}
+
+
+def test_holed_partition_shards_equal_the_parent_batch_by_batch(holed):
+    g, tiling, labels, part = holed
+    ids = [5, 0, 4, 7, 1]                                                   # permuted, with the empty tile
+    sh = part.shard(ids)
+    assert len(sh) == 5
+    for nt in ("tx", "bd"):
+        assert sh.node_sizes[nt].tolist() == part.node_sizes[nt][ids].tolist()
+        assert sh.node_indptr[nt].tolist() == [0] + part.node_sizes[nt][ids].cumsum(0).tolist()
+    for loc in ([], [0], [1], [2], [3], [4], [3, 1], [2, 4], [4, 3, 2, 1, 0]):
+        _same_batch(sh.batch(loc), part.batch([ids[i] for i in loc]))
+    sub = sh.shard([3, 2, 0])                                               # a shard of a shard
+    for loc in ([0], [1], [2], [2, 1, 0]):
+        _same_batch(sub.batch(loc), part.batch([[7, 4, 5][i] for i in loc]))
+    none = part.shard([])
+    assert len(none) == 0 and none.batch([]).num_graphs == 0 and none.resident_bytes() == part.shard([]).resident_bytes()
+    _same_batch(none.batch([]), part.batch([]))
+    # the resident_bytes contract: a shard owns what it keeps
+    assert not (_storages(sh) & _storages(part)) and not (_storages(sub) & _storages(sh))
+    assert sub.resident_bytes() < sh.resident_bytes() < part.resident_bytes()
+    assert part.checksum() == T.partition_by_tiling(g, tiling, margin=1.0).checksum()
+
+
+def test_shard_carries_the_settings_and_starts_with_an_empty_store(holed):
+    g, tiling, labels, _ = holed
+    part = T.partition_by_tiling(g, tiling, margin=1.0)
+    default = T.TilePartition.csr_sort_max_edges
+    assert part.persist_max is None and part.csr_max_tiles == 1 and part._csr is None and part.csr_sort_max_edges == default
+    plain = part.shard([2, 3])
+    assert plain.persist_max is None and plain.csr_max_tiles == 1 and plain.csr_sort_max_edges == default
+    part.persist_max, part.csr_sort_max_edges, part.csr_max_tiles = 5, 123, 7
+    part.batch([0]); part.batch([1, 2])
+    assert len(part._persist) == 2
+    sh = part.shard([2, 3])
+    assert (sh.persist_max, sh.csr_sort_max_edges, sh.csr_max_tiles) == (5, 123, 7)
+    assert len(sh._persist) == 0 and sh._csr is None and sh._src_unique == {}
+    assert sh.shard([1]).csr_sort_max_edges == 123                          # ... and so do its own shards
+    assert T.TilePartition.csr_sort_max_edges == default                    # the override stayed on the instance
+
+
+def test_a_shard_has_every_attribute_a_fresh_partition_has(holed):
+    """A shard goes through the initialiser of a fresh partition: no attribute can be missing from it."""
+    g, tiling, labels, _ = holed
+    part = T.partition_by_tiling(g, tiling, margin=1.0)
+    fresh = set(vars(part))
+    assert {"persist_max", "csr_max_tiles", "_csr", "_src_unique", "_persist", "_zero_vec", "node_perm", "node_indptr",
+            "node_sizes", "edge_indptr", "edge_sizes", "data", "num_tiles"} <= fresh
+    assert set(vars(part.shard([3, 1]))) == fresh and set(vars(part.shard([]))) == fresh
+    part.batch([0]); part.batch([0, 1])                                     # using a partition adds no attribute either
+    assert set(vars(part)) == fresh
+    assert set(vars(part.shard([0]).shard([0]))) == fresh
+
+
+# (the parent commit's single module segger_amd/tiles.py: what it defined, and the project types it re-exported;
+#  names of the standard library, typing and torch that it merely imported are not part of the surface)
+TILES_NAMES = ("EdgeType", "HeteroBatch", "NODE_SKIP", "PredictQuadTreeIndex", "PredictTileIndex", "PredictTiles",
+               "QuadTreeTiling", "SquareTiling", "TileBatchSampler", "TilePartition", "_BinnedPredictTiles", "_indexed",
+               "best_fit_decreasing", "first_fit_decreasing_bucketed", "harmonic_k", "partition_by_tiling")
+
+
+def test_tiles_package_keeps_the_import_surface_of_the_module():
+    import importlib
+    mod = importlib.import_module("segger_amd.tiles")
+    for name in TILES_NAMES:
+        assert hasattr(mod, name), name
+        assert getattr(__import__("segger_amd.tiles", fromlist=[name]), name) is getattr(mod, name)
+    from segger_amd.tiles import (PredictQuadTreeIndex, PredictTileIndex, PredictTiles, QuadTreeTiling,  # noqa: F401
+                                  SquareTiling, TileBatchSampler, TilePartition, partition_by_tiling)
+    assert issubclass(PredictTileIndex, PredictTiles) and issubclass(PredictQuadTreeIndex, PredictTiles)
