@@ -23,24 +23,20 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import ops
-from .graph import EdgeCSR, EdgeGraph, batch_cache, build_edge_graph, edge_graph, graph_capture, padded_view_segments
-from .hetero import HeteroBatch, TX_BD, TX_NB_BD, TX_TX
+from . import capture as cap, ops
+from .graph import EdgeGraph, batch_cache, edge_graph, graph_capture, padded_view_segments
+from .hetero import TX_BD, TX_NB_BD, TX_TX
 
-_EDGE_TYPES = (TX_TX, TX_BD, TX_NB_BD)
+_EDGES = {"__".join(et): et for et in (TX_TX, TX_BD, TX_NB_BD)}          # size key -> edge type
+_E_TT = "__".join(TX_TX)
 
 
-def bucket_sizes(batch, granularity: float = 1.25, floor: int = 1024) -> Dict[str, int]:
-    """Round every node / edge count up to the next power of ``granularity`` (>= floor + 1 for the dummy)."""
-    def up(n: int) -> int:
-        b = floor
-        while b < n + 1:
-            b = int(b * granularity) + 1
-        return b
-    sizes = {"tx": up(batch["tx"].num_nodes), "bd": up(batch["bd"].num_nodes)}
-    for et in _EDGE_TYPES:
-        sizes["__".join(et)] = up(int(batch[et].edge_index.shape[1]))
-    return sizes
+def bucket_sizes(batch, granularity: float = 1.25, floor: int = 1024, headroom: int = 0) -> Dict[str, int]:
+    """Round every node / edge count up to the next power of ``granularity`` (>= floor + 1 for the dummy).  The boundary
+    side is cheap: everything but the transcripts and their neighbour edges gets ``headroom`` granules more."""
+    c = cap.counts(batch, _EDGES)
+    return {k: cap.ladder(c[k], granularity, floor, 0 if k in ("tx", _E_TT) else headroom)
+            for k in ("tx", "bd", *_EDGES)}
 
 
 class GraphedPredictor:
@@ -58,17 +54,15 @@ class GraphedPredictor:
         dev = next(model.parameters()).device
         self.dev = dev
         nt, nb = sizes["tx"], sizes["bd"]
-        z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+        z = cap.zeros_on(dev)
         self.inp = {
             "tx_x": z(nt, dtype=torch.int32), "tx_pos": z(nt, 2), "tx_batch": z(nt, dtype=torch.long),
             "bd_x": z(nb, bd_dim), "bd_pos": z(nb, 2), "bd_batch": z(nb, dtype=torch.long),
             "bd_index": z(nb, dtype=torch.long),
         }
-
-        def csr(n_rows, n_cols, n_edges):
-            return EdgeCSR(z(n_rows + 1, dtype=torch.long), z(n_edges, dtype=torch.int32),
-                           z(n_edges, dtype=torch.int32), n_rows, n_cols)
-        e = {et: sizes["__".join(et)] for et in _EDGE_TYPES}
+        self._nodes = {t: {a: self.inp[f"{t}_{a}"] for a in ("x", "pos", "batch")} for t in ("tx", "bd")}
+        csr = lambda n_rows, n_cols, n_edges: cap.static_csr(n_rows, n_cols, n_edges, dev)
+        e = {et: sizes[k] for k, et in _EDGES.items()}
         self.graphs: Dict[Tuple[str, str, str], EdgeGraph] = {
             TX_TX: EdgeGraph(csr(nt, nt, e[TX_TX]), None, nt, nt, e[TX_TX]),
             TX_BD: EdgeGraph(csr(nb, nt, e[TX_BD]), None, nt, nb, e[TX_BD]),
@@ -79,17 +73,13 @@ class GraphedPredictor:
         # the per-graph min / max tables are sized for max_graphs, so one captured graph serves batches of any
         # number of tiles up to that (graphs without nodes are never read)
         self.num_graphs = int(max_graphs)
+        self._limits = {**self.sizes, "graphs": self.num_graphs}
 
     def fits(self, batch) -> bool:
-        s = self.sizes
-        return (batch["tx"].num_nodes < s["tx"] and batch["bd"].num_nodes < s["bd"]
-                and all(int(batch[et].edge_index.shape[1]) <= s["__".join(et)] for et in _EDGE_TYPES)
-                and int(getattr(batch, "num_graphs", 1)) <= self.num_graphs)
+        return cap.fits(self._limits, batch, _EDGES)
 
     def waste(self, batch) -> float:
-        s = self.sizes
-        return max(s["__".join(TX_TX)] / max(int(batch[TX_TX].edge_index.shape[1]), 1),
-                   s["tx"] / max(batch["tx"].num_nodes, 1))
+        return cap.waste(self.sizes, batch, _EDGES, _E_TT)
 
     # -- staging ------------------------------------------------------------------------------
     @torch.no_grad()
@@ -103,12 +93,8 @@ class GraphedPredictor:
         g_tt = edge_graph(cache, TX_TX, batch[TX_TX].edge_index, n_tx, n_tx, need_by_src=False, validate=False)
         g_tb = edge_graph(cache, TX_BD, batch[TX_BD].edge_index, n_tx, n_bd, need_by_src=False, validate=False)
         g_nb = edge_graph(cache, TX_NB_BD, batch[TX_NB_BD].edge_index, n_tx, n_bd, need_by_dst=False, validate=False)
-        I = self.inp
-        segs = [(I["tx_x"], tx["x"], "const", 0, 0, 0), (I["tx_pos"], tx["pos"], "tile", 2, 0, 0),
-                (I["tx_batch"], tx["batch"], "tile", 1, 0, 0),
-                (I["bd_x"], bd["x"], "tile", max(int(bd["x"][0].numel()), 1), 0, 0),
-                (I["bd_pos"], bd["pos"], "tile", 2, 0, 0), (I["bd_batch"], bd["batch"], "tile", 1, 0, 0),
-                (I["bd_index"], bd["index"], "tile", 1, 0, 0)]
+        # nodes: dummies are copies of node 0 (gene id 0)
+        segs = cap.node_segments(self._nodes, tx, bd, 0) + [(self.inp["bd_index"], bd["index"], "tile", 1, 0, 0)]
         segs += padded_view_segments(self.graphs[TX_TX].by_dst, g_tt.by_dst, n_tx, None)
         segs += padded_view_segments(self.graphs[TX_BD].by_dst, g_tb.by_dst, n_bd, ("mod", n_tx, nt - n_tx))
         segs += padded_view_segments(self.graphs[TX_NB_BD].by_src, g_nb.by_src, n_tx, ("mod", n_bd, nb - n_bd))
@@ -143,11 +129,7 @@ class GraphedPredictor:
             raise RuntimeError("GraphedPredictor needs model.eval()")
         self._stage(batch)
         if self.graph is None:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._run()                              # warm-up on a side stream (lazy inits, allocator)
-            torch.cuda.current_stream().wait_stream(s)
+            cap.on_side_stream(self._run)            # warm-up (lazy inits, allocator)
             self.graph = torch.cuda.CUDAGraph()
             with graph_capture(self.graph):
                 self._run()
@@ -181,20 +163,12 @@ class GraphedPredictorPool:
         self.buckets: list = []
 
     def _pick(self, batch) -> GraphedPredictor:
-        fit = [b for b in self.buckets if b.fits(batch)]
-        best = min(fit, key=lambda b: b.waste(batch)) if fit else None
-        full = len(self.buckets) >= self.max_buckets
-        if best is None or (best.waste(batch) > self.granularity ** 2 and not full):
-            if full:
-                raise RuntimeError(f"no captured bucket holds this batch and {self.max_buckets} buckets exist")
-            sizes = bucket_sizes(batch, self.granularity, floor=256)
-            for k in sizes:                               # the boundary side is cheap: one granule of headroom more
-                if k != "tx" and k != "__".join(TX_TX):
-                    sizes[k] = int(sizes[k] * self.granularity) + 1
-            best = GraphedPredictor(self.model, sizes, self.bd_dim, self.min_similarity,
-                                    max(self.max_graphs, int(getattr(batch, "num_graphs", 1))))
-            self.buckets.append(best)
-        return best
+        return cap.pick(self.buckets, batch, lambda: self._capture(batch), self.granularity, self.max_buckets,
+                        f"no captured bucket holds this batch and {self.max_buckets} buckets exist")
+
+    def _capture(self, batch) -> GraphedPredictor:
+        return GraphedPredictor(self.model, bucket_sizes(batch, self.granularity, floor=256, headroom=1), self.bd_dim,
+                                self.min_similarity, max(self.max_graphs, int(getattr(batch, "num_graphs", 1))))
 
     def predict(self, batch):
         return self._pick(batch).predict(batch)

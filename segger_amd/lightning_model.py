@@ -26,7 +26,7 @@ from . import ops
 from .graph import batch_cache, edge_graph, flush_validation
 from .hetero import TX_BD, TX_NB_BD
 from .ist_encoder import ISTEncoder
-from .triplet_loss import MetricLoss, TripletLoss
+from .triplet_loss import MetricLoss, TripletLoss, boundary_loss_mask, loss_inputs, masked_count
 
 try:  # pragma: no cover - lightning is not in the build image
     from lightning import LightningModule as _Base
@@ -211,19 +211,11 @@ class LitISTEncoder(_Base):
             raise RuntimeError("call setup() (or set_similarities) before computing losses")
         if embeddings is None:
             embeddings = self.forward(batch)
-        tx_mask = batch['tx']['mask']
-        # (kept with the batch: the samplers' per-batch indices are keyed by the mask tensor they were built from, and a
-        # mask recomputed every step would rebuild the boundary index -- ~50 small launches -- every step)
-        bm, bc = batch['bd']['mask'], batch['bd']['cluster']
-        cache = batch_cache(batch)
-        mkey = ("bd_loss_mask", bm.data_ptr(), bc.data_ptr(), int(bm.numel()))
-        bd_mask = cache.get(mkey)
-        if bd_mask is None:
-            bd_mask = cache[mkey] = bm & (bc >= 0)
         u_tx, u_bd = uniforms if uniforms is not None else (None, None)
         if (self.fused_loss_head and embeddings['tx'].is_cuda and embeddings['tx'].shape[1] % 2 == 0
                 and embeddings['tx'].shape[0] > 0 and embeddings['bd'].shape[0] > 0):
-            return self._losses_fused(batch, embeddings, tx_mask, bd_mask, u_tx, u_bd, dst_neg)
+            return self._losses_fused(batch, embeddings, u_tx, u_bd, dst_neg)
+        tx_mask, bd_mask = batch['tx']['mask'], boundary_loss_mask(batch, batch_cache(batch))
         loss_tx = self.loss_tx.forward_masked(embeddings['tx'], batch['tx']['cluster'], tx_mask, batch_cache(batch),
                                               uniforms=u_tx)
         loss_bd = self.loss_bd.forward_masked(embeddings['bd'], batch['bd']['cluster'], bd_mask, uniforms=u_bd,
@@ -235,25 +227,21 @@ class LitISTEncoder(_Base):
 
     fused_loss_head = True      # the three losses + their weighted sum as one autograd node (ops.loss_head) on the GPU
 
-    def _losses_fused(self, batch, embeddings, tx_mask, bd_mask, u_tx, u_bd, dst_neg):
+    def _losses_fused(self, batch, embeddings, u_tx, u_bd, dst_neg):
         """The same four values through ``ops.loss_head``: samplers as in the unfused route (same draws from the same
         generators, in the same order), then ONE node for the three loss kernels and the weighted sum."""
-        from .triplet_loss import _cached_index, _masked_count
         cache = batch_cache(batch)
         z_tx, z_bd = embeddings['tx'], embeddings['bd']
         dev = z_tx.device
         n_tx, n_bd = z_tx.shape[0], z_bd.shape[0]
         tx_lab, bd_lab = batch['tx']['cluster'], batch['bd']['cluster']
-        ix_tx = _cached_index(self.loss_tx.selector, "tx_triplet_index", tx_lab, tx_mask, cache)
+        ix_tx, ix_bd, _, of_tx = loss_inputs(self.loss_tx, self.loss_bd, batch, cache)
         if "anchors" not in ix_tx:
             ix_tx["anchors"] = torch.arange(n_tx, device=dev)
-            ix_tx["rescale"] = float(n_tx) / _masked_count(tx_mask)
+            ix_tx["rescale"] = float(n_tx) / masked_count(ix_tx["mask"])
         if "head_a" not in ix_tx:               # per-loss rescaling: loss_tx from a mean over all rows to the masked ones
             ix_tx["head_a"] = torch.cat([ix_tx["rescale"].reshape(1).float(), torch.ones(2, device=dev)])
         pos, neg, _, _ = self.loss_tx.selector.sample_triplets(tx_lab, u_tx, index=ix_tx)
-        ix_bd = _cached_index(self.loss_bd.selector, "bd_metric_index", bd_lab, bd_mask, cache)
-        if "weight" not in ix_bd:
-            ix_bd["weight"] = bd_mask.float() / _masked_count(bd_mask)
         bpos, bneg, dp, dn = self.loss_bd.selector.sample_triplets(bd_lab, u_bd, index=ix_bd)
         sg = None
         if n_bd > 1:                                                         # :173-175
@@ -263,11 +251,6 @@ class LitISTEncoder(_Base):
             g = edge_graph(cache, TX_BD, batch[TX_BD].edge_index, n_tx, n_bd,
                            need_by_src="lazy" if torch.is_grad_enabled() else False, validate="deferred")
             sg = (src_pos, dst_pos, dst_neg, self._sg_margin, 1e-6, g.by_dst, g.src_unique)
-            # "the segmentation triplet anchored at transcript r": what lets the one-launch loss head gather a transcript's
-            # whole gradient row instead of scattering into it; depends on the edge list only -> kept with the tile set
-            store = cache.get("persistent")
-            keep, okey = (store, "sg_of_tx") if store is not None else (cache, ("sg_of_tx", src_pos.data_ptr(), int(src_pos.numel()), n_tx))
-            of_tx = (lambda: keep.get(okey) if keep.get(okey) is not None else keep.setdefault(okey, ops.anchor_index(src_pos, n_tx)))
         w = self._scheduled_weights(self._w_start, self._w_end)
         key = tuple(float(v) for v in w)
         wdev = self.__dict__.setdefault("_head_weights", {})
@@ -278,6 +261,8 @@ class LitISTEncoder(_Base):
             b = wdev[(key, dev)] = torch.tensor(key, dtype=torch.float32, device=dev)
         spec = ops.LossHeadSpec((ix_tx["anchors"], pos, neg, self.loss_tx.margin, self.loss_tx.eps),
                                 (bpos, bneg, dp, dn, ix_bd["weight"], 1e-8), sg, sg_kind=self._sg_loss_type,
+                                # (of_tx: "the segmentation triplet anchored at transcript r", what lets the one-launch
+                                #  loss head gather a transcript's whole gradient row instead of scattering into it)
                                 tx_anchors_are_rows=True, sg_of_tx=of_tx if sg is not None else None)
         out = ops.loss_head(z_tx, z_bd, ix_tx["head_a"], b, spec)
         return out[0], out[1], out[2], out[3]

@@ -36,31 +36,27 @@ graph.  Covered by a two-rank gloo test on one GPU; not yet run over RCCL on a m
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 from torch import Tensor
 
-from . import ops
+from . import capture as cap, ops      # (`capture` is also an argument name here)
 from .graph import EdgeCSR, EdgeGraph, batch_cache, edge_graph, graph_capture, padded_view_segments
 from .hetero import TX_BD, TX_TX
 from .ist_encoder import StagedInputs, rows_by_gene
+from .triplet_loss import loss_inputs, masked_count
+
+_EDGES = {"e_tt": TX_TX, "e_tb": TX_BD}                       # size key -> edge type
 
 
 def step_bucket(batch, granularity: float = 1.06, floor: int = 256) -> Dict[str, int]:
     """Bucket sizes for one batch: counts rounded up to the next power of ``granularity`` (> the count: every node type
     keeps at least one dummy).  The boundary-side counts are a small part of the work and get one granule of headroom
     more, so that batches which agree on the transcript side share a bucket."""
-    def up(n: int, extra: int = 0) -> int:
-        b = floor
-        while b <= n:
-            b = int(b * granularity) + 1
-        for _ in range(extra):
-            b = int(b * granularity) + 1
-        return b
-    e_tt, e_tb = int(batch[TX_TX].edge_index.shape[1]), int(batch[TX_BD].edge_index.shape[1])
-    return {"tx": up(batch["tx"].num_nodes), "bd": up(batch["bd"].num_nodes, 1), "e_tt": up(e_tt), "e_tb": up(e_tb, 1),
-            "graphs": up(int(getattr(batch, "num_graphs", 1)), 1)}
+    c = cap.counts(batch, _EDGES)
+    up = lambda key, extra=0: cap.ladder(c[key], granularity, floor, extra)
+    return {"tx": up("tx"), "bd": up("bd", 1), "e_tt": up("e_tt"), "e_tb": up("e_tb", 1), "graphs": up("graphs", 1)}
 
 
 USE_ADAM_KERNEL = True       # (False: torch's fused Adam inside the captured step -- A/B switch)
@@ -70,6 +66,12 @@ DEFER_LOSS_FINISH = True     # (False: the one-launch loss head's finishing laun
 STEP_INC = 256               # what a training forward advances the encoder's dropout counter by (ist_encoder.py)
 
 
+class StepEnd(NamedTuple):
+    """What ``_run_grads`` leaves to the end of the step (``_opt_step``)."""
+    counter_inc: int = 0          # the dropout-counter advance a merged-draws step read ahead of
+    adam_advanced: bool = False   # Adam's step counters already moved (in the draws launch)
+
+
 class GraphedTrainStep:
     """The captured step of ONE shape bucket (see :class:`GraphedTrainer` for the per-batch dispatch).  A batch is
     written into the bucket's static buffers by ONE launch (``ops.stage`` -> ``segger_stage``): node features, the three
@@ -77,12 +79,10 @@ class GraphedTrainStep:
     indices are all "copy the batch's own (cached) arrays, fill the padding by a formula" segments."""
 
     def __init__(self, lit_model, optimizer, sizes: Dict[str, int], template, grad_sync=None, grad_bucket=None):
-        if grad_bucket is None and hasattr(getattr(grad_sync, "__self__", None), "pack"):
-            grad_bucket, grad_sync = grad_sync.__self__, None     # bucket.all_reduce_mean given as the callable
-        self.grad_sync, self.grad_bucket = grad_sync, grad_bucket
-        self.split = grad_sync is not None or grad_bucket is not None
-        if grad_bucket is not None:
-            grad_bucket._ensure()                             # the flat buffer must exist before anything is captured
+        self.exchange = cap.exchange_of(grad_sync, grad_bucket)
+        self.split = self.exchange.split
+        if self.exchange.bucket is not None:
+            self.exchange.bucket._ensure()                    # the flat buffer must exist before anything is captured
         if lit_model.loss_tx is None or lit_model.loss_bd is None:
             raise RuntimeError("call setup() (or set_similarities) before training")
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
@@ -96,7 +96,7 @@ class GraphedTrainStep:
         for sel in (lit_model.loss_tx.selector, lit_model.loss_bd.selector):      # no host -> device copy in a capture
             sel.similarity, sel.dissimilarity = sel.similarity.to(dev), sel.dissimilarity.to(dev)
         nt, nb, ett, etb = sizes["tx"], sizes["bd"], sizes["e_tt"], sizes["e_tb"]
-        z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+        z = cap.zeros_on(dev)
         i32, i64 = torch.int32, torch.int64
         self.n_genes = int(lit_model.model.lin_first["tx"].weight.shape[0])
         # positions / graph ids of both node types back to back: the encoder runs its positional embedder once over
@@ -111,8 +111,7 @@ class GraphedTrainStep:
                       "bd": {"x": z(nb, *template["bd"]["x"].shape[1:], dtype=self._bd_dtype(lit_model, template)),
                              "pos": self.pos_all[nt:], "batch": z(nb, dtype=i64)}}
 
-        def csr(n_rows, n_cols, n_edges):
-            return EdgeCSR(z(n_rows + 1, dtype=i64), z(n_edges, dtype=i32), z(n_edges, dtype=i32), n_rows, n_cols)
+        csr = lambda n_rows, n_cols, n_edges: cap.static_csr(n_rows, n_cols, n_edges, dev)
         self.g_tt = EdgeGraph(csr(nt, nt, ett), csr(nt, nt, ett), nt, nt, ett)
         self.g_tb = EdgeGraph(csr(nb, nt, etb), None, nt, nb, etb, None, True)        # one-pass backward (see above)
         by_gene_col = z(nt, dtype=i32)
@@ -146,8 +145,6 @@ class GraphedTrainStep:
         self._training: Optional[bool] = None
         self._iota = torch.arange(nt, device=dev)
         self._captured_hp = None
-        self._late = (0, False)                               # (dropout-counter advance owed to the step's end, Adam's counters advanced)
-        self._warming = False
         # The captured forward runs on ALIASES of the parameters (same storage, distinct autograd leaves).  A leaf's
         # gradient sink (its AccumulateGrad node) belongs to the stream it was created on and lives as long as any
         # autograd graph mentions it: after an eager step whose loss the caller still holds, the parameters' own
@@ -162,7 +159,8 @@ class GraphedTrainStep:
         self.draws = None                                     # tests: fixed (tx pos/neg, bd pos/neg/dp/dn, dst_neg)
         # queue the backward's partial sums and run them as one launch (ops.deferred_reductions).  Only sound when no
         # autograd node READS a parameter gradient before the backward ends (a parameter used by two nodes has its two
-        # gradients added on the spot): verified numerically during the warm-up of every capture, see _warm_up
+        # gradients added on the spot): verified numerically during the warm-up of every capture, see _warm_up, which
+        # settles this for the runs that follow
         self.defer_sums = True
 
     @staticmethod
@@ -171,16 +169,11 @@ class GraphedTrainStep:
         return dt if (src.is_floating_point and dt in (torch.bfloat16, torch.float16)) else src
 
     def fits(self, batch) -> bool:
-        s = self.sizes
-        e_tb = int(batch[TX_BD].edge_index.shape[1])
-        return (batch["bd"].num_nodes < s["bd"] and int(batch[TX_TX].edge_index.shape[1]) <= s["e_tt"]
-                and e_tb <= s["e_tb"] and batch["tx"].num_nodes < s["tx"]
-                and int(getattr(batch, "num_graphs", 1)) <= s["graphs"])
+        return cap.fits(self.sizes, batch, _EDGES)
 
     def waste(self, batch) -> float:
         """Padded / real size of the transcript side (what a step costs)."""
-        s = self.sizes
-        return max(s["e_tt"] / max(int(batch[TX_TX].edge_index.shape[1]), 1), s["tx"] / max(batch["tx"].num_nodes, 1))
+        return cap.waste(self.sizes, batch, _EDGES, "e_tt")
 
     # ------------------------------------------------------------------------------------------- staging
     def _sampler_segments(self, dst: dict, ix: dict, n_total: int) -> list:
@@ -192,7 +185,6 @@ class GraphedTrainStep:
 
     @torch.no_grad()
     def stage(self, batch) -> None:
-        from .triplet_loss import _cached_index, _masked_count
         if not self.fits(batch):
             raise ValueError("batch does not fit this bucket")
         lit, s = self.lit, self.sizes
@@ -207,23 +199,12 @@ class GraphedTrainStep:
         e_tb = g_tb.n_edges
         # what depends on the tile set only (kept across epochs by tiles.TilePartition; per batch object otherwise)
         keep = store if store is not None else cache
-        ix_tx = keep.get("tx_triplet_index") if store is not None else None
-        if ix_tx is None:
-            ix_tx = _cached_index(lit.loss_tx.selector, "tx_triplet_index", tx["cluster"], tx["mask"], cache)
+        ix_tx, ix_bd, _, of_tx = loss_inputs(lit.loss_tx, lit.loss_bd, batch, cache)
         a0 = ("rows_over_masked", nt)                         # loss_tx: mean over the padded rows -> mean over the masked real ones
         if a0 not in ix_tx:
-            ix_tx[a0] = (float(nt) / _masked_count(ix_tx["mask"])).reshape(1)
-        ix_bd = keep.get("bd_metric_index") if store is not None else None
-        if ix_bd is None:
-            ix_bd = _cached_index(lit.loss_bd.selector, "bd_metric_index", bd["cluster"],
-                                  bd["mask"] & (bd["cluster"] >= 0), cache)
-        if "weight" not in ix_bd:
-            ix_bd["weight"] = ix_bd["mask"].float() / _masked_count(ix_bd["mask"])
+            ix_tx[a0] = (float(nt) / masked_count(ix_tx["mask"])).reshape(1)
         by_gene = rows_by_gene(tx["x"], self.n_genes, cache)
         ei = batch[TX_BD].edge_index
-        of_tx = keep.get("sg_of_tx")
-        if of_tx is None:
-            of_tx = keep["sg_of_tx"] = ops.anchor_index(ei[0], n_tx)
         w = lit._scheduled_weights(lit._w_start, lit._w_end)
         bd_x, x_dt = bd["x"], self.nodes["bd"]["x"].dtype
         if bd_x.dtype != x_dt:
@@ -234,19 +215,14 @@ class GraphedTrainStep:
             bd_x = hit
         fb = ops.float_bits
         dummies = ("mod", n_tx, nt - n_tx)                    # dummy transcripts, round robin
-        N = self.nodes
-        segs = [
-            # nodes: dummies are copies of node 0 (gene id: the last gene, whose rows-by-gene group they extend)
-            (N["tx"]["x"], tx["x"], "const", self.n_genes - 1, 0, 0),
-            (N["tx"]["pos"], tx["pos"], "tile", 2, 0, 0), (N["tx"]["batch"], tx["batch"], "tile", 1, 0, 0),
-            (N["bd"]["x"], bd_x, "tile", max(int(bd_x[0].numel()), 1), 0, 0),
-            (N["bd"]["pos"], bd["pos"], "tile", 2, 0, 0), (N["bd"]["batch"], bd["batch"], "tile", 1, 0, 0),
+        # nodes: dummies are copies of node 0 (gene id: the last gene, whose rows-by-gene group they extend)
+        segs = cap.node_segments(self.nodes, tx, bd, self.n_genes - 1, bd_x) + [
             (self.batch_all[nt:], bd["batch"], "tile", 1, 0, 0, s["graphs"]),
             (self.by_gene.indptr, by_gene.indptr[: self.n_genes], "const", nt, 0, 0),
             (self.by_gene.col, by_gene.col, "div", n_tx, 1, 0),
             # segmentation triplets: padded ones carry -1 and are skipped by the kernels
             (self.sg_src, ei[0], *dummies, 0), (self.sg_pos, ei[1], "const", -1, 0, 0),
-            (self.sg_of_tx, of_tx, "const", -1, 0, 0), (self.tx_state, None, "const", 0, 0, 0),
+            (self.sg_of_tx, of_tx(), "const", -1, 0, 0), (self.tx_state, None, "const", 0, 0, 0),
             (self.bd_weight, ix_bd["weight"], "const", 0, 0, 0),
             (self.n_bd, None, "const", n_bd, 0, 0),
             (self.minmax[0], None, "const", fb(float("inf")), 0, 0), (self.minmax[1], None, "const", fb(float("-inf")), 0, 0),
@@ -268,16 +244,14 @@ class GraphedTrainStep:
         ops.stage(segs, self.dev)
 
     # ------------------------------------------------------------------------------------------- the step
-    def _run(self) -> None:
-        self._run_grads()
-        self._opt_step()
+    def _run(self, warm: bool = False) -> None:
+        self._opt_step(self._run_grads(self.defer_sums, adam_counters=not warm and not self.split))
 
-    def _opt_step(self) -> None:
+    def _opt_step(self, end: StepEnd) -> None:
         """Adam on the hand-written kernel (two launches for all tensors -- one when the step's first launch advanced the
         step counters; torch's fused multi-tensor Adam takes three and ~40 us for the encoder's 60 small tensors); any other
         optimizer steps itself.  The dropout counter a merged-draws step read un-advanced moves on here."""
-        inc, adv = self._late
-        self._late = (0, False)
+        inc, adv = end
         enc = self.lit.model
         if USE_ADAM_KERNEL and ops.adam_step(self.opt, steps_advanced=adv, counter=enc._step_dev if inc else None,
                                              counter_inc=inc, hyper_dev=self.hyper if self._hyper_on_device else None):
@@ -297,7 +271,10 @@ class GraphedTrainStep:
         if inc:
             ops.step_advance(enc._step_dev, inc)
 
-    def _run_grads(self) -> None:
+    def _run_grads(self, defer_sums: bool, adam_counters: bool) -> StepEnd:
+        """Forward, losses, backward; ``.grad`` of the parameters and ``self.out`` set.  ``defer_sums``: see __init__.
+        ``adam_counters``: the draws launch may advance Adam's step counters -- not in a warm-up, which ends in
+        ``optimizer.step()``, and not in split mode, whose empty steps replay Adam's graph without this one."""
         lit, enc, s = self.lit, self.lit.model, self.sizes
         nt = s["tx"]
         tx, bd = self.nodes["tx"], self.nodes["bd"]
@@ -305,7 +282,7 @@ class GraphedTrainStep:
         staged = StagedInputs(self.by_gene, self.pos_all, self.batch_all, self.minmax)
         fixed = self.draws
         drawn = None
-        self._late = (0, False)
+        end = StepEnd()
         if MERGED_DRAWS and fixed is None:
             # ALL of the step's random draws in its first launch (ops.step_draws), from the dropout counter as it stands + the
             # advance it receives at the END of the step (inside Adam's launch): the same masks and triplets as advancing
@@ -314,9 +291,7 @@ class GraphedTrainStep:
             views = enc.plane_views(graphs, seed_offset=inc) if enc.training else None
             p_drop = enc.conv_layers[0].conv[TX_TX].dropout
             adv = None
-            # (not while warming up -- that step ends in optimizer.step() -- and not in split mode, whose empty steps replay
-            # Adam's graph without this one)
-            if USE_ADAM_KERNEL and not self._warming and not self.split:
+            if USE_ADAM_KERNEL and adam_counters:
                 adv = ops.adam_step_counters(self.opt, self._params)
             planes, samples, dst_neg = ops.step_draws(
                 [(c, sd) for _, _, c, sd in views] if views else [], enc.n_heads, p_drop,
@@ -324,7 +299,7 @@ class GraphedTrainStep:
                 enc._step_dev, advance=adv)
             staged = staged._replace(draws=(enc.planes_of(views, planes) if views else None, inc))
             drawn = (samples, dst_neg)
-            self._late = (inc, adv is not None)
+            end = StepEnd(inc, adv is not None)
         z = torch.func.functional_call(
             enc, self._alias,
             ({"tx": tx["x"], "bd": bd["x"]}, {TX_TX: None, TX_BD: None}, {"tx": tx["pos"], "bd": bd["pos"]},
@@ -350,7 +325,7 @@ class GraphedTrainStep:
                                 tx_state=self.tx_state, grad_out_hint=self._e_loss,
                                 defer_finish=DEFER_LOSS_FINISH)      # the losses are read after the backward (self.out after the replay)
         out = ops.loss_head(z["tx"], z["bd"], self.head_a, self.scal[3:6], spec)
-        if self.defer_sums:                                   # ~30 partial sums of the backward as one launch
+        if defer_sums:                                        # ~30 partial sums of the backward as one launch
             with ops.deferred_reductions(self.dev):
                 grads = torch.autograd.grad(out, self._leaves, self._e_loss, allow_unused=True)
         else:
@@ -358,6 +333,7 @@ class GraphedTrainStep:
         for p, g in zip(self._params, grads):
             p.grad = g
         self.out = out.detach()
+        return end
 
     def _warm_up(self, keep) -> None:
         """One eager step before the capture.  With deferred partial sums it is run twice from the same random
@@ -365,14 +341,12 @@ class GraphedTrainStep:
         agree (up to the order of float atomics in the loss kernels); if they do not, some autograd node consumed a
         gradient before the queued sums ran, and this step falls back to immediate sums."""
         if self.defer_sums:
-            self.defer_sums = False
-            self._run_grads()
+            self._run_grads(False, adam_counters=False)
             ref = [None if p.grad is None else p.grad.detach().clone() for p in self._params]
             with torch.no_grad():
                 self.lit.model._step_dev.copy_(keep[3])       # same dropout masks and sampler draws again
                 self.tx_state.zero_()                         # (what the staging launch does before every step)
-            self.defer_sums = True
-            self._run_grads()
+            self._run_grads(True, adam_counters=False)
             names = {id(p): n for n, p in self.lit.model.named_parameters()}
             why = None
             for p, r in zip(self._params, ref):
@@ -395,10 +369,10 @@ class GraphedTrainStep:
                 import warnings
                 warnings.warn("GraphedTrainStep: a parameter gradient is consumed inside the backward pass "
                               f"({why}); partial sums are launched where they are produced (more kernel nodes)")
-                self._run_grads()
+                self._run_grads(False, adam_counters=False)
             self.opt.step()
         else:
-            self._run()
+            self._run(warm=True)
 
     @torch.no_grad()
     def _snapshot(self):
@@ -444,15 +418,7 @@ class GraphedTrainStep:
         elif self.graph is None or self._training != lit.model.training:
             lit.model._materialize_bd(self.nodes["bd"]["x"].shape[1], self.dev)
             keep = self._snapshot()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                     # warm-up: lazy inits, allocator, optimizer state
-                self._warming = True
-                try:
-                    self._warm_up(keep)
-                finally:
-                    self._warming = False
-            torch.cuda.current_stream().wait_stream(side)
+            cap.on_side_stream(lambda: self._warm_up(keep))       # lazy inits, allocator, optimizer state
             self._restore(keep)                               # ... which must not count as a training step
             self.tx_state.zero_()                             # (the warm-up's forward left its chains: staged state again)
             aliases = list(self._alias.values())
@@ -464,12 +430,11 @@ class GraphedTrainStep:
                         self._run()
                 else:                                         # forward + backward (+ pack) | <exchange> | Adam
                     with graph_capture(self.graph):
-                        self._run_grads()
-                        if self.grad_bucket is not None:      # gradients -> the bucket's flat buffer; .grad = its slices
-                            self.grad_bucket.pack()
+                        end = self._run_grads(self.defer_sums, adam_counters=False)
+                        self.exchange.pack()                  # gradients -> a bucket's flat buffer; .grad = its slices
                     self.graph_opt = torch.cuda.CUDAGraph()
                     with graph_capture(self.graph_opt, pool=self.graph.pool()):
-                        self._opt_step()
+                        self._opt_step(end)                   # (the dropout counter advances here, on empty steps too)
             # the graph holds raw pointers into these buffers: they must outlive it whatever happens to the cache
             self._pack_refs = [(pk, pk.w, pk.b, pk._wt) for pk in ops.packs_of(aliases)]
             self._grads = [p.grad for p in self._params]
@@ -487,30 +452,19 @@ class GraphedTrainStep:
 
     def _replay(self, empty: bool = False) -> None:
         """Fused mode: one replay.  Split mode: replay forward + backward (``empty``: zero the gradients instead -- this
-        rank ran out of batches), hand this bucket's gradient tensors to the parameters, let ``grad_sync`` exchange
+        rank ran out of batches), hand this bucket's gradient tensors to the parameters, let the exchange reduce
         them (exactly ONE collective per step on every rank: the warm-up of a capture never synchronises), replay
         Adam."""
         if not self.split:
             self.graph.replay()
             return
-        if self.grad_bucket is not None:
-            if empty:
-                self.grad_bucket.zero()
-            else:
-                self.graph.replay()                           # ends with the pack into the flat buffer
-                for p, v in zip(self.grad_bucket.params, self.grad_bucket.views):
-                    p.grad = v
-            self.grad_bucket.all_reduce_mean(packed=True)
-            self.graph_opt.replay()                           # reads the buffer's slices
-            return
         if empty:
-            torch._foreach_zero_([g for g in self._grads if g is not None])
+            self.exchange.zero(self._params, self._grads)
         else:
-            self.graph.replay()
-        for p, g in zip(self._params, self._grads):
-            p.grad = g
-        self.grad_sync()          # must average IN PLACE: the captured optimizer reads the tensors .grad points at now
-        self.graph_opt.replay()
+            self.graph.replay()                               # (with a bucket: ends with the pack into the flat buffer)
+            self.exchange.adopt(self._params, self._grads)
+        self.exchange.reduce()
+        self.graph_opt.replay()                               # reads the tensors .grad points at now
 
     def empty_step(self) -> None:
         self._replay(empty=True)
@@ -530,43 +484,32 @@ class GraphedTrainer:
         One collective per ``step`` call on every rank; ``step(None)`` is the empty step of a rank that ran out of
         batches: zeros into the exchange, then Adam."""
         self.lit, self.opt, self.granularity, self.max_buckets = lit_model, optimizer, granularity, max_buckets
-        if grad_bucket is None and hasattr(getattr(grad_sync, "__self__", None), "pack"):
-            grad_bucket, grad_sync = grad_sync.__self__, None
-        self.grad_sync, self.grad_bucket = grad_sync, grad_bucket
+        self.exchange = cap.exchange_of(grad_sync, grad_bucket)
         self.buckets: List[GraphedTrainStep] = []
         self.n_captures = 0
         self._last: Optional[GraphedTrainStep] = None
 
     def _empty_step(self) -> None:
-        if self.grad_sync is None and self.grad_bucket is None:
+        if not self.exchange.split:
             return
         if self._last is not None and self._last.graph_opt is not None:
             self._last.empty_step()
             return
-        if self.grad_bucket is not None:                      # no bucket captured yet on this rank: eager
-            self.grad_bucket.zero()
-            self.grad_bucket.all_reduce_mean(packed=True)
-        else:
-            for g in self.opt.param_groups:
-                for p in g["params"]:
-                    if p.requires_grad:
-                        p.grad = torch.zeros_like(p)
-            self.grad_sync()
+        # no bucket captured yet on this rank: eager
+        self.exchange.zero([p for g in self.opt.param_groups for p in g["params"] if p.requires_grad])
+        self.exchange.reduce()
         self.opt.step()
 
     def step(self, batch) -> Optional[Tensor]:
         if batch is None:
             return self._empty_step()
-        fit = [b for b in self.buckets if b.fits(batch)]
-        best = min(fit, key=lambda b: b.waste(batch)) if fit else None
-        full = len(self.buckets) >= self.max_buckets
-        if best is None or (best.waste(batch) > self.granularity ** 2 and not full):
-            if full:
-                raise RuntimeError(f"no captured bucket holds this batch and {self.max_buckets} buckets exist: "
-                                   f"raise `granularity` or `max_buckets`")
-            best = GraphedTrainStep(self.lit, self.opt, step_bucket(batch, self.granularity), batch, self.grad_sync,
-                                    self.grad_bucket)
-            self.buckets.append(best)
-            self.n_captures += 1
-        self._last = best
-        return best.step(batch)
+        self._last = cap.pick(
+            self.buckets, batch, lambda: self._capture(batch), self.granularity, self.max_buckets,
+            f"no captured bucket holds this batch and {self.max_buckets} buckets exist: raise `granularity` or `max_buckets`")
+        return self._last.step(batch)
+
+    def _capture(self, batch) -> GraphedTrainStep:
+        made = GraphedTrainStep(self.lit, self.opt, step_bucket(batch, self.granularity), batch, self.exchange.sync,
+                                self.exchange.bucket)
+        self.n_captures += 1
+        return made

@@ -10,11 +10,13 @@ device; sampling uses torch's device RNG exactly where the reference does
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
 from torch.nn import functional as F
+
+from .hetero import TX_BD
 
 
 class FastTripletSelector:
@@ -112,24 +114,67 @@ class FastTripletSelector:
         return positives, negatives, d_pos, d_neg
 
 
-def _masked_count(mask: Tensor) -> Tensor:
+def masked_count(mask: Tensor) -> Tensor:
     return mask.sum().clamp_(min=1).float()
 
 
+def _kept(cache: dict, name: str, built_from: Callable[[], tuple], build: Callable):
+    """One key rule for what is derived from a batch's tensors: kept in the store a tile partition attaches to the
+    batches of one tile set (``cache["persistent"]``: a tile's labels, masks and edges never change, so it survives
+    from epoch to epoch), else in the batch's own cache, keyed by the tensors it was built from (``built_from()``)."""
+    store = cache.get("persistent")
+    keep, key = (cache, (name, *built_from())) if store is None else (store, name)
+    hit = keep.get(key)
+    if hit is None:
+        hit = keep[key] = build()
+    return hit
+
+
 def _cached_index(selector: FastTripletSelector, name: str, labels: Tensor, mask: Tensor, cache: Optional[dict]) -> dict:
-    """The selector's index of a batch, kept (i) in the batch's own cache, keyed by the tensors it was built from, or
-    (ii) in the store a tile partition attaches to the batches of one tile set (``cache["persistent"]``: labels and
-    masks of a tile never change, so the index survives from epoch to epoch)."""
+    """The selector's index of a batch, kept with the batch or its tile set (``_kept``)."""
     if cache is None:
         return selector.build_index(labels, mask)
+    return _kept(cache, name, lambda: (mask.data_ptr(), labels.data_ptr(), int(labels.numel())),
+                 lambda: selector.build_index(labels, mask))
+
+
+def boundary_loss_mask(batch, cache: dict) -> Tensor:
+    """``mask & (cluster >= 0)`` of the boundaries, kept: the samplers' indices are keyed by the mask tensor they were
+    built from, and a mask recomputed every step would rebuild the boundary index -- ~50 small launches -- every step."""
+    bm, bc = batch["bd"]["mask"], batch["bd"]["cluster"]
+    return _kept(cache, "bd_loss_mask", lambda: (bm.data_ptr(), bc.data_ptr(), int(bm.numel())), lambda: bm & (bc >= 0))
+
+
+class LossInputs(NamedTuple):
+    ix_tx: dict                   # the transcript selector's index
+    ix_bd: dict                   # the boundary selector's index, with ``weight`` = mask / masked count
+    bd_mask: Tensor               # the boundary loss mask the index was built under
+    sg_of_tx: Callable[[], Tensor]    # -> int32 [n_tx]: the tx-belongs-bd edge anchored at each transcript (-1: none)
+
+
+def loss_inputs(loss_tx: "TripletLoss", loss_bd: "MetricLoss", batch, cache: dict) -> LossInputs:
+    """What the fused loss head reads of a batch besides the embeddings, the same whether the step runs eagerly or is
+    staged into a captured one; every piece is built once per batch / tile set (``_kept``).  ``sg_of_tx`` is built on
+    the first call: only a backward over segmentation triplets needs it."""
+    tx, bd = batch["tx"], batch["bd"]
+    ix_tx = _cached_index(loss_tx.selector, "tx_triplet_index", tx["cluster"], tx["mask"], cache)
     store = cache.get("persistent")
-    key = name if store is not None else (name, mask.data_ptr(), labels.data_ptr(), int(labels.numel()))
-    if store is None:
-        store = cache
-    index = store.get(key)
-    if index is None:
-        index = store[key] = selector.build_index(labels, mask)
-    return index
+    ix_bd = store.get("bd_metric_index") if store is not None else None
+    if ix_bd is None:
+        ix_bd = _cached_index(loss_bd.selector, "bd_metric_index", bd["cluster"], boundary_loss_mask(batch, cache), cache)
+    if "weight" not in ix_bd:
+        ix_bd["weight"] = ix_bd["mask"].float() / masked_count(ix_bd["mask"])
+
+    def sg_of_tx() -> Tensor:
+        def built_from():
+            ei = batch[TX_BD].edge_index
+            return ei.data_ptr(), int(ei.shape[1]), tx.num_nodes
+
+        def build():
+            from . import ops
+            return ops.anchor_index(batch[TX_BD].edge_index[0], tx.num_nodes)
+        return _kept(cache, "sg_of_tx", built_from, build)
+    return LossInputs(ix_tx, ix_bd, ix_bd["mask"], sg_of_tx)
 
 
 class TripletLoss(torch.nn.TripletMarginLoss):
@@ -162,7 +207,7 @@ class TripletLoss(torch.nn.TripletMarginLoss):
         index = _cached_index(self.selector, "tx_triplet_index", labels, mask, cache)
         if "anchors" not in index:
             index["anchors"] = torch.arange(n, device=labels.device)
-            index["rescale"] = float(n) / _masked_count(mask)
+            index["rescale"] = float(n) / masked_count(mask)
         pos, neg, _, _ = self.selector.sample_triplets(labels, uniforms, index=index)
         if embeddings.is_cuda:
             from . import ops
@@ -197,7 +242,7 @@ class MetricLoss:
             return 0.0
         index = _cached_index(self.selector, "bd_metric_index", labels, mask, cache)
         if "weight" not in index:
-            index["weight"] = mask.float() / _masked_count(mask)
+            index["weight"] = mask.float() / masked_count(mask)
         pos, neg, d_pos, d_neg = self.selector.sample_triplets(labels, uniforms, index=index)
         if embeddings.is_cuda:
             from . import ops

@@ -3,6 +3,7 @@ fan-out / fan-in nodes and the nodes that are not kernels:   python tools/graph_
 import collections, os, re, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segger_amd import LitISTEncoder
+from segger_amd.capture import tightest
 from segger_amd.fov import build_fov_batches
 from segger_amd.synthetic import SyntheticSpec
 from segger_amd import train_step_graph as tsg
@@ -28,7 +29,7 @@ tr = tsg.GraphedTrainer(m, m.configure_optimizers(capturable=True))
 for ids in batches:
     tr.step(part.batch(ids))
 torch.cuda.synchronize()
-b = tr.buckets[0]
+b = tightest(tr.buckets, part.batch(batches[0]))        # the step the first batch replays
 b.graph.debug_dump(out)
 txt = open(out).read()
 nodes = dict(re.findall(r'"?(\w+)"?\s*\[[^\]]*label="([^"]*)"', txt))
