@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "mma.h"
 #include "post_common.h"
 #include "rings.h"
 #include "sort_config.h"
@@ -125,15 +126,8 @@ __global__ __launch_bounds__(kBndScanThreads) void bnd_scan_kernel(BndSegs s, in
 // iterations, 2^l h vertices) with index q comes from the vertices q >> 1 and (q >> 1) + 1 of level l - 1, so vertex j of
 // level S depends on S + 1 consecutive (cyclic) ring vertices from j >> S on.  w holds, level after level, the S - l + 1
 // consecutive vertices of level l from index j >> (S - l) on; which two entries of the previous level make entry t
-// depends on the parity of that index alone: the array indices are compile-time constants and w stays in registers.
-// f(int_c<0>{}) .. f(int_c<N - 1>{}): a loop whose counter is a constant expression in its body
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (N > 0) {
-    static_for<N - 1>(f);
-    f(int_c<N - 1>{});
-  }
-}
+// depends on the parity of that index alone: the array indices are compile-time constants (mma.h's static_for) and w
+// stays in registers.
 
 // N + 1 consecutive vertices of a level in w -> the N of the next level that start at an index of parity b, in w
 template <int N>

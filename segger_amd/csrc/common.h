@@ -199,6 +199,37 @@ template <> struct Vec8<f16_t> {
   }
 };
 
+// One, two or four consecutive channels as fp32, and the store of one.  p must be aligned to the bytes it covers.
+template <typename T> __device__ __forceinline__ float load1(const T* p);
+template <> __device__ __forceinline__ float load1<float>(const float* p) { return *p; }
+template <> __device__ __forceinline__ float load1<bf16_t>(const bf16_t* p) { return __uint_as_float((uint32_t)p->v << 16); }
+template <> __device__ __forceinline__ float load1<f16_t>(const f16_t* p) {
+  return static_cast<float>(__builtin_bit_cast(_Float16, p->v));
+}
+
+template <typename T> __device__ __forceinline__ void load2(const T* p, float& a, float& b) {      // bf16_t / f16_t
+  Vec8<T>::unpack2(*reinterpret_cast<const uint32_t*>(p), a, b);
+}
+template <> __device__ __forceinline__ void load2<float>(const float* p, float& a, float& b) {
+  const float2 v = *reinterpret_cast<const float2*>(p);
+  a = v.x; b = v.y;
+}
+
+template <typename T> __device__ __forceinline__ void load4(const T* p, float (&f)[4]) {           // bf16_t / f16_t
+  const uint2 v = *reinterpret_cast<const uint2*>(p);
+  Vec8<T>::unpack2(v.x, f[0], f[1]);
+  Vec8<T>::unpack2(v.y, f[2], f[3]);
+}
+template <> __device__ __forceinline__ void load4<float>(const float* p, float (&f)[4]) {
+  const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+  f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+}
+
+template <typename T> __device__ __forceinline__ void store1(T* p, float v) {                      // bf16_t / f16_t
+  p->v = (uint16_t)(Vec8<T>::pack(v, 0.f) & 0xffffu);
+}
+template <> __device__ __forceinline__ void store1<float>(float* p, float v) { *p = v; }
+
 // ------------------------------------------------------- cross-lane --------
 // DPP within a 16-lane row (ctrl must be a compile-time constant).
 template <int CTRL>
@@ -278,12 +309,22 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   return fmaf(0.3989422804014327f * x, e, normal_cdf(x));
 }
 
+// sigmoid twice: the exact form the loss kernels use (their values are compared with torch's), and the hardware
+// rcp / exp2 form of the activations inside the GEMM epilogues -- different bits, not interchangeable
+__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float sigmoid_fast(float z) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
+}
+__device__ __forceinline__ float softplus(float x) {              // log(1 + e^x), stable
+  return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x)));
+}
+
 __device__ __forceinline__ float silu_grad(float z) {             // d/dz z sigmoid(z)
-  const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
+  const float sg = sigmoid_fast(z);
   return sg * (1.0f + z * (1.0f - sg));
 }
 __device__ __forceinline__ float act_apply(float z, int kind) {   // kind 1 = GELU (erf form), 2 = SiLU
-  return kind == 1 ? gelu_erf(z) : z * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
+  return kind == 1 ? gelu_erf(z) : z * sigmoid_fast(z);
 }
 // y *= d act / d gate in a GEMM epilogue: kind 1 = GELU (erf form), 2 = SiLU
 __device__ __forceinline__ float gate_grad(float g, int kind) { return kind == 1 ? gelu_erf_grad(g) : silu_grad(g); }

@@ -12,11 +12,6 @@
 namespace segger {
 namespace {
 
-template <typename T> __device__ __forceinline__ float ld1(const T* p);
-template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { return __uint_as_float((uint32_t)p->v << 16); }
-template <> __device__ __forceinline__ float ld1<f16_t>(const f16_t* p) { return static_cast<float>(__builtin_bit_cast(_Float16, p->v)); }
-
 // ---------------------------------------------------------------------------------------------
 // posfreq: out[(n*2 + c), :] = [cos(p * f_j) | sin(p * f_j)],  p = (pos[n,c] - lo) / (hi - lo + eps)
 // one thread = 8 consecutive j of one (n, c): a 16-byte (32-byte for fp32) store into each half

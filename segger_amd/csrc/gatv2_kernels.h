@@ -16,6 +16,7 @@
 // handed to the gathering lanes by DPP row-broadcast (GS=16) or ds_bpermute.
 #pragma once
 #include "common.h"
+#include "mma.h"
 
 namespace segger {
 
@@ -107,13 +108,7 @@ struct GatParams {
 //    edges always sit in lanes 0..U-1 of the row (row_newbcast:u) because the
 //    id register is rotated by U lanes (row_ror:U) after every batch.
 //  * otherwise: ds_bpermute with a computed slot.
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (N > 0) {
-    static_for<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
+// (the batches of U edges are unrolled with mma.h's static_for)
 
 // The kernel bodies are functions (two of them can share a launch: gatv2_*_pair_kernel) and take the parameter block BY
 // VALUE: handed over by const reference the fp32 source pass came out of the register allocator 32 % slower (2.70 vs

@@ -91,11 +91,6 @@ __device__ __forceinline__ void tile_gemm(int K, int i0, int j0, FA a, FB b, FE 
     for (int c = 0; c < 4; ++c) epilogue(i0 + 2 * ti + r, j0 + tj + 16 * c, acc[r][c]);
 }
 
-template <typename T> __device__ __forceinline__ void st1(T* p, float v);
-template <> __device__ __forceinline__ void st1<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, float v) { p->v = (uint16_t)(Vec8<bf16_t>::pack(v, 0.f) & 0xffffu); }
-template <> __device__ __forceinline__ void st1<f16_t>(f16_t* p, float v) { p->v = (uint16_t)(Vec8<f16_t>::pack(v, 0.f) & 0xffffu); }
-
 // ---- forward: [ T tiles | cast of the positional half (Wc, Wc^T) ] ----------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void gene_table_fwd_kernel(GeneTable p) {
@@ -112,7 +107,7 @@ __global__ __launch_bounds__(256) void gene_table_fwd_kernel(GeneTable p) {
                 int wi;
                 w_row(p, m, wi);
                 if (p.b[wi]) v += p.b[wi][m - p.m_off[wi]];
-                st1(static_cast<T*>(p.tab) + (int64_t)g * p.ld_tab + m, v);
+                store1(static_cast<T*>(p.tab) + (int64_t)g * p.ld_tab + m, v);
               });
   } else {
     // Wc[m, d] = W[m, D + d] in the compute dtype, and its transpose [D, M]
@@ -121,8 +116,8 @@ __global__ __launch_bounds__(256) void gene_table_fwd_kernel(GeneTable p) {
     const int m = (int)(e / D), d = (int)(e % D);
     int wi;
     const float v = w_row(p, m, wi)[D + d];
-    if (p.wc) st1(static_cast<T*>(p.wc) + (int64_t)m * D + d, v);
-    if (p.wc_t) st1(static_cast<T*>(p.wc_t) + (int64_t)d * M + m, v);
+    if (p.wc) store1(static_cast<T*>(p.wc) + (int64_t)m * D + d, v);
+    if (p.wc_t) store1(static_cast<T*>(p.wc_t) + (int64_t)d * M + m, v);
   }
 }
 

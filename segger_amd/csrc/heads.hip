@@ -10,13 +10,8 @@ namespace {
 // ---------------------------------------------------------------------------
 // Row fragments: a row of C channels is covered by LPC lanes x 8 channels when
 // C == 8*LPC (LPC a power of two <= 16), otherwise by one wave striding channels.
+// Narrower pieces of a row come through common.h's load1 / load2 / load4.
 // ---------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float load1(const T* p);
-template <> __device__ __forceinline__ float load1<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float load1<bf16_t>(const bf16_t* p) { return __uint_as_float((uint32_t)p->v << 16); }
-template <> __device__ __forceinline__ float load1<f16_t>(const f16_t* p) {
-  return static_cast<float>(__builtin_bit_cast(_Float16, p->v));
-}
 
 struct ArgmaxParams {
   const int64_t* indptr; const int32_t* col; const int32_t* eid;
@@ -385,19 +380,7 @@ __global__ __launch_bounds__(256) void triplet_pos_kernel(TripletParams p) {
 //   * positive row j: accumulated in registers over the group, added to grad_b ONCE per boundary;
 //   * negative row: fp32 atomics (uniformly sampled: uncontended).
 // Every row of z_a / z_b is read once per triplet (the two-kernel route reads them twice).  Lane gl of a 16-lane group
-// owns the channel pairs 2 gl + 32 k, k < C / 32 (C % 32 == 0, C <= 128): 4-byte loads for 16-bit embeddings.
-template <typename T> __device__ __forceinline__ void load2(const T* p, float& a, float& b);
-template <> __device__ __forceinline__ void load2<float>(const float* p, float& a, float& b) {
-  const float2 v = *reinterpret_cast<const float2*>(p);
-  a = v.x; b = v.y;
-}
-template <> __device__ __forceinline__ void load2<bf16_t>(const bf16_t* p, float& a, float& b) {
-  Vec8<bf16_t>::unpack2(*reinterpret_cast<const uint32_t*>(p), a, b);
-}
-template <> __device__ __forceinline__ void load2<f16_t>(const f16_t* p, float& a, float& b) {
-  Vec8<f16_t>::unpack2(*reinterpret_cast<const uint32_t*>(p), a, b);
-}
-
+// owns the channel pairs 2 gl + 32 k, k < C / 32 (C % 32 == 0, C <= 128): 4-byte loads for 16-bit embeddings (load2).
 template <typename T, int KP>
 __global__ __launch_bounds__(256) void triplet_grouped_kernel(TripletParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -478,11 +461,6 @@ __global__ __launch_bounds__(256) void triplet_grouped_kernel(TripletParams p) {
 //     loss = 1/(2n) sum_e [ softplus(-<a_e, p_e>) + softplus(<a_e, n_e>) ]
 //     d/d lp = (sigmoid(lp) - 1) / (2n),  d/d ln = sigmoid(ln) / (2n)
 // Same gather / scatter structure as the triplet kernels: 16 lanes per edge, channel pairs 2 gl + 32 k.
-__device__ __forceinline__ float softplus_f(float x) {          // log(1 + e^x), stable
-  return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x)));
-}
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
-
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void bce_edge_kernel(TripletParams p) {
   __shared__ float wsum[4];
@@ -513,10 +491,10 @@ __global__ __launch_bounds__(256) void bce_edge_kernel(TripletParams p) {
     lp = lane_block_sum<16>(lp);
     ln = lane_block_sum<16>(ln);
     if (!BWD) {
-      if (ok && gl == 0) acc += softplus_f(-lp) + softplus_f(ln);
+      if (ok && gl == 0) acc += softplus(-lp) + softplus(ln);
     } else if (ok) {
       const float sc = p.scale_dev ? p.scale * p.scale_dev[0] : p.scale;
-      const float dlp = (sigmoid_f(lp) - 1.0f) * sc, dln = sigmoid_f(ln) * sc;
+      const float dlp = (sigmoid(lp) - 1.0f) * sc, dln = sigmoid(ln) * sc;
       for (int c = 2 * gl; c < C; c += 32) {
         float a0, a1, p0, p1, n0, n1;
         load2(za + ia * p.ld_za + c, a0, a1);
@@ -574,7 +552,7 @@ __global__ __launch_bounds__(256) void bce_grouped_kernel(TripletParams p) {
     lp = lane_block_sum<16>(lp);
     ln = lane_block_sum<16>(ln);
     if (ok) {                                            // group-uniform
-      const float dlp = (sigmoid_f(lp) - 1.0f) * sc, dln = sigmoid_f(ln) * sc;
+      const float dlp = (sigmoid(lp) - 1.0f) * sc, dln = sigmoid(ln) * sc;
 #pragma unroll
       for (int k = 0; k < KP; ++k) {
         acc[k][0] = fmaf(dlp, av[k][0], acc[k][0]); acc[k][1] = fmaf(dlp, av[k][1], acc[k][1]);
@@ -608,22 +586,6 @@ __global__ __launch_bounds__(256) void bce_grouped_kernel(TripletParams p) {
 // C == 64 fast path: a lane owns 4 consecutive channels (one 8-byte load per row for 16-bit embeddings, 16 bytes
 // for fp32), 16 lanes per triplet, 4 triplets per wave-iteration; the backward issues two packed (or four fp32)
 // atomics per row and lane.
-template <typename T> __device__ __forceinline__ void load4(const T* p, float (&f)[4]);
-template <> __device__ __forceinline__ void load4<float>(const float* p, float (&f)[4]) {
-  const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-  f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-}
-template <> __device__ __forceinline__ void load4<bf16_t>(const bf16_t* p, float (&f)[4]) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void load4<f16_t>(const f16_t* p, float (&f)[4]) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  Vec8<f16_t>::unpack(v.x, f[0], f[1]);
-  Vec8<f16_t>::unpack(v.y, f[2], f[3]);
-}
-
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void triplet_c64_kernel(TripletParams p) {
   __shared__ float wsum[4];

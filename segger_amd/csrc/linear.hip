@@ -11,34 +11,19 @@
 //   * W is streamed through LDS in chunks of 64 output columns shared by the 4
 //     waves (row stride K*2+16 B: conflict-free ds_read_b128 of A fragments), with
 //     the next chunk prefetched into registers under the MFMAs;
-//   * D = W_tile * X_tile^T  (v_mfma_f32_32x32x16): a lane owns one DATA ROW and
+//   * D = W_tile * X_tile^T  (v_mfma_f32_32x32x16, mma.h's Mfma<T>::run): a lane owns one DATA ROW and
 //     4-column groups, so the epilogue packs 4 bf16 -> ds_write_b64 into a wave-private
 //     LDS tile and streams it out as full 128-byte row segments (16 B per lane).
 #include <algorithm>
 #include "common.h"
+#include "mma.h"
 #include "post_common.h"
 
 namespace segger {
 namespace {
 
-typedef __bf16   bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8  __attribute__((ext_vector_type(8)));
-typedef float    f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kRowsPerBlock = 128;
 constexpr int kChunk = 64;             // output columns per W chunk
-
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16_t> {
-  static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<f16_t> {
-  static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
 
 struct LinearParams {
   const void* x; int64_t ldx;
@@ -194,10 +179,7 @@ __device__ __forceinline__ void linear_fwd_body(const LinearParams p, const int6
           Vec8<T>::unpack2(zz.x, z[0], z[1]);
           Vec8<T>::unpack2(zz.y, z[2], z[3]);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z[j]));
-            v[j] *= sg * (1.0f + z[j] * (1.0f - sg));         // d/dz [z sigmoid(z)]
-          }
+          for (int j = 0; j < 4; ++j) v[j] *= silu_grad(z[j]);
         }
         uint2 pk;
         pk.x = Vec8<T>::pack(v[0], v[1]);

@@ -8,19 +8,15 @@
 //   segger_linear_fwd (dtype f32):   Y[n, M] = X[n, K] W[M, K]^T + b            (also dX = dY W, called with W^T)
 //   segger_linear_wgrad (dtype f32): dW[M, K] = dY[n, M]^T X[n, K],  db = sum_n dY
 //
-// Operand layout of v_mfma_f32_32x32x2_f32: lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31],
-// ONE float each.  The k order of a product is free as long as A and B agree, so a lane fetches FOUR consecutive k of its
-// row with one 16-byte load (lane half h covers k = 8 t + 4 h + u, u = 0..3) and feeds them to four MFMAs.
+// Operand layout of v_mfma_f32_32x32x2_f32 (mma.h's mfma_f32): lane l supplies A[i = l & 31][k = l >> 5] and
+// B[k = l >> 5][j = l & 31], ONE float each.  The k order of a product is free as long as A and B agree, so a lane fetches
+// FOUR consecutive k of its row with one 16-byte load (lane half h covers k = 8 t + 4 h + u, u = 0..3) and feeds them to
+// four MFMAs.
 #include "common.h"
+#include "mma.h"
 
 namespace segger {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------ forward / dX
 struct LinF32Params {

@@ -11,30 +11,17 @@
 //
 //   segger_linear_fwd_f32_split:  Y[n, M] = X[n, K] W^T + b,  W given as three bf16 planes [3][M][K] (hi, mid, lo)
 //     K = 128 (forward of the 128 -> M projections), or K = 384 with M = 128 (their data gradient dX = dY W: W^T planes)
+//
+// Every barrier below is mma.h's lds_barrier() (lgkmcnt(0) + s_barrier, no vmcnt drain: the prefetches stay in flight).
 #include <cstdlib>
 #include "common.h"
+#include "mma.h"
 #include "post_common.h"
 
 namespace segger {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float pk2 __attribute__((ext_vector_type(2)));          // a register pair for v_pk_mul / v_pk_add / v_pk_fma_f32
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// A workgroup barrier that orders LDS traffic only: this wave's LDS operations have completed (lgkmcnt(0)), then s_barrier.
-// __syncthreads() is a release fence as well -- s_waitcnt vmcnt(0): every global load in flight (the prefetch these kernels
-// live on) and every output store would have to drain at each barrier.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("" ::: "memory");                         // (compiler: no memory access moves across)
-  __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0)
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 struct SplitParams {
   const float* x; int64_t ldx;
@@ -145,14 +132,14 @@ __global__ __launch_bounds__(256, K == 128 ? 2 : SEGGER_FS_K384_WAVES) void line
       const u32x4 wl0 = *reinterpret_cast<const u32x4*>(lds + 2 * kCH * kWS + off);
       const u32x4 wl1 = *reinterpret_cast<const u32x4*>(lds + 2 * kCH * kWS + off + 32 * kWS);
 #ifdef EXP_FS_ONEMFMA       // bounding build: one product instead of six
-      acc0 = mfma_bf16(wh0 ^ wm0 ^ wl0, xh[s] ^ xm[s] ^ xl[s], acc0); acc1 = mfma_bf16(wh1 ^ wm1 ^ wl1, xh[s] ^ xm[s] ^ xl[s], acc1);
+      acc0 = Mfma<bf16_t>::run(wh0 ^ wm0 ^ wl0, xh[s] ^ xm[s] ^ xl[s], acc0); acc1 = Mfma<bf16_t>::run(wh1 ^ wm1 ^ wl1, xh[s] ^ xm[s] ^ xl[s], acc1);
 #else
-      acc0 = mfma_bf16(wl0, xh[s], acc0); acc1 = mfma_bf16(wl1, xh[s], acc1);        // smallest terms first
-      acc0 = mfma_bf16(wh0, xl[s], acc0); acc1 = mfma_bf16(wh1, xl[s], acc1);
-      acc0 = mfma_bf16(wm0, xm[s], acc0); acc1 = mfma_bf16(wm1, xm[s], acc1);
-      acc0 = mfma_bf16(wm0, xh[s], acc0); acc1 = mfma_bf16(wm1, xh[s], acc1);
-      acc0 = mfma_bf16(wh0, xm[s], acc0); acc1 = mfma_bf16(wh1, xm[s], acc1);
-      acc0 = mfma_bf16(wh0, xh[s], acc0); acc1 = mfma_bf16(wh1, xh[s], acc1);
+      acc0 = Mfma<bf16_t>::run(wl0, xh[s], acc0); acc1 = Mfma<bf16_t>::run(wl1, xh[s], acc1);        // smallest terms first
+      acc0 = Mfma<bf16_t>::run(wh0, xl[s], acc0); acc1 = Mfma<bf16_t>::run(wh1, xl[s], acc1);
+      acc0 = Mfma<bf16_t>::run(wm0, xm[s], acc0); acc1 = Mfma<bf16_t>::run(wm1, xm[s], acc1);
+      acc0 = Mfma<bf16_t>::run(wm0, xh[s], acc0); acc1 = Mfma<bf16_t>::run(wm1, xh[s], acc1);
+      acc0 = Mfma<bf16_t>::run(wh0, xm[s], acc0); acc1 = Mfma<bf16_t>::run(wh1, xm[s], acc1);
+      acc0 = Mfma<bf16_t>::run(wh0, xh[s], acc0); acc1 = Mfma<bf16_t>::run(wh1, xh[s], acc1);
 #endif
     }
   };
@@ -264,13 +251,6 @@ __global__ __launch_bounds__(256, K == 128 ? 2 : SEGGER_FS_K384_WAVES) void line
 // width * 2 + 64 bytes: the transposing reads are conflict-free); the MFMA operands -- the row index is the k dimension
 // of both -- come out of LDS transposed by ds_read_b64_tr_b16.  One barrier per stage.  Partial sums per workgroup in the
 // layout of the other weight-gradient kernels (summed in slab order by reduce_partials: deterministic).
-typedef short s16x4s __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x2s lds_read_tr_s(const unsigned char* p) {
-  const s16x4s v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4s*)(const_cast<unsigned char*>(p)));
-  return __builtin_bit_cast(u32x2s, v);
-}
-
 struct WgSplitParams {
   const float* dy; int64_t ld_dy;
   const float* x; int64_t ld_x;
@@ -279,10 +259,10 @@ struct WgSplitParams {
 };
 
 // 4 consecutive floats -> 4 bf16 of each plane
-__device__ __forceinline__ void split4(const f32x4 v, u32x2s& hi, u32x2s& mid, u32x2s& lo) {
+__device__ __forceinline__ void split4(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
 #ifdef EXP_FS_NOSPLIT
-  hi = u32x2s{__float_as_uint(v.x), __float_as_uint(v.y)}; mid = u32x2s{__float_as_uint(v.z), __float_as_uint(v.w)};
-  lo = u32x2s{__float_as_uint(v.x) + 1u, __float_as_uint(v.w)};
+  hi = u32x2{__float_as_uint(v.x), __float_as_uint(v.y)}; mid = u32x2{__float_as_uint(v.z), __float_as_uint(v.w)};
+  lo = u32x2{__float_as_uint(v.x) + 1u, __float_as_uint(v.w)};
   return;
 #endif
   const uint32_t h0 = Vec8<bf16_t>::pack(v.x, v.y), h1 = Vec8<bf16_t>::pack(v.z, v.w);
@@ -291,18 +271,11 @@ __device__ __forceinline__ void split4(const f32x4 v, u32x2s& hi, u32x2s& mid, u
   const float r0 = v.x - a, r1 = v.y - b, r2 = v.z - c, r3 = v.w - d;
   const uint32_t m0 = Vec8<bf16_t>::pack(r0, r1), m1 = Vec8<bf16_t>::pack(r2, r3);
   Vec8<bf16_t>::unpack2(m0, a, b); Vec8<bf16_t>::unpack2(m1, c, d);
-  hi = u32x2s{h0, h1}; mid = u32x2s{m0, m1};
-  lo = u32x2s{Vec8<bf16_t>::pack(r0 - a, r1 - b), Vec8<bf16_t>::pack(r2 - c, r3 - d)};
+  hi = u32x2{h0, h1}; mid = u32x2{m0, m1};
+  lo = u32x2{Vec8<bf16_t>::pack(r0 - a, r1 - b), Vec8<bf16_t>::pack(r2 - c, r3 - d)};
 }
 
 constexpr int kWgRows = 16;                    // rows per stage = one 32x32x16 k-step
-template <int N, typename F>
-__device__ __forceinline__ void static_for_wgs(F&& f) {
-  if constexpr (N > 0) {
-    static_for_wgs<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
 
 template <int M, int K, int NW>
 __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams p) {
@@ -383,17 +356,17 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
     unsigned char* buf = lds + ((s - s_beg) & 1) * BUF;
 #pragma unroll
     for (int j = 0; j < PIECES; ++j) {
-      u32x2s h, m, l;
+      u32x2 h, m, l;
 #ifdef EXP_WGS_NOSPLIT      // bounding build: no VALU split (planes = raw words)
-      h = u32x2s{__float_as_uint(ring[SL][j].x), __float_as_uint(ring[SL][j].y)};
-      m = u32x2s{__float_as_uint(ring[SL][j].z), __float_as_uint(ring[SL][j].w)}; l = h;
+      h = u32x2{__float_as_uint(ring[SL][j].x), __float_as_uint(ring[SL][j].y)};
+      m = u32x2{__float_as_uint(ring[SL][j].z), __float_as_uint(ring[SL][j].w)}; l = h;
 #else
       split4(ring[SL][j], h, m, l);
 #endif
       const int plane = pis_y[j] ? PY : PX;
-      *reinterpret_cast<u32x2s*>(buf + pdst[j]) = h;
-      *reinterpret_cast<u32x2s*>(buf + pdst[j] + plane) = m;
-      *reinterpret_cast<u32x2s*>(buf + pdst[j] + 2 * plane) = l;
+      *reinterpret_cast<u32x2*>(buf + pdst[j]) = h;
+      *reinterpret_cast<u32x2*>(buf + pdst[j] + plane) = m;
+      *reinterpret_cast<u32x2*>(buf + pdst[j] + 2 * plane) = l;
       if (pis_y[j]) dbp[j] = dbp[j] + ring[SL][j];
     }
     fetch(slot_c, s + AH);
@@ -403,14 +376,14 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
     for (int q = 0; q < 3; ++q) {
 #pragma unroll
       for (int a = 0; a < MT; ++a) {
-        const u32x2s lo = lds_read_tr_s(buf + q * PY + off_y + a * 64);
-        const u32x2s hi = lds_read_tr_s(buf + q * PY + off_y + a * 64 + 4 * SY);
+        const u32x2 lo = lds_read_tr(buf + q * PY + off_y + a * 64);
+        const u32x2 hi = lds_read_tr(buf + q * PY + off_y + a * 64 + 4 * SY);
         fa[q][a] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
 #pragma unroll
       for (int b = 0; b < KT; ++b) {
-        const u32x2s lo = lds_read_tr_s(buf + q * PX + off_x + b * 64);
-        const u32x2s hi = lds_read_tr_s(buf + q * PX + off_x + b * 64 + 4 * SX);
+        const u32x2 lo = lds_read_tr(buf + q * PX + off_x + b * 64);
+        const u32x2 hi = lds_read_tr(buf + q * PX + off_x + b * 64 + 4 * SX);
         fb[q][b] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
     }
@@ -420,14 +393,14 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
       for (int b = 0; b < KT; ++b) {
         f32x16 c = acc[a][b];
 #ifdef EXP_WGS_ONEMFMA      // bounding build: one product instead of six
-        c = mfma_bf16(fa[0][a] ^ fa[1][a] ^ fa[2][a], fb[0][b] ^ fb[1][b] ^ fb[2][b], c);
+        c = Mfma<bf16_t>::run(fa[0][a] ^ fa[1][a] ^ fa[2][a], fb[0][b] ^ fb[1][b] ^ fb[2][b], c);
 #else
-        c = mfma_bf16(fa[2][a], fb[0][b], c);                    // smallest terms first
-        c = mfma_bf16(fa[0][a], fb[2][b], c);
-        c = mfma_bf16(fa[1][a], fb[1][b], c);
-        c = mfma_bf16(fa[1][a], fb[0][b], c);
-        c = mfma_bf16(fa[0][a], fb[1][b], c);
-        c = mfma_bf16(fa[0][a], fb[0][b], c);
+        c = Mfma<bf16_t>::run(fa[2][a], fb[0][b], c);                    // smallest terms first
+        c = Mfma<bf16_t>::run(fa[0][a], fb[2][b], c);
+        c = Mfma<bf16_t>::run(fa[1][a], fb[1][b], c);
+        c = Mfma<bf16_t>::run(fa[1][a], fb[0][b], c);
+        c = Mfma<bf16_t>::run(fa[0][a], fb[1][b], c);
+        c = Mfma<bf16_t>::run(fa[0][a], fb[0][b], c);
 #endif
         acc[a][b] = c;
       }
@@ -483,9 +456,9 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
         sl[j][0] = Vec8<bf16_t>::pack(la.x, la.y); sl[j][1] = Vec8<bf16_t>::pack(lb.x, lb.y);
       } else if constexpr (ph == 3) {
         const int plane = pis_y[j] ? PY : PX;
-        *reinterpret_cast<u32x2s*>(nbuf + pdst[j]) = u32x2s{sh[j][0], sh[j][1]};
-        *reinterpret_cast<u32x2s*>(nbuf + pdst[j] + plane) = u32x2s{sm[j][0], sm[j][1]};
-        *reinterpret_cast<u32x2s*>(nbuf + pdst[j] + 2 * plane) = u32x2s{sl[j][0], sl[j][1]};
+        *reinterpret_cast<u32x2*>(nbuf + pdst[j]) = u32x2{sh[j][0], sh[j][1]};
+        *reinterpret_cast<u32x2*>(nbuf + pdst[j] + plane) = u32x2{sm[j][0], sm[j][1]};
+        *reinterpret_cast<u32x2*>(nbuf + pdst[j] + 2 * plane) = u32x2{sl[j][0], sl[j][1]};
       } else {
         fetch_piece(j, st + 2);
       }
@@ -494,7 +467,7 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
   // prologue: stage s_beg's planes into buffer 0, stage s_beg + 1's rows into the ring
 #pragma unroll
   for (int j = 0; j < PIECES; ++j) fetch_piece(j, s_beg);
-  static_for_wgs<NCH>([&](auto c_c) {
+  static_for<NCH>([&](auto c_c) {
     if constexpr (decltype(c_c)::value % 5 != 4) side(c_c, lds, s_beg - 1);
   });
 #pragma unroll
@@ -521,22 +494,22 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
     auto read_a = [&](int a) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        const u32x2s lo = lds_read_tr_s(buf + q * PY + off_y + a * 64);
-        const u32x2s hi = lds_read_tr_s(buf + q * PY + off_y + a * 64 + 4 * SY);
+        const u32x2 lo = lds_read_tr(buf + q * PY + off_y + a * 64);
+        const u32x2 hi = lds_read_tr(buf + q * PY + off_y + a * 64 + 4 * SY);
         fa[q][a] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
     };
     auto read_b = [&](int b) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        const u32x2s lo = lds_read_tr_s(buf + q * PX + off_x + b * 64);
-        const u32x2s hi = lds_read_tr_s(buf + q * PX + off_x + b * 64 + 4 * SX);
+        const u32x2 lo = lds_read_tr(buf + q * PX + off_x + b * 64);
+        const u32x2 hi = lds_read_tr(buf + q * PX + off_x + b * 64 + 4 * SX);
         fb[q][b] = u32x4{lo.x, lo.y, hi.x, hi.y};
       }
     };
     read_a(0); read_b(0);
     __builtin_amdgcn_sched_barrier(0);
-    static_for_wgs<NMF>([&](auto i_c) {
+    static_for<NMF>([&](auto i_c) {
       constexpr int i = decltype(i_c)::value;
       constexpr int tile = i / 6, pr = i % 6, a = tile / KT, b = tile % KT;
       // column block b + 1 behind the first MFMA of row block 0; row block a + 1 behind the first MFMA of row block a's second tile
@@ -544,9 +517,9 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
       if constexpr (pr == 1 && b == (KT > 1 ? 1 : 0) && a + 1 < MT) read_a(a + 1);
       constexpr int qa = pr == 0 ? 2 : (pr == 2 || pr == 3) ? 1 : 0;       // smallest terms first (as above)
       constexpr int qb = pr == 1 ? 2 : (pr == 2 || pr == 4) ? 1 : 0;
-      acc[a][b] = mfma_bf16(fa[qa][a], fb[qb][b], acc[a][b]);
+      acc[a][b] = Mfma<bf16_t>::run(fa[qa][a], fb[qb][b], acc[a][b]);
       // chunks [i * NCH / NMF, (i + 1) * NCH / NMF) of the side work behind this MFMA
-      static_for_wgs<(i + 1) * NCH / NMF - i * NCH / NMF>([&](auto d_c) {
+      static_for<(i + 1) * NCH / NMF - i * NCH / NMF>([&](auto d_c) {
         side(std::integral_constant<int, i * NCH / NMF + decltype(d_c)::value>{}, nbuf, s);
       });
       __builtin_amdgcn_sched_barrier(0);
@@ -557,12 +530,12 @@ __global__ __launch_bounds__(NW * 64) void wgrad_f32_split_kernel(WgSplitParams 
     printf("wave %d: %lld stages, per stage %lld clocks, of which at the barrier %lld\n", wave, st_n, st_tot / st_n, st_bar / st_n);
 #endif
 #else
-  static_for_wgs<AH>([&](auto d) { fetch(d, s_beg + decltype(d)::value); });
+  static_for<AH>([&](auto d) { fetch(d, s_beg + decltype(d)::value); });
   int64_t s = s_beg;
 #pragma unroll 1
   for (; s + AH <= s_end; s += AH)
-    static_for_wgs<AH>([&](auto d) { stage(d, s + decltype(d)::value); });
-  static_for_wgs<AH>([&](auto d) { if (s + decltype(d)::value < s_end) stage(d, s + decltype(d)::value); });
+    static_for<AH>([&](auto d) { stage(d, s + decltype(d)::value); });
+  static_for<AH>([&](auto d) { if (s + decltype(d)::value < s_end) stage(d, s + decltype(d)::value); });
 #endif
 
   // acc tile (a, b) element e of lane l is dW[m][k]: m = 32 (wm MT + a) + (e & 3) + 8 (e >> 2) + 4 (l >> 5), k = 32 (wk KT + b) + (l & 31)
@@ -761,12 +734,12 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
   };
   unsigned char* const cbase = lds + rg * XS + l32 * 8;
   auto commit_piece = [&](int buf_off, int j) {
-    u32x2s hi, mid, lo;
+    u32x2 hi, mid, lo;
     split4(raw[j], hi, mid, lo);
     unsigned char* d = cbase + buf_off + (j / CPL) * 8 * XS + (j % CPL) * 256;
-    *reinterpret_cast<u32x2s*>(d) = hi;
-    *reinterpret_cast<u32x2s*>(d + PLANE) = mid;
-    *reinterpret_cast<u32x2s*>(d + 2 * PLANE) = lo;
+    *reinterpret_cast<u32x2*>(d) = hi;
+    *reinterpret_cast<u32x2*>(d + PLANE) = mid;
+    *reinterpret_cast<u32x2*>(d + 2 * PLANE) = lo;
   };
   // the finished tile waiting for its store: accumulators, byte offsets of this lane's row in y / gate (~0: no row), gate
   f32x16 pend[NCT];
@@ -908,13 +881,13 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
       } else if constexpr (c == 6) {
         unsigned char* d = cbase + nxt + (jp / CPL) * 8 * XS + (jp % CPL) * 256;
 #ifdef EXP_FS_NOSPLIT
-        *reinterpret_cast<u32x2s*>(d) = u32x2s{__float_as_uint(cva.x), __float_as_uint(cva.y)};
-        *reinterpret_cast<u32x2s*>(d + PLANE) = u32x2s{__float_as_uint(cvb.x), __float_as_uint(cvb.y)};
-        *reinterpret_cast<u32x2s*>(d + 2 * PLANE) = u32x2s{__float_as_uint(cva.x) + 1u, __float_as_uint(cvb.y)};
+        *reinterpret_cast<u32x2*>(d) = u32x2{__float_as_uint(cva.x), __float_as_uint(cva.y)};
+        *reinterpret_cast<u32x2*>(d + PLANE) = u32x2{__float_as_uint(cvb.x), __float_as_uint(cvb.y)};
+        *reinterpret_cast<u32x2*>(d + 2 * PLANE) = u32x2{__float_as_uint(cva.x) + 1u, __float_as_uint(cvb.y)};
 #else
-        *reinterpret_cast<u32x2s*>(d) = u32x2s{ch0, ch1};
-        *reinterpret_cast<u32x2s*>(d + PLANE) = u32x2s{cm0, cm1};
-        *reinterpret_cast<u32x2s*>(d + 2 * PLANE) = u32x2s{cl0, cl1};
+        *reinterpret_cast<u32x2*>(d) = u32x2{ch0, ch1};
+        *reinterpret_cast<u32x2*>(d + PLANE) = u32x2{cm0, cm1};
+        *reinterpret_cast<u32x2*>(d + 2 * PLANE) = u32x2{cl0, cl1};
 #endif
       } else {
         fetch_piece(t + 2 * G, jp);
@@ -965,7 +938,7 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
         }
       }
     };
-    static_for_wgs<NKS>([&](auto s_c) {
+    static_for<NKS>([&](auto s_c) {
       constexpr int s = decltype(s_c)::value;
 #ifdef EXP_FS_STAMPS
       if constexpr (s == 0) { c1 = clock64(); }
@@ -977,7 +950,7 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
         for (int q = 0; q < 3; ++q) xf[(s + 1) & 1][q] = *reinterpret_cast<const u32x4*>(cur + q * PLANE + 32 * (s + 1));
       }
       __builtin_amdgcn_sched_barrier(0);           // (the scheduler would sink each read to just before its MFMA)
-      static_for_wgs<6>([&](auto i_c) {
+      static_for<6>([&](auto i_c) {
         constexpr int i = decltype(i_c)::value, slot = s * 6 + i;
         // the six products of a k-step, smallest terms first: (w lo, x hi) (w hi, x lo) (w mid, x mid) (w mid, x hi)
         // (w hi, x mid) (w hi, x hi)
@@ -988,7 +961,7 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
 #endif
         {
 #pragma unroll
-          for (int ct = 0; ct < NCT; ++ct) acc[ct][s % NPAR] = mfma_bf16(wf[wq][ct][s], xf[s & 1][xq], acc[ct][s % NPAR]);
+          for (int ct = 0; ct < NCT; ++ct) acc[ct][s % NPAR] = Mfma<bf16_t>::run(wf[wq][ct][s], xf[s & 1][xq], acc[ct][s % NPAR]);
         }
         if constexpr (GATE != 0 && s < HEAD && 2 * s + 1 < 16) {
           gate_stage(s_c, i_c);
@@ -997,7 +970,7 @@ __global__ __launch_bounds__(256, 1) void linear_f32_split_wres_kernel(SplitPara
         if constexpr (slot >= S0 && slot < S0 + SPAN) {
           constexpr int g0 = (slot - S0) * NCHK / SPAN, g1 = (slot + 1 - S0) * NCHK / SPAN;
           if constexpr (g1 > g0) {
-            static_for_wgs<g1 - g0>([&](auto d_c) { chunk(std::integral_constant<int, g0 + decltype(d_c)::value>{}); });
+            static_for<g1 - g0>([&](auto d_c) { chunk(std::integral_constant<int, g0 + decltype(d_c)::value>{}); });
             __builtin_amdgcn_sched_barrier(0);
           }
         }

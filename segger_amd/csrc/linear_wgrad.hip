@@ -24,55 +24,18 @@
 // a stage goes through a double-buffered LDS tile so that it leaves as full rows, one 8- or 16-byte store per lane,
 // issued one stage later (after the ring's barrier).  The stores share vmcnt with the LDS-DMA loads: the counted
 // waits below include them.
+//
+// The MFMA wrappers (Mfma<T>: run, run16, sum2), the transposing read (lds_read_tr) and the counted waits and LDS-only
+// barrier are mma.h's; the LDS-DMA load, its buffer resource and the stage geometry have this one user and live here.
 #include <cstdlib>
 #include "common.h"
+#include "mma.h"
 #include "post_common.h"
 
 namespace segger {
 namespace {
 
-typedef __bf16   bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8  __attribute__((ext_vector_type(8)));
-typedef __bf16   bf16x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2v  __attribute__((ext_vector_type(2)));
-typedef float    f32x16 __attribute__((ext_vector_type(16)));
-typedef short    s16x4  __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2  __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-
 constexpr int kStageRows = 16;           // rows per LDS stage = one 32x32x16 k-step
-
-template <typename T> struct WgMfma;
-template <> struct WgMfma<bf16_t> {
-  static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 run16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  // c + lo(a) + hi(a)
-  static __device__ __forceinline__ float sum2(uint32_t a, float c) {
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, a), __builtin_bit_cast(bf16x2v, 0x3f803f80u), c, false);
-  }
-};
-template <> struct WgMfma<f16_t> {
-  static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 run16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float sum2(uint32_t a, float c) {
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2v, a), __builtin_bit_cast(f16x2v, 0x3c003c00u), c, false);
-  }
-};
-
-// 4 rows x 16 columns of 16-bit elements, transposed: lane i of a 16-lane group receives column i of the 4 rows
-__device__ __forceinline__ u32x2 lds_read_tr(const unsigned char* p) {
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(const_cast<unsigned char*>(p)));
-  return __builtin_bit_cast(u32x2, v);
-}
 
 struct WgradParams {
   const void* dy; int64_t ld_dy;
@@ -93,7 +56,6 @@ struct WgradParams {
 // that hipcc does not count it: it would otherwise drain vmcnt to 0 in front of every LDS read (it cannot tell
 // which LDS bytes an asynchronous load will write), which is the pipelining this kernel lives on.  M0 carries the
 // destination; it is saved and restored inside the statement (cdna_hip_programming.md 5.7).
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void lds_dma16(i32x4 rsrc, uint32_t lds_dst, int voffset, int soffset) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\t"
@@ -124,10 +86,6 @@ template <int M, int K, int NW, bool GEN = false> struct WgGeo {
   static constexpr int IMG_G = IMG + kStageRows * SX;
   static constexpr bool GATE_OK = !GEN && IMG % 1024 == 0 && IMG_G <= BUF;
 };
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {   // lgkmcnt / expcnt untouched
-  __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
-}
 
 // The kernel body is a function (two of them can share a launch: wgrad_pair_kernel) and takes the parameter block by
 // value (gatv2_kernels.h: by const reference a body came out of the register allocator slower); `lds` = the workgroup's
@@ -292,8 +250,7 @@ __device__ __forceinline__ void wgrad_body(const WgradParams p, const int64_t bi
       else wait_vmcnt<(kAhead - 1) * P + 3>();
       // a bare barrier (+ the LDS writes of the previous iteration's dX tile drained): __syncthreads() would add a
       // release fence, i.e. vmcnt(0) -- the loads in flight are the pipelining this kernel lives on
-      __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0)
-      __builtin_amdgcn_s_barrier();
+      lds_barrier_unfenced();
     }
     issue(s + kAhead);
     if constexpr (DX) {
@@ -311,8 +268,8 @@ __device__ __forceinline__ void wgrad_body(const WgradParams p, const int64_t bi
 #pragma unroll
       for (int a = 0; a < MT; ++a) {
         float d = dbias[a];
-        d = WgMfma<T>::sum2(fa[a].x, d); d = WgMfma<T>::sum2(fa[a].y, d);
-        d = WgMfma<T>::sum2(fa[a].z, d); d = WgMfma<T>::sum2(fa[a].w, d);
+        d = Mfma<T>::sum2(fa[a].x, d); d = Mfma<T>::sum2(fa[a].y, d);
+        d = Mfma<T>::sum2(fa[a].z, d); d = Mfma<T>::sum2(fa[a].w, d);
         dbias[a] = d;
       }
     }
@@ -332,7 +289,7 @@ __device__ __forceinline__ void wgrad_body(const WgradParams p, const int64_t bi
         const u32x4 fb = u32x4{Vec8<T>::pack(v[0], v[1]), Vec8<T>::pack(v[2], v[3]), Vec8<T>::pack(v[4], v[5]),
                                Vec8<T>::pack(v[6], v[7])};
 #pragma unroll
-        for (int a = 0; a < MT; ++a) acc[a][b] = WgMfma<T>::run(fa[a], fb, acc[a][b]);
+        for (int a = 0; a < MT; ++a) acc[a][b] = Mfma<T>::run(fa[a], fb, acc[a][b]);
       }
     } else {
 #pragma unroll
@@ -341,7 +298,7 @@ __device__ __forceinline__ void wgrad_body(const WgradParams p, const int64_t bi
         const u32x2 hi = lds_read_tr(base + off_x + b * 64 + 4 * SX);
         const u32x4 fb = u32x4{lo.x, lo.y, hi.x, hi.y};
 #pragma unroll
-        for (int a = 0; a < MT; ++a) acc[a][b] = WgMfma<T>::run(fa[a], fb, acc[a][b]);
+        for (int a = 0; a < MT; ++a) acc[a][b] = Mfma<T>::run(fa[a], fb, acc[a][b]);
       }
     }
     if constexpr (DX) {
@@ -354,7 +311,7 @@ __device__ __forceinline__ void wgrad_body(const WgradParams p, const int64_t bi
       for (int ks = 0; ks < KS; ++ks) {
         const u32x4 fy = *reinterpret_cast<const u32x4*>(base + dj * SY + (32 * ks + 8 * dq) * 2);
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) dacc[ct] = WgMfma<T>::run16(wf[ct][ks], fy, dacc[ct]);
+        for (int ct = 0; ct < CT; ++ct) dacc[ct] = Mfma<T>::run16(wf[ct][ks], fy, dacc[ct]);
       }
       unsigned char* ot = lds_out + (s & 1) * G::OUT + dj * SO;
       if (gated) {                                       // this lane's 4 columns of row dj of the staged gate rows
@@ -377,13 +334,12 @@ __device__ __forceinline__ void wgrad_body(const WgradParams p, const int64_t bi
   }
   if constexpr (DX) {
     if (n_local > 0) {                                       // the last stage's tile (the only one that may be partial)
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
+      lds_barrier_unfenced();
       store_dx(n_local - 1, true);
     }
   }
   // the ring ran kAhead stages past the slab (zero reads): let them land before the wave ends
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vmcnt<0>();
 
   // ---- partial results: acc tile (a, b) element e of lane l is dW[m][k] with
   //      m = 32*(wm*MT + a) + (e & 3) + 8*(e >> 2) + 4*(l >> 5),  k = 32*(wk*KT + b) + (l & 31) -----------------------
@@ -459,10 +415,6 @@ constexpr int kPbBuf = 8 * 1024;                       // one 1 KiB DMA chunk pe
 // cover the memory latency at this stage rate (measured 1.9 TB/s); 6 ahead, + the current stage + the one consume() reads
 constexpr int kPbAhead = 6, kPbSlots = kPbAhead + 2;
 constexpr int kPbWidth2 = kPbD * kPbD + kPbD, kPbWidth0 = kPbD * kPbF + kPbD;
-
-__device__ __forceinline__ float sigmoid_fast(float z) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
-}
 
 // Two row sets (the transcripts' and the boundaries' positions: the embedder is called once per node type on large batches)
 // share ONE launch and ONE sum of partials: blocks [0, n_first) work on `pa`, the rest on `pb`, whose partial rows follow
@@ -542,7 +494,7 @@ __global__ __launch_bounds__(512, 2) void posmlp_bwd_kernel(PosBwdParams pa, Pos
   // these are the kernel's only compiler-visible global loads: retire them here, or hipcc -- which cannot see the
   // asm DMA loads sharing the counter -- waits for them with vmcnt(0) at their first use INSIDE the loop, draining the
   // ring every iteration (seen in the ISA of the first version: 1.9 TB/s)
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vmcnt<0>();
   asm volatile("" : "+v"(wf[0]), "+v"(wf[1]));
 
   auto consume = [&](int t) {
@@ -553,11 +505,11 @@ __global__ __launch_bounds__(512, 2) void posmlp_bwd_kernel(PosBwdParams pa, Pos
       const u32x2 lo = lds_read_tr(pb + off_a + wm2 * 64), hi = lds_read_tr(pb + off_a + wm2 * 64 + 4 * S);
       const u32x4 fa = u32x4{lo.x, lo.y, hi.x, hi.y};
       if (wk2 == 0) {
-        db2 = WgMfma<T>::sum2(fa.x, db2); db2 = WgMfma<T>::sum2(fa.y, db2);
-        db2 = WgMfma<T>::sum2(fa.z, db2); db2 = WgMfma<T>::sum2(fa.w, db2);
+        db2 = Mfma<T>::sum2(fa.x, db2); db2 = Mfma<T>::sum2(fa.y, db2);
+        db2 = Mfma<T>::sum2(fa.z, db2); db2 = Mfma<T>::sum2(fa.w, db2);
       }
       const u32x2 lo2 = lds_read_tr(th + off_a + wk2 * 64), hi2 = lds_read_tr(th + off_a + wk2 * 64 + 4 * S);
-      acc2 = WgMfma<T>::run(fa, u32x4{lo2.x, lo2.y, hi2.x, hi2.y}, acc2);
+      acc2 = Mfma<T>::run(fa, u32x4{lo2.x, lo2.y, hi2.x, hi2.y}, acc2);
     }
     u32x4 fd[2];
 #pragma unroll
@@ -569,8 +521,8 @@ __global__ __launch_bounds__(512, 2) void posmlp_bwd_kernel(PosBwdParams pa, Pos
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         float d = db0[a];
-        d = WgMfma<T>::sum2(fd[a].x, d); d = WgMfma<T>::sum2(fd[a].y, d);
-        d = WgMfma<T>::sum2(fd[a].z, d); d = WgMfma<T>::sum2(fd[a].w, d);
+        d = Mfma<T>::sum2(fd[a].x, d); d = Mfma<T>::sum2(fd[a].y, d);
+        d = Mfma<T>::sum2(fd[a].z, d); d = Mfma<T>::sum2(fd[a].w, d);
         db0[a] = d;
       }
     }
@@ -589,14 +541,13 @@ __global__ __launch_bounds__(512, 2) void posmlp_bwd_kernel(PosBwdParams pa, Pos
     const u32x4 fb = u32x4{Vec8<T>::pack(v[0], v[1]), Vec8<T>::pack(v[2], v[3]), Vec8<T>::pack(v[4], v[5]),
                            Vec8<T>::pack(v[6], v[7])};
 #pragma unroll
-    for (int a = 0; a < 2; ++a) acc0[a] = WgMfma<T>::run(fd[a], fb, acc0[a]);
+    for (int a = 0; a < 2; ++a) acc0[a] = Mfma<T>::run(fd[a], fb, acc0[a]);
   };
 
   for (int d = 0; d < kPbAhead; ++d) issue(d);
   for (int s = 0; s < n_local; ++s) {
     wait_vmcnt<kPbAhead - 1>();
-    __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0): last iteration's tile writes and reads
-    __builtin_amdgcn_s_barrier();
+    lds_barrier_unfenced();                                // (drained: last iteration's tile writes and reads)
     issue(s + kPbAhead);                                   // the slot consume(s - 2) read last
     const unsigned char* base = lds + (s % NB) * BUF;
     if (!lo_half) {                                        // h1 tile: 4 elements per thread of waves 4..7
@@ -613,7 +564,7 @@ __global__ __launch_bounds__(512, 2) void posmlp_bwd_kernel(PosBwdParams pa, Pos
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const u32x4 fy = *reinterpret_cast<const u32x4*>(base + dj * S + (32 * ks + 8 * dq) * 2);
-        dacc = WgMfma<T>::run16(wf[ks], fy, dacc);
+        dacc = Mfma<T>::run16(wf[ks], fy, dacc);
       }
       const u32x2 zv = *reinterpret_cast<const u32x2*>(base + kPbOffZ + dj * S + (16 * wave + 4 * dq) * 2);
       float z[4];
@@ -621,21 +572,17 @@ __global__ __launch_bounds__(512, 2) void posmlp_bwd_kernel(PosBwdParams pa, Pos
       Vec8<T>::unpack2(zv.y, z[2], z[3]);
       float o[4] = {dacc.x, dacc.y, dacc.z, dacc.w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float sg = sigmoid_fast(z[e]);
-        o[e] *= sg * (1.0f + z[e] * (1.0f - sg));          // SiLU'(z)
-      }
+      for (int e = 0; e < 4; ++e) o[e] *= silu_grad(z[e]);
       *reinterpret_cast<u32x2*>(tile_d + (s & 1) * TILE + dj * S + (16 * wave + 4 * dq) * 2) =
           u32x2{Vec8<T>::pack(o[0], o[1]), Vec8<T>::pack(o[2], o[3])};
     }
     if (s > 0) consume(s - 1);
   }
   if (n_local > 0) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();
+    lds_barrier_unfenced();
     consume(n_local - 1);
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);                      // the ring ran kPbAhead stages past the slab
+  wait_vmcnt<0>();                                         // the ring ran kPbAhead stages past the slab
 
   float* out2 = p.part2 + (int64_t)bid * kPbWidth2;
   float* out0 = p.part0 + (int64_t)bid * kPbWidth0;

@@ -40,63 +40,25 @@ constexpr int kChainCap = 64;                      // entries a row's chain hold
 constexpr int32_t kOverflow = -2;                  // next[code]: the contribution is not chained (hot row)
 
 // ---- CPL consecutive channels as fp32 ---------------------------------------------------------------------------
-template <typename T, int CPL> struct Row;
-template <int CPL> struct Row<float, CPL> {
-  static __device__ __forceinline__ void load(const float* p, float (&f)[CPL]) {
-    if constexpr (CPL == 2) { const float2 v = *reinterpret_cast<const float2*>(p); f[0] = v.x; f[1] = v.y; }
-    else {
-#pragma unroll
-      for (int k = 0; k < CPL; k += 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + k);
-        f[k] = v.x; f[k + 1] = v.y; f[k + 2] = v.z; f[k + 3] = v.w;
-      }
-    }
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&f)[CPL]) {
-    if constexpr (CPL == 2) *reinterpret_cast<float2*>(p) = float2{f[0], f[1]};
-    else {
-#pragma unroll
-      for (int k = 0; k < CPL; k += 4) *reinterpret_cast<f32x4*>(p + k) = f32x4{f[k], f[k + 1], f[k + 2], f[k + 3]};
-    }
-  }
-};
-template <typename T, int CPL> struct Row16 {      // bf16_t / f16_t
+// (CPL in {2, 4, 8}: common.h's load2, load4 and Vec8<T>::load; the stores have this one user)
+template <typename T, int CPL> struct Row {
+  static_assert(CPL == 2 || CPL == 4 || CPL == 8, "a lane owns 2, 4 or 8 channels");
   static __device__ __forceinline__ void load(const T* p, float (&f)[CPL]) {
-    if constexpr (CPL == 2) {
-      Vec8<T>::unpack2(*reinterpret_cast<const uint32_t*>(p), f[0], f[1]);
-    } else if constexpr (CPL == 4) {
-      const uint2 v = *reinterpret_cast<const uint2*>(p);
-      Vec8<T>::unpack2(v.x, f[0], f[1]); Vec8<T>::unpack2(v.y, f[2], f[3]);
-    } else {
-      Vec8<T>::load(p, f);
-    }
+    if constexpr (CPL == 2) load2(p, f[0], f[1]);
+    else if constexpr (CPL == 4) load4(p, f);
+    else Vec8<T>::load(p, f);
   }
   static __device__ __forceinline__ void store(T* p, const float (&f)[CPL]) {
-    if constexpr (CPL == 2) {
-      *reinterpret_cast<uint32_t*>(p) = Vec8<T>::pack(f[0], f[1]);
-    } else if constexpr (CPL == 4) {
-      *reinterpret_cast<uint2*>(p) = uint2{Vec8<T>::pack(f[0], f[1]), Vec8<T>::pack(f[2], f[3])};
+    if constexpr (CPL == 8) Vec8<T>::store(p, f);
+    else if constexpr (sizeof(T) == 4) {
+      if constexpr (CPL == 2) *reinterpret_cast<float2*>(p) = float2{f[0], f[1]};
+      else *reinterpret_cast<f32x4*>(p) = f32x4{f[0], f[1], f[2], f[3]};
     } else {
-      Vec8<T>::store(p, f);
+      if constexpr (CPL == 2) *reinterpret_cast<uint32_t*>(p) = Vec8<T>::pack(f[0], f[1]);
+      else *reinterpret_cast<uint2*>(p) = uint2{Vec8<T>::pack(f[0], f[1]), Vec8<T>::pack(f[2], f[3])};
     }
   }
 };
-template <int CPL> struct Row<bf16_t, CPL> : Row16<bf16_t, CPL> {};
-template <int CPL> struct Row<f16_t, CPL> : Row16<f16_t, CPL> {};
-
-template <typename T> __device__ __forceinline__ void ld2(const T* p, float& a, float& b);
-template <> __device__ __forceinline__ void ld2<float>(const float* p, float& a, float& b) {
-  const float2 v = *reinterpret_cast<const float2*>(p); a = v.x; b = v.y;
-}
-template <> __device__ __forceinline__ void ld2<bf16_t>(const bf16_t* p, float& a, float& b) {
-  Vec8<bf16_t>::unpack2(*reinterpret_cast<const uint32_t*>(p), a, b);
-}
-template <> __device__ __forceinline__ void ld2<f16_t>(const f16_t* p, float& a, float& b) {
-  Vec8<f16_t>::unpack2(*reinterpret_cast<const uint32_t*>(p), a, b);
-}
-
-__device__ __forceinline__ float softplus_(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
-__device__ __forceinline__ float sigmoid_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 struct LossHeadParams {
   const void* ztx; int64_t ld_ztx; int64_t n_tx;
@@ -235,7 +197,7 @@ __global__ __launch_bounds__(256) void loss_head_fwd_kernel(LossHeadParams p) {
 #pragma unroll
         for (int k = 0; k < CPL; ++k) { s0 = fmaf(a[k], pp[k], s0); s1 = fmaf(a[k], nn[k], s1); }
         s0 = lane_block_sum<16>(s0); s1 = lane_block_sum<16>(s1);
-        if (ok && gl == 0) acc += softplus_(-s0) + softplus_(s1);
+        if (ok && gl == 0) acc += softplus(-s0) + softplus(s1);
       } else {
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
@@ -424,7 +386,7 @@ __global__ __launch_bounds__(256) void loss_head_bwd_kernel(LossHeadParams p) {
 #pragma unroll
               for (int k = 0; k < CPL; ++k) { s0 = fmaf(a[k], pj[k], s0); s1 = fmaf(a[k], nv[k], s1); }
               s0 = lane_block_sum<16>(s0); s1 = lane_block_sum<16>(s1);
-              const float dlp = (sigmoid_(s0) - 1.0f) * sc_sg, dln = sigmoid_(s1) * sc_sg;
+              const float dlp = (sigmoid(s0) - 1.0f) * sc_sg, dln = sigmoid(s1) * sc_sg;
 #pragma unroll
               for (int k = 0; k < CPL; ++k) g[k] += dlp * pj[k] + dln * nv[k];
             } else {
@@ -500,7 +462,7 @@ __global__ __launch_bounds__(256) void loss_head_bwd_kernel(LossHeadParams p) {
     float pj[KP][2], acc[KP][2];
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
-      ld2(zbd + j * p.ld_zbd + 2 * gl + 32 * k, pj[k][0], pj[k][1]);
+      load2(zbd + j * p.ld_zbd + 2 * gl + 32 * k, pj[k][0], pj[k][1]);
       acc[k][0] = 0.f; acc[k][1] = 0.f;
     }
     for (int64_t s0 = beg; s0 < end; s0 += 16) {
@@ -514,14 +476,14 @@ __global__ __launch_bounds__(256) void loss_head_bwd_kernel(LossHeadParams p) {
       if (p.sg_kind == SEGGER_LOSS_BCE) {
 #pragma unroll
         for (int k = 0; k < KP; ++k) {
-          ld2(ztx + ia * p.ld_ztx + 2 * gl + 32 * k, av[k][0], av[k][1]);
-          ld2(zbd + in * p.ld_zbd + 2 * gl + 32 * k, nv[k][0], nv[k][1]);
+          load2(ztx + ia * p.ld_ztx + 2 * gl + 32 * k, av[k][0], av[k][1]);
+          load2(zbd + in * p.ld_zbd + 2 * gl + 32 * k, nv[k][0], nv[k][1]);
           t0 = fmaf(av[k][0], pj[k][0], fmaf(av[k][1], pj[k][1], t0));
           t1 = fmaf(av[k][0], nv[k][0], fmaf(av[k][1], nv[k][1], t1));
         }
         t0 = lane_block_sum<16>(t0); t1 = lane_block_sum<16>(t1);
         if (ok) {
-          const float dlp = (sigmoid_(t0) - 1.0f) * sc, dln = sigmoid_(t1) * sc;
+          const float dlp = (sigmoid(t0) - 1.0f) * sc, dln = sigmoid(t1) * sc;
 #pragma unroll
           for (int k = 0; k < KP; ++k) {
             acc[k][0] = fmaf(dlp, av[k][0], acc[k][0]); acc[k][1] = fmaf(dlp, av[k][1], acc[k][1]);
@@ -534,8 +496,8 @@ __global__ __launch_bounds__(256) void loss_head_bwd_kernel(LossHeadParams p) {
 #pragma unroll
         for (int k = 0; k < KP; ++k) {
           float n0, n1;
-          ld2(ztx + ia * p.ld_ztx + 2 * gl + 32 * k, av[k][0], av[k][1]);
-          ld2(zbd + in * p.ld_zbd + 2 * gl + 32 * k, n0, n1);
+          load2(ztx + ia * p.ld_ztx + 2 * gl + 32 * k, av[k][0], av[k][1]);
+          load2(zbd + in * p.ld_zbd + 2 * gl + 32 * k, n0, n1);
           dp[k][0] = av[k][0] - pj[k][0] + p.sg_eps; dp[k][1] = av[k][1] - pj[k][1] + p.sg_eps;
           dn[k][0] = av[k][0] - n0 + p.sg_eps;       dn[k][1] = av[k][1] - n1 + p.sg_eps;
           t0 = fmaf(dp[k][0], dp[k][0], t0); t0 = fmaf(dp[k][1], dp[k][1], t0);

@@ -10,26 +10,11 @@
 // dW0 = dz1^T F regenerates F the same way (segger_posmlp_wgrad: linear_wgrad.hip's kernel with a generated operand).  The second GEMM consumes the first one's accumulators without a transpose:
 // the k order of a GEMM is free, so the A operand (W2) is read from LDS in the order the accumulator lanes hold h1.
 #include "common.h"
+#include "mma.h"
 #include "post_common.h"
 
 namespace segger {
 namespace {
-
-typedef __bf16   bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8  __attribute__((ext_vector_type(8)));
-typedef float    f32x16 __attribute__((ext_vector_type(16)));
-
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16_t> {
-  static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<f16_t> {
-  static __device__ __forceinline__ f32x16 run(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
 
 constexpr int kFreq = 256, kHalf = 128, kDim = 64;
 constexpr int kW0Stride = kFreq * 2 + 16;      // bytes per LDS row of W0 [64, 256]
@@ -172,7 +157,7 @@ __global__ __launch_bounds__(kPmWaves * 64, 2) void posmlp_fwd_kernel(PosMlpPara
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           z[j] = acc[ct][4 * gq + j] + bq[j];
-          hq[j] = z[j] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z[j]));
+          hq[j] = z[j] * sigmoid_fast(z[j]);
         }
         h1p[ct][2 * gq] = Vec8<T>::pack(hq[0], hq[1]);
         h1p[ct][2 * gq + 1] = Vec8<T>::pack(hq[2], hq[3]);
