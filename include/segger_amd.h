@@ -2037,6 +2037,87 @@ int segger_fragments_finalize(int32_t* parent, const uint8_t* unassigned, int64_
                               int64_t first_id, int64_t* fragment, int32_t* root, int32_t* size, int64_t capacity,
                               int64_t* counters, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
 
+/* ----------------------------------------------------------------------
+ * Buffered-boundary count matrices (csrc/buffered_counts.hip; segger_amd.buffered_counts): the polygon x gene
+ * count matrix of boundaries grown by a distance -- the reference's get_buffered_counts -> buffer_polygons ->
+ * get_expression_matrix (src/segger/metrics/segment.py), the nucleus-expansion baseline -- as a CSR, without the pair list.
+ * The join of segger_polygon_join_* and the histogram of segger_expression_build fused: one wave owns one polygon and builds
+ * the polygon's gene histogram in LDS where the hits are found.  A point inside several grown polygons is counted in each.
+ * Purely additive: three new symbols, SEGGER_ABI_VERSION stays 32.
+ *
+ * The predicate, the arithmetic, the rings (a CSR of single exterior rings in fp64, a closing duplicate dropped, fewer than
+ *   3 vertices match nothing, at most SEGGER_MORPH_MAX_VERTS), the uniform grid, the walk and its margin are
+ *   segger_polygon_join_*'s above, bit for bit: both units compile csrc/ring_predicate.h and csrc/join_grid.h.
+ *
+ * Inputs beyond the join's:  gene [n_points] int32, the gene of every point;  n_genes, 1 .. SEGGER_BCOUNT_MAX_GENES.  A point
+ *   whose gene lies outside [0, n_genes) is never an index: when it matches a polygon it is counted in n_bad (once per
+ *   polygon it matches) and in n_pairs, and takes part in nothing else.
+ *
+ * Two calls (the size of the result is known on the device only):
+ *   segger_buffered_counts_count  bins the points (keys, cell starts, cell-ordered points, and gene in cell order beside
+ *       them) and the polygons (by route), then per polygon p writes the number of distinct in-range genes it hits to
+ *       indptr[p + 1] and the number of matched in-range points to cell_count[p], and scans indptr on the device:
+ *         indptr     [n_polygons + 1] int64   row offsets, indptr[n_polygons] = nnz <= min(n_pairs, n_polygons n_genes);
+ *         cell_count [n_polygons]     int64   = the sum of the row's counts, <= n_points;
+ *         counters   [SEGGER_BCOUNT_COUNTERS] int64 (zeroed by the call):  0 n_pairs, the matched (point, polygon) pairs,
+ *                    out-of-range genes included;  1 nnz;  2 n_bad;  3 n_overflow_rows, the polygons with more than
+ *                    SEGGER_BCOUNT_TOUCHED distinct genes;  4 n_large_tier, the polygons (of 3 or more vertices) that ran
+ *                    on the large tier: all of them when n_genes > SEGGER_BCOUNT_SMALL_GENES, none otherwise.
+ *   segger_buffered_counts_fill   the same traversal again, with the same inputs and the workspace as the count call left
+ *       it, indptr and cell_count as it wrote them: writes indices (the gene id, strictly ascending inside a row) and
+ *       counts (int32, >= 1) at indptr[p] .. indptr[p + 1).  Nothing is written at or beyond capacity entries, nor outside the polygon's own row.
+ *
+ * The histogram.  int32 hist[n_genes] per wave in LDS, zero between polygons.  A hit is an LDS atomic add on its gene; the
+ *   lane that sees the old value 0 appends the gene to the wave's touched list (SEGGER_BCOUNT_TOUCHED entries, the slot from
+ *   a ballot).  After the walk the touched list is sorted (csrc/wave_sort.h, the bitonic network of segger_rings_resort),
+ *   the row is written from it and exactly those entries of hist are zeroed: the cost of a polygon does not grow with
+ *   n_genes.  A polygon with more distinct genes than the list holds is written by one ordered scan of hist instead
+ *   (n_overflow_rows).  Two tiers:
+ *     small  n_genes <= SEGGER_BCOUNT_SMALL_GENES: 8 KB of hist and 2 KB of list a wave; rings of n <= 64 vertices in
+ *            registers, four waves a workgroup (40 KB); longer rings one single-wave workgroup with the 64 KB ring stage
+ *            (74 KB, two a CU);
+ *     large  n_genes <= SEGGER_BCOUNT_MAX_GENES: one single-wave workgroup per polygon, the whole histogram in LDS.
+ *   SEGGER_BCOUNT_MAX_GENES = (SEGGER_BCOUNT_LDS_BYTES - 65536 - 4 SEGGER_BCOUNT_TOUCHED) / 4 = (163840 - 65536 - 2048) / 4
+ *   = 24064: the 160 KB of LDS a CDNA4 workgroup can address, minus the 64 KB ring stage of the long-ring route, minus the
+ *   touched list, in int32 entries.  Larger panels need a key-sort route, which is NOT BUILT; nor is a histogram sized by
+ *   n_genes (every panel above SEGGER_BCOUNT_SMALL_GENES runs one wave a workgroup).
+ *   Integer atomics only, no floating-point accumulation, no scratch.  Every output is a function of the inputs alone -- the
+ *   sums are integers and the rows are sorted -- the same bytes for any grid, any launch geometry and either tier.
+ *
+ * Errors found on the device (the int32 at byte 0 of the workspace, as the join's; the bits are the join's):
+ *     SEGGER_BCOUNT_ERR_OFFSETS, _CAP, _BUFFER  as SEGGER_PJOIN_ERR_*; such a polygon has an empty row;
+ *     SEGGER_BCOUNT_ERR_FILL    the fill found other sizes than indptr and the count call left, or more entries than capacity.
+ *
+ * Workspace: segger_buffered_counts_workspace_bytes(n_points, n_polygons, n_genes, nx, ny) =
+ *   segger_polygon_join_workspace_bytes(n_points, n_polygons, nx, ny) + up(4 N), N = max(n_points, 1), up() rounding up to
+ *   256 (n_genes is checked and changes nothing).  256-byte aligned.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: everything segger_polygon_join_* rejects
+ *   (n_points and n_polygons below 2^31 - 1), n_genes outside 1 .. SEGGER_BCOUNT_MAX_GENES, a NULL or misaligned gene (4 bytes),
+ *   indptr, cell_count, counters (8 bytes), indices or counts (4 bytes).  n_points = 0 or n_polygons = 0 returns SEGGER_OK
+ *   without touching a pointer or the device: nothing is written, the caller knows the result is all zeros.
+ * ---------------------------------------------------------------------- */
+#define SEGGER_BCOUNT_SMALL_GENES 2048
+#define SEGGER_BCOUNT_TOUCHED 512
+#define SEGGER_BCOUNT_LDS_BYTES 163840
+#define SEGGER_BCOUNT_MAX_GENES ((SEGGER_BCOUNT_LDS_BYTES - 65536 - 4 * SEGGER_BCOUNT_TOUCHED) / 4)      /* 24064 */
+#define SEGGER_BCOUNT_COUNTERS 5
+#define SEGGER_BCOUNT_ERR_OFFSETS 1
+#define SEGGER_BCOUNT_ERR_CAP 2
+#define SEGGER_BCOUNT_ERR_BUFFER 4
+#define SEGGER_BCOUNT_ERR_FILL 8
+int64_t segger_buffered_counts_workspace_bytes(int64_t n_points, int64_t n_polygons, int64_t n_genes, int32_t nx, int32_t ny);
+int segger_buffered_counts_count(const double* points /* [N, 2] */, int64_t n_points, const int32_t* gene /* [N] */,
+                                 int64_t n_genes, const int64_t* ring_offsets, const double* xy, int64_t n_polygons,
+                                 int64_t n_vertices, const double* buffer /* [P] fp64 or NULL = 0 */, int32_t predicate,
+                                 double x0, double y0, double cell, int32_t nx, int32_t ny, int64_t* indptr /* [P + 1] */,
+                                 int64_t* cell_count /* [P] */, int64_t* counters, void* workspace, int64_t workspace_bytes,
+                                 segger_stream_t stream);
+int segger_buffered_counts_fill(const double* points, int64_t n_points, const int32_t* gene, int64_t n_genes,
+                                const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                                const double* buffer, int32_t predicate, double x0, double y0, double cell, int32_t nx,
+                                int32_t ny, const int64_t* indptr, const int64_t* cell_count, int32_t* indices, int32_t* counts,
+                                int64_t capacity, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -32,6 +32,9 @@ SIMPLIFY_SMALL_VERTS, SIMPLIFY_COUNTERS, SIMPLIFY_ERR_TOL = 256, 8, 4           
 RING_OK, RING_TOO_FEW, RING_TOUCH = 0, 1, 2                                                            # SEGGER_RING_*
 OVERLAP_SMALL_VERTS, OVERLAP_WIDE_CELLS = 256, 64                                                      # SEGGER_OVERLAP_*
 FRAGMENTS_COUNTERS, FRAGMENTS_CHUNK, FRAGMENTS_MAX_CHANNELS = 8, 2048, 1024                            # SEGGER_FRAGMENTS_*
+BCOUNT_SMALL_GENES, BCOUNT_TOUCHED, BCOUNT_LDS_BYTES, BCOUNT_COUNTERS = 2048, 512, 163840, 5           # SEGGER_BCOUNT_*
+BCOUNT_MAX_GENES = (BCOUNT_LDS_BYTES - 65536 - 4 * BCOUNT_TOUCHED) // 4                                # 24064
+BCOUNT_ERR_FILL = 8
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -404,6 +407,11 @@ EXPORTS = {
     "segger_fragments_update": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp,
                                           C.c_int64, C.c_float, vp, vp, vp]),
     "segger_fragments_finalize": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
+    "segger_buffered_counts_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "segger_buffered_counts_count": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_double,
+                                               C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp]),
+    "segger_buffered_counts_fill": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_double,
+                                              C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -18,9 +18,11 @@
 // The two polygon kernels are templates on "count" / "fill" over ONE traversal (polygon_body): the wave walks the rows of
 // grid cells that overlap the ring's bounds grown by d and a rounding margin, each row one contiguous span of the
 // cell-ordered points, 64 points at a time, one point per lane, and loops over the edges accumulating the crossing parity
-// and the smallest squared distance.  A match's slot is the polygon's offset + the matches before it in the traversal
-// (hit_slot): no atomic decides a slot, so the list of a polygon is in (cell row, cell, point id) order whatever the
-// scheduling, and the same call gives the same bytes.
+// and the smallest squared distance (ring_predicate.h: ring_match and the cell range, shared with buffered_counts.hip).
+// A match's slot is the polygon's offset + the matches before it in the traversal (hit_slot): no atomic decides a slot,
+// so the list of a polygon is in (cell row, cell, point id) order whatever the scheduling, and the same call gives the
+// same bytes.  The keys, cells and binning kernels wrap join_grid.h's bodies, and the layout and the host checks are that
+// header's too: buffered_counts.hip bins with the same code.
 //
 // Arithmetic: float64, the point and the vertices translated to the ring's first vertex, FMA contraction off, so with
 // coordinates that are exactly representable after the translation the cross product, and with it the parity and "on the
@@ -34,64 +36,35 @@
 #include "common.h"
 #include "post_common.h"
 #include "rings.h"
+#include "ring_predicate.h"
 #include "sort_config.h"
+#include "join_grid.h"
 
 #pragma clang fp contract(off)
 
 namespace segger {
 namespace {
 
-constexpr int kPjThreads = 256;
+constexpr int kPjThreads = kGridThreads;
 constexpr int kPjWaves = kPjThreads / kWave;
 
-// ---------------------------------------------------------------- the points ---
+// ---------------------------------------------------------------- the points, the polygons: join_grid.h ---
 __global__ __launch_bounds__(kPjThreads) void pjoin_keys_kernel(const double* __restrict__ pts, int64_t n, UniformGrid g,
                                                                 unsigned long long* __restrict__ keys) {
-  const int64_t stride = (int64_t)gridDim.x * kPjThreads;
-  for (int64_t i = (int64_t)blockIdx.x * kPjThreads + threadIdx.x; i < n; i += stride) {
-    const double2 p = reinterpret_cast<const double2*>(pts)[i];
-    const int cx = cell_of(p.x, g.x0, g.inv_cell, g.nx), cy = cell_of(p.y, g.y0, g.inv_cell, g.ny);
-    keys[i] = ((unsigned long long)((int64_t)cy * g.nx + cx) << 32) | (unsigned long long)i;
-  }
+  grid_keys_body(pts, n, g, keys);
 }
 
 __global__ __launch_bounds__(kPjThreads) void pjoin_cells_kernel(const unsigned long long* __restrict__ keys_sorted,
                                                                  const double* __restrict__ pts, int64_t n, int64_t n_cells,
                                                                  int32_t* __restrict__ cell_start, double2* __restrict__ sorted_pts) {
-  const int64_t stride = (int64_t)gridDim.x * kPjThreads;
-  for (int64_t s = (int64_t)blockIdx.x * kPjThreads + threadIdx.x; s < n; s += stride) {
-    const unsigned long long key = keys_sorted[s];
-    sorted_pts[s] = reinterpret_cast<const double2*>(pts)[key & 0xffffffffull];
-    const int64_t k = (int64_t)(key >> 32);                          // < n_cells: the keys kernel clamped it
-    const int64_t kprev = s > 0 ? (int64_t)(keys_sorted[s - 1] >> 32) : -1;
-    for (int64_t c = kprev + 1; c <= k; ++c) cell_start[c] = (int32_t)s;
-    if (s == n - 1)
-      for (int64_t c = k + 1; c <= n_cells; ++c) cell_start[c] = (int32_t)n;
-  }
+  grid_cells_body<false>(keys_sorted, pts, nullptr, n, n_cells, cell_start, sorted_pts, nullptr);
 }
 
-// ---------------------------------------------------------------- the polygons ---
 __global__ __launch_bounds__(kPjThreads) void pjoin_bin_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
                                                                const double* __restrict__ buffer, int64_t P, int64_t V,
                                                                int64_t* __restrict__ pair_offsets, int32_t* __restrict__ words,
                                                                int32_t* __restrict__ list_short, int32_t* __restrict__ list_long) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t stride = (int64_t)gridDim.x * kPjThreads;
-  // whole waves iterate together: append_by_route needs every lane of a wave in the loop
-  for (int64_t base = (int64_t)blockIdx.x * kPjThreads + (threadIdx.x & ~(kWave - 1)); base < P; base += stride) {
-    const int64_t p = base + lane;
-    int route = -1;                                                  // -1: matches nothing
-    if (p < P) {
-      const RingClass c = classify_ring(off, xy, p, V);
-      int bad = c.bad;
-      if (buffer && !(buffer[p] >= 0.0 && buffer[p] < INFINITY)) bad |= SEGGER_PJOIN_ERR_BUFFER;
-      if (bad) atomicOr(&words[kWordFlag], bad);
-      pair_offsets[p + 1] = 0;                                       // the count; the polygon kernels overwrite theirs
-      if (p == 0) pair_offsets[0] = 0;
-      if (!bad && c.n >= 3) route = ring_route(c.n);
-    }
-    append_by_route(route, p, words, list_short, list_long);
-  }
+  bin_rings_body(off, xy, buffer, P, V, pair_offsets, nullptr, words, list_short, list_long);
 }
 
 struct JoinArgs {
@@ -117,16 +90,8 @@ __device__ __forceinline__ void polygon_body(const Ring& ring, int n, P2 org, do
   const int lane = threadIdx.x & (kWave - 1);
   const double d = a.buffer ? a.buffer[p] : 0.0;
   const double dd = d * d;
-  // Every matching point has dist2 <= d^2 or lies inside the ring, so in exact arithmetic it is within the bounds grown by
-  // d.  The margin covers the rounding of dist2, of the translation and of the subtraction below (a few ulp of the
-  // coordinates: 2^-40 of them is four thousand ulp); cell_of is monotone, so a point inside the grown bounds is in a
-  // walked cell whatever the grid, and the result does not depend on the grid.
-  const double m = d + d * 0x1p-20 + 0x1p-40 * fmax(fmax(fabs(xmin), fabs(xmax)), fmax(fabs(ymin), fabs(ymax)));
-  // (readfirstlane: the values are the same in every lane already; it tells the compiler so, and the loops become scalar)
-  const int cx0 = __builtin_amdgcn_readfirstlane(cell_of(xmin - m, a.g.x0, a.g.inv_cell, a.g.nx));
-  const int cx1 = __builtin_amdgcn_readfirstlane(cell_of(xmax + m, a.g.x0, a.g.inv_cell, a.g.nx));
-  const int cy0 = __builtin_amdgcn_readfirstlane(cell_of(ymin - m, a.g.y0, a.g.inv_cell, a.g.ny));
-  const int cy1 = __builtin_amdgcn_readfirstlane(cell_of(ymax + m, a.g.y0, a.g.inv_cell, a.g.ny));
+  const CellRange r = grown_cell_range(xmin, ymin, xmax, ymax, d, a.g);              // ring_predicate.h: margin and all
+  const int cx0 = r.cx0, cx1 = r.cx1, cy0 = r.cy0, cy1 = r.cy1;
   int64_t begin = 0, end = 0;
   if (kFill) {
     begin = a.pair_offsets[p];
@@ -143,29 +108,7 @@ __device__ __forceinline__ void polygon_body(const Ring& ring, int n, P2 org, do
       const bool valid = s < s1;
       const double2 t = a.pts[valid ? s : s0];
       const double px = t.x - org.x, py = t.y - org.y;
-      bool inside = false;
-      double best = INFINITY;
-      P2 va = ring.uni(0);
-      for (int j = 0; j < n; ++j) {
-        const P2 vb = ring.uni(j + 1 == n ? 0 : j + 1);
-        const double ex = vb.x - va.x, ey = vb.y - va.y;
-        const double wx = px - va.x, wy = py - va.y;
-        const double cr = ex * wy - ey * wx;
-        const double dot = wx * ex + wy * ey;
-        const double len2 = ex * ex + ey * ey;
-        const bool a_below = va.y <= py, b_below = vb.y <= py;       // the half-open rule
-        inside ^= (a_below && !b_below && cr > 0.0) || (!a_below && b_below && cr < 0.0);
-        double d2;
-        if (dot <= 0.0 || len2 == 0.0) d2 = wx * wx + wy * wy;
-        else if (dot >= len2) {
-          const double ux = px - vb.x, uy = py - vb.y;
-          d2 = ux * ux + uy * uy;
-        } else d2 = cr * cr / len2;
-        best = fmin(best, d2);
-        va = vb;
-      }
-      const bool hit = valid && (a.predicate == SEGGER_PJOIN_CONTAINS ? (best < dd || (inside && best > 0.0))
-                                                                      : (best <= dd || inside));
+      const bool hit = valid && ring_match(ring, n, px, py, dd, a.predicate);            // ring_predicate.h: the one predicate
       hit_slot<kFill>(hit, begin, end, found, [&](int64_t slot) { a.out[slot] = (int64_t)(a.keys[s] & 0xffffffffull); });
     }
   }
@@ -200,60 +143,16 @@ __global__ __launch_bounds__(kWave) void pjoin_long_kernel(JoinArgs a, const int
   }
 }
 
-struct PjLayout {
-  RingLists rings;
-  size_t keys, pts, cell_start, temp, total;
-  size_t temp_bytes;
-  int key_bits;
-};
+using PjLayout = GridLayout;                                         // join_grid.h: the layout and the checks
+using PjCall = GridCall;
 
-// with n_points, n_polygons and n_cells below 2^31 every term is below 2^36 bytes: nothing here can overflow
-PjLayout pj_layout(int64_t N, int64_t P, int64_t n_cells) {
-  PjLayout l;
-  l.key_bits = 32 + bit_length((unsigned long long)(n_cells > 1 ? n_cells - 1 : 1));
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  Carver c;
-  l.rings = take_ring_lists(c, P);
-  l.keys = c.take(n * 8);                                            // sorted keys: cell << 32 | point id
-  l.pts = c.take(n * 16);                                            // cell-ordered points; before that, the unsorted keys
-  l.cell_start = c.take((size_t)(n_cells + 1) * 4);
-  size_t t = 0;
-  unsigned long long* k64 = nullptr;
-  (void)rocprim::radix_sort_keys<NoScratchSortConfig>(nullptr, t, k64, k64, n, 0, (unsigned)l.key_bits, (hipStream_t)0);
-  l.temp_bytes = t;
-  l.temp = c.take(t > 0 ? t : 1);
-  l.total = c.total();
-  return l;
-}
-
-int pj_check_sizes(const char* who, int64_t N, int64_t P, int32_t nx, int32_t ny) {
-  SEGGER_REQUIRE(N >= 0 && P >= 0, "%s: negative n_points or n_polygons", who);
-  SEGGER_REQUIRE(N < 0x7fffffffLL && P < 0x7fffffffLL, "%s: 2^31 - 1 points or polygons, or more", who);
-  SEGGER_REQUIRE(nx >= 1 && ny >= 1 && (int64_t)nx * ny < 0x7fffffffLL, "%s: bad grid: nx, ny >= 1 and nx * ny < 2^31 - 1", who);
-  return SEGGER_OK;
-}
-
-struct PjCall {
-  const double* points; int64_t N; const int64_t* ring_offsets; const double* xy; int64_t P, V; const double* buffer;
-  int32_t predicate; double x0, y0, cell; int32_t nx, ny; const int64_t* pair_offsets; void* workspace; int64_t workspace_bytes;
-};
+PjLayout pj_layout(int64_t N, int64_t P, int64_t n_cells) { return grid_layout(N, P, n_cells, false); }
 
 // everything both entry points reject; *empty = nothing to do (no pointer was looked at)
 int pj_check(const char* who, const PjCall& c, bool* empty) {
   *empty = false;
-  const int rc = pj_check_sizes(who, c.N, c.P, c.nx, c.ny);
-  if (rc != SEGGER_OK) return rc;
-  SEGGER_REQUIRE(c.V >= 0, "%s: negative n_vertices", who);
-  SEGGER_REQUIRE(c.workspace_bytes >= 0, "%s: negative workspace_bytes", who);
-  SEGGER_REQUIRE(c.predicate == SEGGER_PJOIN_CONTAINS || c.predicate == SEGGER_PJOIN_INTERSECTS,
-                 "%s: predicate %d is neither SEGGER_PJOIN_CONTAINS nor SEGGER_PJOIN_INTERSECTS", who, (int)c.predicate);
-  SEGGER_REQUIRE(c.cell > 0.0 && c.cell < INFINITY && c.x0 - c.x0 == 0.0 && c.y0 - c.y0 == 0.0,
-                 "%s: bad grid: the origin must be finite and the cell side positive and finite", who);
-  if (c.N == 0 || c.P == 0) { *empty = true; return SEGGER_OK; }
-  const size_t need = pj_layout(c.N, c.P, (int64_t)c.nx * c.ny).total;
-  return check_ring_call(who, c.ring_offsets, c.xy, c.V, c.workspace, c.workspace_bytes, need,
-                         OtherPointers{c.points && c.pair_offsets, is_aligned(c.pair_offsets, 8) && is_aligned(c.buffer, 8),
-                                       is_aligned(c.points, 16), "ring_offsets, pair_offsets and buffer", "points and xy"});
+  const int rc = grid_check_sizes(who, c.N, c.P, c.nx, c.ny);
+  return rc != SEGGER_OK ? rc : grid_check(who, c, empty);
 }
 
 JoinArgs join_args(const PjCall& c, const PjLayout& l, int64_t* pair_offsets, int64_t* out, int64_t capacity) {
@@ -291,7 +190,7 @@ int launch_polygons(const PjCall& c, const PjLayout& l, const JoinArgs& a, hipSt
 using namespace segger;
 
 extern "C" int64_t segger_polygon_join_workspace_bytes(int64_t n_points, int64_t n_polygons, int32_t nx, int32_t ny) {
-  const int rc = pj_check_sizes("segger_polygon_join_workspace_bytes", n_points, n_polygons, nx, ny);
+  const int rc = grid_check_sizes("segger_polygon_join_workspace_bytes", n_points, n_polygons, nx, ny);
   if (rc != SEGGER_OK) return rc;
   return (int64_t)pj_layout(n_points, n_polygons, (int64_t)nx * ny).total;
 }
@@ -303,7 +202,7 @@ extern "C" int segger_polygon_join_count(const double* points, int64_t n_points,
   const char* who = "segger_polygon_join_count";
   hipStream_t stream = (hipStream_t)stream_;
   const PjCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
-                 pair_offsets, workspace, workspace_bytes};
+                 pair_offsets, workspace, workspace_bytes, false, nullptr, "ring_offsets, pair_offsets and buffer"};
   bool empty = false;
   const int rc = pj_check(who, c, &empty);
   if (rc != SEGGER_OK || empty) return rc;
@@ -344,7 +243,7 @@ extern "C" int segger_polygon_join_fill(const double* points, int64_t n_points, 
   const char* who = "segger_polygon_join_fill";
   hipStream_t stream = (hipStream_t)stream_;
   const PjCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
-                 pair_offsets, workspace, workspace_bytes};
+                 pair_offsets, workspace, workspace_bytes, false, nullptr, "ring_offsets, pair_offsets and buffer"};
   bool empty = false;
   const int rc = pj_check(who, c, &empty);
   if (rc != SEGGER_OK) return rc;

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "post_common.h"
 #include "rings.h"
+#include "wave_sort.h"
 
 #pragma clang fp contract(off)
 
@@ -148,17 +149,7 @@ __global__ __launch_bounds__(kWave) void rr_sort_kernel(RrSort a, const int32_t*
     }
     for (int k = lane; k < padded; k += kWave) idx[k] = (uint16_t)k;
     __syncthreads();
-    for (int k = 2; k <= padded; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = lane; t < (padded >> 1); t += kWave) {
-          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;          // every pair of the stage once
-          const int x = idx[i], y = idx[l];
-          const bool swap = (i & k) == 0 ? before(d, n, y, x) : before(d, n, x, y);
-          if (swap) { idx[i] = (uint16_t)y; idx[l] = (uint16_t)x; }
-        }
-        __syncthreads();
-      }
-    }
+    wave_bitonic_sort(idx, padded, [&](int x, int y) { return before(d, n, x, y); }, BlockSync{});      // wave_sort.h
     // A closing duplicate stays in the ring, next to its twin: it has vertex 0's d and the index n, so it follows vertex 0
     // and every vertex with the same d (they sort by index, all below n).
     int dup_at = n;

@@ -1,0 +1,65 @@
+// The predicate of the points-in-buffered-polygons units, once (polygon_join.hip, buffered_counts.hip; included after
+// rings.h): what one point is to one ring grown by d, and which grid cells a wave has to walk to meet every point that can
+// match.  include/segger_amd.h (segger_polygon_join_*) has the definition; both units run THIS code, so a pair is in the
+// join's list exactly when it is in the count matrix, bit for bit, and a fix is made here and nowhere else.
+//
+// Floating point: `#pragma clang fp contract(off)`, as rings.h sets it, to the end of the including unit: the cross product
+// of coordinates that are exact after the translation must stay exact.
+#pragma once
+#include <math.h>
+
+#include "rings.h"
+
+#pragma clang fp contract(off)
+
+namespace segger {
+
+// Is the point (px, py) -- translated to the ring's first vertex, as the ring's n >= 3 vertices are -- in the ring grown by
+// d, dd = d * d?  Every lane evaluates its own point over the same edges (ring.uni): crossing parity with the half-open
+// rule and the smallest squared distance to a closed edge.  Per edge (a, b) and point t:  e = b - a, w = t - a,
+// cr = e.x w.y - e.y w.x, dot = w.e, len2 = e.e;  dist2 = |w|^2 if dot <= 0 or len2 == 0, |t - b|^2 if dot >= len2,
+// cr cr / len2 otherwise.
+template <class Ring>
+__device__ __forceinline__ bool ring_match(const Ring& ring, int n, double px, double py, double dd, int predicate) {
+  bool inside = false;
+  double best = INFINITY;
+  P2 va = ring.uni(0);
+  for (int j = 0; j < n; ++j) {
+    const P2 vb = ring.uni(j + 1 == n ? 0 : j + 1);
+    const double ex = vb.x - va.x, ey = vb.y - va.y;
+    const double wx = px - va.x, wy = py - va.y;
+    const double cr = ex * wy - ey * wx;
+    const double dot = wx * ex + wy * ey;
+    const double len2 = ex * ex + ey * ey;
+    const bool a_below = va.y <= py, b_below = vb.y <= py;           // the half-open rule
+    inside ^= (a_below && !b_below && cr > 0.0) || (!a_below && b_below && cr < 0.0);
+    double d2;
+    if (dot <= 0.0 || len2 == 0.0) d2 = wx * wx + wy * wy;
+    else if (dot >= len2) {
+      const double ux = px - vb.x, uy = py - vb.y;
+      d2 = ux * ux + uy * uy;
+    } else d2 = cr * cr / len2;
+    best = fmin(best, d2);
+    va = vb;
+  }
+  return predicate == SEGGER_PJOIN_CONTAINS ? (best < dd || (inside && best > 0.0)) : (best <= dd || inside);
+}
+
+// The cells cx0 .. cx1 x cy0 .. cy1 that overlap a ring's bounds (on the coordinates as given, the same in every lane)
+// grown by d.  Every matching point has dist2 <= d^2 or lies inside the ring, so in exact arithmetic it is within the
+// bounds grown by d.  The margin covers the rounding of dist2, of the translation and of the subtraction below (a few ulp
+// of the coordinates: 2^-40 of them is four thousand ulp); cell_of is monotone, so a point inside the grown bounds is in a
+// walked cell whatever the grid, and the result does not depend on the grid.
+// (readfirstlane: the values are the same in every lane already; it tells the compiler so, and the loops become scalar)
+struct CellRange { int cx0, cx1, cy0, cy1; };
+__device__ __forceinline__ CellRange grown_cell_range(double xmin, double ymin, double xmax, double ymax, double d, const UniformGrid& g) {
+  const double m = d + d * 0x1p-20 + 0x1p-40 * fmax(fmax(fabs(xmin), fabs(xmax)), fmax(fabs(ymin), fabs(ymax)));
+  CellRange r;
+  r.cx0 = __builtin_amdgcn_readfirstlane(cell_of(xmin - m, g.x0, g.inv_cell, g.nx));
+  r.cx1 = __builtin_amdgcn_readfirstlane(cell_of(xmax + m, g.x0, g.inv_cell, g.nx));
+  r.cy0 = __builtin_amdgcn_readfirstlane(cell_of(ymin - m, g.y0, g.inv_cell, g.ny));
+  r.cy1 = __builtin_amdgcn_readfirstlane(cell_of(ymax + m, g.y0, g.inv_cell, g.ny));
+  return r;
+}
+
+}  // namespace segger

@@ -31,7 +31,7 @@ tests/polygon_join_cases.py holds a float64 and an exact rational oracle of the 
 from __future__ import annotations
 
 import math
-from typing import Optional, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -48,26 +48,25 @@ def _empty(device) -> Tensor:
     return torch.empty(2, 0, dtype=torch.int64, device=device)
 
 
-def points_in_polygons(points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer: Union[None, float, Tensor] = None,
-                       predicate: str = "contains", points_per_cell: float = 2.0) -> Tensor:
-    """Every (point, polygon) pair with the point in the polygon grown by its ``buffer``.
+class JoinInputs(NamedTuple):
+    """What the two units that walk points against grown rings (this one and :mod:`segger_amd.buffered_counts`) hand to
+    their entry points: the tensors as the device code reads them, the sizes and the grid."""
+    pts: Tensor
+    ring_offsets: Tensor
+    xy: Tensor
+    buf: Optional[Tensor]
+    n_points: int
+    n_polygons: int
+    n_vertices: int
+    predicate: int
+    grid: Tuple[float, float, float, int, int]                       # x0, y0, cell, nx, ny
 
-    ``points`` is ``[N, 2]`` of any float dtype (converted to float64, exact for float32 positions); ``ring_offsets``
-    ``[P + 1]`` and ``xy`` ``[V, 2]`` are the CSR of rings :func:`segger_amd.morphology.polygon_props` takes; ``buffer`` is
-    ``None`` (0), a float, or a ``[P]`` tensor of distances ``>= 0``; ``predicate`` is ``"contains"`` or ``"intersects"``
-    (the module docstring defines both).
 
-    Returns an int64 ``[2, E]`` device tensor, row 0 the point id and row 1 the polygon id -- the reference's
-    ``index_query`` and ``index_match`` -- sorted by (point, polygon), without duplicates, bit-identical from call to
-    call and for any ``points_per_cell`` (the grid that bins the points decides the speed and nothing else; it follows
-    :func:`segger_amd.neighbors.knn_grid`'s sizing rule over the union of the points' and the grown rings' extents).
-
-    Raises ``ValueError`` for bad shapes or dtypes, an unknown predicate, a ring above ``SEGGER_MORPH_MAX_VERTS`` (naming
-    the polygon), negative or non-finite ``buffer``, non-finite coordinates, and offsets the device found descending or out
-    of range.  No polygons or no points gives ``[2, 0]`` and launches nothing.  Waits for the device four times: the
-    longest ring (in the shared ring validation), the extent of the points and the rings together with the finiteness
-    checks, the pair total, and the error word."""
-    who = "points_in_polygons"
+def join_inputs(who: str, points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer: Union[None, float, Tensor], predicate: str,
+                points_per_cell: float, others: Tuple[Optional[Tensor], ...] = (), hint: str = "") -> Optional[JoinInputs]:
+    """The argument checks, the ``buffer`` forms, the extent and finiteness synchronisation and the grid rule of
+    :func:`points_in_polygons`, in the name of the caller ``who``; ``others`` are further tensors that must be on the
+    device.  ``None``: no points, no polygons or no vertices -- nothing matches and nothing is launched."""
     if predicate not in _PREDICATES:
         raise ValueError(f"{who}: predicate {predicate!r} is neither 'contains' nor 'intersects'")
     if not isinstance(points, Tensor) or points.dim() != 2 or points.shape[1] != 2 or not points.is_floating_point():
@@ -93,15 +92,14 @@ def points_in_polygons(points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer:
         buf = None if d == 0.0 else torch.full((n_polygons,), d, dtype=torch.float64, device=xy.device)
     if isinstance(buffer, Tensor) and not buf.is_cuda and n_polygons and not bool(((buf >= 0) & buf.isfinite()).all()):
         raise ValueError(f"{who}: buffer must be finite and >= 0")   # host tensors: refused before the device is asked for
-    L.need_device(who, points, ring_offsets, xy, buf, hint="tests/polygon_join_cases.py holds the CPU oracle")
-    dev = xy.device
+    L.need_device(who, points, ring_offsets, xy, buf, *others, hint=hint)
     if n_points == 0 or n_polygons == 0:
-        return _empty(dev)
+        return None
     if n_vertices == 0:
         if bool((ring_offsets != 0).any()):
             raise ValueError(f"{who}: ring_offsets of polygon {int((ring_offsets[1:] != 0).nonzero()[0])} are negative, "
                              f"descending or beyond the 0 vertices")
-        return _empty(dev)
+        return None
     pts = points.detach().to(torch.float64).contiguous()
 
     # one synchronisation: the extent of the points, of the rings and of the buffer; a NaN anywhere is a NaN in its
@@ -121,11 +119,41 @@ def points_in_polygons(points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer:
     cell = math.sqrt(w * h * points_per_cell / n_points)                               # knn_grid's rule
     cell = max(cell, math.sqrt(w * h / (4.0 * n_points)), max(w, h) / 30000.0)         # <= 4n cells, < 2^31 cells
     nx, ny = int(w / cell) + 1, int(h / cell) + 1
+    return JoinInputs(pts, ring_offsets, xy, buf, n_points, n_polygons, n_vertices, _PREDICATES[predicate], (x0, y0, cell, nx, ny))
+
+
+def points_in_polygons(points: Tensor, ring_offsets: Tensor, xy: Tensor, buffer: Union[None, float, Tensor] = None,
+                       predicate: str = "contains", points_per_cell: float = 2.0) -> Tensor:
+    """Every (point, polygon) pair with the point in the polygon grown by its ``buffer``.
+
+    ``points`` is ``[N, 2]`` of any float dtype (converted to float64, exact for float32 positions); ``ring_offsets``
+    ``[P + 1]`` and ``xy`` ``[V, 2]`` are the CSR of rings :func:`segger_amd.morphology.polygon_props` takes; ``buffer`` is
+    ``None`` (0), a float, or a ``[P]`` tensor of distances ``>= 0``; ``predicate`` is ``"contains"`` or ``"intersects"``
+    (the module docstring defines both).
+
+    Returns an int64 ``[2, E]`` device tensor, row 0 the point id and row 1 the polygon id -- the reference's
+    ``index_query`` and ``index_match`` -- sorted by (point, polygon), without duplicates, bit-identical from call to
+    call and for any ``points_per_cell`` (the grid that bins the points decides the speed and nothing else; it follows
+    :func:`segger_amd.neighbors.knn_grid`'s sizing rule over the union of the points' and the grown rings' extents).
+
+    Raises ``ValueError`` for bad shapes or dtypes, an unknown predicate, a ring above ``SEGGER_MORPH_MAX_VERTS`` (naming
+    the polygon), negative or non-finite ``buffer``, non-finite coordinates, and offsets the device found descending or out
+    of range.  No polygons or no points gives ``[2, 0]`` and launches nothing.  Waits for the device four times: the
+    longest ring (in the shared ring validation), the extent of the points and the rings together with the finiteness
+    checks, the pair total, and the error word."""
+    who = "points_in_polygons"
+    j = join_inputs(who, points, ring_offsets, xy, buffer, predicate, points_per_cell,
+                    hint="tests/polygon_join_cases.py holds the CPU oracle")
+    if j is None:
+        return _empty(xy.device)
+    pts, ring_offsets, xy, buf, n_points, n_polygons, n_vertices = j[:7]
+    dev = xy.device
+    x0, y0, cell, nx, ny = j.grid
 
     ws, ws_bytes = L.workspace("segger_polygon_join_workspace_bytes", dev, n_points, n_polygons, nx, ny)
     pair_offsets = torch.empty(n_polygons + 1, dtype=torch.int64, device=dev)
     args = (pts.data_ptr(), n_points, ring_offsets.data_ptr(), xy.data_ptr(), n_polygons, n_vertices, L.ptr(buf),
-            _PREDICATES[predicate], x0, y0, cell, nx, ny, pair_offsets.data_ptr())
+            j.predicate, x0, y0, cell, nx, ny, pair_offsets.data_ptr())
     L.call("segger_polygon_join_count", dev, *args, ws.data_ptr(), ws_bytes)
     total = int(pair_offsets[-1])                                                       # the second synchronisation
     point_id = torch.empty(total, dtype=torch.int64, device=dev)
