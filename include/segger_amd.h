@@ -2118,6 +2118,83 @@ int segger_buffered_counts_fill(const double* points, int64_t n_points, const in
                                 int32_t ny, const int64_t* indptr, const int64_t* cell_count, int32_t* indices, int32_t* counts,
                                 int64_t capacity, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
 
+/* ----------------------------------------------------------------------
+ * Nearest boundaries (csrc/nearest_boundaries.hip; segger_amd.nearest): for every point the k best of the
+ * polygons that segger_polygon_join_* pairs it with, each with its squared distance to the ring and the crossing parity --
+ * the two numbers the join's predicate computes and folds into one bit.  A prediction graph with a bounded degree (the
+ * reference documents prediction_graph_max_k and ignores it in its shape mode), the signed distance of a transcript to an
+ * outline, and erosion as a mask (inside and dist2 >= d d) are read from them.  Purely additive: four new symbols,
+ * SEGGER_ABI_VERSION stays 32.
+ *
+ * Candidates.  The rings, the predicate, the arithmetic, the uniform grid, the walk and its margin are
+ *   segger_polygon_join_*'s above: all units compile csrc/ring_predicate.h and csrc/join_grid.h, so the candidates of a point
+ *   are the polygons the join lists for it under the same buffer and predicate, bit for bit.
+ * Key of a candidate.  parity and dist2 as the join defines them (fp64, coordinates translated to the ring's first vertex,
+ *   contraction off);  s = dist2 == 0 ? +0 : (parity ? -dist2 : dist2).  Candidates are ordered by (s, polygon id) ascending:
+ *   deeper inside first, then nearer outside; equal s (duplicate polygons, a point on two rings) goes to the lower id.  The
+ *   order is strict and total on a point's candidates: a polygon pairs with a point once.
+ *
+ * Three calls (the number of candidates is known on the device only):
+ *   segger_nearest_boundaries_count   bins the points and the polygons as the join does; every match adds one to the
+ *       count of its point (an integer atomic); a one-workgroup scan turns the counts into
+ *         pair_offsets [n_points + 1] int64   (zeroed by the call), pair_offsets[n_points] = the join's pair total.
+ *   segger_nearest_boundaries_fill    the same traversal again, same inputs, the workspace as the count call left it:
+ *       a match takes slot pair_offsets[point] + (an integer atomic add on the point's cursor) and writes
+ *         pair_key     [capacity] fp64    s;
+ *         pair_polygon [capacity] int32   the polygon id, bit 31 set when parity is true (ids are below 2^31 - 1).
+ *       Nothing is written at or beyond capacity, nor outside the point's own segment.  The order of a segment's slots
+ *       depends on scheduling; nothing that follows depends on it.
+ *   segger_nearest_boundaries_select  needs no grid and no workspace.  For point i with c = its candidates, entry j < k:
+ *       the smallest (s, id) above entry j - 1 -- k passes over the segment, nothing kept but the last pick: no list in
+ *       registers or LDS, no sort.  One lane per point; a point with more than SEGGER_NEAREST_LANE_MAX candidates is
+ *       done by its whole wave (lanes stride over the segment, a shuffle reduction takes the minimum).  Writes
+ *         polygon_out [n_points, k] int32   the id, n_polygons for j >= c;
+ *         dist2_out   [n_points, k] fp64    |s|, +inf for j >= c;
+ *         inside_out  [n_points, k] uint8   the parity, 0 for j >= c;
+ *         count_out   [n_points]    int32   c, BEFORE the cap k;
+ *         counters    [SEGGER_NEAREST_COUNTERS] int64 (zeroed by the call):  0 n_pairs = pair_offsets[n_points];  1 n_kept, the
+ *                     sum of min(c, k);  2 n_truncated_points, the points with c > k;  3 max_count.
+ *   Integer atomics only, no floating-point accumulation, no scratch; LDS: the 64 KB ring stage of the long-ring route and
+ *   nothing else.  Every output is a function of the inputs alone: the same bytes for any grid and any launch geometry.
+ *
+ * Errors found on the device (the int32 at byte 0 of the workspace, as the join's; the bits are the join's):
+ *     SEGGER_NEAREST_ERR_OFFSETS, _CAP, _BUFFER  as SEGGER_PJOIN_ERR_*; such a polygon is nobody's candidate;
+ *     SEGGER_NEAREST_ERR_FILL    the fill found more matches of a point than pair_offsets holds, or than capacity.
+ *
+ * Workspace: segger_nearest_boundaries_workspace_bytes(n_points, n_polygons, nx, ny) =
+ *   segger_polygon_join_workspace_bytes(n_points, n_polygons, nx, ny) + up(4 N), N = max(n_points, 1), up() rounding up to
+ *   256: the join's layout and an int32 cursor per point.  256-byte aligned.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: everything segger_polygon_join_* rejects, in its
+ *   words (count, fill);  k outside 1 .. SEGGER_NEAREST_MAX_K (select);  a negative capacity;  NULL or misaligned pair_key,
+ *   dist2_out, counters (8 bytes), pair_polygon, polygon_out, count_out (4 bytes), inside_out.  n_points = 0 or
+ *   n_polygons = 0 returns SEGGER_OK from count and fill without touching a pointer or the device; select with n_points = 0
+ *   likewise, and with n_polygons = 0 or capacity = 0 (pair_key and pair_polygon may then be NULL) it writes the padding.
+ * NOT BUILT: k above SEGGER_NEAREST_MAX_K; holes and multi-part polygons; the eroded geometry as rings (GEOS's buffer(-d));
+ *   a scan over more than one workgroup (pair_offsets is scanned by the 1024 threads of counts_to_offsets_kernel).
+ * ---------------------------------------------------------------------- */
+#define SEGGER_NEAREST_MAX_K 16
+#define SEGGER_NEAREST_LANE_MAX 32
+#define SEGGER_NEAREST_COUNTERS 4
+#define SEGGER_NEAREST_ERR_OFFSETS 1
+#define SEGGER_NEAREST_ERR_CAP 2
+#define SEGGER_NEAREST_ERR_BUFFER 4
+#define SEGGER_NEAREST_ERR_FILL 8
+int64_t segger_nearest_boundaries_workspace_bytes(int64_t n_points, int64_t n_polygons, int32_t nx, int32_t ny);
+int segger_nearest_boundaries_count(const double* points /* [N, 2] */, int64_t n_points, const int64_t* ring_offsets,
+                                    const double* xy, int64_t n_polygons, int64_t n_vertices,
+                                    const double* buffer /* [P] fp64 or NULL = 0 */, int32_t predicate, double x0, double y0,
+                                    double cell, int32_t nx, int32_t ny, int64_t* pair_offsets /* [N + 1] */, void* workspace,
+                                    int64_t workspace_bytes, segger_stream_t stream);
+int segger_nearest_boundaries_fill(const double* points, int64_t n_points, const int64_t* ring_offsets, const double* xy,
+                                   int64_t n_polygons, int64_t n_vertices, const double* buffer, int32_t predicate, double x0,
+                                   double y0, double cell, int32_t nx, int32_t ny, const int64_t* pair_offsets,
+                                   double* pair_key, int32_t* pair_polygon, int64_t capacity, void* workspace,
+                                   int64_t workspace_bytes, segger_stream_t stream);
+int segger_nearest_boundaries_select(const int64_t* pair_offsets, const double* pair_key, const int32_t* pair_polygon,
+                                     int64_t capacity, int64_t n_points, int64_t n_polygons, int32_t k, int32_t* polygon_out,
+                                     double* dist2_out, uint8_t* inside_out, int32_t* count_out, int64_t* counters,
+                                     segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

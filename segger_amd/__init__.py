@@ -18,7 +18,9 @@ from . import morphology  # noqa: F401
 from .morphology import polygon_props, morphology_features, rings_from_padded  # noqa: F401
 from . import geometry  # noqa: F401
 from .geometry import points_in_polygons  # noqa: F401
-from .neighbors import prediction_graph_shape  # noqa: F401
+from .neighbors import prediction_graph_shape, prediction_graph_nearest  # noqa: F401
+from . import nearest  # noqa: F401
+from .nearest import nearest_boundaries, signed_distance  # noqa: F401
 from . import boundaries  # noqa: F401
 from .boundaries import cell_boundaries, segmentation_boundaries  # noqa: F401
 from .boundaries import cell_outlines, segmentation_outlines  # noqa: F401

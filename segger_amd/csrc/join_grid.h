@@ -1,6 +1,6 @@
-// The front half of the two units that walk points against grown rings (polygon_join.hip, buffered_counts.hip; included
-// after rings.h and sort_config.h): the points binned into the uniform grid (keys, cell starts, cell-ordered points and --
-// for the counts -- their genes), the polygons binned by route, the layout of the workspace and the host checks of an
+// The front half of the units that walk points against grown rings (polygon_join.hip, buffered_counts.hip,
+// nearest_boundaries.hip; included after rings.h and sort_config.h): the points binned into the uniform grid (keys, cell
+// starts, cell-ordered points and -- for the counts -- their genes), the polygons binned by route, the layout of the workspace and the host checks of an
 // entry point.  "The join's grid" is one definition: the key format, the cell-start writing and the layout are fixed here
 // and nowhere else.  Each unit keeps thin __global__ wrappers of its own around the bodies below (its kernels keep their
 // names in its assembly), as with post_common.h's scan.
@@ -50,7 +50,8 @@ __device__ __forceinline__ void grid_cells_body(const unsigned long long* __rest
 
 // ---------------------------------------------------------------- the polygons ---
 // one thread per polygon: checks its ring (rings.h) and its distance, zeroes its entry of `sizes` (the counts a scan turns
-// into offsets: [p + 1], and [0]) and of `zeroed` (may be NULL), appends a ring of 3 or more vertices to the list of its route
+// into offsets: [p + 1], and [0]; NULL in a unit whose sizes are per point) and of `zeroed` (may be NULL), appends a ring of 3 or
+// more vertices to the list of its route
 __device__ __forceinline__ void bin_rings_body(const int64_t* __restrict__ off, const double* __restrict__ xy,
                                                const double* __restrict__ buffer, int64_t P, int64_t V, int64_t* __restrict__ sizes,
                                                int64_t* __restrict__ zeroed, int32_t* __restrict__ words,
@@ -66,9 +67,11 @@ __device__ __forceinline__ void bin_rings_body(const int64_t* __restrict__ off, 
       int bad = c.bad;
       if (buffer && !(buffer[p] >= 0.0 && buffer[p] < INFINITY)) bad |= SEGGER_PJOIN_ERR_BUFFER;
       if (bad) atomicOr(&words[kWordFlag], bad);
-      sizes[p + 1] = 0;                                              // the count; the polygon kernels overwrite theirs
+      if (sizes) {
+        sizes[p + 1] = 0;                                            // the count; the polygon kernels overwrite theirs
+        if (p == 0) sizes[0] = 0;
+      }
       if (zeroed) zeroed[p] = 0;
-      if (p == 0) sizes[0] = 0;
       if (!bad && c.n >= 3) route = ring_route(c.n);
     }
     append_by_route(route, p, words, list_short, list_long);

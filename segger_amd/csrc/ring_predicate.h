@@ -1,7 +1,8 @@
-// The predicate of the points-in-buffered-polygons units, once (polygon_join.hip, buffered_counts.hip; included after
-// rings.h): what one point is to one ring grown by d, and which grid cells a wave has to walk to meet every point that can
-// match.  include/segger_amd.h (segger_polygon_join_*) has the definition; both units run THIS code, so a pair is in the
-// join's list exactly when it is in the count matrix, bit for bit, and a fix is made here and nowhere else.
+// The predicate of the points-in-buffered-polygons units, once (polygon_join.hip, buffered_counts.hip,
+// nearest_boundaries.hip; included after rings.h): what one point is to one ring grown by d, and which grid cells a wave has to walk to meet every point that can
+// match.  include/segger_amd.h (segger_polygon_join_*) has the definition; all units run THIS code, so a pair is in the
+// join's list exactly when it is in the count matrix and among the candidates of the nearest boundaries, bit for bit, and a
+// fix is made here and nowhere else.
 //
 // Floating point: `#pragma clang fp contract(off)`, as rings.h sets it, to the end of the including unit: the cross product
 // of coordinates that are exact after the translation must stay exact.
@@ -14,13 +15,17 @@
 
 namespace segger {
 
-// Is the point (px, py) -- translated to the ring's first vertex, as the ring's n >= 3 vertices are -- in the ring grown by
-// d, dd = d * d?  Every lane evaluates its own point over the same edges (ring.uni): crossing parity with the half-open
+// What is the point (px, py) -- translated to the ring's first vertex, as the ring's n >= 3 vertices are -- to the ring, and
+// is it in the ring grown by d, dd = d * d?  Every lane evaluates its own point over the same edges (ring.uni): crossing parity with the half-open
 // rule and the smallest squared distance to a closed edge.  Per edge (a, b) and point t:  e = b - a, w = t - a,
 // cr = e.x w.y - e.y w.x, dot = w.e, len2 = e.e;  dist2 = |w|^2 if dot <= 0 or len2 == 0, |t - b|^2 if dot >= len2,
 // cr cr / len2 otherwise.
+// ring_distance returns the two numbers, ring_decide folds them into the predicate's answer, ring_match is both; the join
+// and the counts keep the answer, nearest_boundaries.hip the numbers as well.
+struct RingDistance { bool inside; double best; };                   // crossing parity, smallest squared distance
+
 template <class Ring>
-__device__ __forceinline__ bool ring_match(const Ring& ring, int n, double px, double py, double dd, int predicate) {
+__device__ __forceinline__ RingDistance ring_distance(const Ring& ring, int n, double px, double py) {
   bool inside = false;
   double best = INFINITY;
   P2 va = ring.uni(0);
@@ -42,7 +47,17 @@ __device__ __forceinline__ bool ring_match(const Ring& ring, int n, double px, d
     best = fmin(best, d2);
     va = vb;
   }
-  return predicate == SEGGER_PJOIN_CONTAINS ? (best < dd || (inside && best > 0.0)) : (best <= dd || inside);
+  return RingDistance{inside, best};
+}
+
+// the predicate on the two numbers: dd = d * d
+__device__ __forceinline__ bool ring_decide(const RingDistance& r, double dd, int predicate) {
+  return predicate == SEGGER_PJOIN_CONTAINS ? (r.best < dd || (r.inside && r.best > 0.0)) : (r.best <= dd || r.inside);
+}
+
+template <class Ring>
+__device__ __forceinline__ bool ring_match(const Ring& ring, int n, double px, double py, double dd, int predicate) {
+  return ring_decide(ring_distance(ring, n, px, py), dd, predicate);
 }
 
 // The cells cx0 .. cx1 x cy0 .. cy1 that overlap a ring's bounds (on the coordinates as given, the same in every lane)

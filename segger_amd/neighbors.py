@@ -8,7 +8,8 @@ Restates reference ``src/segger/data/utils/neighbors.py``:
   row 0 is the QUERY point (source) and row 1 the neighbour (target);
 * ``setup_transcripts_graph`` (``:166-180``) -> :func:`transcripts_graph`;
 * ``setup_prediction_graph`` (``:200-241``): ``mode="uniform"`` -> :func:`prediction_graph_uniform`, the shape-based
-  modes ``"cell"`` (the default) and ``"nucleus"`` -> :func:`prediction_graph_shape`.
+  modes ``"cell"`` (the default) and ``"nucleus"`` -> :func:`prediction_graph_shape`; with the ``max_k`` the reference
+  documents and its shape mode ignores -> ``prediction_graph_shape(..., max_k=...)`` and :func:`prediction_graph_nearest`.
 """
 from __future__ import annotations
 
@@ -95,7 +96,36 @@ def prediction_graph_uniform(tx_pos: Tensor, bd_pos: Tensor, max_k: int, max_dis
     return ei
 
 
-def prediction_graph_shape(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, buffer_ratio: float = 0.05) -> Tensor:
+def _nearest_edges(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, max_k: int, buffer, predicate: str) -> Tensor:
+    """the kept candidates of :func:`segger_amd.nearest.nearest_boundaries` as a ``[2, E]`` int64 edge index sorted by
+    (transcript, polygon)"""
+    from .nearest import nearest_boundaries
+    polygon = nearest_boundaries(tx_pos, ring_offsets, xy, max_k, buffer=buffer, predicate=predicate)["polygon"]
+    n_polygons = int(ring_offsets.numel()) - 1
+    polygon = polygon.long().sort(dim=1).values                      # the padding, n_polygons, sorts last
+    keep = polygon != n_polygons
+    row = torch.arange(polygon.shape[0], device=polygon.device).unsqueeze(1).expand_as(polygon)
+    return torch.stack([row[keep], polygon[keep]])
+
+
+def prediction_graph_nearest(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, max_k: int = 3, max_dist: float = 1.0,
+                             predicate: str = "intersects") -> Tensor:
+    """The prediction graph with a bounded degree: every transcript -> its ``max_k`` best boundaries among the polygons
+    grown by ``max_dist`` that hold it -- the reference's documented ``prediction_graph_max_k = 3`` and
+    ``prediction_graph_max_dist = 1.0`` (``data/data_module.py:110-115``), upstream segger's ``k_bd`` / ``dist_bd``, on polygon
+    boundaries instead of centroids (:func:`prediction_graph_uniform` is wrong for elongated cells).  "Best" is
+    :func:`segger_amd.nearest.nearest_boundaries`' order: the polygons the transcript is inside, deepest first, then the
+    nearest ones outside, ties to the lower id.
+
+    Returns the ``TX_NB_BD`` edge index ``[2, E]`` int64, row 0 the transcript and row 1 the polygon, sorted by
+    (transcript, polygon) as :func:`prediction_graph_shape`'s; at most ``max_k`` edges a transcript.  ``max_k`` is
+    ``1 .. SEGGER_NEAREST_MAX_K``; ``max_dist`` is a uniform buffer ``>= 0`` (negative: ``ValueError``; erosion is a mask
+    over ``nearest_boundaries``' ``inside`` and ``dist2``, see :mod:`segger_amd.nearest`)."""
+    return _nearest_edges(tx_pos, ring_offsets, xy, max_k, float(max_dist), predicate)
+
+
+def prediction_graph_shape(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, buffer_ratio: float = 0.05,
+                           max_k: Optional[int] = None) -> Tensor:
     """``setup_prediction_graph(mode='cell' | 'nucleus')`` (``neighbors.py:223-238``), the reference's default
     (``ISTDataModule.prediction_graph_mode = "cell"``, ``prediction_graph_buffer_ratio = 0.05``): every boundary polygon
     is grown by ``d = sqrt(area / pi) * buffer_ratio`` and every transcript is joined to every grown polygon that contains
@@ -108,8 +138,13 @@ def prediction_graph_shape(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, buf
     transcript (``index_query``), row 1 the polygon (``index_match``), sorted by (transcript, polygon).
 
     The reference selects the rows of one ``boundary_type`` (cell or nucleus) before the call -- pass only those rings --
-    and ignores ``max_k`` in this mode, so there is no such argument.  ``buffer_ratio < 0`` is a ``ValueError``: GEOS's
-    erosion (a negative buffer) is not built."""
+    and ignores ``max_k`` in this mode: ``max_k=None``, the default, does the same and every transcript gets as many edges
+    as there are grown polygons over it.  An int (``1 .. SEGGER_NEAREST_MAX_K``) caps each transcript at its ``max_k`` best
+    among the grown polygons, in :func:`segger_amd.nearest.nearest_boundaries`' order (deepest inside first, then nearest
+    outside, ties to the lower id), which bounds the shape buckets of :class:`segger_amd.capture.GraphedPredictorPool`.
+    ``buffer_ratio < 0`` is a ``ValueError``: GEOS's erosion (a negative buffer) is not built as geometry; membership in
+    an eroded polygon is the mask ``inside & (dist2 >= d * d)`` over ``nearest_boundaries``' result
+    (:mod:`segger_amd.nearest`)."""
     from .geometry import points_in_polygons
     from .morphology import polygon_props
     buffer_ratio = float(buffer_ratio)
@@ -118,4 +153,6 @@ def prediction_graph_shape(tx_pos: Tensor, ring_offsets: Tensor, xy: Tensor, buf
     area = polygon_props(ring_offsets, xy)["area"]
     d = torch.sqrt(area / math.pi) * buffer_ratio
     d = torch.where(area.isnan(), torch.zeros_like(d), d)           # an empty ring has no area and matches nothing
+    if max_k is not None:
+        return _nearest_edges(tx_pos, ring_offsets, xy, max_k, d, "contains")
     return points_in_polygons(tx_pos, ring_offsets, xy, buffer=d, predicate="contains")
