@@ -11,15 +11,17 @@
 //   bcount_bin_kernel     one thread per polygon: checks its ring and its distance, zeroes its row size and cell_count,
 //                         appends a ring of 3 or more vertices to the list of its route;
 //                         (these three are wrappers around join_grid.h's bodies, which polygon_join.hip wraps as well: one
-//                         key format, one cell-start rule, one workspace layout and one set of host checks for both units)
+//                         key format, one cell-start rule, one workspace layout, one set of host checks and one front --
+//                         grid_front -- for the units)
 //   bcount_short_kernel   n <= 64: one wave per polygon, the ring in registers.  Small tier: four waves a workgroup, each
 //                         with its own hist[SEGGER_BCOUNT_SMALL_GENES] and touched list; large tier: one wave a workgroup,
 //                         hist[SEGGER_BCOUNT_MAX_GENES];
 //   bcount_long_kernel    64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the ring in LDS (64 KB)
 //                         beside the histogram of its tier;
 //   counts_to_offsets_kernel<int64>  one workgroup: row sizes -> indptr, in place, and nnz.
-// The polygon kernels are templates on count / fill and on the tier over ONE body (count_body): the join's walk
-// (ring_predicate.h: grown_cell_range, ring_match), and per hit an LDS atomic add on hist[gene]; the lane that sees the old
+// The polygon kernels are templates on count / fill and on the tier: their LDS, rings.h's loops (short_ring_loop,
+// long_ring_loop) and ONE body (count_body), a sink of the join's walk (ring_predicate.h: walk_grown_ring; the arguments
+// and the launches are join_grid.h's): per hit an LDS atomic add on hist[gene]; the lane that sees the old
 // value 0 appends the gene to the touched list at a ballot-derived slot.  After the walk the list is sorted (wave_sort.h),
 // the row is written from it and exactly those entries of hist are zeroed again.  More distinct genes than the list holds:
 // one ordered scan of hist writes the row and zeroes all of it.
@@ -81,15 +83,12 @@ __global__ __launch_bounds__(kBcThreads) void bcount_bin_kernel(const int64_t* _
   bin_rings_body(off, xy, buffer, P, V, indptr, cell_count, words, list_short, list_long);
 }
 
+constexpr FrontKernels kBcFront{bcount_keys_kernel, bcount_cells_kernel, bcount_bin_kernel,
+                                "bcount_keys_kernel", "bcount_cells_kernel", "bcount_bin_kernel"};
+
 struct CountArgs {
-  const int64_t* off;
-  const double* xy;
-  const double* buffer;                                              // [P] or NULL = 0
-  int predicate;
+  WalkCommon c;                                                      // join_grid.h
   int n_genes;
-  UniformGrid g;
-  const int32_t* cell_start;
-  const double2* pts;                                                // cell-ordered
   const int32_t* gene;                                               // cell-ordered
   int64_t* indptr;                                                   // count: [p + 1] is written; fill: read
   int64_t* cell_count;                                               // count: written; fill: read
@@ -97,48 +96,34 @@ struct CountArgs {
   int32_t* counts;                                                   // fill
   int64_t capacity;
   unsigned long long* counters;                                      // count
-  int32_t* words;
 };
 
 // what a wave adds to the counters once, after its last polygon
 struct WaveTotals { unsigned long long pairs = 0, bad = 0, overflow = 0, large = 0; };
 
-// One polygon, one wave, every lane active.  n >= 3 vertices translated to org; xmin .. ymax are the ring's bounds on the
-// coordinates as given (the same in every lane).  hist[0 .. n_genes) is zero on entry and on return; `touched` is the
-// wave's list.  kSync orders the wave's LDS traffic (wave_sort.h).
+// One polygon, one wave, every lane active: r is what rings.h's loops hand over.  hist[0 .. n_genes) is zero on entry and
+// on return; `touched` is the wave's list.  kSync orders the wave's LDS traffic (wave_sort.h).
 template <bool kFill, class Sync, class Ring>
-__device__ __forceinline__ void count_body(const Ring& ring, int n, P2 org, double xmin, double ymin, double xmax, double ymax,
-                                           int64_t p, const CountArgs& a, int32_t* hist, int32_t* touched, WaveTotals& tot, Sync sync) {
+__device__ __forceinline__ void count_body(const ListedRing<Ring>& r, const CountArgs& a, int32_t* hist, int32_t* touched,
+                                           WaveTotals& tot, Sync sync) {
   const int lane = threadIdx.x & (kWave - 1);
-  const double d = a.buffer ? a.buffer[p] : 0.0;
-  const double dd = d * d;
-  const CellRange r = grown_cell_range(xmin, ymin, xmax, ymax, d, a.g);
+  const int64_t p = r.p;
   int64_t n_hit = 0, n_good = 0;
   int distinct = 0;                                                  // the same in every lane
-  for (int cy = r.cy0; cy <= r.cy1; ++cy) {
-    const int64_t row = (int64_t)cy * a.g.nx;
-    const int s0 = __builtin_amdgcn_readfirstlane(a.cell_start[row + r.cx0]);
-    const int s1 = __builtin_amdgcn_readfirstlane(a.cell_start[row + r.cx1 + 1]);
-    for (int sb = s0; sb < s1; sb += kWave) {
-      const int s = sb + lane;
-      const bool valid = s < s1;
-      const double2 t = a.pts[valid ? s : s0];
-      const double px = t.x - org.x, py = t.y - org.y;
-      const bool hit = valid && ring_match(ring, n, px, py, dd, a.predicate);
-      const int g = hit ? a.gene[s] : -1;
-      const bool good = hit && (unsigned)g < (unsigned)a.n_genes;    // any other gene is never an index
-      n_hit += (int64_t)__popcll(__ballot(hit));
-      n_good += (int64_t)__popcll(__ballot(good));
-      bool fresh = false;
-      if (good) fresh = atomicAdd(&hist[g], 1) == 0;                 // two lanes on one gene: one of them sees 0
-      const unsigned long long m = __ballot(fresh);
-      if (fresh) {
-        const int pos = distinct + (int)__popcll(m & ((1ull << lane) - 1));
-        if (pos < kTouched) touched[pos] = g;
-      }
-      distinct += (int)__popcll(m);
+  walk_polygon(a.c, r, [&](bool hit, int s, const RingDistance&) {
+    const int g = hit ? a.gene[s] : -1;
+    const bool good = hit && (unsigned)g < (unsigned)a.n_genes;      // any other gene is never an index
+    n_hit += (int64_t)__popcll(__ballot(hit));
+    n_good += (int64_t)__popcll(__ballot(good));
+    bool fresh = false;
+    if (good) fresh = atomicAdd(&hist[g], 1) == 0;                   // two lanes on one gene: one of them sees 0
+    const unsigned long long m = __ballot(fresh);
+    if (fresh) {
+      const int pos = distinct + (int)__popcll(m & ((1ull << lane) - 1));
+      if (pos < kTouched) touched[pos] = g;
     }
-  }
+    distinct += (int)__popcll(m);
+  });
   sync();                                                            // hist and the list are complete
   const bool overflow = distinct > kTouched;
   tot.pairs += (unsigned long long)n_hit;
@@ -186,7 +171,7 @@ __device__ __forceinline__ void count_body(const Ring& ring, int n, P2 org, doub
   }
   sync();
   if (lane == 0 && (begin + distinct != a.indptr[p + 1] || begin + distinct > a.capacity || a.cell_count[p] != n_good))
-    atomicOr(&a.words[kWordFlag], SEGGER_BCOUNT_ERR_FILL);
+    atomicOr(&a.c.words[kWordFlag], SEGGER_BCOUNT_ERR_FILL);
 }
 
 template <bool kFill>
@@ -210,17 +195,12 @@ __global__ __launch_bounds__(kLarge ? kWave : kBcThreads) void bcount_short_kern
   __shared__ int32_t hist[kWaves][tier_genes(kLarge)];
   __shared__ int32_t touched[kWaves][kTouched];
   const int wave = (int)(threadIdx.x >> 6);
-  const int count = a.words[kWordShort];
-  const int n_waves = (int)gridDim.x * kWaves;
   WaveTotals tot;
   zero_hist(hist[wave], a.n_genes, WaveSync{});
-  for (int w = (int)blockIdx.x * kWaves + wave; w < count; w += n_waves) {                                      // wave-uniform
-    const int64_t p = list[w];
-    const ShortRing s = load_short_ring(a.off, a.xy, p);             // 3 .. 64 vertices
-    count_body<kFill>(s.ring, s.n, s.first, wave_min_f64(s.mine.x), wave_min_f64(s.mine.y), wave_max_f64(s.mine.x),
-                      wave_max_f64(s.mine.y), p, a, hist[wave], touched[wave], tot, WaveSync{});
+  short_ring_loop(a.c.off, a.c.xy, a.c.words, list, kWaves, [&](const auto& r) {
+    count_body<kFill>(r, a, hist[wave], touched[wave], tot, WaveSync{});
     tot.large += kLarge ? 1u : 0u;
-  }
+  });
   add_totals<kFill>(a, tot);
 }
 
@@ -229,23 +209,19 @@ __global__ __launch_bounds__(kWave) void bcount_long_kernel(CountArgs a, const i
   __shared__ double2 pts[SEGGER_MORPH_MAX_VERTS];
   __shared__ int32_t hist[tier_genes(kLarge)];
   __shared__ int32_t touched[kTouched];
-  const int count = a.words[kWordLong];
   WaveTotals tot;
   zero_hist(hist, a.n_genes, BlockSync{});
-  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
-    const int64_t p = list[w];
-    const LongRing r = stage_long_ring(a.off, a.xy, p, pts);
-    LdsRing ring{pts};
-    count_body<kFill>(ring, r.n, r.first, wave_min_f64(r.xmin), wave_min_f64(r.ymin), wave_max_f64(r.xmax), wave_max_f64(r.ymax),
-                      p, a, hist, touched, tot, BlockSync{});
+  long_ring_loop(a.c.off, a.c.xy, a.c.words, list, pts, [&](const auto& r) {
+    count_body<kFill>(r, a, hist, touched, tot, BlockSync{});
     tot.large += kLarge ? 1u : 0u;
-  }
+  });
   add_totals<kFill>(a, tot);
 }
 
 // ---------------------------------------------------------------- host ---
 using BcLayout = GridLayout;                                         // join_grid.h: the join's layout and, behind it, the genes
 using BcCall = GridCall;
+constexpr const char* kBcNames8 = "ring_offsets, indptr and buffer";
 
 BcLayout bc_layout(int64_t N, int64_t P, int64_t n_cells) { return grid_layout(N, P, n_cells, true); }
 
@@ -266,36 +242,21 @@ int bc_check(const char* who, const BcCall& c, int64_t G, bool* empty) {
 
 CountArgs count_args(const BcCall& c, int64_t G, const BcLayout& l) {
   CountArgs a{};
-  a.off = c.ring_offsets;
-  a.xy = c.xy;
-  a.buffer = c.buffer;
-  a.predicate = c.predicate;
+  a.c = walk_common(c, l);
   a.n_genes = (int)G;
-  a.g = UniformGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny};
-  a.cell_start = at<int32_t>(c.workspace, l.cell_start);
-  a.pts = at<double2>(c.workspace, l.pts);
   a.gene = at<int32_t>(c.workspace, l.gene);
   a.indptr = const_cast<int64_t*>(c.offsets);
-  a.words = at<int32_t>(c.workspace, l.rings.words);
   return a;
 }
 
+// the tier's kernels: the small one runs four waves a workgroup on the short route, the large one one
 template <bool kFill, bool kLarge>
-int launch_tier(const BcCall& c, const BcLayout& l, const CountArgs& a, hipStream_t stream) {
-  const int cus = cu_count_or_default();
-  constexpr int kWaves = kLarge ? 1 : kBcWaves;
-  hipLaunchKernelGGL((bcount_short_kernel<kFill, kLarge>), dim3(grid_stride_blocks(c.P, kWaves, (int64_t)cus * (kLarge ? 1 : 4))),
-                     dim3(kLarge ? kWave : kBcThreads), 0, stream, a, (const int32_t*)at<int32_t>(c.workspace, l.rings.list_short));
-  SEGGER_LAUNCH_CHECK("bcount_short_kernel");
-  hipLaunchKernelGGL((bcount_long_kernel<kFill, kLarge>), dim3(grid_stride_blocks(c.P, 1, (int64_t)cus * (kLarge ? 1 : 2))), dim3(kWave), 0,
-                     stream, a, (const int32_t*)at<int32_t>(c.workspace, l.rings.list_long));
-  SEGGER_LAUNCH_CHECK("bcount_long_kernel");
-  return SEGGER_OK;
-}
+constexpr RingKernels<CountArgs> kBcRings{bcount_short_kernel<kFill, kLarge>, "bcount_short_kernel", kLarge ? 1 : kBcWaves, kLarge ? 1 : 4,
+                                          bcount_long_kernel<kFill, kLarge>, "bcount_long_kernel", kLarge ? 1 : 2};
 
 template <bool kFill>
 int launch_polygons(const BcCall& c, const BcLayout& l, const CountArgs& a, hipStream_t stream) {
-  return a.n_genes > SEGGER_BCOUNT_SMALL_GENES ? launch_tier<kFill, true>(c, l, a, stream) : launch_tier<kFill, false>(c, l, a, stream);
+  return launch_ring_kernels(a.n_genes > SEGGER_BCOUNT_SMALL_GENES ? kBcRings<kFill, true> : kBcRings<kFill, false>, c, l, a, stream);
 }
 
 }  // namespace
@@ -316,43 +277,21 @@ extern "C" int segger_buffered_counts_count(const double* points, int64_t n_poin
                                             int64_t workspace_bytes, segger_stream_t stream_) {
   const char* who = "segger_buffered_counts_count";
   hipStream_t stream = (hipStream_t)stream_;
-  const BcCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
-                 indptr, workspace, workspace_bytes, true, gene, "ring_offsets, indptr and buffer"};
+  const BcCall c = grid_call(points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
+                             indptr, workspace, workspace_bytes, kBcNames8, true, gene);
   bool empty = false;
-  const int rc = bc_check(who, c, n_genes, &empty);
+  int rc = bc_check(who, c, n_genes, &empty);
   if (rc != SEGGER_OK || empty) return rc;
   SEGGER_REQUIRE(cell_count && counters, "%s: NULL pointer", who);
   SEGGER_REQUIRE(is_aligned(cell_count, 8) && is_aligned(counters, 8), "%s: cell_count and counters must be 8-byte aligned", who);
-  const int64_t n_cells = (int64_t)nx * ny;
-  const BcLayout l = bc_layout(n_points, n_polygons, n_cells);
+  const BcLayout l = bc_layout(n_points, n_polygons, (int64_t)nx * ny);
   CountArgs a = count_args(c, n_genes, l);
   a.cell_count = cell_count;
   a.counters = reinterpret_cast<unsigned long long*>(counters);
-  unsigned long long* keys_in = at<unsigned long long>(workspace, l.pts);      // dead once sorted: the points go there
-  unsigned long long* keys = at<unsigned long long>(workspace, l.keys);
-  const int cus = cu_count_or_default();
-  SEGGER_HIP(hipMemsetAsync(a.words, 0, kRingWordsBytes, stream));
   SEGGER_HIP(hipMemsetAsync(counters, 0, SEGGER_BCOUNT_COUNTERS * sizeof(int64_t), stream));
-  hipLaunchKernelGGL(bcount_keys_kernel, dim3(grid_stride_blocks(n_points, kBcThreads, (int64_t)cus * 32)), dim3(kBcThreads), 0,
-                     stream, points, n_points, a.g, keys_in);
-  SEGGER_LAUNCH_CHECK("bcount_keys_kernel");
-  size_t temp_bytes = l.temp_bytes;
-  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, l.temp), temp_bytes, keys_in, keys, (size_t)n_points,
-                                                           0, (unsigned)l.key_bits, stream));
-  hipLaunchKernelGGL(bcount_cells_kernel, dim3(grid_stride_blocks(n_points, kBcThreads, (int64_t)cus * 32)), dim3(kBcThreads), 0,
-                     stream, (const unsigned long long*)keys, points, gene, n_points, n_cells, at<int32_t>(workspace, l.cell_start),
-                     at<double2>(workspace, l.pts), at<int32_t>(workspace, l.gene));
-  SEGGER_LAUNCH_CHECK("bcount_cells_kernel");
-  hipLaunchKernelGGL(bcount_bin_kernel, dim3(grid_stride_blocks(n_polygons, kBcThreads, (int64_t)cus * 8)), dim3(kBcThreads), 0,
-                     stream, ring_offsets, xy, buffer, n_polygons, n_vertices, indptr, cell_count, a.words,
-                     at<int32_t>(workspace, l.rings.list_short), at<int32_t>(workspace, l.rings.list_long));
-  SEGGER_LAUNCH_CHECK("bcount_bin_kernel");
-  const int rc2 = launch_polygons<false>(c, l, a, stream);
-  if (rc2 != SEGGER_OK) return rc2;
-  hipLaunchKernelGGL((counts_to_offsets_kernel<int64_t>), dim3(1), dim3(kScanThreads), 0, stream, indptr, n_polygons,
-                     counters + kCtrNnz);
-  SEGGER_LAUNCH_CHECK("counts_to_offsets_kernel");
-  return SEGGER_OK;
+  rc = grid_front(kBcFront, c, l, indptr, cell_count, stream);
+  if (rc == SEGGER_OK) rc = launch_polygons<false>(c, l, a, stream);
+  return rc != SEGGER_OK ? rc : launch_offsets_scan(indptr, n_polygons, counters + kCtrNnz, stream);
 }
 
 extern "C" int segger_buffered_counts_fill(const double* points, int64_t n_points, const int32_t* gene, int64_t n_genes,
@@ -363,13 +302,12 @@ extern "C" int segger_buffered_counts_fill(const double* points, int64_t n_point
                                            segger_stream_t stream_) {
   const char* who = "segger_buffered_counts_fill";
   hipStream_t stream = (hipStream_t)stream_;
-  const BcCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
-                 indptr, workspace, workspace_bytes, true, gene, "ring_offsets, indptr and buffer"};
+  const BcCall c = grid_call(points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
+                             indptr, workspace, workspace_bytes, kBcNames8, true, gene);
   bool empty = false;
-  const int rc = bc_check(who, c, n_genes, &empty);
-  if (rc != SEGGER_OK) return rc;
-  SEGGER_REQUIRE(capacity >= 0, "%s: negative capacity", who);
-  if (empty || capacity == 0) return SEGGER_OK;
+  int rc = bc_check(who, c, n_genes, &empty);
+  if (rc == SEGGER_OK) rc = grid_check_capacity(who, capacity, &empty);
+  if (rc != SEGGER_OK || empty) return rc;
   SEGGER_REQUIRE(cell_count && indices && counts, "%s: NULL pointer", who);
   SEGGER_REQUIRE(is_aligned(cell_count, 8), "%s: cell_count must be 8-byte aligned", who);
   SEGGER_REQUIRE(is_aligned(indices, 4) && is_aligned(counts, 4), "%s: indices and counts must be 4-byte aligned", who);

@@ -1,6 +1,6 @@
 // segger_nearest_boundaries_count / _fill / _select: for every point the k best boundaries among the polygons the join
-// pairs it with, each with its squared distance to the ring and the crossing parity -- the numbers ring_match computes and
-// folds into one bit.  include/segger_amd.h has the contract.  A prediction graph with a bounded degree ("the k nearest
+// pairs it with, each with its squared distance to the ring and the crossing parity -- the numbers ring_distance computes
+// and ring_decide folds into one bit.  include/segger_amd.h has the contract.  A prediction graph with a bounded degree ("the k nearest
 // boundaries within a distance"), the signed distance of a transcript to an outline, and erosion as a mask all read them.
 //
 // Kernels, one stream, no host synchronisation inside an entry point:
@@ -9,8 +9,9 @@
 //   near_long_kernel    64 < n <= SEGGER_MORPH_MAX_VERTS: one single-wave workgroup per polygon, the ring in LDS (64 KB);
 //   counts_to_offsets_kernel<int64>  one workgroup: candidates per point -> pair_offsets, in place;
 //   near_select_kernel  one lane per point, or the whole wave for a point with more than SEGGER_NEAREST_LANE_MAX candidates.
-// The two polygon kernels are templates on count / fill over ONE traversal (walk_body), the join's (ring_predicate.h:
-// grown_cell_range, ring_distance, ring_decide -- a candidate is a pair of the join, bit for bit).  Count: an integer atomic
+// The two polygon kernels are rings.h's loops around walk_body, a template on count / fill and this unit's sink of the
+// join's walk (ring_predicate.h: walk_grown_ring -- a candidate is a pair of the join, bit for bit; the arguments and the
+// launches are join_grid.h's).  It is the sink that keeps the numbers (RingDistance) of a match.  Count: an integer atomic
 // add on pair_offsets[point + 1].  Fill: the slot of a match is pair_offsets[point] + an integer atomic add on the point's
 // cursor; it holds s (fp64) and the polygon id with the parity in bit 31.
 //
@@ -54,97 +55,71 @@ __global__ __launch_bounds__(kNbThreads) void near_keys_kernel(const double* __r
 }
 
 __global__ __launch_bounds__(kNbThreads) void near_cells_kernel(const unsigned long long* __restrict__ keys_sorted,
-                                                                const double* __restrict__ pts, int64_t n, int64_t n_cells,
-                                                                int32_t* __restrict__ cell_start, double2* __restrict__ sorted_pts) {
+                                                                const double* __restrict__ pts, const int32_t*, int64_t n,
+                                                                int64_t n_cells, int32_t* __restrict__ cell_start,
+                                                                double2* __restrict__ sorted_pts, int32_t*) {
   grid_cells_body<false>(keys_sorted, pts, nullptr, n, n_cells, cell_start, sorted_pts, nullptr);
 }
 
 // the sizes of this unit are per point (pair_offsets, zeroed by the entry point): the binning kernel zeroes none
 __global__ __launch_bounds__(kNbThreads) void near_bin_kernel(const int64_t* __restrict__ off, const double* __restrict__ xy,
-                                                              const double* __restrict__ buffer, int64_t P, int64_t V,
-                                                              int32_t* __restrict__ words, int32_t* __restrict__ list_short,
+                                                              const double* __restrict__ buffer, int64_t P, int64_t V, int64_t*,
+                                                              int64_t*, int32_t* __restrict__ words, int32_t* __restrict__ list_short,
                                                               int32_t* __restrict__ list_long) {
   bin_rings_body(off, xy, buffer, P, V, nullptr, nullptr, words, list_short, list_long);
 }
 
+constexpr FrontKernels kNbFront{near_keys_kernel, near_cells_kernel, near_bin_kernel,
+                                "near_keys_kernel", "near_cells_kernel", "near_bin_kernel"};
+
 struct WalkArgs {
-  const int64_t* off;
-  const double* xy;
-  const double* buffer;                                              // [P] or NULL = 0
-  int predicate;
-  UniformGrid g;
-  const int32_t* cell_start;
-  const double2* pts;                                                // cell-ordered
-  const unsigned long long* keys;                                    // cell-ordered; the low word is the point id
+  WalkCommon c;                                                      // join_grid.h
   int64_t* pair_offsets;                                             // count: [point + 1] is added to; fill: read
   int32_t* cursor;                                                   // fill: [point], zero on entry
   double* pair_key;                                                  // fill: s of a candidate
   uint32_t* pair_polygon;                                            // fill: its polygon, the parity in bit 31
   int64_t capacity;
-  int32_t* words;
 };
 
-// One polygon, one wave, every lane active.  n >= 3 vertices translated to org; xmin .. ymax are the ring's bounds on the
-// coordinates as given (the same in every lane).
+// One polygon, one wave, every lane active: r is what rings.h's loops hand over.  This unit's sink of the walk: a match is
+// a candidate of its point (the join's pairs, bit for bit).
 template <bool kFill, class Ring>
-__device__ __forceinline__ void walk_body(const Ring& ring, int n, P2 org, double xmin, double ymin, double xmax, double ymax,
-                                          int64_t p, const WalkArgs& a) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const double d = a.buffer ? a.buffer[p] : 0.0;
-  const double dd = d * d;
-  const CellRange r = grown_cell_range(xmin, ymin, xmax, ymax, d, a.g);
-  for (int cy = r.cy0; cy <= r.cy1; ++cy) {
-    const int64_t row = (int64_t)cy * a.g.nx;
-    const int s0 = __builtin_amdgcn_readfirstlane(a.cell_start[row + r.cx0]);
-    const int s1 = __builtin_amdgcn_readfirstlane(a.cell_start[row + r.cx1 + 1]);
-    for (int sb = s0; sb < s1; sb += kWave) {
-      const int s = sb + lane;
-      const bool valid = s < s1;
-      const double2 t = a.pts[valid ? s : s0];
-      const RingDistance rd = ring_distance(ring, n, t.x - org.x, t.y - org.y);
-      if (!(valid && ring_decide(rd, dd, a.predicate))) continue;    // ring_predicate.h: the join's pairs, bit for bit
-      const int64_t id = (int64_t)(a.keys[s] & 0xffffffffull);       // < n_points: the keys kernel wrote it
-      if (!kFill) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(&a.pair_offsets[id + 1]), 1ull);
+__device__ __forceinline__ void walk_body(const ListedRing<Ring>& r, const WalkArgs& a) {
+  const int64_t p = r.p;
+  walk_polygon(a.c, r, [&](bool hit, int s, const RingDistance& rd) {
+    if (!hit) return;
+    const int64_t id = (int64_t)(a.c.keys[s] & 0xffffffffull);       // < n_points: the keys kernel wrote it
+    if (!kFill) {
+      atomicAdd(reinterpret_cast<unsigned long long*>(&a.pair_offsets[id + 1]), 1ull);
+    } else {
+      const int64_t begin = a.pair_offsets[id];
+      int64_t end = a.pair_offsets[id + 1];
+      if (end > a.capacity) end = a.capacity;                        // nothing is ever written at or beyond either
+      const int64_t slot = begin + (int64_t)atomicAdd(&a.cursor[id], 1);
+      if (begin >= 0 && slot < end) {
+        a.pair_key[slot] = rd.best == 0.0 ? 0.0 : (rd.inside ? -rd.best : rd.best);
+        a.pair_polygon[slot] = (uint32_t)p | (rd.inside ? kParityBit : 0u);
       } else {
-        const int64_t begin = a.pair_offsets[id];
-        int64_t end = a.pair_offsets[id + 1];
-        if (end > a.capacity) end = a.capacity;                      // nothing is ever written at or beyond either
-        const int64_t slot = begin + (int64_t)atomicAdd(&a.cursor[id], 1);
-        if (begin >= 0 && slot < end) {
-          a.pair_key[slot] = rd.best == 0.0 ? 0.0 : (rd.inside ? -rd.best : rd.best);
-          a.pair_polygon[slot] = (uint32_t)p | (rd.inside ? kParityBit : 0u);
-        } else {
-          atomicOr(&a.words[kWordFlag], SEGGER_NEAREST_ERR_FILL);
-        }
+        atomicOr(&a.c.words[kWordFlag], SEGGER_NEAREST_ERR_FILL);
       }
     }
-  }
+  });
 }
 
 template <bool kFill>
 __global__ __launch_bounds__(kNbThreads) void near_short_kernel(WalkArgs a, const int32_t* __restrict__ list) {
-  const int count = a.words[kWordShort];
-  const int n_waves = (int)gridDim.x * kNbWaves;
-  for (int w = (int)blockIdx.x * kNbWaves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {                // wave-uniform
-    const int64_t p = list[w];
-    const ShortRing s = load_short_ring(a.off, a.xy, p);             // 3 .. 64 vertices
-    walk_body<kFill>(s.ring, s.n, s.first, wave_min_f64(s.mine.x), wave_min_f64(s.mine.y), wave_max_f64(s.mine.x),
-                     wave_max_f64(s.mine.y), p, a);
-  }
+  short_ring_loop(a.c.off, a.c.xy, a.c.words, list, kNbWaves, [&](const auto& r) { walk_body<kFill>(r, a); });
 }
 
 template <bool kFill>
 __global__ __launch_bounds__(kWave) void near_long_kernel(WalkArgs a, const int32_t* __restrict__ list) {
   __shared__ double2 pts[SEGGER_MORPH_MAX_VERTS];
-  const int count = a.words[kWordLong];
-  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
-    const int64_t p = list[w];
-    const LongRing r = stage_long_ring(a.off, a.xy, p, pts);
-    LdsRing ring{pts};
-    walk_body<kFill>(ring, r.n, r.first, wave_min_f64(r.xmin), wave_min_f64(r.ymin), wave_max_f64(r.xmax), wave_max_f64(r.ymax), p, a);
-  }
+  long_ring_loop(a.c.off, a.c.xy, a.c.words, list, pts, [&](const auto& r) { walk_body<kFill>(r, a); });
 }
+
+template <bool kFill>
+constexpr RingKernels<WalkArgs> kNbRings{near_short_kernel<kFill>, "near_short_kernel", kNbWaves, 8,
+                                         near_long_kernel<kFill>, "near_long_kernel", 2};
 
 // ---------------------------------------------------------------- the selection ---
 // A candidate as the selection compares it: the bits of s mapped so that their unsigned order is the order of the doubles
@@ -256,6 +231,7 @@ __global__ __launch_bounds__(kNbThreads) void near_select_kernel(SelectArgs a) {
 
 // ---------------------------------------------------------------- host ---
 using NbCall = GridCall;
+constexpr const char* kNbNames8 = "ring_offsets, pair_offsets and buffer";
 struct NbLayout { GridLayout grid; size_t cursor, total; };          // the join's layout and, behind it, a cursor per point
 
 NbLayout nb_layout(int64_t N, int64_t P, int64_t n_cells) {
@@ -280,30 +256,10 @@ int nb_check(const char* who, const NbCall& c, bool* empty) {
 
 WalkArgs walk_args(const NbCall& c, const NbLayout& l) {
   WalkArgs a{};
-  a.off = c.ring_offsets;
-  a.xy = c.xy;
-  a.buffer = c.buffer;
-  a.predicate = c.predicate;
-  a.g = UniformGrid{c.x0, c.y0, 1.0 / c.cell, c.nx, c.ny};
-  a.cell_start = at<int32_t>(c.workspace, l.grid.cell_start);
-  a.pts = at<double2>(c.workspace, l.grid.pts);
-  a.keys = at<unsigned long long>(c.workspace, l.grid.keys);
+  a.c = walk_common(c, l.grid);
   a.pair_offsets = const_cast<int64_t*>(c.offsets);
   a.cursor = at<int32_t>(c.workspace, l.cursor);
-  a.words = at<int32_t>(c.workspace, l.grid.rings.words);
   return a;
-}
-
-template <bool kFill>
-int launch_polygons(const NbCall& c, const NbLayout& l, const WalkArgs& a, hipStream_t stream) {
-  const int cus = cu_count_or_default();
-  hipLaunchKernelGGL((near_short_kernel<kFill>), dim3(grid_stride_blocks(c.P, kNbWaves, (int64_t)cus * 8)), dim3(kNbThreads), 0,
-                     stream, a, (const int32_t*)at<int32_t>(c.workspace, l.grid.rings.list_short));
-  SEGGER_LAUNCH_CHECK("near_short_kernel");
-  hipLaunchKernelGGL((near_long_kernel<kFill>), dim3(grid_stride_blocks(c.P, 1, (int64_t)cus * 2)), dim3(kWave), 0, stream, a,
-                     (const int32_t*)at<int32_t>(c.workspace, l.grid.rings.list_long));
-  SEGGER_LAUNCH_CHECK("near_long_kernel");
-  return SEGGER_OK;
 }
 
 }  // namespace
@@ -323,39 +279,16 @@ extern "C" int segger_nearest_boundaries_count(const double* points, int64_t n_p
                                                void* workspace, int64_t workspace_bytes, segger_stream_t stream_) {
   const char* who = "segger_nearest_boundaries_count";
   hipStream_t stream = (hipStream_t)stream_;
-  const NbCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
-                 pair_offsets, workspace, workspace_bytes, false, nullptr, "ring_offsets, pair_offsets and buffer"};
+  const NbCall c = grid_call(points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
+                             pair_offsets, workspace, workspace_bytes, kNbNames8);
   bool empty = false;
-  const int rc = nb_check(who, c, &empty);
+  int rc = nb_check(who, c, &empty);
   if (rc != SEGGER_OK || empty) return rc;
-  const int64_t n_cells = (int64_t)nx * ny;
-  const NbLayout l = nb_layout(n_points, n_polygons, n_cells);
-  const WalkArgs a = walk_args(c, l);
-  unsigned long long* keys_in = at<unsigned long long>(workspace, l.grid.pts);      // dead once sorted: the points go there
-  unsigned long long* keys = at<unsigned long long>(workspace, l.grid.keys);
-  const int cus = cu_count_or_default();
-  SEGGER_HIP(hipMemsetAsync(a.words, 0, kRingWordsBytes, stream));
+  const NbLayout l = nb_layout(n_points, n_polygons, (int64_t)nx * ny);
   SEGGER_HIP(hipMemsetAsync(pair_offsets, 0, (size_t)(n_points + 1) * sizeof(int64_t), stream));
-  hipLaunchKernelGGL(near_keys_kernel, dim3(grid_stride_blocks(n_points, kNbThreads, (int64_t)cus * 32)), dim3(kNbThreads), 0,
-                     stream, points, n_points, a.g, keys_in);
-  SEGGER_LAUNCH_CHECK("near_keys_kernel");
-  size_t temp_bytes = l.grid.temp_bytes;
-  SEGGER_HIP(rocprim::radix_sort_keys<NoScratchSortConfig>(at<char>(workspace, l.grid.temp), temp_bytes, keys_in, keys,
-                                                           (size_t)n_points, 0, (unsigned)l.grid.key_bits, stream));
-  hipLaunchKernelGGL(near_cells_kernel, dim3(grid_stride_blocks(n_points, kNbThreads, (int64_t)cus * 32)), dim3(kNbThreads), 0,
-                     stream, (const unsigned long long*)keys, points, n_points, n_cells, at<int32_t>(workspace, l.grid.cell_start),
-                     at<double2>(workspace, l.grid.pts));
-  SEGGER_LAUNCH_CHECK("near_cells_kernel");
-  hipLaunchKernelGGL(near_bin_kernel, dim3(grid_stride_blocks(n_polygons, kNbThreads, (int64_t)cus * 8)), dim3(kNbThreads), 0,
-                     stream, ring_offsets, xy, buffer, n_polygons, n_vertices, a.words,
-                     at<int32_t>(workspace, l.grid.rings.list_short), at<int32_t>(workspace, l.grid.rings.list_long));
-  SEGGER_LAUNCH_CHECK("near_bin_kernel");
-  const int rc2 = launch_polygons<false>(c, l, a, stream);
-  if (rc2 != SEGGER_OK) return rc2;
-  hipLaunchKernelGGL((counts_to_offsets_kernel<int64_t>), dim3(1), dim3(kScanThreads), 0, stream, pair_offsets, n_points,
-                     (int64_t*)nullptr);
-  SEGGER_LAUNCH_CHECK("counts_to_offsets_kernel");
-  return SEGGER_OK;
+  rc = grid_front(kNbFront, c, l.grid, nullptr, nullptr, stream);
+  if (rc == SEGGER_OK) rc = launch_ring_kernels(kNbRings<false>, c, l.grid, walk_args(c, l), stream);
+  return rc != SEGGER_OK ? rc : launch_offsets_scan(pair_offsets, n_points, nullptr, stream);
 }
 
 extern "C" int segger_nearest_boundaries_fill(const double* points, int64_t n_points, const int64_t* ring_offsets, const double* xy,
@@ -365,13 +298,12 @@ extern "C" int segger_nearest_boundaries_fill(const double* points, int64_t n_po
                                               int64_t workspace_bytes, segger_stream_t stream_) {
   const char* who = "segger_nearest_boundaries_fill";
   hipStream_t stream = (hipStream_t)stream_;
-  const NbCall c{points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
-                 pair_offsets, workspace, workspace_bytes, false, nullptr, "ring_offsets, pair_offsets and buffer"};
+  const NbCall c = grid_call(points, n_points, ring_offsets, xy, n_polygons, n_vertices, buffer, predicate, x0, y0, cell, nx, ny,
+                             pair_offsets, workspace, workspace_bytes, kNbNames8);
   bool empty = false;
-  const int rc = nb_check(who, c, &empty);
-  if (rc != SEGGER_OK) return rc;
-  SEGGER_REQUIRE(capacity >= 0, "%s: negative capacity", who);
-  if (empty || capacity == 0) return SEGGER_OK;
+  int rc = nb_check(who, c, &empty);
+  if (rc == SEGGER_OK) rc = grid_check_capacity(who, capacity, &empty);
+  if (rc != SEGGER_OK || empty) return rc;
   SEGGER_REQUIRE(pair_key && pair_polygon, "%s: NULL pointer", who);
   SEGGER_REQUIRE(is_aligned(pair_key, 8) && is_aligned(pair_polygon, 4), "%s: pair_key must be 8-byte and pair_polygon 4-byte aligned", who);
   const NbLayout l = nb_layout(n_points, n_polygons, (int64_t)nx * ny);
@@ -380,7 +312,7 @@ extern "C" int segger_nearest_boundaries_fill(const double* points, int64_t n_po
   a.pair_polygon = reinterpret_cast<uint32_t*>(pair_polygon);
   a.capacity = capacity;
   SEGGER_HIP(hipMemsetAsync(a.cursor, 0, (size_t)n_points * sizeof(int32_t), stream));
-  return launch_polygons<true>(c, l, a, stream);
+  return launch_ring_kernels(kNbRings<true>, c, l.grid, a, stream);
 }
 
 extern "C" int segger_nearest_boundaries_select(const int64_t* pair_offsets, const double* pair_key, const int32_t* pair_polygon,

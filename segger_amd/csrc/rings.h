@@ -193,6 +193,41 @@ __device__ __forceinline__ LongRing stage_long_ring(const int64_t* __restrict__ 
   return r;
 }
 
+// The loops of the polygon kernels of the units that walk points against rings (polygon_join.hip, buffered_counts.hip,
+// nearest_boundaries.hip): every listed ring of a route, loaded, with its bounds on the coordinates as given reduced over
+// the wave, handed to body(ListedRing).  Short: `waves` waves a workgroup, one ring a wave; long: a workgroup of one wave
+// and its stage pts[SEGGER_MORPH_MAX_VERTS].
+// What a body receives, the same in every lane but for a RegRing's vertex: polygon p, its store `ring` of n >= 3 open
+// vertices translated to `first`, and xmin .. ymax, the ring's bounds on the coordinates as given.
+template <class Ring>
+struct ListedRing { Ring ring; int n; P2 first; double xmin, ymin, xmax, ymax; int64_t p; };
+
+template <class Body>
+__device__ __forceinline__ void short_ring_loop(const int64_t* __restrict__ off, const double* __restrict__ xy,
+                                                const int32_t* __restrict__ words, const int32_t* __restrict__ list, int waves, Body&& body) {
+  const int count = words[kWordShort];
+  const int n_waves = (int)gridDim.x * waves;
+  for (int w = (int)blockIdx.x * waves + (int)(threadIdx.x >> 6); w < count; w += n_waves) {                   // wave-uniform
+    const int64_t p = list[w];
+    const ShortRing s = load_short_ring(off, xy, p);                 // 3 .. 64 vertices
+    body(ListedRing<RegRing>{s.ring, s.n, s.first, wave_min_f64(s.mine.x), wave_min_f64(s.mine.y), wave_max_f64(s.mine.x),
+                             wave_max_f64(s.mine.y), p});
+  }
+}
+
+template <class Body>
+__device__ __forceinline__ void long_ring_loop(const int64_t* __restrict__ off, const double* __restrict__ xy,
+                                               const int32_t* __restrict__ words, const int32_t* __restrict__ list,
+                                               double2* __restrict__ pts, Body&& body) {
+  const int count = words[kWordLong];
+  for (int w = (int)blockIdx.x; w < count; w += (int)gridDim.x) {
+    const int64_t p = list[w];
+    const LongRing r = stage_long_ring(off, xy, p, pts);
+    body(ListedRing<LdsRing>{LdsRing{pts}, r.n, r.first, wave_min_f64(r.xmin), wave_min_f64(r.ymin), wave_max_f64(r.xmax),
+                             wave_max_f64(r.ymax), p});
+  }
+}
+
 // ---------------------------------------------------------------- gift wrapping: the march, one wave ---
 // The convex hull of the n points of a store (own / uni as above), counter-clockwise from the lowest (x, then y, then
 // index) point: from the current hull vertex the next one is the most clockwise point as seen from it, ties (collinear
