@@ -394,6 +394,63 @@ int segger_adam_step_ex(const segger_adam_tensor* tensors, int32_t n_tensors, do
 int segger_adam_step_dev(const segger_adam_tensor* tensors, int32_t n_tensors, const double* hyper, int32_t flags,
                          int64_t* counter, int64_t counter_inc, segger_stream_t stream);
 
+/*
+ * The gradient guard: what stands between loss.backward() and optimizer.step() in a mixed-precision training loop --
+ *   scaler.unscale_(opt); torch.nn.utils.clip_grad_norm_(params, max_norm); scaler.step(opt); scaler.update()
+ * (torch/nn/utils/clip_grad.py, torch/amp/grad_scaler.py) -- decided ON THE DEVICE, without a host synchronisation, so
+ * that a captured training step (hipGraph) can carry it.  The reference leaves all three to Lightning
+ * (`gradient_clip_val`, the precision plugin); a replayed graph is out of Lightning's reach.
+ *
+ * segger_guard_state (DEVICE, 40 bytes, 8-byte aligned; the caller initialises scale > 0 and zeroes the rest):
+ *   coef            what segger_adam_step_guarded multiplies every gradient by: clip / scale   (0 on a skipped step)
+ *   skip            1: some gradient element is inf or NaN -- GradScaler's found_inf; the update writes nothing
+ *   norm            the global L2 norm of the UNSCALED gradients, sqrt(sum g^2) / scale (clip_grad_norm_'s return value);
+ *                   NaN on a skipped step
+ *   scale           the loss scale the NEXT backward is seeded with (GradScaler._scale)
+ *   growth_tracker  clean steps since the scale last changed (GradScaler._growth_tracker)
+ *   n_skipped, n_clipped   running totals (steps skipped; steps with clip < 1)
+ * All arithmetic in double until the last cast, with `scale` the value the state held when the call began:
+ *   true_norm = sqrt(sum) / scale;   clip = max_norm > 0 ? min(1, max_norm / (true_norm + 1e-6)) : 1   (torch's formula)
+ *   coef = (float)(clip / scale);    skip = any non-finite element
+ *   growth_interval > 0 (a dynamic scale), as GradScaler.update:  skip: scale *= backoff, tracker = 0;  otherwise
+ *   tracker += 1 and, when it reaches growth_interval, scale *= growth, tracker = 0.   growth_interval == 0: a static scale.
+ *
+ * segger_grad_guard: two passes over the table segger_adam_step takes (only grad, step and numel are read), in the
+ * update's own (tensor, offset) blocks of 2048 elements, 64 tensors a launch.  Pass 1, one workgroup per block: the block's
+ * sum of grad^2 in float64 and its any-non-finite bit into the block's workspace slot; pass 2, ONE workgroup: the slots
+ * summed first to last, the state written.  Every sum has one fixed order and nothing is added atomically: the same
+ * gradients give the same bytes on every run.  On a skipped step with cfg.flags & SEGGER_ADAM_STEPS_ADVANCED pass 2 takes
+ * 1.0f off every step counter of the table again (torch's fused Adam: _foreach_sub_(steps, found_inf)).
+ * cfg is a HOST struct (copied into the kernel arguments); n_tensors == 0 does nothing.  Enqueue-only.
+ * workspace: segger_grad_guard_workspace_bytes(n_tensors, total_blocks) bytes, 256-byte aligned, total_blocks = the sum
+ * over the tensors of ceil(numel / 2048): 16 bytes a block + 8 bytes a tensor, each region rounded up to 256.
+ *
+ * segger_adam_step_guarded: segger_adam_step_dev with g * state->coef for g (one fp32 multiply) and, when state->skip is
+ * set, no tensor byte written; *counter still advances.  Without SEGGER_ADAM_STEPS_ADVANCED its counter launch adds 1
+ * only when skip == 0.
+ */
+typedef struct segger_guard_state {
+  float coef;
+  int32_t skip;
+  double norm;
+  float scale;
+  int32_t growth_tracker;
+  int64_t n_skipped;
+  int64_t n_clipped;
+} segger_guard_state;
+typedef struct segger_guard_cfg {
+  double max_norm;           /* 0: no clipping */
+  double growth;             /* >= 1 */
+  double backoff;            /* in (0, 1) */
+  int32_t growth_interval;   /* 0: static scale */
+  int32_t flags;             /* SEGGER_ADAM_STEPS_ADVANCED */
+} segger_guard_cfg;
+int64_t segger_grad_guard_workspace_bytes(int32_t n_tensors, int64_t total_blocks);
+int segger_grad_guard(const segger_adam_tensor* tensors, int32_t n_tensors, const segger_guard_cfg* cfg,
+                      segger_guard_state* state, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+int segger_adam_step_guarded(const segger_adam_tensor* tensors, int32_t n_tensors, const double* hyper, int32_t flags,
+                             int64_t* counter, int64_t counter_inc, const segger_guard_state* state, segger_stream_t stream);
+
 /* segger_transpose_many: dst [cols, rows] = src [rows, cols]^T for n_segs contiguous 16-bit matrices in one launch:
  * the W^T copies the data-gradient GEMMs (dX = dY W on segger_linear_fwd) need after every optimizer step. */
 typedef struct {

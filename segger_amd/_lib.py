@@ -98,6 +98,20 @@ class AdamTensor(C.Structure):
                 ("step", C.c_void_p), ("numel", C.c_int64)]
 
 
+class GuardState(C.Structure):          # segger_guard_state: lives on the DEVICE; here for its layout (offsets, size)
+    _fields_ = [("coef", C.c_float), ("skip", C.c_int32), ("norm", C.c_double), ("scale", C.c_float),
+                ("growth_tracker", C.c_int32), ("n_skipped", C.c_int64), ("n_clipped", C.c_int64)]
+
+
+class GuardCfg(C.Structure):            # segger_guard_cfg (host)
+    _fields_ = [("max_norm", C.c_double), ("growth", C.c_double), ("backoff", C.c_double),
+                ("growth_interval", C.c_int32), ("flags", C.c_int32)]
+
+
+ADAM_STEPS_ADVANCED = 1                 # SEGGER_ADAM_STEPS_ADVANCED
+ADAM_ELEMS_PER_BLOCK = 2048             # the (tensor, offset) block of segger_adam_step / segger_grad_guard
+
+
 class StageSeg(C.Structure):
     _fields_ = [
         ("dst", vp), ("src", vp),
@@ -252,6 +266,9 @@ EXPORTS = {
     "segger_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "segger_adam_step_ex": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, vp, C.c_int64, vp]),
     "segger_adam_step_dev": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]),
+    "segger_adam_step_guarded": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp]),
+    "segger_grad_guard_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "segger_grad_guard": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.POINTER(GuardCfg), vp, vp, C.c_int64, vp]),
     "segger_transpose_many": (C.c_int, [C.POINTER(TransposeSeg), C.c_int32, vp]),
     "segger_posmlp_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "segger_posmlp_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp,

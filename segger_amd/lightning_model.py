@@ -280,16 +280,25 @@ class LitISTEncoder(_Base):
         return self._step(batch, "train")
 
     # ------------------------------------------------- whole-step hipGraph under Lightning (opt-in, not in the reference)
-    def enable_graphed_training(self, enabled: bool = True, **trainer_kw) -> "LitISTEncoder":
+    def enable_graphed_training(self, enabled: bool = True, *, clip_grad_norm: Optional[float] = None, loss_scale=None,
+                                skip_nonfinite: bool = False, **trainer_kw) -> "LitISTEncoder":
         """Opt in BEFORE ``Trainer.fit``: every ``training_step`` becomes one hipGraph replay of the whole step (batch
         staging, forward, the three losses, backward, fused Adam: :class:`segger_amd.train_step_graph.GraphedTrainer`,
         1.3 ms instead of a host-bound 3-5 ms per default 1M-edge batch).  The module switches to Lightning's MANUAL
         optimisation (``automatic_optimization = False``): ``training_step`` drives the optimizer that
         ``configure_optimizers`` returned (now with device-side step counters) and Lightning's own backward / optimizer
-        step / ``zero_grad`` are not run -- so gradient clipping, ``accumulate_grad_batches`` and precision plugins do
-        not apply (the reference's ``Trainer(logger, max_epochs, reload_dataloaders_every_n_epochs, callbacks)``,
-        cli/segment.py:400-405, uses none of them).  Single process: under data parallelism build the
+        step / ``zero_grad`` are not run -- so the Trainer's ``gradient_clip_val``, ``accumulate_grad_batches`` and
+        precision plugins do not apply (the reference's ``Trainer(logger, max_epochs, reload_dataloaders_every_n_epochs,
+        callbacks)``, cli/segment.py:400-405, uses none of them).  What they would have given is asked for HERE and decided
+        on the device inside the replayed step (the gradient guard, ``ops.grad_guard``): ``clip_grad_norm`` (global L2
+        norm, ``torch.nn.utils.clip_grad_norm_``), ``loss_scale`` (a float: static; ``"dynamic"``: ``torch.amp.GradScaler``'s
+        65536 / x2 every 2000 clean steps / x0.5 on an overflow) and ``skip_nonfinite`` (implied by the other two: a step
+        with an inf / NaN gradient changes nothing).  With a guard on, ``train:grad_norm`` and ``train:loss_scale`` are
+        logged.  Still not available: ``accumulate_grad_batches``, ``clip_grad_value_``, norms other than L2,
+        per-parameter-group settings, ``error_if_nonfinite=True``.  Single process: under data parallelism build the
         ``GraphedTrainer`` yourself with a ``dp.FlatGradBucket``.  ``trainer_kw``: ``granularity`` / ``max_buckets``."""
+        if clip_grad_norm is not None or loss_scale is not None or skip_nonfinite:
+            trainer_kw = dict(trainer_kw, clip_grad_norm=clip_grad_norm, loss_scale=loss_scale, skip_nonfinite=skip_nonfinite)
         self._graphed_kw = dict(trainer_kw) if enabled else None
         self._graphed_trainer = None
         self.automatic_optimization = not enabled
@@ -325,6 +334,9 @@ class LitISTEncoder(_Base):
         bs = getattr(batch, "num_graphs", 1)
         for i, name in enumerate(("loss_tx", "loss_bd", "loss_sg")):
             self.log(f"train:{name}", out[i], prog_bar=True, batch_size=bs)
+        if tr.guard is not None:                            # device views, copied: the next replay overwrites them
+            self.log("train:grad_norm", tr.guard.norm.clone(), batch_size=bs)
+            self.log("train:loss_scale", tr.guard.scale.clone(), batch_size=bs)
         return out[3]
 
     def _advance_manual_step_progress(self) -> None:

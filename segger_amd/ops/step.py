@@ -1,5 +1,6 @@
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import torch
@@ -81,8 +82,104 @@ def adam_hyper(opt) -> Optional[tuple]:
     return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
 
 
+class GuardState:
+    """The device side of a gradient guard (``segger_guard_state`` + the workspace of ``segger_grad_guard``), allocated
+    once.  ``norm`` (float64: the unscaled global L2 norm of the last step, NaN when it was skipped), ``scale`` (float32:
+    the loss scale the next backward is seeded with), ``n_skipped`` / ``n_clipped`` (int64 totals), ``skipped`` (int32,
+    0 / 1: the last step), ``coef`` and ``growth_tracker`` are 0-dim VIEWS of the device struct: nothing waits for the
+    device until one of them is read (``float(state.norm)``)."""
+
+    def __init__(self, device, scale: float = 1.0):
+        scale = float(scale)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"GuardState: the loss scale must be positive and finite, not {scale}")
+        S = _lib.GuardState
+        self.device = torch.device(device)
+        self.buf = torch.zeros(C.sizeof(S), dtype=torch.uint8, device=self.device)
+
+        def view(name, dtype):
+            f = getattr(S, name)
+            return self.buf[f.offset:f.offset + f.size].view(dtype).reshape(())
+        self.coef, self.skipped = view("coef", torch.float32), view("skip", torch.int32)
+        self.norm, self.scale = view("norm", torch.float64), view("scale", torch.float32)
+        self.growth_tracker = view("growth_tracker", torch.int32)
+        self.n_skipped, self.n_clipped = view("n_skipped", torch.int64), view("n_clipped", torch.int64)
+        self.scale.fill_(scale)
+        self.coef.fill_(1.0 / scale)
+        self._workspaces: list = []          # every one ever handed out stays alive: captured graphs hold their addresses
+        self._hyper: dict = {}
+
+    def workspace(self, n_tensors: int, total_blocks: int) -> Tensor:
+        need = int(_lib.load().segger_grad_guard_workspace_bytes(int(n_tensors), int(total_blocks)))
+        if need < 0:
+            _lib.check(need, "segger_grad_guard_workspace_bytes")
+        if not self._workspaces or self._workspaces[-1].numel() < need:
+            self._workspaces.append(torch.empty(max(need, 256), dtype=torch.uint8, device=self.device))
+        return self._workspaces[-1]
+
+    def hyper(self, values: tuple) -> Tensor:
+        """float64[4] on the device holding ``values`` (an eager guarded step without a staged array)."""
+        if values not in self._hyper:
+            self._hyper[values] = torch.tensor(values, dtype=torch.float64, device=self.device)
+        return self._hyper[values]
+
+
+def adam_init_state(opt) -> None:
+    """Adam's initial state (``step`` = 0 as an fp32 device scalar, zero moments -- what a capturable
+    ``torch.optim.Adam._init_group`` creates on its first step) for every parameter with a gradient that has none yet: the
+    kernels run on existing state only, and a guarded step cannot leave its first update to ``optimizer.step()``."""
+    for g in opt.param_groups:
+        for p in g["params"]:
+            if p.grad is None or opt.state.get(p):
+                continue
+            st = opt.state[p]
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+
+def _adam_table(rows):
+    arr = (_lib.AdamTensor * len(rows))()
+    for a, (p, gr, m, v, st) in zip(arr, rows):
+        a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.step, a.numel = (p.data_ptr(), gr.data_ptr(), m.data_ptr(),
+                                                                     v.data_ptr(), st.data_ptr(), p.numel())
+    return arr
+
+
+def _guarded_rows(opt, who: str):
+    jobs = _adam_jobs(opt)
+    jobs = None if jobs is None else [(g, rows) for g, rows in jobs if rows]
+    if jobs is None or len(jobs) != 1:
+        raise RuntimeError(f"{who}: the gradient guard needs an optimizer segger_adam_step covers -- a plain capturable "
+                           "torch.optim.Adam (no amsgrad / weight decay / maximize, a Python float learning rate), fp32 "
+                           "contiguous parameters and gradients on the device, existing state (ops.adam_init_state), no "
+                           "GradScaler attached -- with exactly one parameter group that has gradients")
+    return jobs[0]
+
+
+def grad_guard(opt, state: GuardState, *, max_norm: Optional[float] = None, growth: float = 2.0, backoff: float = 0.5,
+               growth_interval: int = 0, steps_advanced: bool = False) -> None:
+    """``segger_grad_guard`` over the gradients of ``opt``'s parameters: global-norm clipping (``max_norm``; None / 0 =
+    off), the loss scale ``state.scale`` the backward was seeded with (``growth_interval`` = 0: static; > 0: grown by
+    ``growth`` after that many clean steps in a row, cut by ``backoff`` on a skipped one, as ``torch.amp.GradScaler``) and
+    the skip on a non-finite gradient, decided on the device and left in ``state`` for ``adam_step(..., guard=state)``.
+    ``steps_advanced``: Adam's step counters were advanced at the head of the step; a skipped step takes that back.
+    Enqueue-only, two launches per 64 tensors.  An optimizer the Adam kernel does not cover is an error."""
+    g, rows = _guarded_rows(opt, "grad_guard")
+    cfg = _lib.GuardCfg(float(max_norm or 0.0), float(growth), float(backoff), int(growth_interval),
+                        _lib.ADAM_STEPS_ADVANCED if steps_advanced else 0)
+    arr = _adam_table(rows)
+    blocks = sum((r[0].numel() + _lib.ADAM_ELEMS_PER_BLOCK - 1) // _lib.ADAM_ELEMS_PER_BLOCK for r in rows)
+    dev = rows[0][0].device
+    ws = state.workspace(len(rows), blocks)
+    with _lib.on_device(dev):
+        rc = _lib.load().segger_grad_guard(arr, len(rows), C.byref(cfg), state.buf.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _lib.stream_ptr(dev))
+    _lib.check(rc, "segger_grad_guard")
+
+
 def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = None, counter_inc: int = 0,
-              hyper_dev: Optional[Tensor] = None) -> bool:
+              hyper_dev: Optional[Tensor] = None, guard: Optional[GuardState] = None) -> bool:
     """``optimizer.step()`` of a plain capturable ``torch.optim.Adam`` through ``segger_adam_step``: every parameter tensor
     in two launches, on the optimizer's own state tensors (checkpoints and eager ``optimizer.step()`` calls stay
     interchangeable).  -> False, nothing done, when the optimizer is anything else (amsgrad, weight decay, maximize, a
@@ -91,8 +188,15 @@ def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = Non
     ``counter`` (int64[1] on the device): ``counter += counter_inc`` rides in the update launch.  ``hyper_dev`` (float64[4]
     on the device = lr, beta1, beta2, eps; one parameter group): the kernel reads them from there when it RUNS
     (``segger_adam_step_dev``) -- a captured step follows a learning-rate schedule without a new capture.
+    ``guard`` (a :class:`GuardState` that :func:`grad_guard` has just filled): ``segger_adam_step_guarded`` -- every gradient
+    times ``guard.coef``, nothing written on a skipped step (``counter`` still advances); an optimizer the kernel does not
+    cover is then an ERROR, not ``False``: the caller's own ``optimizer.step()`` would drop the guard.
     (Host cost ~135 us per call for 60 tensors, nearly all of it the per-tensor attribute reads; a cached launch table
     that re-checked pointers and state identity per step measured the same -- tools/host_phases.py.)"""
+    if guard is not None:
+        g, rows = _guarded_rows(opt, "adam_step")
+        if hyper_dev is None:
+            hyper_dev = guard.hyper((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])))
     # torch's AMP contract for fused optimizers (``_step_supports_amp_scaling``): ``GradScaler.step`` skips its own unscale /
     # inf check and hands both to the optimizer as ``grad_scale`` / ``found_inf``.  The kernel reads neither: torch's fused
     # step does the scaled, skippable update.
@@ -107,14 +211,15 @@ def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = Non
         raise ValueError("adam_step: hyper_dev must be a contiguous float64[4] tensor on the device")
     lib = _lib.load()
     for g, rows in jobs:
-        arr = (_lib.AdamTensor * len(rows))()
-        for a, (p, gr, m, v, st) in zip(arr, rows):
-            a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.step, a.numel = (p.data_ptr(), gr.data_ptr(), m.data_ptr(),
-                                                                         v.data_ptr(), st.data_ptr(), p.numel())
+        arr = _adam_table(rows)
         dev = rows[0][0].device
         b1, b2 = g["betas"]
         with _lib.on_device(dev):
-            if hyper_dev is not None:
+            if guard is not None:
+                rc = lib.segger_adam_step_guarded(arr, len(rows), hyper_dev.data_ptr(), 1 if steps_advanced else 0,
+                                                  _lib.ptr(counter), int(counter_inc), guard.buf.data_ptr(),
+                                                  _lib.stream_ptr(dev))
+            elif hyper_dev is not None:
                 rc = lib.segger_adam_step_dev(arr, len(rows), hyper_dev.data_ptr(), 1 if steps_advanced else 0,
                                               _lib.ptr(counter), int(counter_inc), _lib.stream_ptr(dev))
             else:

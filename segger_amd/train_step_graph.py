@@ -72,13 +72,59 @@ class StepEnd(NamedTuple):
     adam_advanced: bool = False   # Adam's step counters already moved (in the draws launch)
 
 
+DYNAMIC_LOSS_SCALE = dict(init_scale=65536.0, growth=2.0, backoff=0.5, growth_interval=2000)   # torch.amp.GradScaler's defaults
+
+
+def guard_config(clip_grad_norm=None, loss_scale=None, skip_nonfinite: bool = False) -> Optional[dict]:
+    """The gradient guard a step was asked for -- ``ops.grad_guard``'s keyword arguments + ``init_scale`` -- or None when
+    all three are off.  ``clip_grad_norm``: the maximal global L2 norm; ``loss_scale``: a float (static) or "dynamic";
+    ``skip_nonfinite`` alone: scale 1, no clipping, only the skip."""
+    if clip_grad_norm is None and loss_scale is None and not skip_nonfinite:
+        return None
+    cfg = dict(max_norm=0.0, init_scale=1.0, growth=2.0, backoff=0.5, growth_interval=0)
+    if clip_grad_norm is not None:
+        cfg["max_norm"] = float(clip_grad_norm)
+        if not (0.0 < cfg["max_norm"] < float("inf")):
+            raise ValueError(f"clip_grad_norm must be positive and finite, not {clip_grad_norm!r}")
+    if isinstance(loss_scale, str):
+        if loss_scale != "dynamic":
+            raise ValueError(f'loss_scale is a float, "dynamic" or None, not {loss_scale!r}')
+        cfg.update(DYNAMIC_LOSS_SCALE)
+    elif loss_scale is not None:
+        cfg["init_scale"] = float(loss_scale)
+        if not (0.0 < cfg["init_scale"] < float("inf")):
+            raise ValueError(f"loss_scale must be positive and finite, not {loss_scale!r}")
+    return cfg
+
+
+def make_guard(cfg: Optional[dict], optimizer, device):
+    """The ``ops.GuardState`` of a guarded step; an optimizer the Adam kernel does not cover is refused HERE, with the
+    reason: torch's own ``optimizer.step()`` inside the capture would silently drop the guard."""
+    if cfg is None:
+        return None
+    if not USE_ADAM_KERNEL or ops.adam_hyper(optimizer) is None:
+        raise RuntimeError("clip_grad_norm / loss_scale / skip_nonfinite are applied by the hand-written Adam kernel "
+                           "(segger_adam_step_guarded), which does not cover this optimizer: it takes one parameter group "
+                           "of a plain capturable torch.optim.Adam (no amsgrad / weight decay / maximize, a Python float "
+                           "learning rate)" + ("" if USE_ADAM_KERNEL else "; USE_ADAM_KERNEL is off"))
+    return ops.GuardState(device, cfg["init_scale"])
+
+
 class GraphedTrainStep:
     """The captured step of ONE shape bucket (see :class:`GraphedTrainer` for the per-batch dispatch).  A batch is
     written into the bucket's static buffers by ONE launch (``ops.stage`` -> ``segger_stage``): node features, the three
     CSR views, the rows-by-gene grouping of the embedding gradient, the segmentation triplets and the loss samplers'
-    indices are all "copy the batch's own (cached) arrays, fill the padding by a formula" segments."""
+    indices are all "copy the batch's own (cached) arrays, fill the padding by a formula" segments.
 
-    def __init__(self, lit_model, optimizer, sizes: Dict[str, int], template, grad_sync=None, grad_bucket=None):
+    ``clip_grad_norm`` / ``loss_scale`` / ``skip_nonfinite`` (see :func:`guard_config`; all off by default, and the step
+    then issues exactly the launches it always did): a gradient guard between the backward and Adam, on the device --
+    the backward is seeded with the loss scale read from ``guard.scale`` (the forward and the returned losses are
+    unscaled), ``ops.grad_guard`` decides clip factor / skip / next scale, the guarded Adam applies them.  ``guard``: the
+    ``ops.GuardState`` to share (a :class:`GraphedTrainer` hands all its buckets one)."""
+
+    def __init__(self, lit_model, optimizer, sizes: Dict[str, int], template, grad_sync=None, grad_bucket=None,
+                 clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False, guard=None):
+        self.guard_cfg = guard_config(clip_grad_norm, loss_scale, skip_nonfinite)
         self.exchange = cap.exchange_of(grad_sync, grad_bucket)
         self.split = self.exchange.split
         if self.exchange.bucket is not None:
@@ -138,6 +184,8 @@ class GraphedTrainStep:
         self.hyper = z(4, dtype=torch.float64)
         self._hyper_on_device = USE_ADAM_KERNEL and ops.adam_hyper(optimizer) is not None
         self._e_loss = torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev)          # d / d out of out[3], the total loss
+        # (guarded: [3] is overwritten with the loss scale at the head of every step, by a device-side copy)
+        self.guard = (guard if guard is not None else make_guard(self.guard_cfg, optimizer, dev)) if self.guard_cfg else None
         self.out: Optional[Tensor] = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.graph_opt: Optional[torch.cuda.CUDAGraph] = None      # split mode (grad_sync): Adam as a graph of its own
@@ -245,14 +293,24 @@ class GraphedTrainStep:
 
     # ------------------------------------------------------------------------------------------- the step
     def _run(self, warm: bool = False) -> None:
-        self._opt_step(self._run_grads(self.defer_sums, adam_counters=not warm and not self.split))
+        self._opt_step(self._run_grads(self.defer_sums, adam_counters=not warm and not self.split, warm=warm), warm=warm)
 
-    def _opt_step(self, end: StepEnd) -> None:
+    def _opt_step(self, end: StepEnd, warm: bool = False) -> None:
         """Adam on the hand-written kernel (two launches for all tensors -- one when the step's first launch advanced the
         step counters; torch's fused multi-tensor Adam takes three and ~40 us for the encoder's 60 small tensors); any other
-        optimizer steps itself.  The dropout counter a merged-draws step read un-advanced moves on here."""
+        optimizer steps itself.  The dropout counter a merged-draws step read un-advanced moves on here.  Guarded (not in
+        a warm-up, which is rolled back and must not touch the guard's state): ``ops.grad_guard`` (two launches), then the
+        guarded Adam; a skipped step's counters are taken back by the guard when the draws launch advanced them."""
         inc, adv = end
         enc = self.lit.model
+        if self.guard is not None and not warm:
+            c = self.guard_cfg
+            ops.adam_init_state(self.opt)                     # (an eager first step: nothing has created the state yet)
+            ops.grad_guard(self.opt, self.guard, max_norm=c["max_norm"], growth=c["growth"], backoff=c["backoff"],
+                           growth_interval=c["growth_interval"], steps_advanced=adv)
+            ops.adam_step(self.opt, steps_advanced=adv, counter=enc._step_dev if inc else None, counter_inc=inc,
+                          hyper_dev=self.hyper, guard=self.guard)
+            return
         if USE_ADAM_KERNEL and ops.adam_step(self.opt, steps_advanced=adv, counter=enc._step_dev if inc else None,
                                              counter_inc=inc, hyper_dev=self.hyper if self._hyper_on_device else None):
             return
@@ -271,11 +329,19 @@ class GraphedTrainStep:
         if inc:
             ops.step_advance(enc._step_dev, inc)
 
-    def _run_grads(self, defer_sums: bool, adam_counters: bool) -> StepEnd:
+    def _run_grads(self, defer_sums: bool, adam_counters: bool, warm: bool = True) -> StepEnd:
         """Forward, losses, backward; ``.grad`` of the parameters and ``self.out`` set.  ``defer_sums``: see __init__.
         ``adam_counters``: the draws launch may advance Adam's step counters -- not in a warm-up, which ends in
-        ``optimizer.step()``, and not in split mode, whose empty steps replay Adam's graph without this one."""
+        ``optimizer.step()``, and not in split mode, whose empty steps replay Adam's graph without this one.
+        ``warm``: a warm-up's backward is seeded with 1 whatever the guard's loss scale is (its gradients are compared
+        and thrown away; an overflow at the initial dynamic scale is the guard's business, not the warm-up's)."""
         lit, enc, s = self.lit, self.lit.model, self.sizes
+        if self.guard is not None:
+            with torch.no_grad():                             # the backward's seed: the loss scale as the device holds it NOW
+                if warm:
+                    self._e_loss[3:4].fill_(1.0)
+                else:
+                    self._e_loss[3:4].copy_(self.guard.scale.reshape(1))
         nt = s["tx"]
         tx, bd = self.nodes["tx"], self.nodes["bd"]
         graphs = {TX_TX: self.g_tt, TX_BD: self.g_tb}
@@ -430,7 +496,7 @@ class GraphedTrainStep:
                         self._run()
                 else:                                         # forward + backward (+ pack) | <exchange> | Adam
                     with graph_capture(self.graph):
-                        end = self._run_grads(self.defer_sums, adam_counters=False)
+                        end = self._run_grads(self.defer_sums, adam_counters=False, warm=False)
                         self.exchange.pack()                  # gradients -> a bucket's flat buffer; .grad = its slices
                     self.graph_opt = torch.cuda.CUDAGraph()
                     with graph_capture(self.graph_opt, pool=self.graph.pool()):
@@ -477,13 +543,22 @@ class GraphedTrainer:
     captured, the tightest fit is used whatever it wastes, and a batch no bucket holds is an error."""
 
     def __init__(self, lit_model, optimizer, granularity: float = 1.06, max_buckets: int = 24, grad_sync=None,
-                 grad_bucket=None):
+                 grad_bucket=None, clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False):
         """Data parallelism: ``grad_bucket`` = a ``dp.FlatGradBucket`` over the model's parameters (the captured
         backward packs into its flat buffer, Adam reads its slices; per step one all-reduce and one divide run eagerly
         between the two graphs), or ``grad_sync`` = any callable that averages the tensors ``.grad`` points at IN PLACE.
         One collective per ``step`` call on every rank; ``step(None)`` is the empty step of a rank that ran out of
-        batches: zeros into the exchange, then Adam."""
+        batches: zeros into the exchange, then Adam.
+
+        ``clip_grad_norm`` / ``loss_scale`` (a float or "dynamic") / ``skip_nonfinite``: the gradient guard of
+        :class:`GraphedTrainStep`, one state (``self.guard``: ``norm``, ``scale``, ``n_skipped``, ``n_clipped``,
+        ``skipped`` as device views) shared by all buckets.  Under data parallelism the guard sits in the SECOND graph,
+        behind the exchange: it sees the averaged gradients, every rank holds the same bytes and takes the same decision
+        (a non-finite value survives a sum)."""
         self.lit, self.opt, self.granularity, self.max_buckets = lit_model, optimizer, granularity, max_buckets
+        self._guard_kw = dict(clip_grad_norm=clip_grad_norm, loss_scale=loss_scale, skip_nonfinite=skip_nonfinite)
+        cfg = guard_config(**self._guard_kw)
+        self.guard = None if cfg is None else make_guard(cfg, optimizer, next(lit_model.parameters()).device)
         self.exchange = cap.exchange_of(grad_sync, grad_bucket)
         self.buckets: List[GraphedTrainStep] = []
         self.n_captures = 0
@@ -510,6 +585,6 @@ class GraphedTrainer:
 
     def _capture(self, batch) -> GraphedTrainStep:
         made = GraphedTrainStep(self.lit, self.opt, step_bucket(batch, self.granularity), batch, self.exchange.sync,
-                                self.exchange.bucket)
+                                self.exchange.bucket, guard=self.guard, **self._guard_kw)
         self.n_captures += 1
         return made
