@@ -691,6 +691,40 @@ int segger_loss_head_supported(int32_t channels, int32_t dtype);
 int segger_loss_head_fwd(const segger_loss_head_args* args, segger_stream_t stream);
 int segger_loss_head_bwd(const segger_loss_head_args* args, segger_stream_t stream);
 
+/*
+ * segger_loss_head_ordered_fwd / _bwd: the same head with an ORDERED backward (csrc/loss_head_ordered.hip) -- the
+ * deterministic training mode.  For given inputs (the embeddings, tx_pos / tx_neg / bd_pos / bd_neg / sg_*, the weights,
+ * grad_out) every byte of out, grad_tx and grad_bd is a function of those inputs alone: no float atomic is on the
+ * route (the radix sort's integer atomics cannot show in a keys-only result), nothing depends on the scheduling or on the grid.  Same struct and the same meaning of every
+ * field, except:
+ *   tx_state, tx_next, tx_hot_id, tx_hot_acc must be NULL (there are no chains and no hot rows); tx_w [n_tx, 2] alone says
+ *   "a training step", and nothing needs zero-filling by the caller;  grad_bd [n_bd, C] fp32 is WRITTEN by the backward,
+ *   every row once (the forward does not touch it);  workspace: segger_loss_head_ordered_workspace_bytes(), 256-byte
+ *   aligned, the SAME buffer in both calls (the forward leaves the sorted contribution keys and the rows' segment offsets
+ *   in it): sized from the three counts alone, so a captured step allocates it with its other static buffers.
+ * Forward: segger_loss_head_fwd's loss kernel (+ finish, or neither with DEFER_FINISH), whose partial sums are added in a
+ *   fixed order on both paths; with tx_w given, then one key per possible contribution (2 n_tx + 2 n_bd + n_sg keys:
+ *   target row, role, contributor id; an inactive one sorts behind every row), one keys-only radix sort, one binary search
+ *   per row for its segment.  No allocation, no host wait: all of it can be captured.
+ * Backward, THE ORDER of every sum (fp32, rounded once per row):
+ *   transcript row r: (1) its own anchor term of loss_tx; (2) the terms of the triplets that name r as positive, by
+ *     ascending triplet id; (3) of those that name it as negative, by ascending triplet id; (4) the anchor term of its
+ *     segmentation triplet sg_of_tx[r]; then the row normalisation's backward when y_tx is given.  With at most 64 terms
+ *     under (2) + (3) they are added one after the other onto (1).  With more, term k of that list (k from 0, positives
+ *     first) is added to partial sum P[k mod 16], each P starting at zero and adding in list order, and the row is
+ *     ((1) + P[0] + ... + P[15]) + (4), left to right.
+ *   boundary row j: (1) its own loss_bd term, + P[0] + ... + P[15] left to right, where the list that feeds P[k mod 16]
+ *     is: (2) the loss_bd terms of the nodes that name j as positive, by ascending node; (3) as negative, by ascending
+ *     node; (4) the sampled loss_sg negatives that hit j, by ascending triplet id; and then, k counting from 0 again,
+ *     (5) j's own loss_sg positives in the order of sg_pos_indptr / sg_pos_eid.
+ *   Which of the two transcript forms a row takes is decided by the length of its list: the order is a function of the
+ *   indices only.  Every loop is bounded by the number of keys and every id read from the workspace is checked against
+ *   its matrix: a stale workspace gives wrong numbers, never a spinning kernel or an access outside the buffers.
+ */
+size_t segger_loss_head_ordered_workspace_bytes(int64_t n_tx, int64_t n_bd, int64_t n_sg);
+int segger_loss_head_ordered_fwd(const segger_loss_head_args* args, segger_stream_t stream);
+int segger_loss_head_ordered_bwd(const segger_loss_head_args* args, segger_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Positional embedder, stage 1: per-graph min / max of node positions.
  * Replaces the Python loop over graphs in Positional2dEmbedder.forward

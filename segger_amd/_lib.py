@@ -359,6 +359,9 @@ EXPORTS = {
     "segger_loss_head_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "segger_loss_head_fwd": (C.c_int, [C.POINTER(LossHeadArgs), vp]),
     "segger_loss_head_bwd": (C.c_int, [C.POINTER(LossHeadArgs), vp]),
+    "segger_loss_head_ordered_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "segger_loss_head_ordered_fwd": (C.c_int, [C.POINTER(LossHeadArgs), vp]),
+    "segger_loss_head_ordered_bwd": (C.c_int, [C.POINTER(LossHeadArgs), vp]),
     "segger_knn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "segger_knn_grid": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                   C.c_int32, C.c_int32, vp, vp, vp, C.c_size_t, vp]),

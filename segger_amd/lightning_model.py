@@ -122,6 +122,9 @@ class LitISTEncoder(_Base):
         self._graphed_trainer = None
         import os
         on = lambda name: os.environ.get(name, "").strip().lower() in ("1", "true", "yes", "on")
+        # bit-reproducible training (off by default): the loss head's ordered backward, here on the fused
+        # eager path and in every captured step; the unfused loss routes are refused
+        self.deterministic = on("SEGGER_AMD_DETERMINISTIC")
         if on("SEGGER_AMD_FAST"):
             self.fast()            # `SEGGER_AMD_FAST=1 segger segment ...`: the CLI builds the module from parsed arguments only
         elif on("SEGGER_AMD_GRAPHED"):
@@ -215,6 +218,10 @@ class LitISTEncoder(_Base):
         if (self.fused_loss_head and embeddings['tx'].is_cuda and embeddings['tx'].shape[1] % 2 == 0
                 and embeddings['tx'].shape[0] > 0 and embeddings['bd'].shape[0] > 0):
             return self._losses_fused(batch, embeddings, u_tx, u_bd, dst_neg)
+        if self.deterministic:
+            raise NotImplementedError("deterministic=True is not implemented on the unfused loss route (one autograd node per "
+                                      "loss: csrc/heads.hip's kernels add with float atomics); it needs the fused loss head "
+                                      "(fused_loss_head, embeddings on the GPU, an even width, at least one boundary)")
         tx_mask, bd_mask = batch['tx']['mask'], boundary_loss_mask(batch, batch_cache(batch))
         loss_tx = self.loss_tx.forward_masked(embeddings['tx'], batch['tx']['cluster'], tx_mask, batch_cache(batch),
                                               uniforms=u_tx)
@@ -263,7 +270,8 @@ class LitISTEncoder(_Base):
                                 (bpos, bneg, dp, dn, ix_bd["weight"], 1e-8), sg, sg_kind=self._sg_loss_type,
                                 # (of_tx: "the segmentation triplet anchored at transcript r", what lets the one-launch
                                 #  loss head gather a transcript's whole gradient row instead of scattering into it)
-                                tx_anchors_are_rows=True, sg_of_tx=of_tx if sg is not None else None)
+                                tx_anchors_are_rows=True, sg_of_tx=of_tx if sg is not None else None,
+                                deterministic=self.deterministic)
         out = ops.loss_head(z_tx, z_bd, ix_tx["head_a"], b, spec)
         return out[0], out[1], out[2], out[3]
 
@@ -281,7 +289,8 @@ class LitISTEncoder(_Base):
 
     # ------------------------------------------------- whole-step hipGraph under Lightning (opt-in, not in the reference)
     def enable_graphed_training(self, enabled: bool = True, *, clip_grad_norm: Optional[float] = None, loss_scale=None,
-                                skip_nonfinite: bool = False, **trainer_kw) -> "LitISTEncoder":
+                                skip_nonfinite: bool = False, deterministic: Optional[bool] = None,
+                                **trainer_kw) -> "LitISTEncoder":
         """Opt in BEFORE ``Trainer.fit``: every ``training_step`` becomes one hipGraph replay of the whole step (batch
         staging, forward, the three losses, backward, fused Adam: :class:`segger_amd.train_step_graph.GraphedTrainer`,
         1.3 ms instead of a host-bound 3-5 ms per default 1M-edge batch).  The module switches to Lightning's MANUAL
@@ -296,7 +305,16 @@ class LitISTEncoder(_Base):
         with an inf / NaN gradient changes nothing).  With a guard on, ``train:grad_norm`` and ``train:loss_scale`` are
         logged.  Still not available: ``accumulate_grad_batches``, ``clip_grad_value_``, norms other than L2,
         per-parameter-group settings, ``error_if_nonfinite=True``.  Single process: under data parallelism build the
-        ``GraphedTrainer`` yourself with a ``dp.FlatGradBucket``.  ``trainer_kw``: ``granularity`` / ``max_buckets``."""
+        ``GraphedTrainer`` yourself with a ``dp.FlatGradBucket``.  ``trainer_kw``: ``granularity`` / ``max_buckets``.
+
+        ``deterministic=True`` (or ``SEGGER_AMD_DETERMINISTIC=1``; None keeps what the module has): bit-identical weights
+        from a seed -- on one GPU, for one seed and one sequence of batches and buckets.  The loss head then takes its
+        ordered backward (``ops.LossHeadSpec(deterministic=True)``: no float atomic; cost: profiles/deterministic_step_before_after.txt), here
+        and on the fused eager path; the unfused loss routes raise ``NotImplementedError``."""
+        if deterministic is not None:
+            self.deterministic = bool(deterministic)
+        if self.deterministic:
+            trainer_kw = dict(trainer_kw, deterministic=True)
         if clip_grad_norm is not None or loss_scale is not None or skip_nonfinite:
             trainer_kw = dict(trainer_kw, clip_grad_norm=clip_grad_norm, loss_scale=loss_scale, skip_nonfinite=skip_nonfinite)
         self._graphed_kw = dict(trainer_kw) if enabled else None

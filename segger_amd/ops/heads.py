@@ -242,7 +242,8 @@ class LossHeadSpec:
     named forms they are read as from here on (``TxTriplets``, ``BdMetric``, ``SgTriplets``)."""
 
     def __init__(self, tx, bd, sg, sg_kind: str = "triplet", tx_anchors_are_rows: bool = False, sg_of_tx=None,
-                 tx_state: Optional[Tensor] = None, grad_out_hint: Optional[Tensor] = None, defer_finish: bool = False):
+                 tx_state: Optional[Tensor] = None, grad_out_hint: Optional[Tensor] = None, defer_finish: bool = False,
+                 deterministic: bool = False):
         self.tx, self.bd, self.sg = TxTriplets(*tx), BdMetric(*bd), (None if sg is None else SgTriplets(*sg))
         self.sg_kind = sg_kind                                             # "bce": margin / eps unused
         # loss_tx's anchors are arange(n_tx) (possibly with -1 positives = skipped): lets the backward STORE the anchors'
@@ -258,6 +259,11 @@ class LossHeadSpec:
         # the returned loss tensor is then only valid once the backward has run (a captured training step reads it after the
         # replay); the caller promises that a backward with exactly the hinted gradient follows
         self.defer_finish = bool(defer_finish)
+        # the ordered backward of the one-launch head (segger_loss_head_ordered_fwd / _bwd): every byte of the gradients and
+        # the losses a function of the inputs alone, no float atomic; the routes through csrc/heads.hip's atomic kernels
+        # ("anchor_rows", "kernel_by_kernel", and the atomic side launch of a transcript that anchors two segmentation
+        # triplets) are refused with a NotImplementedError -- never silently non-deterministic
+        self.deterministic = bool(deterministic)
 
 
 def _indices(spec: LossHeadSpec, anchors: bool = True) -> _Indices:
@@ -433,8 +439,10 @@ def _loss_head_args(z_tx, z_bd, a, b, idx: _Indices, spec: LossHeadSpec, graw, w
     g.a, g.b, g.grad_raw = a.data_ptr(), b.data_ptr(), graw.data_ptr()
     g.workspace, g.workspace_bytes, g.ticket = ws.data_ptr(), ws.numel(), _ticket(z_tx.device).data_ptr()
     if st is not None:
-        g.tx_w, g.tx_state, g.tx_next, g.grad_bd = st.tx_w.data_ptr(), st.head.data_ptr(), st.nxt.data_ptr(), st.gbd.data_ptr()
-        g.tx_hot_id, g.tx_hot_acc = st.nxt[2 * n_tx:].data_ptr(), st.hot_acc.data_ptr()
+        g.tx_w, g.grad_bd = st.tx_w.data_ptr(), st.gbd.data_ptr()
+        if st.head is not None:                      # (the ordered route keeps no chains and no hot rows)
+            g.tx_state, g.tx_next = st.head.data_ptr(), st.nxt.data_ptr()
+            g.tx_hot_id, g.tx_hot_acc = st.nxt[2 * n_tx:].data_ptr(), st.hot_acc.data_ptr()
     return g
 
 
@@ -462,18 +470,25 @@ class _LossHeadFused(torch.autograd.Function):
         n_sg = int(idx.sg_src.numel()) if idx.sg_src is not None else 0
         out = torch.empty(4, dtype=torch.float32, device=dev)
         graw = torch.empty(3, dtype=torch.float32, device=dev)
-        ws = torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, n_sg), dtype=torch.uint8, device=dev)
+        ordered = spec.deterministic
+        if ordered and n_sg and not callable(spec.sg.anchors_unique) and not spec.sg.anchors_unique:
+            raise NotImplementedError(_REFUSED % "the atomic side launch (segger_triplet_bwd) of segmentation triplets whose "
+                                                 "anchors are not unique")
+        ws_bytes = (lib.segger_loss_head_ordered_workspace_bytes if ordered else lib.segger_loss_head_workspace_bytes)
+        ws = torch.empty(ws_bytes(n_tx, n_bd, n_sg), dtype=torch.uint8, device=dev)
         st = None
         if need:
             tx_w = torch.empty((n_tx, 2), dtype=torch.float32, device=dev)
-            head = spec.tx_state
-            if head is None:
-                head = torch.zeros(2 * n_tx + 4, dtype=torch.int32, device=dev)
-            elif head.dtype != torch.int32 or head.numel() < 2 * n_tx + 4 or not head.is_contiguous():
-                raise ValueError("loss_head: tx_state must be a contiguous int32 [2 n_tx + 4] tensor (zero-filled)")
-            n_hot = int(lib.segger_loss_head_max_hot_rows(n_tx))
-            nxt = torch.empty(2 * n_tx + n_tx + n_hot, dtype=torch.int32, device=dev)        # chain links | hot ids + arrivals
-            hot_acc = torch.empty((n_hot, c), dtype=torch.float32, device=dev)
+            head = nxt = hot_acc = None                      # (the ordered route: no chains, no hot rows; tx_state unused)
+            if not ordered:
+                head = spec.tx_state
+                if head is None:
+                    head = torch.zeros(2 * n_tx + 4, dtype=torch.int32, device=dev)
+                elif head.dtype != torch.int32 or head.numel() < 2 * n_tx + 4 or not head.is_contiguous():
+                    raise ValueError("loss_head: tx_state must be a contiguous int32 [2 n_tx + 4] tensor (zero-filled)")
+                n_hot = int(lib.segger_loss_head_max_hot_rows(n_tx))
+                nxt = torch.empty(2 * n_tx + n_tx + n_hot, dtype=torch.int32, device=dev)    # chain links | hot ids + arrivals
+                hot_acc = torch.empty((n_hot, c), dtype=torch.float32, device=dev)
             gbd = torch.empty((n_bd, c), dtype=torch.float32, device=dev)
             hint = spec.grad_out_hint
             if hint is not None:
@@ -486,8 +501,8 @@ class _LossHeadFused(torch.autograd.Function):
         if st is not None and st.hint is not None:
             g.grad_out, g.reserved_ = st.hint.data_ptr(), (_lib.LOSS_HEAD_DEFER_FINISH if st.deferred else 0)
         with _lib.on_device(dev):
-            rc = lib.segger_loss_head_fwd(C.byref(g), _lib.stream_ptr(dev))
-        _lib.check(rc, "segger_loss_head_fwd")
+            rc = (lib.segger_loss_head_ordered_fwd if ordered else lib.segger_loss_head_fwd)(C.byref(g), _lib.stream_ptr(dev))
+        _lib.check(rc, "segger_loss_head_ordered_fwd" if ordered else "segger_loss_head_fwd")
         if need:
             ctx.save_for_backward(t_tx, t_bd, z_tx, z_bd, a, b, *idx)
             ctx.spec, ctx.state, ctx.prenorm, ctx.eps = spec, st, prenorm, (float(eps_tx), float(eps_bd))
@@ -501,7 +516,8 @@ class _LossHeadFused(torch.autograd.Function):
         dev, dt = z_tx.device, z_tx.dtype
         n_tx, c = int(z_tx.shape[0]), int(z_tx.shape[1])
         n_bd = int(z_bd.shape[0])
-        if getattr(ctx, "_ran", False):
+        ordered = spec.deterministic
+        if getattr(ctx, "_ran", False) and not ordered:             # (the ordered route writes every row: nothing to re-arm)
             # a second backward over the same graph (retain_graph=True): the forward launch zero-filled the boundary
             # gradient and armed the hot rows' accumulators / arrival counters ONCE -- re-arm them, or this pass would add
             # on top of the first one's sums and never finish a hot row
@@ -517,6 +533,9 @@ class _LossHeadFused(torch.autograd.Function):
         uniq, of_tx = False, None
         if n_sg:
             uniq = _anchors_unique(sg.anchors_unique)
+            if ordered and not uniq:
+                raise NotImplementedError(_REFUSED % "the atomic side launch (segger_triplet_bwd) of segmentation triplets "
+                                                     "whose anchors are not unique")
             if uniq:
                 of_tx = spec.sg_of_tx() if callable(spec.sg_of_tx) else spec.sg_of_tx
                 if of_tx is None:
@@ -530,8 +549,9 @@ class _LossHeadFused(torch.autograd.Function):
         out_dummy = torch.empty(4, dtype=torch.float32, device=dev)
         if st.deferred and not hinted:
             raise RuntimeError("loss_head: defer_finish promised a backward with the hinted gradient")
-        ws = st.ws if st.deferred else torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, n_sg), dtype=torch.uint8,
-                                                   device=dev)
+        # (the ordered route's workspace holds the forward's sorted keys: always the forward's own)
+        ws = st.ws if st.deferred or ordered else torch.empty(lib.segger_loss_head_workspace_bytes(n_tx, n_bd, n_sg),
+                                                              dtype=torch.uint8, device=dev)
         g = _loss_head_args(z_tx, z_bd, a, b, idx, spec, st.graw, ws, st)
         g.out = out_dummy.data_ptr()
         if st.deferred:
@@ -549,7 +569,10 @@ class _LossHeadFused(torch.autograd.Function):
             if not hinted:                                                       # (else the forward left the factors behind)
                 _lib.check(lib.segger_loss_combine_bwd(g_out.data_ptr(), a.data_ptr(), b.data_ptr(), 3, st.graw.data_ptr(),
                                                        stream), "segger_loss_combine_bwd")
-            _lib.check(lib.segger_loss_head_bwd(C.byref(g), stream), "segger_loss_head_bwd")
+            if ordered:
+                _lib.check(lib.segger_loss_head_ordered_bwd(C.byref(g), stream), "segger_loss_head_ordered_bwd")
+            else:
+                _lib.check(lib.segger_loss_head_bwd(C.byref(g), stream), "segger_loss_head_bwd")
             if n_sg and not uniq:
                 # a transcript anchors two segmentation triplets (never in segger's data): their anchor terms by atomics
                 # on top of the rows just written, the boundary side having been done by the launch above
@@ -575,8 +598,13 @@ class _LossHeadFused(torch.autograd.Function):
         return gtx, st.gbd.to(dt), None, None, None, None, None, None, None
 
 
+_REFUSED = ("loss_head: deterministic=True is not implemented on the route through %s: its kernels (csrc/heads.hip) add "
+            "with float atomics, whose order varies from run to run; only the one-launch head has an ordered backward")
+
+
 def loss_head_route(z_tx: Tensor, z_bd: Tensor, spec: LossHeadSpec) -> str:
-    """-> "one_launch_prenorm" | "one_launch" | "anchor_rows" | "kernel_by_kernel": the route :func:`loss_head` takes."""
+    """-> "one_launch_prenorm" | "one_launch" | "anchor_rows" | "kernel_by_kernel": the route :func:`loss_head` takes.
+    With ``spec.deterministic`` the two one-launch routes run the ordered backward and the other two are refused."""
     pt = _prenorm_of(z_tx)
     if loss_head_fused_supported(z_tx, z_bd, spec):
         pb = _prenorm_of(z_bd)
@@ -604,6 +632,8 @@ def loss_head(z_tx: Tensor, z_bd: Tensor, a: Tensor, b: Tensor, spec: LossHeadSp
     ``LitISTEncoder.get_losses`` and their weighted sum as one autograd node (see :class:`_LossHead`).  ``a`` / ``b``:
     float32[3] on the device."""
     route = loss_head_route(z_tx, z_bd, spec)
+    if spec.deterministic and route in ("anchor_rows", "kernel_by_kernel"):
+        raise NotImplementedError(_REFUSED % f'"{route}" (the separate triplet, metric and loss_sg launches)')
     if route == "one_launch_prenorm":
         (y_tx, eps_tx), (y_bd, eps_bd) = _prenorm_of(z_tx), _prenorm_of(z_bd)
         return _LossHeadFused.apply(y_tx, y_bd, a, b, spec, z_tx.detach(), z_bd.detach(), eps_tx, eps_bd)

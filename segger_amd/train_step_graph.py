@@ -120,11 +120,18 @@ class GraphedTrainStep:
     then issues exactly the launches it always did): a gradient guard between the backward and Adam, on the device --
     the backward is seeded with the loss scale read from ``guard.scale`` (the forward and the returned losses are
     unscaled), ``ops.grad_guard`` decides clip factor / skip / next scale, the guarded Adam applies them.  ``guard``: the
-    ``ops.GuardState`` to share (a :class:`GraphedTrainer` hands all its buckets one)."""
+    ``ops.GuardState`` to share (a :class:`GraphedTrainer` hands all its buckets one).
+
+    ``deterministic`` (off by default, and the step then issues exactly the launches it always did): the loss head takes
+    its ordered backward (``ops.LossHeadSpec(deterministic=True)``) -- the one place of a step where float atomics landed
+    in a varying order -- so that the same seed and the same batches give the same bytes: parameters, Adam state, losses
+    and the guard's state.  The warm-up's comparison of deferred against immediate sums then demands equal bytes."""
 
     def __init__(self, lit_model, optimizer, sizes: Dict[str, int], template, grad_sync=None, grad_bucket=None,
-                 clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False, guard=None):
+                 clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False, guard=None,
+                 deterministic: bool = False):
         self.guard_cfg = guard_config(clip_grad_norm, loss_scale, skip_nonfinite)
+        self.deterministic = bool(deterministic)
         self.exchange = cap.exchange_of(grad_sync, grad_bucket)
         self.split = self.exchange.split
         if self.exchange.bucket is not None:
@@ -209,7 +216,10 @@ class GraphedTrainStep:
         # autograd node READS a parameter gradient before the backward ends (a parameter used by two nodes has its two
         # gradients added on the spot): verified numerically during the warm-up of every capture, see _warm_up, which
         # settles this for the runs that follow
-        self.defer_sums = True
+        # (deterministic: the queued and the immediate sums add in two fixed but DIFFERENT orders -- conv.att's gradient differs
+        # by an ulp -- so the warm-up's byte comparison could never pass: the sums are launched where they are produced,
+        # without the warm-up's second run)
+        self.defer_sums = not self.deterministic
 
     @staticmethod
     def _bd_dtype(lit_model, template):
@@ -389,7 +399,8 @@ class GraphedTrainStep:
                                 (self.sg_src, self.sg_pos, dst_neg, lit._sg_margin, 1e-6, self.g_tb.by_dst, True),
                                 sg_kind=lit._sg_loss_type, tx_anchors_are_rows=True, sg_of_tx=self.sg_of_tx,
                                 tx_state=self.tx_state, grad_out_hint=self._e_loss,
-                                defer_finish=DEFER_LOSS_FINISH)      # the losses are read after the backward (self.out after the replay)
+                                defer_finish=DEFER_LOSS_FINISH,      # the losses are read after the backward (self.out after the replay)
+                                deterministic=self.deterministic)
         out = ops.loss_head(z["tx"], z["bd"], self.head_a, self.scal[3:6], spec)
         if defer_sums:                                        # ~30 partial sums of the backward as one launch
             with ops.deferred_reductions(self.dev):
@@ -425,7 +436,12 @@ class GraphedTrainStep:
                     # differ by a few per cent of a small gradient (seen: 1.4 % on lin_last's bias); a gradient that was
                     # read before its sum was launched is garbage, not a rounding difference: 10 % of the largest
                     # entry separates the two
-                    if not bool(torch.isfinite(g).all()) or diff > 0.1 * scale + 1e-6:
+                    # (deterministic: no atomic decides an order anywhere in the step -- the two runs give equal bytes)
+                    if self.deterministic:
+                        differs = not torch.equal(g, r)
+                    else:
+                        differs = not bool(torch.isfinite(g).all()) or diff > 0.1 * scale + 1e-6
+                    if differs:
                         why = f"{names.get(id(p))}: differs by {diff:.3e} (scale {scale:.3e})"
                 if why:
                     break
@@ -543,7 +559,8 @@ class GraphedTrainer:
     captured, the tightest fit is used whatever it wastes, and a batch no bucket holds is an error."""
 
     def __init__(self, lit_model, optimizer, granularity: float = 1.06, max_buckets: int = 24, grad_sync=None,
-                 grad_bucket=None, clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False):
+                 grad_bucket=None, clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False,
+                 deterministic: bool = False):
         """Data parallelism: ``grad_bucket`` = a ``dp.FlatGradBucket`` over the model's parameters (the captured
         backward packs into its flat buffer, Adam reads its slices; per step one all-reduce and one divide run eagerly
         between the two graphs), or ``grad_sync`` = any callable that averages the tensors ``.grad`` points at IN PLACE.
@@ -554,7 +571,13 @@ class GraphedTrainer:
         :class:`GraphedTrainStep`, one state (``self.guard``: ``norm``, ``scale``, ``n_skipped``, ``n_clipped``,
         ``skipped`` as device views) shared by all buckets.  Under data parallelism the guard sits in the SECOND graph,
         behind the exchange: it sees the averaged gradients, every rank holds the same bytes and takes the same decision
-        (a non-finite value survives a sum)."""
+        (a non-finite value survives a sum).
+
+        ``deterministic``: every bucket's step takes the loss head's ordered backward (:class:`GraphedTrainStep`): one GPU,
+        one seed and one sequence of batches and buckets give bit-identical parameters, Adam state and losses.  Across
+        different bucket sequences only as far as padding stays out of every sum; under data parallelism only as far as
+        the collective is reproducible."""
+        self.deterministic = bool(deterministic)
         self.lit, self.opt, self.granularity, self.max_buckets = lit_model, optimizer, granularity, max_buckets
         self._guard_kw = dict(clip_grad_norm=clip_grad_norm, loss_scale=loss_scale, skip_nonfinite=skip_nonfinite)
         cfg = guard_config(**self._guard_kw)
@@ -585,6 +608,6 @@ class GraphedTrainer:
 
     def _capture(self, batch) -> GraphedTrainStep:
         made = GraphedTrainStep(self.lit, self.opt, step_bucket(batch, self.granularity), batch, self.exchange.sync,
-                                self.exchange.bucket, guard=self.guard, **self._guard_kw)
+                                self.exchange.bucket, guard=self.guard, deterministic=self.deterministic, **self._guard_kw)
         self.n_captures += 1
         return made
