@@ -267,11 +267,15 @@ int segger_gatv2_bwd(const segger_gatv2_bwd_args* args, segger_stream_t stream);
 /* The backward of both edge types of one HeteroConv layer (ist_encoder.py:109-134 under autograd): `a` a two-pass edge
  * type (tx-neighbors-tx), `b` a one-pass one (src_unique: tx-belongs-bd) whose grad_xl is the matrix `a` zero-fills
  * (a->zero_rows_out == b->grad_xl with b->grad_xl_zeroed set, or neither set).  Same results as segger_gatv2_bwd(a)
- * followed by segger_gatv2_bwd(b).  For batches of at most SEGGER_BWD_PAIR_MAX_ROWS source nodes (environment
- * override of the same name, read once) of one specialised geometry and storage type, with a's destinations and b's
- * sources indexing the same nodes, the zero fill moves into a's DESTINATION pass and a's source pass shares ONE launch
- * with b's destination pass (b's few hundred latency-bound blocks run beside a's); otherwise the two calls run as they
- * are. */
+ * followed by segger_gatv2_bwd(b) (b's row gradients and sums to rounding: inside the merged kernel its body walks
+ * another number of rows at a time and sums grad_att by endpoint).  At every batch size -- unless the environment
+ * variable SEGGER_BWD_PAIR_MAX_ROWS (read once) caps the source nodes of `a` up to which this happens; 0: never -- for
+ * one specialised geometry and storage type, with `b` in wave-per-row mode and a's destinations and b's sources
+ * indexing the same nodes, the zero fill moves into a's DESTINATION pass, a's source pass shares ONE launch with b's
+ * destination pass (b's latency-bound blocks run beside a's), and the slab sums of both edge types share one launch
+ * pair; otherwise the two calls run as they are.  SEGGER_BWD_ONE_PASS_IN_PAIR_KERNEL=1 (read once) makes
+ * segger_gatv2_bwd launch a wave-per-row one-pass backward as that merged kernel with an empty `a` side: the merged
+ * launch's body for `b` by itself, bit for bit, for comparisons and timing. */
 int segger_gatv2_bwd_pair(const segger_gatv2_bwd_args* a, const segger_gatv2_bwd_args* b, segger_stream_t stream);
 /*
  * segger_dropout_bits: the attention-dropout mask of n_seeds layers as bit planes over the slots of one CSR view:

@@ -11,9 +11,9 @@ namespace segger {
 // its columns are summed into the same partials, split into row ranges of its own.
 constexpr int kSlabSplits = 128;
 
-__global__ __launch_bounds__(256) void slab_reduce_stage1(const float* __restrict__ slab, int64_t nblocks, int width,
-                                                         const float* __restrict__ slab2, int64_t nblocks2, int width2,
-                                                         float* __restrict__ part) {
+__device__ __forceinline__ void slab_stage1_body(const float* __restrict__ slab, int64_t nblocks, int width,
+                                                 const float* __restrict__ slab2, int64_t nblocks2, int width2,
+                                                 float* __restrict__ part) {
   __shared__ float sm[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int colx = blockIdx.x * 64 + lane;
@@ -42,14 +42,44 @@ __global__ __launch_bounds__(256) void slab_reduce_stage1(const float* __restric
   if (wave == 0 && colx < width) part[(int64_t)blockIdx.y * width + colx] = sm[0][lane] + sm[1][lane] + sm[2][lane] + sm[3][lane];
 }
 
-__global__ __launch_bounds__(256) void slab_reduce_stage2(const float* __restrict__ part, int width, int hc,
-                                                         float* __restrict__ grad_att, float* __restrict__ grad_bias) {
+__device__ __forceinline__ void slab_stage2_body(const float* __restrict__ part, int width, int hc,
+                                                 float* __restrict__ grad_att, float* __restrict__ grad_bias) {
   const int colx = blockIdx.x * 256 + threadIdx.x;
   if (colx >= width) return;
   float t = 0.f;
   for (int r = 0; r < kSlabSplits; ++r) t += part[(int64_t)r * width + colx];
   if (colx < hc) grad_att[colx] = t;
   else if (grad_bias) grad_bias[colx - hc] = t;
+}
+
+__global__ __launch_bounds__(256) void slab_reduce_stage1(const float* __restrict__ slab, int64_t nblocks, int width,
+                                                         const float* __restrict__ slab2, int64_t nblocks2, int width2,
+                                                         float* __restrict__ part) {
+  slab_stage1_body(slab, nblocks, width, slab2, nblocks2, width2, part);
+}
+__global__ __launch_bounds__(256) void slab_reduce_stage2(const float* __restrict__ part, int width, int hc,
+                                                         float* __restrict__ grad_att, float* __restrict__ grad_bias) {
+  slab_stage2_body(part, width, hc, grad_att, grad_bias);
+}
+
+// The sums of TWO backwards (the edge types of one hetero layer: segger_gatv2_bwd_pair) in one stage-1 / stage-2 pair:
+// blockIdx.z picks the job, every job runs the body above on its own slabs and partials -- each sum is the sum, term by
+// term and in the same order, that its own launch pair would form.  The grid covers the wider job.
+struct SlabJob {
+  const float *slab, *slab2; float *part, *grad_att, *grad_bias;
+  int64_t nblocks, nblocks2;
+  int width, width2, hc;
+};
+struct SlabJobs { SlabJob job[2]; };
+
+__global__ __launch_bounds__(256) void slab_reduce_stage1_pair(SlabJobs j) {
+  const SlabJob& s = j.job[blockIdx.z];
+  if ((int)blockIdx.x * 64 >= s.width) return;            // (the whole workgroup: no barrier is left waiting)
+  slab_stage1_body(s.slab, s.nblocks, s.width, s.slab2, s.nblocks2, s.width2, s.part);
+}
+__global__ __launch_bounds__(256) void slab_reduce_stage2_pair(SlabJobs j) {
+  const SlabJob& s = j.job[blockIdx.z];
+  slab_stage2_body(s.part, s.width, s.hc, s.grad_att, s.grad_bias);
 }
 
 // zero the first `pieces` 16-byte pieces of every row of a pitched matrix
@@ -326,13 +356,17 @@ int bwd_zero_fill(const GatBwdPlan& b, hipStream_t stream) {
 
 // grad_att / grad_bias from the per-block slabs the passes left behind: dst_blocks rows of the destination pass and,
 // after a source pass, src_blocks rows of grad_att alone
+ReduceSeg slab_seg(const GatBwdPlan& b, int64_t dst_blocks, int64_t src_blocks) {
+  const int hc = b.heads * b.channels;
+  return ReduceSeg{b.ws.slab, dst_blocks, 2 * hc, hc, b.grad_att, b.grad_bias, b.ws.part, b.ws.slab_src,
+                   (int32_t)src_blocks, src_blocks > 0 ? hc : 0};
+}
+
 int bwd_reduce_slab(const GatBwdPlan& b, int64_t dst_blocks, int64_t src_blocks, hipStream_t stream) {
   if (!b.specialised) return SEGGER_OK;                   // the generic kernels write grad_att / grad_bias themselves
   const int hc = b.heads * b.channels, width = 2 * hc;
   const int width2 = src_blocks > 0 ? hc : 0;
-  if (defer_reduce(ReduceSeg{b.ws.slab, dst_blocks, width, hc, b.grad_att, b.grad_bias, b.ws.part, b.ws.slab_src,
-                             (int32_t)src_blocks, width2}, stream))
-    return SEGGER_OK;
+  if (defer_reduce(slab_seg(b, dst_blocks, src_blocks), stream)) return SEGGER_OK;
   hipLaunchKernelGGL(slab_reduce_stage1, dim3((width + 63) / 64, kSlabSplits), dim3(256), 0, stream,
                      b.ws.slab, dst_blocks, width, b.ws.slab_src, src_blocks, width2, b.ws.part);
   hipLaunchKernelGGL(slab_reduce_stage2, dim3((width + 255) / 256), dim3(256), 0, stream,
@@ -341,13 +375,44 @@ int bwd_reduce_slab(const GatBwdPlan& b, int64_t dst_blocks, int64_t src_blocks,
   return SEGGER_OK;
 }
 
+// The two sums of a merged backward pair (`a`: both passes' slabs, `b`: the one-pass form's) in one launch pair instead of
+// two.  With the partial-sum queue of reduce.hip active (captured steps) both go to it, as they do one by one.
+int bwd_reduce_slab_pair(const GatBwdPlan& a, int64_t a_dst_blocks, int64_t a_src_blocks, const GatBwdPlan& b,
+                         int64_t b_dst_blocks, hipStream_t stream) {
+  const int hc_a = a.heads * a.channels, hc_b = b.heads * b.channels;
+  if (defer_reduce(slab_seg(a, a_dst_blocks, a_src_blocks), stream)) return bwd_reduce_slab(b, b_dst_blocks, 0, stream);
+  SlabJobs j{};
+  j.job[0] = SlabJob{a.ws.slab, a.ws.slab_src, a.ws.part, a.grad_att, a.grad_bias, a_dst_blocks, a_src_blocks,
+                     2 * hc_a, a_src_blocks > 0 ? hc_a : 0, hc_a};
+  j.job[1] = SlabJob{b.ws.slab, nullptr, b.ws.part, b.grad_att, b.grad_bias, b_dst_blocks, 0, 2 * hc_b, 0, hc_b};
+  const int width = 2 * (hc_a > hc_b ? hc_a : hc_b);
+  hipLaunchKernelGGL(slab_reduce_stage1_pair, dim3((width + 63) / 64, kSlabSplits, 2), dim3(256), 0, stream, j);
+  hipLaunchKernelGGL(slab_reduce_stage2_pair, dim3((width + 255) / 256, 1, 2), dim3(256), 0, stream, j);
+  SEGGER_LAUNCH_CHECK("slab_reduce pair kernels");
+  return SEGGER_OK;
+}
+
+// SEGGER_BWD_ONE_PASS_IN_PAIR_KERNEL=1 (read once): segger_gatv2_bwd runs the wave-per-row one-pass form as the merged
+// kernel of segger_gatv2_bwd_pair with an EMPTY source-pass side instead of as gatv2_bwd_dst_kernel -- the merged launch's
+// tx-belongs-bd body by itself, for bit comparisons against the merged launch and for timing.  Results agree with the
+// default kernel to rounding (another number of rows in flight, the lean grad_att form).
+bool bwd_one_pass_in_pair_kernel() {
+  static const bool v = [] { const char* e = getenv("SEGGER_BWD_ONE_PASS_IN_PAIR_KERNEL"); return e && atoi(e) != 0; }();
+  return v;
+}
+
 // passes: 0 both, 1 the destination pass with its sums, 2 the source pass alone, 3 the destination pass without sums
 int run_bwd(const GatBwdPlan& b, int passes, hipStream_t stream) {
   SEGGER_REQUIRE(passes >= 0 && passes <= 3, "segger_gatv2_bwd: passes must be 0 (both), 1 (destination), 2 (source) or 3");
   if (passes != 2) {
     if (b.zero_fill) CHECK_RC(bwd_zero_fill(b, stream));
     if (b.n_dst > 0) {
-      CHECK_RC(launch_pass(Pass::BwdDst, b, b.dst, b.wpr_dst, stream));
+      if (b.one_pass && b.specialised && b.wpr_dst && bwd_one_pass_in_pair_kernel()) {
+        const GatParams none{};                            // (no block of the source pass: its parameters are never read)
+        CHECK_RC(launch_specialised(Kind::BwdSrcDstPair, b.dtype, none, &b.dst, b.heads, b.channels, false, stream));
+      } else {
+        CHECK_RC(launch_pass(Pass::BwdDst, b, b.dst, b.wpr_dst, stream));
+      }
       // the one-pass form and passes = 1 end here: the sums of the destination pass alone
       if (b.one_pass || passes == 1) CHECK_RC(bwd_reduce_slab(b, b.dst.nblocks, 0, stream));
     } else {                                                // no destination: the sums are zero
@@ -362,8 +427,11 @@ int run_bwd(const GatBwdPlan& b, int passes, hipStream_t stream) {
   return SEGGER_OK;
 }
 
-// largest tx-neighbors-tx source count for which segger_gatv2_bwd_pair merges the launches (what it saves is a fixed
-// ~5 us per layer: the launch of a kernel that is latency-bound at these sizes)
+// largest tx-neighbors-tx source count for which segger_gatv2_bwd_pair merges the launches: every size unless the
+// environment says otherwise.  What the merger saves is the one-pass launch, latency-bound at every size (~5 us per layer
+// on the captured 1M-edge step, 68 us per layer on the C2 tile), and one slab-sum launch pair.
+// SEGGER_BWD_PAIR_MAX_ROWS=262144 restores the route rule of the builds before the merged kernel kept the source pass's
+// occupancy (separate launches above that size), =0 separate launches at every size: both routes from one build.
 int64_t bwd_pair_max_rows() {
   static const int64_t v = [] {
     const char* e = getenv("SEGGER_BWD_PAIR_MAX_ROWS");
@@ -438,7 +506,7 @@ extern "C" int segger_gatv2_bwd_pair(const segger_gatv2_bwd_args* a, const segge
   // and b a one-pass, wave-per-row one of the same specialised geometry and storage type; both non-empty; b's grad_xl
   // is the matrix a was asked to zero-fill (or a was asked for none and b's is not zeroed yet) and a's destinations
   // index the same nodes as b's sources -- a's DESTINATION pass then zero-fills it, since its source pass now runs
-  // beside b's stores; and the batch is small enough for the merger to pay (bwd_pair_max_rows)
+  // beside b's stores; and the route switch allows the size (bwd_pair_max_rows: every size by default)
   const bool zero_by_a = a->zero_rows_out ? (a->zero_rows_out == b->grad_xl && a->ld_zero == b->ld_gxl && b->grad_xl_zeroed)
                                           : !b->grad_xl_zeroed;
   const bool one = !pa.one_pass && pb.one_pass && pa.dtype == pb.dtype && pa.heads == pb.heads && pa.channels == pb.channels &&
@@ -454,8 +522,7 @@ extern "C" int segger_gatv2_bwd_pair(const segger_gatv2_bwd_args* a, const segge
   CHECK_RC(src_pass(a, pa, nullptr, 0, a_src));
   CHECK_RC(launch_pass(Pass::BwdDst, pa, a_dst, false, stream));
   CHECK_RC(launch_specialised(Kind::BwdSrcDstPair, pa.dtype, a_src, &pb.dst, pa.heads, pa.channels, false, stream));
-  CHECK_RC(bwd_reduce_slab(pa, a_dst.nblocks, a_src.nblocks, stream));
-  return bwd_reduce_slab(pb, pb.dst.nblocks, 0, stream);
+  return bwd_reduce_slab_pair(pa, a_dst.nblocks, a_src.nblocks, pb, pb.dst.nblocks, stream);
 }
 
 extern "C" int segger_gatv2_has_specialised(int32_t heads, int32_t channels) {

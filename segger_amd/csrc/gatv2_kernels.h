@@ -660,7 +660,11 @@ __global__ __launch_bounds__(256, SEGGER_FWD_WAVES) void gatv2_fwd_pair_kernel(G
 // The caller zero-fills grad_xl first (sources without an out-edge).  Without a source pass there are no by-source
 // sums, so the direct form keeps grad_att as per-edge sums (Pt, Qt).
 // (the direct form keeps 8 more values per lane live: it is built for 2 waves per SIMD instead of spilling)
-template <typename T, int H, int LPH, bool WPR, bool DIRECT, int UFORCE = 0>
+// LEAN (direct form only; the merged launch below, where this body has to fit the SOURCE pass's register budget): with one
+// out-edge per source the by-source half of the endpoint split above is a per-EDGE term, x_l[i] * (c1 de + c2 de sgn(t)),
+// and the by-destination half the per-row term of the two-pass form.  One packed accumulator (Pt) takes both instead of
+// Pt and Qt: the same two packed operations per channel pair and edge, eight registers fewer.
+template <typename T, int H, int LPH, bool WPR, bool DIRECT, int UFORCE = 0, bool LEAN = false>
 __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t bid) {
   using G = Geo<H, LPH>;
   // 4 rows in flight measured -2.6 % on the flagship geometry (H = 2, group-per-row); the other variants would spill
@@ -708,6 +712,8 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
     int ch0r = L.ch0;
     asm volatile("" : "+v"(ch0r));
     const int ch0 = ch0r;                      // (shadows the function-scope ch0 for the rest of this iteration)
+    int hr = L.h;                              // likewise the head: `dsum + 2 h` is the pointer pair the lean form spills
+    if constexpr (LEAN) asm volatile("" : "+v"(hr));
 
     f32x2 nxr[4], g[4], Sg[4];
     float D = 0.f, lse = 0.f, Sde = 0.f;
@@ -731,20 +737,14 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
         d2 = pk_fma(g[i], pr[i] - b, d2);
       }
       D = d2.x + d2.y;
-      lse = p.lse[(int64_t)row * H + h];
+      lse = p.lse[(int64_t)row * H + hr];
     }
     D = lane_block_sum<LPH>(D);
     const bool writer = row_ok && L.lane_on && (!WPR || L.grp == 0);
     if (writer) {
-      if (p.zero_rows) {             // zero row of another matrix indexed by THESE rows (the pair form of the backward)
-        f32x2 z[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) z[i] = splat(0.f);
-        store_pairs(static_cast<T*>(p.zero_rows) + row * p.ld_zero + ch0, z);
-      }
       store_pairs(static_cast<T*>(p.gpre) + row * p.ld_gp + ch0, g);
       if (head_leader)      // (lse, D) side by side: the source pass fetches both with one 8-byte load per (edge, head)
-        *reinterpret_cast<float2*>(p.dsum + ((int64_t)row * H + h) * 2) = float2{lse, D};
+        *reinterpret_cast<float2*>(p.dsum + ((int64_t)row * H + hr) * 2) = float2{lse, D};
 #pragma unroll
       for (int i = 0; i < 4; ++i) dbias[i] = dbias[i] + g[i];
     }
@@ -783,8 +783,12 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
           const f32x2 sg = f32x2{sign_mul(nde, nt[i].x), sign_mul(nde, nt[i].y)};    // de * sgn(t)
           Sg[i] = Sg[i] + sg;
           if constexpr (DIRECT) {
-            Pt[i] = pk_fma(nde2, nt[i], Pt[i]);                                      // de * t
-            Qt[i] = pk_fma(-sg, nt[i], Qt[i]);                                       // de * |t|
+            if constexpr (LEAN) {
+              Pt[i] = pk_fma(pk_fma(sg, splat(c2), splat(c1 * de)), v[i], Pt[i]);    // x_l * (c1 de + c2 de sgn(t))
+            } else {
+              Pt[i] = pk_fma(nde2, nt[i], Pt[i]);                                    // de * t
+              Qt[i] = pk_fma(-sg, nt[i], Qt[i]);                                     // de * |t|
+            }
             // the source pass's formula with this edge as the only term
             gx[i] = pk_fma(splat(a_eff), g[i], (a1[i] * de + a2[i] * sg) * kLn2);
           }
@@ -822,6 +826,30 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
       if constexpr (!DIRECT) {       // this row's share of grad_att: x_r * (c1 * Sde + c2 * Sg), with nxr = -x_r
 #pragma unroll
         for (int i = 0; i < 4; ++i) datt2[i] = datt2[i] - nxr[i] * (splat(c1 * Sde) + Sg[i] * c2);
+      } else if constexpr (LEAN) {   // the same share, into the accumulator of the per-edge x_l halves
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Pt[i] = Pt[i] - nxr[i] * (splat(c1 * Sde) + Sg[i] * c2);
+      }
+    }
+  }
+
+  // Zero rows of another matrix indexed by THESE rows (the pair form of the backward), for all of the wave's row batches
+  // at once behind its last edge walk.  Stored inside the row loop, ahead of each walk, the fill cost the C2 destination
+  // pass 51 us (740 -> 792 us, measured; supposed cause, no counter run: on this target stores count in vmcnt like loads,
+  // so the walk's first gathers wait for the write of a row nobody reads).  Out here nothing waits for them.
+  if (p.zero_rows) {
+#pragma unroll 1
+    for (int it = 0; it < p.rows_per_wave_iter; ++it) {
+      const int64_t rbase = ((blk * (int64_t)p.rows_per_wave_iter + it) * 4 + L.wave) * RPW;
+      if (rbase >= p.n_rows) break;
+      const int64_t pos = rbase + (WPR ? 0 : L.grp);
+      const bool row_ok = pos < p.n_rows;
+      const int row = visit_row<WPR>(p.order, pos, row_ok);
+      if (row_ok && L.lane_on && (!WPR || L.grp == 0)) {
+        f32x2 z[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) z[i] = splat(0.f);
+        store_pairs(static_cast<T*>(p.zero_rows) + row * p.ld_zero + L.ch0, z);
       }
     }
   }
@@ -830,7 +858,9 @@ __device__ __forceinline__ void gatv2_bwd_dst_body(SEGGER_BODY_PARAM p, int64_t 
   float datt[8], db[8];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if constexpr (DIRECT) {
+    if constexpr (DIRECT && LEAN) {
+      datt[2 * i] = Pt[i].x; datt[2 * i + 1] = Pt[i].y;
+    } else if constexpr (DIRECT) {
       datt[2 * i] = c1 * Pt[i].x + c2 * Qt[i].x; datt[2 * i + 1] = c1 * Pt[i].y + c2 * Qt[i].y;
     } else {
       datt[2 * i] = datt2[i].x; datt[2 * i + 1] = datt2[i].y;
@@ -1019,13 +1049,24 @@ __global__ __launch_bounds__(256, SEGGER_BWD_SRC_WAVES) void gatv2_bwd_src_kerne
 }
 
 // The source pass of one edge type (`a`: tx-neighbors-tx, group-per-row) and the ONE-PASS destination pass of another
-// (`b`: tx-belongs-bd, wave-per-row, DIRECT) in one launch: b's few hundred latency-bound blocks go first and run beside
-// a's.  Built for the source pass's 3 waves per SIMD with the one-pass body at 2 rows in flight (it spills ~24 registers
-// there, which a 13 us kernel does not notice; at the one-pass form's own 2 waves per SIMD the merged launch measured
-// +0.5 % on the captured 1M-edge step, as built -1.6 %).  Used for small batches only (SEGGER_BWD_PAIR_MAX_ROWS).
+// (`b`: tx-belongs-bd, wave-per-row, DIRECT) in one launch: b's latency-bound blocks go first and run beside a's.
+// The kernel takes the registers of its larger body, and all but a few thousand of its blocks are a's, so the one-pass
+// body must not cost the source pass occupancy.  On 16-bit rows of the geometries listed below the source pass alone
+// allocates <= 128 registers: 4 waves per SIMD, although it only asks for SEGGER_BWD_SRC_WAVES = 3.  Built for 3 waves
+// the merged kernel took 166-168 registers and the source pass lost its fourth wave (with the zero fill it moves into
+// a's destination pass, see there: C2 step +0.27 ms when the merged route was tried at that size).  So there the one-pass body is built LEAN at one row in flight -- beside 60 000 other
+// blocks it has no latency of its own to hide -- and the kernel for 4 waves: <= 128 registers, no scratch.  The other
+// geometries' and fp32's source passes need more than 128 registers by themselves: 3 waves, 2 rows in flight.
 template <typename T, int H, int LPH>
-__global__ __launch_bounds__(256, 3) void gatv2_bwd_src_dst_pair_kernel(GatParams a, GatParams b) {
-  if ((int64_t)blockIdx.x < b.nblocks_padded) gatv2_bwd_dst_body<T, H, LPH, true, true, 2>(b, blockIdx.x);
+struct BwdPairCfg {
+  static constexpr bool four = sizeof(T) == 2 && ((H == 2 && LPH == 8) || (H == 1 && LPH == 8) || (H == 3 && LPH == 4) ||
+                                                  (H == 4 && LPH == 4));
+  static constexpr int waves = four ? 4 : 3, rows_in_flight = four ? 1 : 2;
+};
+template <typename T, int H, int LPH>
+__global__ __launch_bounds__(256, (BwdPairCfg<T, H, LPH>::waves)) void gatv2_bwd_src_dst_pair_kernel(GatParams a, GatParams b) {
+  using Cfg = BwdPairCfg<T, H, LPH>;
+  if ((int64_t)blockIdx.x < b.nblocks_padded) gatv2_bwd_dst_body<T, H, LPH, true, true, Cfg::rows_in_flight, Cfg::four>(b, blockIdx.x);
   else gatv2_bwd_src_body<T, H, LPH, false>(a, (int64_t)blockIdx.x - b.nblocks_padded);
 }
 

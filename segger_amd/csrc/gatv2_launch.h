@@ -20,9 +20,10 @@ static inline int bwd_row_iters(int64_t n_rows) {
   return (int)(it < 1 ? 1 : (it > kBwdRowIters ? kBwdRowIters : it));
 }
 
-// segger_gatv2_bwd_pair merges launches up to this many source rows of the two-pass edge type
+// segger_gatv2_bwd_pair merges launches up to this many source rows of the two-pass edge type: every batch the entry
+// points accept (they refuse 2^31 - 1 rows and more).  The environment variable of the same name overrides it (gatv2.hip)
 #ifndef SEGGER_BWD_PAIR_MAX_ROWS
-#define SEGGER_BWD_PAIR_MAX_ROWS 262144
+#define SEGGER_BWD_PAIR_MAX_ROWS 0x7fffffffLL
 #endif
 
 // (heads, channels/8) combinations with a specialised kernel

@@ -92,8 +92,8 @@ def gatv2_bwd_pair_launch(first: tuple, first_kw: dict, second: tuple, second_kw
     """The backward of both edge types of one hetero layer through ``segger_gatv2_bwd_pair``: ``first`` the two-pass
     edge type (tx-neighbors-tx), ``second`` the one-pass one (tx-belongs-bd), each the positional / keyword arguments
     of :func:`gatv2_bwd_launch`.  ``second``'s ``grad_xl`` is the matrix ``first`` zero-fills (``zero_rows_out``); the
-    library merges the source pass of ``first`` with the destination pass of ``second`` for small batches and runs the
-    two backward passes one after the other otherwise.  -> ((grad_att, grad_bias) of first, of second)."""
+    library merges the source pass of ``first`` with the destination pass of ``second`` (and the two slab sums) where
+    the pair qualifies and runs the two backward passes one after the other otherwise.  -> ((grad_att, grad_bias) of first, of second)."""
     a, gp_a, keep_a, zeroed = _gat_bwd_args(*first, **first_kw)
     b, gp_b, keep_b, _ = _gat_bwd_args(*second, grad_xl_zeroed=zeroed, **second_kw)
     dev = first[1].device
@@ -280,7 +280,7 @@ class _HeteroGatLayer(torch.autograd.Function):
         # the stacked projection gradient on the way, so the one-pass tx-belongs-bd backward needs no fill of its own.
         # (Running tx-belongs-bd on a second stream beside it was measured in round 3: the kernels do overlap, but the
         # small one then takes 10x longer and the big ones 3-7 % longer -- same total)
-        # For small batches the library goes one step further (segger_gatv2_bwd_pair): the tx-neighbors-tx DESTINATION
+        # The library goes one step further (segger_gatv2_bwd_pair, every batch size): the tx-neighbors-tx DESTINATION
         # pass does the zero fill and its source pass shares a launch with the tx-belongs-bd pass.
         (gatt_tt, gbias_tt), (gatt_tb, gbias_tb) = gatv2_bwd_pair_launch(
             (g_tt, xp_tx[:, :hc], xp_tx[:, hc:2 * hc], att_tt, bias_tt, heads, channels, gy_tx, pre_tx, lse_tx,
