@@ -2290,6 +2290,75 @@ int segger_nearest_boundaries_select(const int64_t* pair_offsets, const double* 
                                      double* dist2_out, uint8_t* inside_out, int32_t* count_out, int64_t* counters,
                                      segger_stream_t stream);
 
+/* ----------------------------------------------------------------------
+ * Ring rasterisation (csrc/rasterize.hip; segger_amd.rasterize): an [H, W] int32 label image from a CSR of
+ * rings -- the transform opposite to segger_label_contours.  NO REFERENCE COUNTERPART EXISTS (the reference reads label
+ * images and never writes one), so the contract below is this project's own; cv2.fillPoly and skimage.draw.polygon follow
+ * other pixel rules and could not be run where this was written.  Purely additive: two new symbols, SEGGER_ABI_VERSION
+ * stays 32.
+ *
+ * The rings are segger_polygon_join_*'s: a CSR of single exterior rings in fp64, either orientation, a closing duplicate
+ *   dropped, at most SEGGER_MORPH_MAX_VERTS open vertices; a ring of fewer than 3 matches nothing (n_degenerate).
+ * The frame is segger_label_contours': the pixel in row r, column c stands for the world point (c sx + tx, r sy + ty) --
+ *   one multiplication and one addition in fp64, NOT fused.  sx and sy are finite and non-zero and may be negative.  That
+ *   point is tested against the ring as given; the vertices are never transformed back, no division decides anything.
+ * The predicate is the join's at distance 0, computed by the same code (csrc/ring_predicate.h: ring_decide(ring_distance(),
+ *   0, predicate), the point and the vertices translated to the ring's first vertex, contraction off):
+ *     SEGGER_RASTER_INTERSECTS  the closed set: parity or dist2 == 0;     SEGGER_RASTER_CONTAINS  the open set: parity and
+ *     dist2 > 0.  The pixels of polygon p are, bit for bit, the pairs segger_polygon_join_* lists for p over the pixel
+ *     centres with buffer NULL.  Contour vertices are pixel centres, so INTERSECTS inverts segger_label_contours on a label
+ *     of one component without holes.
+ * Overlaps.  A pixel matched by several polygons goes to the lowest (SEGGER_RASTER_LOWEST) or the highest
+ *   (SEGGER_RASTER_HIGHEST) polygon INDEX -- never the label value: an integer atomic min / max on the index in the image
+ *   itself; a finishing pass replaces the index by labels[index] (labels NULL: index + 1; the caller keeps them >= 1) and
+ *   writes 0 where nothing matched.  No floating-point atomics, no scratch.  Every output but the two counters marked below
+ *   is a function of the inputs alone: the same bytes for any block, either route, any launch geometry and any run.
+ * Outputs (all written by the call when n_polygons > 0):
+ *     image     [height, width] int32;
+ *     n_covered [n_polygons] int64   the pixels of the image the polygon matches, before overlaps are resolved;
+ *     n_won     [n_polygons] int64   the pixels that carry the polygon in `image`;
+ *     counters  [SEGGER_RASTER_COUNTERS] int64:  0 n_pixels_set;  1 n_overlaps = sum n_covered - n_pixels_set;  2 n_empty,
+ *               the polygons with n_covered = 0 (degenerate ones included);  3 n_clipped, the polygons of 3 or more vertices
+ *               whose bounds are not inside the closed rectangle of the pixel centres (tx .. (width - 1) sx + tx and the
+ *               like in y, computed as the centres are);  4 n_degenerate;  5 n_large_tier, the polygons that ran with the
+ *               ring in LDS (ROUTE-DEPENDENT);  6 n_blocks_filled (BLOCK-DEPENDENT).
+ * The walk.  One wave per polygon; rings of n <= reg_max (64 or, to force the LDS tier, 0) vertices in registers, the others
+ *   in 64 KB of LDS, one single-wave workgroup each, as the join's.  The ring's bounds become a clipped pixel range, widened
+ *   by a whole pixel and a rounding margin on every side (csrc/rasterize.hip: pixel_range; the predicate decides membership,
+ *   not the range).  The range is taken in block x block pixels (a power of two, 1 .. SEGGER_RASTER_MAX_BLOCK): ring_distance
+ *   is evaluated once at the block's centre, and when dist2 exceeds (half_diag (1 + 2^-16) + 2^-30 M)^2 -- half_diag the
+ *   distance from the centre to the block's farthest pixel centre, M the magnitude of the coordinates involved; the
+ *   argument is written at block_threshold -- no edge passes through the block and all its pixels share the centre's
+ *   parity: it is filled or skipped whole.  Other blocks are evaluated pixel by pixel, 64 pixels a step, one per lane.
+ *   block = 1 evaluates every pixel of the range.  A large cell costs about area / block^2 + perimeter block evaluations.
+ * Errors found on the device (the int32 at byte 0 of the workspace): SEGGER_RASTER_ERR_OFFSETS, _CAP as SEGGER_MORPH_ERR_*;
+ *   such a polygon matches nothing.
+ * Workspace: segger_rasterize_workspace_bytes(n_polygons) = 256 + 2 up(4 n_polygons), up() rounding up to 256: the words
+ *   and one int32 list per route.  256-byte aligned.
+ * Rejected on the host with SEGGER_EINVAL and a message, nothing launched: negative sizes, 2^31 - 1 polygons or more, height
+ *   or width below 1 or height * width >= 2^31, a zero or non-finite scale, a non-finite translation, an unknown
+ *   predicate or overlap, a block that is no power of two in 1 .. SEGGER_RASTER_MAX_BLOCK, reg_max other than 0 or 64, NULL or
+ *   misaligned ring_offsets, n_covered, n_won, counters (8 bytes), xy (16), image, labels (4; labels may be NULL), a workspace
+ *   that is NULL, misaligned or too small.  n_polygons = 0 returns SEGGER_OK without touching a pointer or the device:
+ *   nothing is written, the caller knows the image is all background.
+ * NOT BUILT: holes and multi-part polygons; anti-aliased (fractional) coverage; writing TIFF or any file; capture into a
+ *   graph; more than one wave per polygon (one huge ring is walked by one wave).
+ * ---------------------------------------------------------------------- */
+#define SEGGER_RASTER_CONTAINS 0
+#define SEGGER_RASTER_INTERSECTS 1
+#define SEGGER_RASTER_LOWEST 0
+#define SEGGER_RASTER_HIGHEST 1
+#define SEGGER_RASTER_MAX_BLOCK 32
+#define SEGGER_RASTER_COUNTERS 7
+#define SEGGER_RASTER_ERR_OFFSETS 1
+#define SEGGER_RASTER_ERR_CAP 2
+int64_t segger_rasterize_workspace_bytes(int64_t n_polygons);
+int segger_rasterize_rings(const int64_t* ring_offsets, const double* xy, int64_t n_polygons, int64_t n_vertices,
+                           const int32_t* labels /* [P] or NULL = index + 1 */, int32_t height, int32_t width, double sx,
+                           double sy, double tx, double ty, int32_t predicate, int32_t overlap, int32_t block, int32_t reg_max,
+                           int32_t* image /* [H, W] */, int64_t* n_covered /* [P] */, int64_t* n_won /* [P] */,
+                           int64_t* counters, void* workspace, int64_t workspace_bytes, segger_stream_t stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

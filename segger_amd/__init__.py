@@ -36,5 +36,7 @@ from . import fragments  # noqa: F401
 from .fragments import FragmentAccumulator, fragment_cells, connected_components, unassigned_mask, merge_fragments  # noqa: F401
 from . import buffered_counts  # noqa: F401  (the module, as phenograph: its function of the same name stays segger_amd.buffered_counts.buffered_counts)
 from .buffered_counts import buffered_counts_regions, buffered_counts_to_scipy, filter_boundaries  # noqa: F401
+from . import rasterize  # noqa: F401
+from .rasterize import rasterize_rings  # noqa: F401
 
 __version__ = "0.1.0"

@@ -36,6 +36,8 @@ BCOUNT_SMALL_GENES, BCOUNT_TOUCHED, BCOUNT_LDS_BYTES, BCOUNT_COUNTERS = 2048, 51
 BCOUNT_MAX_GENES = (BCOUNT_LDS_BYTES - 65536 - 4 * BCOUNT_TOUCHED) // 4                                # 24064
 BCOUNT_ERR_FILL = 8
 NEAREST_MAX_K, NEAREST_LANE_MAX, NEAREST_COUNTERS, NEAREST_ERR_FILL = 16, 32, 4, 8                       # SEGGER_NEAREST_*
+RASTER_CONTAINS, RASTER_INTERSECTS, RASTER_LOWEST, RASTER_HIGHEST = 0, 1, 0, 1                          # SEGGER_RASTER_*
+RASTER_MAX_BLOCK, RASTER_COUNTERS = 32, 7
 
 SEGGER_F32, SEGGER_BF16, SEGGER_F16 = 0, 1, 2
 DTYPE_CODE = {torch.float32: SEGGER_F32, torch.bfloat16: SEGGER_BF16, torch.float16: SEGGER_F16}
@@ -439,6 +441,9 @@ EXPORTS = {
     "segger_nearest_boundaries_fill": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_double, C.c_double,
                                                  C.c_double, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp]),
     "segger_nearest_boundaries_select": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp]),
+    "segger_rasterize_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "segger_rasterize_rings": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                         C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]),
 }
 
 _lib: Optional[C.CDLL] = None
