@@ -455,6 +455,46 @@ int segger_grad_guard(const segger_adam_tensor* tensors, int32_t n_tensors, cons
 int segger_adam_step_guarded(const segger_adam_tensor* tensors, int32_t n_tensors, const double* hyper, int32_t flags,
                              int64_t* counter, int64_t counter_inc, const segger_guard_state* state, segger_stream_t stream);
 
+/*
+ * Gradient accumulation over a window of N micro-steps (Lightning's accumulate_grad_batches) for a captured training step:
+ * every replay runs backward, segger_grad_accumulate, [segger_grad_guard_windowed,] segger_adam_step_windowed, and the
+ * DEVICE decides which of them act -- one graph serves every position of the window, the host decides nothing per step.
+ *
+ * segger_accum_window (DEVICE, 16 bytes, 4-byte aligned; the caller zeroes it once):
+ *   pos      micro-steps summed into the open window (0: none -- the next accumulate OVERWRITES the accumulators)
+ *   close    1: the last segger_grad_accumulate (or a flush) closed the window; what the windowed guard / update act on
+ *   arrived  the accumulate launch's workgroup ticket (0 between launches)
+ *
+ * segger_grad_accumulate: acc = pos == 0 ? g * w : acc + g * w for all tensors in one launch per 64, w = (float)1 / n_window;
+ * the table is segger_adam_step's with `grad` = the micro-step's gradient (read) and `param` = the fp32 ACCUMULATOR
+ * (written; the other fields are not read).  Then pos += 1, close = (pos == n_window), and a closed window's pos is 0.
+ * One thread owns an element; multiply and add are rounded separately; the sum of an element is formed in micro-step
+ * order; no float atomics: the same gradients give the same bytes.  Enqueue-only.
+ * segger_grad_guard_windowed / segger_adam_step_windowed: segger_grad_guard / segger_adam_step_guarded on a table whose
+ * `grad` is the accumulator, acting only when window->close is set: otherwise the guard's state, the step counters, the
+ * moments and the parameters keep their bytes (*counter still advances: every micro-batch draws fresh numbers).  `state`
+ * of the update may be NULL (no guard).  SEGGER_ADAM_STEPS_ADVANCED is refused: the counters move in the update's own
+ * counter launch, when the window closes and the step is not skipped.
+ * segger_accum_window_flush: phase 0: close = (pos > 0) -- what follows applies the sum so far, every term still weighted
+ * 1 / n_window; phase 1: pos = close = 0.  (Lightning closes an open window at the end of an epoch.)
+ * csrc/grad_accum.hip (templates shared with adam.hip: csrc/adam_common.h).  Purely additive: four new symbols, no existing signature or struct changes, SEGGER_ABI_VERSION stays 32.
+ */
+typedef struct segger_accum_window {
+  int32_t pos;
+  int32_t close;
+  int32_t arrived;
+  int32_t reserved_;
+} segger_accum_window;
+int segger_grad_accumulate(const segger_adam_tensor* tensors, int32_t n_tensors, int32_t n_window, segger_accum_window* window,
+                           segger_stream_t stream);
+int segger_grad_guard_windowed(const segger_adam_tensor* tensors, int32_t n_tensors, const segger_guard_cfg* cfg,
+                               segger_guard_state* state, void* workspace, int64_t workspace_bytes,
+                               const segger_accum_window* window, segger_stream_t stream);
+int segger_adam_step_windowed(const segger_adam_tensor* tensors, int32_t n_tensors, const double* hyper, int32_t flags,
+                              int64_t* counter, int64_t counter_inc, const segger_guard_state* state,
+                              const segger_accum_window* window, segger_stream_t stream);
+int segger_accum_window_flush(segger_accum_window* window, int32_t phase, segger_stream_t stream);
+
 /* segger_transpose_many: dst [cols, rows] = src [rows, cols]^T for n_segs contiguous 16-bit matrices in one launch:
  * the W^T copies the data-gradient GEMMs (dX = dY W on segger_linear_fwd) need after every optimizer step. */
 typedef struct {

@@ -110,7 +110,11 @@ class GuardCfg(C.Structure):            # segger_guard_cfg (host)
                 ("growth_interval", C.c_int32), ("flags", C.c_int32)]
 
 
-ADAM_STEPS_ADVANCED = 1                 # SEGGER_ADAM_STEPS_ADVANCED
+class AccumWindow(C.Structure):         # segger_accum_window: lives on the DEVICE; here for its layout
+    _fields_ = [("pos", C.c_int32), ("close", C.c_int32), ("arrived", C.c_int32), ("reserved_", C.c_int32)]
+
+
+ADAM_STEPS_ADVANCED = 1                # SEGGER_ADAM_STEPS_ADVANCED
 ADAM_ELEMS_PER_BLOCK = 2048             # the (tensor, offset) block of segger_adam_step / segger_grad_guard
 
 
@@ -271,6 +275,10 @@ EXPORTS = {
     "segger_adam_step_guarded": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp]),
     "segger_grad_guard_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "segger_grad_guard": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.POINTER(GuardCfg), vp, vp, C.c_int64, vp]),
+    "segger_grad_accumulate": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.c_int32, vp, vp]),
+    "segger_grad_guard_windowed": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.POINTER(GuardCfg), vp, vp, C.c_int64, vp, vp]),
+    "segger_adam_step_windowed": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, vp]),
+    "segger_accum_window_flush": (C.c_int, [vp, C.c_int32, vp]),
     "segger_transpose_many": (C.c_int, [C.POINTER(TransposeSeg), C.c_int32, vp]),
     "segger_posmlp_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "segger_posmlp_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp,

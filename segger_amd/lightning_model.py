@@ -125,12 +125,25 @@ class LitISTEncoder(_Base):
         # bit-reproducible training (off by default): the loss head's ordered backward, here on the fused
         # eager path and in every captured step; the unfused loss routes are refused
         self.deterministic = on("SEGGER_AMD_DETERMINISTIC")
+        # gradient accumulation of the captured step: SEGGER_AMD_ACCUMULATE=N, next to the two switches
+        # above; None: not given.  Checked where it is used (enable_graphed_training): an int >= 1
+        self._accumulate_env = self._accumulate_from_env(os.environ.get("SEGGER_AMD_ACCUMULATE", ""))
         if on("SEGGER_AMD_FAST"):
             self.fast()            # `SEGGER_AMD_FAST=1 segger segment ...`: the CLI builds the module from parsed arguments only
         elif on("SEGGER_AMD_GRAPHED"):
             # captured steps WITHOUT changing the arithmetic width: the reference's fp32 storage, every training step one
             # hipGraph replay -- the recommended drop-in (bench.py `strong.graphed_f32`)
             self.enable_graphed_training()
+
+    @staticmethod
+    def _accumulate_from_env(text: str) -> Optional[int]:
+        text = text.strip()
+        if not text:
+            return None
+        try:
+            return int(text)
+        except ValueError:
+            raise ValueError(f"SEGGER_AMD_ACCUMULATE must be an int >= 1, not {text!r}") from None
 
     # ------------------------------------------------------------------ setup
     def set_similarities(self, tx_similarity: Tensor, bd_similarity: Tensor) -> None:
@@ -290,20 +303,25 @@ class LitISTEncoder(_Base):
     # ------------------------------------------------- whole-step hipGraph under Lightning (opt-in, not in the reference)
     def enable_graphed_training(self, enabled: bool = True, *, clip_grad_norm: Optional[float] = None, loss_scale=None,
                                 skip_nonfinite: bool = False, deterministic: Optional[bool] = None,
-                                **trainer_kw) -> "LitISTEncoder":
+                                accumulate_grad_batches: Optional[int] = None, **trainer_kw) -> "LitISTEncoder":
         """Opt in BEFORE ``Trainer.fit``: every ``training_step`` becomes one hipGraph replay of the whole step (batch
         staging, forward, the three losses, backward, fused Adam: :class:`segger_amd.train_step_graph.GraphedTrainer`,
         1.3 ms instead of a host-bound 3-5 ms per default 1M-edge batch).  The module switches to Lightning's MANUAL
         optimisation (``automatic_optimization = False``): ``training_step`` drives the optimizer that
         ``configure_optimizers`` returned (now with device-side step counters) and Lightning's own backward / optimizer
         step / ``zero_grad`` are not run -- so the Trainer's ``gradient_clip_val``, ``accumulate_grad_batches`` and
-        precision plugins do not apply (the reference's ``Trainer(logger, max_epochs, reload_dataloaders_every_n_epochs,
+        precision plugins do not apply by themselves (the reference's ``Trainer(logger, max_epochs, reload_dataloaders_every_n_epochs,
         callbacks)``, cli/segment.py:400-405, uses none of them).  What they would have given is asked for HERE and decided
         on the device inside the replayed step (the gradient guard, ``ops.grad_guard``): ``clip_grad_norm`` (global L2
         norm, ``torch.nn.utils.clip_grad_norm_``), ``loss_scale`` (a float: static; ``"dynamic"``: ``torch.amp.GradScaler``'s
         65536 / x2 every 2000 clean steps / x0.5 on an overflow) and ``skip_nonfinite`` (implied by the other two: a step
         with an inf / NaN gradient changes nothing).  With a guard on, ``train:grad_norm`` and ``train:loss_scale`` are
-        logged.  Still not available: ``accumulate_grad_batches``, ``clip_grad_value_``, norms other than L2,
+        logged.  ``accumulate_grad_batches=N`` (or ``SEGGER_AMD_ACCUMULATE=N``; an int >= 1, else ``ValueError``): Lightning's
+        gradient accumulation inside the replayed step (:class:`GraphedTrainer`) -- one update per N batches from the sum of
+        their gradients / N, the window position kept on the device, an open window closed at the end of the training epoch
+        (``on_train_epoch_end`` -> ``GraphedTrainer.flush``); ``trainer.global_step`` counts closed windows.  A Trainer whose
+        own ``accumulate_grad_batches`` is > 1 while this argument is not given gets a warning, not a guess.  Still not
+        available: ``clip_grad_value_``, norms other than L2,
         per-parameter-group settings, ``error_if_nonfinite=True``.  Single process: under data parallelism build the
         ``GraphedTrainer`` yourself with a ``dp.FlatGradBucket``.  ``trainer_kw``: ``granularity`` / ``max_buckets``.
 
@@ -315,6 +333,11 @@ class LitISTEncoder(_Base):
             self.deterministic = bool(deterministic)
         if self.deterministic:
             trainer_kw = dict(trainer_kw, deterministic=True)
+        from .ops import accumulate_batches
+        given = accumulate_grad_batches if accumulate_grad_batches is not None else self._accumulate_env
+        self._accumulate_given = given is not None
+        if given is not None and accumulate_batches(given) > 1:
+            trainer_kw = dict(trainer_kw, accumulate_grad_batches=given)
         if clip_grad_norm is not None or loss_scale is not None or skip_nonfinite:
             trainer_kw = dict(trainer_kw, clip_grad_norm=clip_grad_norm, loss_scale=loss_scale, skip_nonfinite=skip_nonfinite)
         self._graphed_kw = dict(trainer_kw) if enabled else None
@@ -346,9 +369,17 @@ class LitISTEncoder(_Base):
             if not all(g.get("capturable", False) for g in opt.param_groups):
                 raise RuntimeError("graphed training needs a capturable optimizer: call enable_graphed_training() "
                                    "before the trainer calls configure_optimizers()")
+            theirs = getattr(self.trainer, "accumulate_grad_batches", 1)
+            if isinstance(theirs, int) and theirs > 1 and not getattr(self, "_accumulate_given", False):
+                import warnings
+                warnings.warn(f"Trainer(accumulate_grad_batches={theirs}) does not reach the captured training step, which "
+                              "owns backward and optimizer.step(): every batch is one update.  Ask for it with "
+                              f"enable_graphed_training(accumulate_grad_batches={theirs}) / fast(accumulate_grad_batches="
+                              f"{theirs}) or SEGGER_AMD_ACCUMULATE={theirs}")      # (once: the trainer is built once)
             tr = self._graphed_trainer = GraphedTrainer(self, opt, **self._graphed_kw)
         out = tr.step(batch).clone()         # [loss_tx, loss_bd, loss_sg, loss]; the trainer's own tensor is overwritten by the next step
-        self._advance_manual_step_progress()
+        if tr.window_closed:                 # (an optimizer step happened: with accumulation, once per window)
+            self._advance_manual_step_progress()
         bs = getattr(batch, "num_graphs", 1)
         for i, name in enumerate(("loss_tx", "loss_bd", "loss_sg")):
             self.log(f"train:{name}", out[i], prog_bar=True, batch_size=bs)
@@ -356,6 +387,14 @@ class LitISTEncoder(_Base):
             self.log("train:grad_norm", tr.guard.norm.clone(), batch_size=bs)
             self.log("train:loss_scale", tr.guard.scale.clone(), batch_size=bs)
         return out[3]
+
+    def on_train_epoch_end(self) -> None:
+        """An accumulation window left open by the epoch's last batches is closed here, as Lightning's own accumulation
+        does: the captured step applies the sum so far (``GraphedTrainer.flush``)."""
+        tr = self._graphed_trainer
+        if tr is not None and not tr.window_closed:
+            tr.flush()
+            self._advance_manual_step_progress()
 
     def _advance_manual_step_progress(self) -> None:
         """The replay stepped the RAW optimizer inside the hipGraph.  Under Lightning's manual optimisation

@@ -107,8 +107,8 @@ from .gatv2 import (gatv2_aggregate, gatv2_bwd_launch, gatv2_bwd_pair_launch, ga
                     hetero_gat_layer)
 from .heads import (LossHeadSpec, _LossHead, _TICKETS, _triplet_args, anchor_index, bce_edge_loss, edge_cos_argmax,
                     loss_head, loss_head_fused_supported, loss_head_route, metric_loss, triplet_edge_loss)
-from .step import (GuardState, adam_hyper, adam_init_state, adam_step, adam_step_counters, double_bits, float_bits, grad_guard,
-                   stage)
+from .step import (GradWindow, GuardState, accumulate_batches, adam_hyper, adam_init_state, adam_step, adam_step_counters,
+                   double_bits, float_bits, grad_accumulate, grad_guard, stage, window_flush)
 from .packs import (_PACKS, _pack_for, alias_of, f32_split_planes, invalidate_weight_cache, invalidate_weights, pack_scope,
                     packs_of)
 from .linear import (colsum, linear, linear_f32_act_launch, linear_f32_gate_launch, linear_f32_gate_supported,

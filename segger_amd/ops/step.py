@@ -124,6 +124,83 @@ class GuardState:
         return self._hyper[values]
 
 
+def accumulate_batches(n) -> int:
+    """``accumulate_grad_batches`` as given -> the window length: an int >= 1 (1: no accumulation), else ``ValueError``."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"accumulate_grad_batches must be an int >= 1, not {n!r}")
+    return n
+
+
+class GradWindow:
+    """The device side of gradient accumulation over ``n`` micro-steps (``segger_accum_window`` + one fp32 accumulator per
+    parameter), allocated once and owned by whoever owns the optimizer's steps -- a :class:`GraphedTrainer` hands all its
+    buckets one, so a window may span buckets.  ``pos`` (micro-steps summed into the open window) and ``close`` (the last
+    accumulate closed it) are 0-dim int32 VIEWS of the device struct: nothing waits for the device until one is read."""
+
+    def __init__(self, params, n: int):
+        self.n = accumulate_batches(n)
+        params = [p for p in params if p.requires_grad]
+        if not params:
+            raise ValueError("GradWindow: no parameter requires a gradient")
+        self.device = params[0].device
+        self.buf = torch.zeros(C.sizeof(_lib.AccumWindow), dtype=torch.uint8, device=self.device)
+        S = _lib.AccumWindow
+        view = lambda name: self.buf[getattr(S, name).offset:getattr(S, name).offset + 4].view(torch.int32).reshape(())
+        self.pos, self.close = view("pos"), view("close")
+        self._acc: dict = {}
+        self._keep: list = []                                 # (the ids stay those of live tensors)
+        self.ensure(params)
+
+    def ensure(self, params) -> None:
+        """An accumulator for every parameter of ``params`` that requires a gradient and has none yet (never call this
+        inside a capture: the tensor would live in the graph's pool)."""
+        for p in params:
+            if p.requires_grad and id(p) not in self._acc:
+                self._acc[id(p)] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+                self._keep.append(p)
+
+    def acc(self, p) -> Tensor:
+        """The accumulator of parameter ``p``: one tensor for the trainer's lifetime."""
+        return self._acc[id(p)]
+
+    def accumulators(self) -> list:
+        return [self._acc[id(p)] for p in self._keep]
+
+
+def grad_accumulate(params, window: GradWindow) -> None:
+    """``segger_grad_accumulate``: ``acc = g / n`` on the first micro-step of a window, ``acc += g / n`` on the others, for the
+    gradients of ``params`` (those with ``.grad`` set) in one launch per 64 tensors; the DEVICE knows the position and moves
+    the window on.  Afterwards ``p.grad`` IS the accumulator: ``grad_guard`` / ``adam_step`` with ``window=`` read it."""
+    rows = []
+    for p in params:
+        g = p.grad
+        if g is None:
+            continue
+        a = window.acc(p)
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and not g.is_sparse and g.shape == a.shape):
+            raise NotImplementedError("accumulate_grad_batches > 1: segger_grad_accumulate takes dense contiguous fp32 "
+                                      f"gradients on the device, not {g.dtype} {tuple(g.shape)}")
+        rows.append((a, g))
+    arr = (_lib.AdamTensor * max(len(rows), 1))()
+    for t, (a, g) in zip(arr, rows):
+        t.param, t.grad, t.numel = a.data_ptr(), g.data_ptr(), a.numel()
+    dev = window.device
+    with _lib.on_device(dev):
+        rc = _lib.load().segger_grad_accumulate(arr, len(rows), window.n, window.buf.data_ptr(), _lib.stream_ptr(dev))
+    _lib.check(rc, "segger_grad_accumulate")
+    for p in params:
+        if p.grad is not None:
+            p.grad = window.acc(p)
+
+
+def window_flush(window: GradWindow, phase: int) -> None:
+    """``segger_accum_window_flush``: phase 0 before the close-only sequence (guard, Adam), phase 1 after it."""
+    dev = window.device
+    with _lib.on_device(dev):
+        rc = _lib.load().segger_accum_window_flush(window.buf.data_ptr(), int(phase), _lib.stream_ptr(dev))
+    _lib.check(rc, "segger_accum_window_flush")
+
+
 def adam_init_state(opt) -> None:
     """Adam's initial state (``step`` = 0 as an fp32 device scalar, zero moments -- what a capturable
     ``torch.optim.Adam._init_group`` creates on its first step) for every parameter with a gradient that has none yet: the
@@ -158,13 +235,17 @@ def _guarded_rows(opt, who: str):
 
 
 def grad_guard(opt, state: GuardState, *, max_norm: Optional[float] = None, growth: float = 2.0, backoff: float = 0.5,
-               growth_interval: int = 0, steps_advanced: bool = False) -> None:
+               growth_interval: int = 0, steps_advanced: bool = False, window: Optional["GradWindow"] = None) -> None:
     """``segger_grad_guard`` over the gradients of ``opt``'s parameters: global-norm clipping (``max_norm``; None / 0 =
     off), the loss scale ``state.scale`` the backward was seeded with (``growth_interval`` = 0: static; > 0: grown by
     ``growth`` after that many clean steps in a row, cut by ``backoff`` on a skipped one, as ``torch.amp.GradScaler``) and
     the skip on a non-finite gradient, decided on the device and left in ``state`` for ``adam_step(..., guard=state)``.
     ``steps_advanced``: Adam's step counters were advanced at the head of the step; a skipped step takes that back.
-    Enqueue-only, two launches per 64 tensors.  An optimizer the Adam kernel does not cover is an error."""
+    Enqueue-only, two launches per 64 tensors.  An optimizer the Adam kernel does not cover is an error.
+    ``window`` (a :class:`GradWindow` behind :func:`grad_accumulate`: ``.grad`` is the accumulator):
+    ``segger_grad_guard_windowed`` -- the decision is taken, and ``state`` touched, only when the window closes."""
+    if window is not None and steps_advanced:
+        raise ValueError("grad_guard: inside an accumulation window Adam's counters are never advanced ahead of the update")
     g, rows = _guarded_rows(opt, "grad_guard")
     cfg = _lib.GuardCfg(float(max_norm or 0.0), float(growth), float(backoff), int(growth_interval),
                         _lib.ADAM_STEPS_ADVANCED if steps_advanced else 0)
@@ -173,13 +254,18 @@ def grad_guard(opt, state: GuardState, *, max_norm: Optional[float] = None, grow
     dev = rows[0][0].device
     ws = state.workspace(len(rows), blocks)
     with _lib.on_device(dev):
-        rc = _lib.load().segger_grad_guard(arr, len(rows), C.byref(cfg), state.buf.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _lib.stream_ptr(dev))
+        if window is not None:
+            rc = _lib.load().segger_grad_guard_windowed(arr, len(rows), C.byref(cfg), state.buf.data_ptr(), ws.data_ptr(),
+                                                        ws.numel(), window.buf.data_ptr(), _lib.stream_ptr(dev))
+        else:
+            rc = _lib.load().segger_grad_guard(arr, len(rows), C.byref(cfg), state.buf.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               _lib.stream_ptr(dev))
     _lib.check(rc, "segger_grad_guard")
 
 
 def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = None, counter_inc: int = 0,
-              hyper_dev: Optional[Tensor] = None, guard: Optional[GuardState] = None) -> bool:
+              hyper_dev: Optional[Tensor] = None, guard: Optional[GuardState] = None,
+              window: Optional["GradWindow"] = None) -> bool:
     """``optimizer.step()`` of a plain capturable ``torch.optim.Adam`` through ``segger_adam_step``: every parameter tensor
     in two launches, on the optimizer's own state tensors (checkpoints and eager ``optimizer.step()`` calls stay
     interchangeable).  -> False, nothing done, when the optimizer is anything else (amsgrad, weight decay, maximize, a
@@ -192,7 +278,12 @@ def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = Non
     times ``guard.coef``, nothing written on a skipped step (``counter`` still advances); an optimizer the kernel does not
     cover is then an ERROR, not ``False``: the caller's own ``optimizer.step()`` would drop the guard.
     (Host cost ~135 us per call for 60 tensors, nearly all of it the per-tensor attribute reads; a cached launch table
-    that re-checked pointers and state identity per step measured the same -- tools/host_phases.py.)"""
+    that re-checked pointers and state identity per step measured the same -- tools/host_phases.py.)
+    ``window`` (a :class:`GradWindow` behind :func:`grad_accumulate`; needs ``hyper_dev``, excludes ``steps_advanced``):
+    ``segger_adam_step_windowed`` -- counters, moments and parameters change only when the window closes (``counter`` still
+    advances); with or without ``guard``."""
+    if window is not None and (steps_advanced or hyper_dev is None):
+        raise ValueError("adam_step: window= needs hyper_dev and excludes steps_advanced")
     if guard is not None:
         g, rows = _guarded_rows(opt, "adam_step")
         if hyper_dev is None:
@@ -215,7 +306,11 @@ def adam_step(opt, steps_advanced: bool = False, counter: Optional[Tensor] = Non
         dev = rows[0][0].device
         b1, b2 = g["betas"]
         with _lib.on_device(dev):
-            if guard is not None:
+            if window is not None:
+                rc = lib.segger_adam_step_windowed(arr, len(rows), hyper_dev.data_ptr(), 0, _lib.ptr(counter), int(counter_inc),
+                                                   guard.buf.data_ptr() if guard is not None else None,
+                                                   window.buf.data_ptr(), _lib.stream_ptr(dev))
+            elif guard is not None:
                 rc = lib.segger_adam_step_guarded(arr, len(rows), hyper_dev.data_ptr(), 1 if steps_advanced else 0,
                                                   _lib.ptr(counter), int(counter_inc), guard.buf.data_ptr(),
                                                   _lib.stream_ptr(dev))

@@ -110,6 +110,25 @@ def make_guard(cfg: Optional[dict], optimizer, device):
     return ops.GuardState(device, cfg["init_scale"])
 
 
+def accumulation_config(accumulate_grad_batches, optimizer, exchange) -> int:
+    """``accumulate_grad_batches`` checked against what the captured step can do with it -> the window length N.  N == 1 is
+    the step as it always was.  N > 1 is refused, with the reason, under data parallelism (when the collective runs
+    relative to the window is a design of its own) and for an optimizer the Adam kernel does not cover (torch's own
+    ``optimizer.step()`` inside the capture cannot be predicated on "the window closes now")."""
+    n = ops.accumulate_batches(accumulate_grad_batches)
+    if n == 1:
+        return n
+    if exchange.split:
+        raise NotImplementedError("accumulate_grad_batches > 1 together with grad_sync / grad_bucket (data parallelism): when "
+                                  "the gradient exchange runs relative to the accumulation window is not designed yet")
+    if not USE_ADAM_KERNEL or ops.adam_hyper(optimizer) is None:
+        raise NotImplementedError("accumulate_grad_batches > 1 closes its window inside the hand-written Adam kernel "
+                                  "(segger_adam_step_windowed), which does not cover this optimizer: it takes one parameter "
+                                  "group of a plain capturable torch.optim.Adam (no amsgrad / weight decay / maximize, a "
+                                  "Python float learning rate)" + ("" if USE_ADAM_KERNEL else "; USE_ADAM_KERNEL is off"))
+    return n
+
+
 class GraphedTrainStep:
     """The captured step of ONE shape bucket (see :class:`GraphedTrainer` for the per-batch dispatch).  A batch is
     written into the bucket's static buffers by ONE launch (``ops.stage`` -> ``segger_stage``): node features, the three
@@ -125,14 +144,24 @@ class GraphedTrainStep:
     ``deterministic`` (off by default, and the step then issues exactly the launches it always did): the loss head takes
     its ordered backward (``ops.LossHeadSpec(deterministic=True)``) -- the one place of a step where float atomics landed
     in a varying order -- so that the same seed and the same batches give the same bytes: parameters, Adam state, losses
-    and the guard's state.  The warm-up's comparison of deferred against immediate sums then demands equal bytes."""
+    and the guard's state.  The warm-up's comparison of deferred against immediate sums then demands equal bytes.
+
+    ``accumulate_grad_batches`` = N (1 by default, and the step then issues exactly the launches it always did; see
+    :class:`GraphedTrainer` for the semantics): every step is a MICRO-step.  Behind the backward one launch
+    (``ops.grad_accumulate``) adds the gradients, times 1 / N, into the fp32 accumulators of ``window`` (the
+    ``ops.GradWindow`` to share: a trainer hands all its buckets one) -- overwriting them when the device-side window
+    counter says this is the window's first micro-step -- and moves the counter on; the guard and Adam then read the
+    ACCUMULATORS and act only when that launch closed the window.  The same graph serves every position of the window;
+    Adam's step counters move in Adam's own counter launch (``adam_counters=False``, as in split mode), never at the head
+    of the step."""
 
     def __init__(self, lit_model, optimizer, sizes: Dict[str, int], template, grad_sync=None, grad_bucket=None,
                  clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False, guard=None,
-                 deterministic: bool = False):
+                 deterministic: bool = False, accumulate_grad_batches: int = 1, window=None):
         self.guard_cfg = guard_config(clip_grad_norm, loss_scale, skip_nonfinite)
         self.deterministic = bool(deterministic)
         self.exchange = cap.exchange_of(grad_sync, grad_bucket)
+        self.accumulate_grad_batches = accumulation_config(accumulate_grad_batches, optimizer, self.exchange)
         self.split = self.exchange.split
         if self.exchange.bucket is not None:
             self.exchange.bucket._ensure()                    # the flat buffer must exist before anything is captured
@@ -196,6 +225,7 @@ class GraphedTrainStep:
         self.out: Optional[Tensor] = None
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.graph_opt: Optional[torch.cuda.CUDAGraph] = None      # split mode (grad_sync): Adam as a graph of its own
+        self.graph_flush: Optional[torch.cuda.CUDAGraph] = None    # accumulation: the close-only sequence (flush)
         self._grads: list = []
         self._training: Optional[bool] = None
         self._iota = torch.arange(nt, device=dev)
@@ -211,6 +241,12 @@ class GraphedTrainStep:
         by_id = {id(p): self._alias[n] for n, p in lit_model.model.named_parameters()}
         self._params = [p for g in optimizer.param_groups for p in g["params"] if p.requires_grad and id(p) in by_id]
         self._leaves = [by_id[id(p)] for p in self._params]
+        self.window = None                                    # accumulation: the shared window + accumulators
+        if self.accumulate_grad_batches > 1:
+            if window is not None and window.n != self.accumulate_grad_batches:
+                raise ValueError(f"the shared window sums {window.n} micro-steps, this step was asked for {self.accumulate_grad_batches}")
+            self.window = window if window is not None else ops.GradWindow(self._params, self.accumulate_grad_batches)
+            self.window.ensure(self._params)                  # (allocated HERE, never inside a capture)
         self.draws = None                                     # tests: fixed (tx pos/neg, bd pos/neg/dp/dn, dst_neg)
         # queue the backward's partial sums and run them as one launch (ops.deferred_reductions).  Only sound when no
         # autograd node READS a parameter gradient before the backward ends (a parameter used by two nodes has its two
@@ -303,7 +339,11 @@ class GraphedTrainStep:
 
     # ------------------------------------------------------------------------------------------- the step
     def _run(self, warm: bool = False) -> None:
-        self._opt_step(self._run_grads(self.defer_sums, adam_counters=not warm and not self.split, warm=warm), warm=warm)
+        accumulate = self.window is not None and not warm     # (a warm-up is rolled back: it must not touch the window)
+        end = self._run_grads(self.defer_sums, adam_counters=not warm and not self.split and not accumulate, warm=warm)
+        if accumulate:
+            ops.grad_accumulate(self._params, self.window)    # acc (+)= grad / N, the window moves on; .grad = acc from here
+        self._opt_step(end, warm=warm)
 
     def _opt_step(self, end: StepEnd, warm: bool = False) -> None:
         """Adam on the hand-written kernel (two launches for all tensors -- one when the step's first launch advanced the
@@ -313,13 +353,9 @@ class GraphedTrainStep:
         guarded Adam; a skipped step's counters are taken back by the guard when the draws launch advanced them."""
         inc, adv = end
         enc = self.lit.model
-        if self.guard is not None and not warm:
-            c = self.guard_cfg
-            ops.adam_init_state(self.opt)                     # (an eager first step: nothing has created the state yet)
-            ops.grad_guard(self.opt, self.guard, max_norm=c["max_norm"], growth=c["growth"], backoff=c["backoff"],
-                           growth_interval=c["growth_interval"], steps_advanced=adv)
-            ops.adam_step(self.opt, steps_advanced=adv, counter=enc._step_dev if inc else None, counter_inc=inc,
-                          hyper_dev=self.hyper, guard=self.guard)
+        window = None if warm else self.window
+        if (self.guard is not None or window is not None) and not warm:
+            self._guarded_update(window, enc._step_dev if inc else None, inc, adv)
             return
         if USE_ADAM_KERNEL and ops.adam_step(self.opt, steps_advanced=adv, counter=enc._step_dev if inc else None,
                                              counter_inc=inc, hyper_dev=self.hyper if self._hyper_on_device else None):
@@ -338,6 +374,48 @@ class GraphedTrainStep:
         self.opt.step()
         if inc:
             ops.step_advance(enc._step_dev, inc)
+
+    def _guarded_update(self, window, counter, inc: int, adv: bool) -> None:
+        """The guard (when there is one) and Adam, both on the device's word: skipped on a non-finite gradient; inside an
+        accumulation window (``window``: ``.grad`` is the accumulator) without effect until the window closes."""
+        ops.adam_init_state(self.opt)                         # (an eager first step: nothing has created the state yet)
+        if self.guard is not None:
+            c = self.guard_cfg
+            ops.grad_guard(self.opt, self.guard, max_norm=c["max_norm"], growth=c["growth"], backoff=c["backoff"],
+                           growth_interval=c["growth_interval"], steps_advanced=adv, window=window)
+        done = ops.adam_step(self.opt, steps_advanced=adv, counter=counter, counter_inc=inc, hyper_dev=self.hyper,
+                             guard=self.guard, window=window)
+        if not done:                                          # (guarded: adam_step raises itself)
+            raise NotImplementedError("accumulate_grad_batches > 1: segger_adam_step_windowed declined this optimizer "
+                                      "(non-fp32 / non-contiguous parameters or state, an AMP grad scaler attached), and "
+                                      "torch's own optimizer.step() cannot wait for the window to close")
+
+    def flush(self) -> None:
+        """Close an open accumulation window early: guard, then Adam on the sum so far (every term still weighted 1 / N),
+        then an empty window -- decided on the device, so with nothing open nothing changes.  Replayed from a graph of its
+        own (Adam alone, as the empty step of split mode) once this bucket has captured its step; eager before that."""
+        w = self.window
+        if w is None:
+            return
+        for p in self._params:                                # (an eager warm-up of another bucket may have left raw gradients)
+            if p.grad is not None:
+                p.grad = w.acc(p)
+        if all(p.grad is None for p in self._params):
+            return                                            # no step ever ran: nothing is open
+
+        def close_only():
+            ops.window_flush(w, 0)
+            self._guarded_update(w, None, 0, False)
+            ops.window_flush(w, 1)
+        if self.graph is None:
+            close_only()
+        else:
+            if self.graph_flush is None:
+                self.graph_flush = torch.cuda.CUDAGraph()
+                with graph_capture(self.graph_flush, pool=self.graph.pool()):
+                    close_only()
+            self.graph_flush.replay()
+        self._params_changed()
 
     def _run_grads(self, defer_sums: bool, adam_counters: bool, warm: bool = True) -> StepEnd:
         """Forward, losses, backward; ``.grad`` of the parameters and ``self.out`` set.  ``defer_sums``: see __init__.
@@ -494,7 +572,7 @@ class GraphedTrainStep:
         lit = self.lit
         self.stage(batch)
         if self.graph is not None and self._captured_hp != self._hyper():
-            self.graph = self.graph_opt = None                # (the old graphs' memory returns to the pool with them)
+            self.graph = self.graph_opt = self.graph_flush = None      # (the old graphs' memory returns to the pool with them)
         if not capture:
             self._run()
         elif self.graph is None or self._training != lit.model.training:
@@ -560,7 +638,7 @@ class GraphedTrainer:
 
     def __init__(self, lit_model, optimizer, granularity: float = 1.06, max_buckets: int = 24, grad_sync=None,
                  grad_bucket=None, clip_grad_norm: Optional[float] = None, loss_scale=None, skip_nonfinite: bool = False,
-                 deterministic: bool = False):
+                 deterministic: bool = False, accumulate_grad_batches: int = 1):
         """Data parallelism: ``grad_bucket`` = a ``dp.FlatGradBucket`` over the model's parameters (the captured
         backward packs into its flat buffer, Adam reads its slices; per step one all-reduce and one divide run eagerly
         between the two graphs), or ``grad_sync`` = any callable that averages the tensors ``.grad`` points at IN PLACE.
@@ -576,13 +654,26 @@ class GraphedTrainer:
         ``deterministic``: every bucket's step takes the loss head's ordered backward (:class:`GraphedTrainStep`): one GPU,
         one seed and one sequence of batches and buckets give bit-identical parameters, Adam state and losses.  Across
         different bucket sequences only as far as padding stays out of every sum; under data parallelism only as far as
-        the collective is reproducible."""
+        the collective is reproducible.
+
+        ``accumulate_grad_batches`` = N (an int >= 1; 1: off -- no accumulator, no added launch), Lightning's semantics: a
+        window is N consecutive ``step(batch)`` calls, each micro-step's gradient counts with weight 1 / N; parameters,
+        Adam's moments and step counters, the guard's scale / growth counter / skip count change only when the window
+        closes; the dropout / sampler counter advances on every micro-step; ``step`` returns each micro-batch's own
+        losses.  ``self.window`` (``ops.GradWindow``: the device-side position + one fp32 accumulator per parameter) is
+        shared by all buckets, so a window may span buckets; the device decides what a replay does, the host nothing.
+        Guard: the loss scale is constant within a window, a non-finite value in any micro-batch skips the whole window
+        (one back-off), the clip norm is the accumulated gradient's.  ``flush()`` closes an open window early.  Refused
+        (``NotImplementedError``) with ``grad_sync`` / ``grad_bucket`` and with an optimizer the Adam kernel declines."""
         self.deterministic = bool(deterministic)
         self.lit, self.opt, self.granularity, self.max_buckets = lit_model, optimizer, granularity, max_buckets
         self._guard_kw = dict(clip_grad_norm=clip_grad_norm, loss_scale=loss_scale, skip_nonfinite=skip_nonfinite)
         cfg = guard_config(**self._guard_kw)
         self.guard = None if cfg is None else make_guard(cfg, optimizer, next(lit_model.parameters()).device)
         self.exchange = cap.exchange_of(grad_sync, grad_bucket)
+        self.accumulate_grad_batches = accumulation_config(accumulate_grad_batches, optimizer, self.exchange)
+        self.window = None                    # ops.GradWindow, made with the first bucket (N > 1 only)
+        self.micro_steps = 0                  # host-side mirror of the window's position: for reporting, decides nothing
         self.buckets: List[GraphedTrainStep] = []
         self.n_captures = 0
         self._last: Optional[GraphedTrainStep] = None
@@ -604,10 +695,29 @@ class GraphedTrainer:
         self._last = cap.pick(
             self.buckets, batch, lambda: self._capture(batch), self.granularity, self.max_buckets,
             f"no captured bucket holds this batch and {self.max_buckets} buckets exist: raise `granularity` or `max_buckets`")
-        return self._last.step(batch)
+        out = self._last.step(batch)
+        self.micro_steps = (self.micro_steps + 1) % self.accumulate_grad_batches
+        return out
+
+    @property
+    def window_closed(self) -> bool:
+        """Did the last ``step`` / ``flush`` leave no window open (always, without accumulation)?"""
+        return self.micro_steps == 0
+
+    def flush(self) -> None:
+        """Close an open accumulation window early, as Lightning does at the end of an epoch: apply the sum accumulated so
+        far, each term still weighted 1 / N.  With nothing open (or without accumulation) it does nothing."""
+        if self.window is not None and self._last is not None:
+            self._last.flush()
+        self.micro_steps = 0
 
     def _capture(self, batch) -> GraphedTrainStep:
+        kw = dict(self._guard_kw)
+        if self.accumulate_grad_batches > 1:
+            if self.window is None:
+                self.window = ops.GradWindow([p for g in self.opt.param_groups for p in g["params"]], self.accumulate_grad_batches)
+            kw.update(accumulate_grad_batches=self.accumulate_grad_batches, window=self.window)
         made = GraphedTrainStep(self.lit, self.opt, step_bucket(batch, self.granularity), batch, self.exchange.sync,
-                                self.exchange.bucket, guard=self.guard, deterministic=self.deterministic, **self._guard_kw)
+                                self.exchange.bucket, guard=self.guard, deterministic=self.deterministic, **kw)
         self.n_captures += 1
         return made
